@@ -11,9 +11,10 @@ A batch pass = the whole hot path with the policy resident on the device: k_roll
 statistics in its epilogue), when N > 1 k_pick_best + ONE RCCL all-gather of every rank's 37 008-byte update packet, k_apply_update
 (the batch form of the reference's write-locked update, multi_simulation.rs:494-508), k_stalled_tables — stream-ordered
 launches, no host synchronisation, world tables and policy resident in HBM before the timed region starts.
-A STEP = `batches_per_step` consecutive batch passes; the number is chosen once, from a calibration of untimed passes,
-so that the K timed steps last at least --min-seconds (0.5 s) — `steps`, `warmup` are the K, W of the command line,
-`ms_per_step` is per step, `ms_per_batch` per pass.
+A STEP = `batches_per_step` consecutive batch passes (--batches-per-step, 1 by default; 0 = calibrate it from untimed passes so
+that the K timed steps last at least --min-seconds) — `steps`, `warmup` are the K, W of the command line, `ms_per_step` is per
+step, `ms_per_batch` per pass.  With a fixed step the run is the same sequence of batches every time, so --dump-outputs DIR
+writes the same outputs for the same arguments: the records of the last timed batch and the policy after its update, as .npy.
 
 Reference semantics kept: a replay episode records and applies every action twice, so once a replay
 episode becomes the best strategy the replayed lists — and the generators each replay episode places — double.  Left to
@@ -30,12 +31,14 @@ headline).  `--trajectory` lets the policy evolve instead (DESIGN.md §4 has tho
 batches did: `config.replay` (generators per replay / seeded episode, best-list length), `config.policy` and
 `config.episodes_failed` (EG_EP_OVERFLOW etc.; failed episodes are NOT counted in `value`).
 
-The N = 1 line also carries `config1` (BASELINE configs[1]: 1 024 episodes per batch, no replay), with a timed region and a
-`roofline` of its own like `config2_seeded`, and `cpu_baseline`.  `roofline.traffic / hbm_frac_measured / valu_busy` come from
+A plain run measures the headline alone.  --full adds every other measurement, each in a timed region of its own after the
+headline's: `config2_replay_hoisted`, `config2_seeded`, `config3_one_rank_state`, `fresh_policy_steady_state` and, at N > 1,
+`sustained_at_n`; the N = 1 line also carries `config1` (BASELINE configs[1]: 1 024 episodes per batch, no replay), with a timed
+region and a `roofline` of its own like `config2_seeded`, and `cpu_baseline`.  `roofline.traffic / hbm_frac_measured / valu_busy` come from
 the committed counter profiles of the same command and are quoted only when that profile was taken on the very library
 being timed (eg_build_hash); `frac_requested` bills only what the code requests from memory.
 
-  python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 """
 from __future__ import annotations
@@ -196,11 +199,11 @@ def measured_peak():
     return best
 
 
-def batch_census(eng, episodes, first, period, had_best):
-    """What the last batch did, from its records: episodes by status, generators per seeded / replay episode, the two
-    byte counts.  (One strided device-to-host copy per field; outside every timed region.)"""
+def batch_census(res, first, period, had_best):
+    """What the last batch did, from its records (`res` = eng.fetch() after the timed region): episodes by status, generators
+    per seeded / replay episode, the two byte counts."""
     import numpy as np
-    res = eng.fetch(episodes)
+    episodes = len(res.status)
     ok = res.status == 0
     idx = np.arange(first, first + episodes)
     rep = (idx % period == 0) if (period and had_best) else np.zeros(episodes, bool)
@@ -211,6 +214,47 @@ def batch_census(eng, episodes, first, period, had_best):
             "chunks_per_search": float(res.n_chunks[ok].sum()) / max(float(res.n_gens[ok].sum()), 1.0),
             "nominal_bytes": float(res.bytes_moved[ok].sum()), "touched_bytes": float(res.bytes_touched()[ok].sum()),
             "requested_bytes": float(res.bytes_requested()[ok].sum())}
+
+
+DUMP_SEED = 20250101                                       # the fixed sample of episodes --dump-outputs writes in full
+DUMP_EPISODES, DUMP_YEARLY, DUMP_LOGS = 16384, 2048, 256    # episodes sampled for the per-episode arrays / yearly rows / logs (<= 46 MB)
+
+
+def dump_outputs(out_dir: str, res, w, first: int) -> dict:
+    """What the timed path computed in its last step, as DIR/<name>.npy (float64; the logs float32, exact for their 8- and
+    16-bit entries): the records of the last batch (`res`, global episode indices first..first+n) and the policy after its
+    update (`w`, pulled from the device).  Batches larger than DUMP_EPISODES are sampled with a fixed seed, the yearly rows
+    and the logs always are; log entries behind an episode's counts are written as 0.  Returns {name: bytes}."""
+    import numpy as np
+    n = len(res.status)
+    rng = np.random.default_rng(DUMP_SEED)
+    pick = lambda k: np.sort(rng.choice(n, size=min(n, k), replace=False))
+    ep, ey, el = pick(DUMP_EPISODES), pick(DUMP_YEARLY), pick(DUMP_LOGS)
+    f64 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+
+    def logs(log, counts):
+        held = np.arange(log.shape[1])[None, :] < counts[:, None]
+        return np.where(held, log, 0).astype(np.float32)
+    arrays = {"episode_index": f64(first + ep), "metrics": f64(res.metrics[ep]), "status": f64(res.status[ep]),
+              "n_run": f64(res.n_run[ep]), "n_def": f64(res.n_def[ep]), "n_act": f64(res.n_act[ep]),
+              "n_gens": f64(res.n_gens[ep]), "n_offsets": f64(res.n_offsets[ep]), "n_draws": f64(res.n_draws[ep]),
+              "n_chunks": f64(res.n_chunks[ep]), "bytes_moved": f64(res.bytes_moved[ep]),
+              "yearly_episode_index": f64(first + ey), "yearly": f64(res.yearly[ey]),
+              "log_episode_index": f64(first + el),
+              "run_log": logs(res.run_log[el], res.n_run[el].sum(1)), "def_log": logs(res.def_log[el], res.n_def[el].sum(1)),
+              "act_log": logs(res.act_log[el], res.n_act[el].sum(1)),
+              "gen_cell": logs(res.gen_cell[el], res.n_gens[el]), "gen_pack": logs(res.gen_pack[el], res.n_gens[el]),
+              "off_pack": logs(res.off_pack[el], res.n_offsets[el])}
+    weights, deficit_weights, count_weights = w.tables()
+    arrays.update({"policy_weights": f64(weights), "policy_deficit_weights": f64(deficit_weights),
+                   "policy_count_weights": f64(count_weights),
+                   "policy_best_list_lengths": f64([[len(l) for l in w.lists(which)] for which in (0, 1)]),
+                   "policy_scalars": f64([w.get(k) for k in sorted(w.SC)])})
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: a.nbytes for name, a in arrays.items()}
 
 
 def timed_loop(trainer, eng, fence, batches):
@@ -309,10 +353,19 @@ def main():
     ap.add_argument("--episodes", type=int, default=16384, help="episodes per GPU per batch (BASELINE configs[2]/[3]: 16384; configs[1]: 1024)")
     ap.add_argument("--seed", type=int, default=12345)
     ap.add_argument("--replay-fraction", type=float, default=0.1, help="configs[2]: 0.1 (every 10th global index replays the best strategy); configs[1]: 0")
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="the K timed steps last at least this long (batches_per_step is sized for it)")
-    ap.add_argument("--batches-per-step", type=int, default=0, help="fix it instead of calibrating (0 = calibrate)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-config1", action="store_true", help="skip the secondary objects (configs[1]: 1024 episodes, no replay; the grown-replay state)")
+    ap.add_argument("--min-seconds", type=float, default=0.5, help="with --batches-per-step 0: the K timed steps last at least this long "
+                                                                   "(batches_per_step is sized for it)")
+    ap.add_argument("--batches-per-step", type=int, default=None,
+                    help="batch passes per timed step (default: 1 for the headline; the --full objects calibrate theirs); "
+                         "0 = calibrate from untimed passes (then the step, and the batches the run makes, depend on the timing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the last batch's records, the policy after its "
+                         "update) to DIR/<name>.npy; the same arguments give the same outputs")
+    ap.add_argument("--full", action="store_true",
+                    help="also every measurement beside the headline (the objects below, config1, cpu_baseline), each with a timed "
+                         "region of its own; a plain run measures the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-config1", action="store_true", help="with --full: skip the secondary objects (configs[1]: 1024 episodes, no replay; the grown-replay state)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only for rehearsal)")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: every rank uses cuda:0 (needs --backend gloo)")
     ap.add_argument("--force-collectives", action="store_true",
@@ -431,11 +484,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    def measure(tr, w, after_warmup=None):
-        """Calibration (untimed for the result: the last 2 passes of 10 size `batches_per_step`), W warm-up steps, K timed steps,
-        then what the last batch did."""
+    def measure(tr, w, after_warmup=None, bps=None):
+        """W warm-up steps, K timed steps of `bps` batch passes, then what the last batch did (`res`: its records, `w`: the policy
+        after its update).  bps = 0: first a calibration (untimed for the result: the last 2 passes of 10 size `batches_per_step`);
+        None: --batches-per-step, else calibrated (the --full objects)."""
         replay = {"best_list_len": int(sum(len(l) for l in w.lists(0))), "best_deficit_list_len": int(sum(len(l) for l in w.lists(1)))}      # (as pushed)
-        bps = args.batches_per_step
+        if bps is None:
+            bps = 0 if args.batches_per_step is None else args.batches_per_step
         calibration = 0
         if bps <= 0:
             for _ in range(8):
@@ -452,10 +507,12 @@ def main():
         elapsed = all_max(elapsed)
         failed = tr.failed_episodes() - failed_before      # episodes of ALL ranks that did not finish (counted by the updates)
         last_first = (tr.step_index - 1) * args.episodes * tr.ws + tr.rank * args.episodes
-        census = batch_census(eng, args.episodes, last_first, tr.replay_period, True)      # (a best strategy exists from the first batch on)
+        res = eng.fetch(args.episodes)
+        census = batch_census(res, last_first, tr.replay_period, True)      # (a best strategy exists from the first batch on)
         tr.sync()                     # device-resident policy -> host copy (after the timed region)
         batches = args.steps * bps
         return {"bps": bps, "calibration": calibration, "elapsed": elapsed, "batches": batches, "failed": failed, "census": census,
+                "res": res, "last_first": last_first,
                 "avg_kernel_s": kernel_ms / max(n_launch, 1) * 1e-3, "avg_grids_s": timed_loop.grids_ms / max(n_launch, 1) * 1e-3, "value": (args.episodes * tr.ws * batches - failed) / elapsed,
                 "replay": replay}
 
@@ -475,7 +532,11 @@ def main():
             os.dup2(saved_stdout, 1); os.close(saved_stdout)
             saved_stdout = None
 
-    m = measure(trainer, weights, restore_stdout)
+    m = measure(trainer, weights, restore_stdout, bps=1 if args.batches_per_step is None else args.batches_per_step)
+    res = m.pop("res")
+    if args.dump_outputs and rank == 0:      # (before anything else runs on this engine: the records are the last timed batch's)
+        dump_outputs(args.dump_outputs, res, weights, m["last_first"])
+    del res
     digests = [policy_digest(weights)]      # (measure() ends with the policy pulled from the device)
     if use_dist:
         digests = [None] * world_size
@@ -544,7 +605,7 @@ def main():
             obj["roofline"] = roofline_object(profile_key, g["census"], args.episodes, g["avg_kernel_s"])
         return obj
 
-    extras = args.replay_fraction > 0.0 and not args.trajectory and not args.no_config1
+    extras = args.full and args.replay_fraction > 0.0 and not args.trajectory and not args.no_config1
     hoisted = side_object(seeded_policy(args.grown), True,
                           "the headline's batches (same pinned policy, same episodes, same update) with the replay hoist on: the batch's replay "
                           "episodes are computed once by a cooperative workgroup and handed to every replay slot",
@@ -582,7 +643,7 @@ def main():
         b = side_object(wf, True, "the same with the replay hoist on")
         line["fresh_policy_steady_state"] = {"per_episode_replays": a, "replay_hoisted": b}
     # ---- second object (N = 1): the grown-replay state of the same workload — what the training loop turns configs[2] into ----
-    if world_size == 1 and not args.no_config1 and args.replay_fraction > 0.0 and not args.trajectory:
+    if args.full and world_size == 1 and not args.no_config1 and args.replay_fraction > 0.0 and not args.trajectory:
         other_grown = not args.grown      # the state the headline was NOT measured in
         wg = seeded_policy(other_grown)
         tg = BatchTrainer(eng, wg, args.episodes, args.seed, 0, 1, None, replay_fraction=args.replay_fraction,
@@ -601,7 +662,7 @@ def main():
                                  "roofline": roofline_object(workload_key(args.episodes, args.replay_fraction) + ("grown" if other_grown else ""), g["census"],
                                                              args.episodes, g["avg_kernel_s"])}
     # ---- second object: BASELINE configs[1] (1024 episodes per batch, no replay), its own policy and timed region ----
-    if world_size == 1 and not args.no_config1 and not (args.episodes == 1024 and args.replay_fraction == 0.0):
+    if args.full and world_size == 1 and not args.no_config1 and not (args.episodes == 1024 and args.replay_fraction == 0.0):
         w1 = ActionWeights()
         t1 = BatchTrainer(eng, w1, 1024, args.seed, 0, 1, None, replay_fraction=0.0, write_yearly=not args.no_yearly, device_resident=True)
         if not args.trajectory:
@@ -613,7 +674,7 @@ def main():
         f0 = t1.failed_episodes()
         el, kms, nl = timed_loop(t1, eng, fence, n1)
         f1 = t1.failed_episodes() - f0
-        c1 = batch_census(eng, 1024, (t1.step_index - 1) * 1024, 0, True)
+        c1 = batch_census(eng.fetch(1024), (t1.step_index - 1) * 1024, 0, True)
         t1.sync()
         line["config1"] = {"workload": "BASELINE configs[1]: 1024 parallel episodes per batch, no replay; batch pass = rollout + batch policy update; "
                                        + ("free-running policy" if args.trajectory else "every batch from ActionWeights::new (pinned like the headline)"),
@@ -621,7 +682,7 @@ def main():
                            "ms_per_batch": el / n1 * 1e3, "episodes_failed": f1,
                            "roofline": roofline_object(workload_key(1024, 0.0), c1, 1024, kms / max(nl, 1) * 1e-3)}
     if rank == 0:
-        if world_size == 1 and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(world)
         print(json.dumps(line), flush=True)
     eng.close()

@@ -13,7 +13,7 @@ CG="--steps 20 --warmup 5 --no-cpu-baseline --no-config1"
 C2="$CG --seeded"
 CH="$CG --replay-hoist"
 C1="--steps 20 --warmup 5 --no-cpu-baseline --episodes 1024 --replay-fraction 0 --batches-per-step 8"
-python bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err
+python bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err
 echo "bench done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${tag}_c2 -- python3 bench.py $C2 > $O/prof_${tag}.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${tag}_cg -- python3 bench.py $CG >> $O/prof_${tag}.log 2>&1

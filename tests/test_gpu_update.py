@@ -176,7 +176,7 @@ def test_two_rank_bench_rehearsal_at_the_real_shard_size():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29537", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--min-seconds", "0.05",
-           "--backend", "gloo", "--share-gpu", "--no-cpu-baseline"]
+           "--backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -198,12 +198,12 @@ def test_two_rank_bench_rehearsal_at_the_real_shard_size():
 
 
 def test_bench_line_contract_on_one_gpu():
-    """`python bench.py --steps K --warmup W` prints ONE JSON line with the driver's keys (steps / warmup echoed), the `roofline`
+    """`python bench.py --steps K --warmup W --full` prints ONE JSON line with the driver's keys (steps / warmup echoed), the `roofline`
     and `cpu_baseline` objects, and the two secondary objects; no episode fails; every batch started from the same policy."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--episodes", "2048",
-                          "--min-seconds", "0.05"], capture_output=True, text=True, timeout=900, cwd=root)
+                          "--min-seconds", "0.05", "--full"], capture_output=True, text=True, timeout=900, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines
@@ -244,6 +244,35 @@ def test_bench_line_contract_on_one_gpu():
     assert list(r)[:4] == ["bound", "valu_busy", "valu_busy_grids", "issue_slot_frac"] and "accounting" in r and "north_star_40pct_of_hbm" in r
     c = line["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["unit"] == "episodes/s" and c["sample"]
+
+
+def test_bench_plain_run_times_k_steps_and_dumps_the_same_outputs(tmp_path):
+    """A plain `python bench.py --steps K --warmup W --dump-outputs DIR` measures the headline alone: K timed steps of one batch
+    each, none of the --full objects.  Its outputs (the last batch's records and the policy after its update) are the same in
+    two runs with the same arguments, bit for bit, float32 / float64 and at most 64 MB."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--episodes", "2048",
+                              "--dump-outputs", d], capture_output=True, text=True, timeout=900, cwd=root)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.strip()][-1]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    line = lines[0]
+    assert line["steps"] == 4 and line["batches_per_step"] == 1 and line["config"]["batches_timed"] == 4 and line["calibration_batches"] == 0
+    assert line["value"] > 0 and abs(line["ms_per_step"] - line["ms_per_batch"]) < 1e-9 * line["ms_per_step"]
+    for key in ("config1", "cpu_baseline", "config2_seeded", "config2_replay_hoisted", "config3_one_rank_state", "fresh_policy_steady_state"):
+        assert key not in line, key
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"metrics", "yearly", "status", "run_log", "policy_weights"} <= set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20 and all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert a["metrics"].shape == (2048, 4) and (a["status"] == 0).all()
+    # no calibration: 1 warm-up batch + 4 timed ones, so the last is the trainer's fifth (global indices from 4 x 2048 on)
+    assert a["episode_index"][0] == 4 * 2048
+    for k in a:
+        assert a[k].tobytes() == b[k].tobytes(), k
 
 
 def test_grids_of_a_batch_overlap_with_a_process_group_up():
