@@ -61,6 +61,8 @@ EXPORTS = [
     "eg_rollout_launch", "eg_rollout_launch_update", "eg_sync", "eg_last_batch_size", "eg_policy_hold", "eg_policy_rewind", "eg_replay_hoist", "eg_replay_hoist_stats", "eg_debug_hoist_stamps", "eg_fetch", "eg_timing_reset", "eg_timing_read", "eg_timing_read_grids", "eg_memory_report", "eg_update_stats", "eg_fetch_scores",
     "eg_fetch_episode_lists", "eg_fetch_record", "eg_fetch_best_run", "eg_best_result_track", "eg_fetch_best_result", "eg_evaluate_action_impact", "eg_place", "eg_find_suitable_location", "eg_debug_fill_lds", "eg_debug_occupy", "eg_policy_apply_reduced", "eg_policy_apply_packet", "eg_train_step",
     "eg_policy_push", "eg_device_rollout", "eg_device_apply", "eg_device_step", "eg_policy_pull",
+    "eg_group_create", "eg_group_destroy", "eg_group_rank", "eg_group_push", "eg_group_step", "eg_group_pull", "eg_group_replay_hoist",
+    "eg_group_best_result_track", "eg_group_fetch_best_result",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -158,6 +160,24 @@ def lib():
     L.eg_device_step.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]
     L.eg_policy_pull.restype = C.c_int32
     L.eg_policy_pull.argtypes = [C.c_void_p, C.c_void_p]
+    L.eg_group_create.restype = C.c_void_p
+    L.eg_group_create.argtypes = [_i32p, C.c_int32, C.POINTER(EgWorld)]
+    L.eg_group_destroy.restype = None
+    L.eg_group_destroy.argtypes = [C.c_void_p]
+    L.eg_group_rank.restype = C.c_void_p
+    L.eg_group_rank.argtypes = [C.c_void_p, C.c_int32]
+    L.eg_group_push.restype = C.c_int32
+    L.eg_group_push.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.eg_group_step.restype = C.c_int32
+    L.eg_group_step.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64]
+    L.eg_group_pull.restype = C.c_int32
+    L.eg_group_pull.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.eg_group_replay_hoist.restype = C.c_int32
+    L.eg_group_replay_hoist.argtypes = [C.c_void_p, C.c_int32]
+    L.eg_group_best_result_track.restype = C.c_int32
+    L.eg_group_best_result_track.argtypes = [C.c_void_p, C.c_int32]
+    L.eg_group_fetch_best_result.restype = C.c_int32
+    L.eg_group_fetch_best_result.argtypes = [C.c_void_p, C.POINTER(EgEpisodeOut), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.eg_policy_append_weight_history.restype = C.c_int32
     L.eg_policy_append_weight_history.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64]
     L.eg_policy_export_improvement_csv.restype = C.c_int32

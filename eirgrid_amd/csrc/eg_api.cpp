@@ -62,6 +62,7 @@ struct eg_ctx {
   uint8_t* d_snap_held = nullptr;      // eg_policy_hold / eg_policy_rewind
   // the reference's best_result fold (multi_simulation.rs:613-620): 0 = not tracked, 1 = optimization_mode None, 2 = cost_only
   int fold_mode = 0; uint8_t* d_fold = nullptr;
+  bool group_member = false;      // owned by an eg_group: the group folds its ranks' results (eg_group_best_result_track), never the context itself
   // Is the best list long (the replay episodes run the heavy-capable variant and are the batch's long pole)?  `list_exact`: the host
   // KNOWS the list the next launch will find on the device (it uploaded, rewound or pulled it and no on-device update has been
   // enqueued since): the replay variant that has nothing to do is then not launched at all.  Otherwise the device may have replaced
@@ -795,6 +796,7 @@ int32_t eg_memory_report(const eg_ctx* c, uint64_t* table_bytes, uint64_t* recor
 
 int32_t eg_best_result_track(eg_ctx* c, int32_t mode) {
   if (!c || mode < 0 || mode > 2) { set_error("eg_best_result_track: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->group_member && mode != 0) { set_error("eg_best_result_track: the context is a rank of an eg_group (use eg_group_best_result_track)"); return EG_ERR_BAD_ARG; }
   EG_HIP(hipSetDevice(c->device));
   if (mode != 0) {
     if (!c->d_fold) EG_HIP(hipMalloc((void**)&c->d_fold, kFoldBytes));
@@ -876,14 +878,14 @@ int32_t eg_policy_push(eg_ctx* c, const eg_policy* p, const eg_opts* o) {
 
 namespace {
 int device_rollout(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t replay_period, void* d_packet, bool pick);
-int device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, void* d_own_packet, uint64_t noise_seed, bool local_pick);
+int device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, size_t packet_stride, void* d_own_packet, uint64_t noise_seed, bool local_pick);
 }  // namespace
 
 int32_t eg_device_rollout(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t replay_period, void* d_packet) {
   return device_rollout(c, seed, first_index, n, replay_period, d_packet, true);
 }
 int32_t eg_device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, void* d_own_packet, uint64_t noise_seed) {
-  return device_apply(c, d_packets, n_packets, d_own_packet, noise_seed, false);
+  return device_apply(c, d_packets, n_packets, EG_PACKET_BYTES, d_own_packet, noise_seed, false);
 }
 // One GPU: the best episode is found inside k_apply_update (from the best-score key the rollout epilogue leaves in the
 // statistics), so a step is three launches: k_rollout, k_apply_update, k_stalled_tables.
@@ -894,7 +896,7 @@ int32_t eg_device_step(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t 
   if (rc != EG_OK) return rc;
   rc = device_rollout(c, seed, first_index, n, replay_period, c->d_packet, false);
   if (rc != EG_OK) return rc;
-  return device_apply(c, c->d_packet, 1, c->d_packet, noise_seed, true);
+  return device_apply(c, c->d_packet, 1, EG_PACKET_BYTES, c->d_packet, noise_seed, true);
 }
 
 namespace {
@@ -912,11 +914,11 @@ int device_rollout(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, u
   return EG_OK;
 }
 
-int device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, void* d_own_packet, uint64_t noise_seed, bool local_pick) {
+int device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, size_t packet_stride, void* d_own_packet, uint64_t noise_seed, bool local_pick) {
   if (!c || !c->snap_valid || !d_packets || n_packets < 1 || !d_own_packet) { set_error("eg_device_apply: bad argument"); return EG_ERR_BAD_ARG; }
   EG_HIP(hipSetDevice(c->device));
   c->list_exact = false;      // from here on the device may hold another best list than the host thinks
-  int lr = launch_apply_update(c->d_snap, d_packets, n_packets, (long long*)d_own_packet, noise_seed, c->out, c->last_n, c->last_first,
+  int lr = launch_apply_update(c->d_snap, d_packets, n_packets, packet_stride, (long long*)d_own_packet, noise_seed, c->out, c->last_n, c->last_first,
                                local_pick && n_packets == 1 && c->last_n > 0, c->d_list_len, nullptr);
   if (lr != 0) { set_error(std::string("k_apply_update launch: ") + hipGetErrorString((hipError_t)lr)); return EG_ERR_HIP; }
   // (the stalled sampler's tables of the updated rows are rebuilt inside k_apply_update)
@@ -1136,4 +1138,233 @@ int32_t eg_find_suitable_location(eg_ctx* c, int32_t year_index, int32_t gen_typ
   return EG_OK;
 }
 
+// ---- eg_group: N ranks, one context each, driven from one host thread --------------------------------------------------
+// A step shards the global batch (parallel.shard_range), runs every rank's shard, exchanges one message per rank — its update
+// packet, followed by its fold block when the best_result fold is tracked — into every rank's gathered buffer, and applies the N
+// packets on every rank (the statistics are integer sums, the candidate choice is order-free: every rank makes the same update).
+// Nothing synchronises the host inside a step; the order comes from events, on the legacy null stream of each rank's device:
+//   ev_sent[r]  recorded by rank r behind its rollout and its message (fold block / empty-shard packet);
+//   ev_recv[q]  recorded by rank q behind the N copies into its gathered buffer, each of which waited for ev_sent of its sender.
+// Read after write: rank q's apply and fold follow the copies into its gathered buffer on q's own stream, and every copy follows
+// the sender's ev_sent — an apply never starts before all N messages have arrived.  Write after read: rank r's apply (which zeroes
+// its packet's statistics) and everything after it on r's stream — its next rollout and message — wait for ev_recv of every
+// other rank, i.e. until every peer has copied r's message; a rank's gathered buffer is only written again by the next step's
+// copies, which its own stream orders behind this step's apply and fold.  (Ranks that share a device share its null stream, so
+// there the order holds twice over; the events are what keeps it on separate devices.)
+struct eg_group {
+  int n = 0;
+  std::vector<eg_ctx*> ctx;
+  std::vector<int> device;
+  // rank r's message (update packet, then FoldEntry[cap]) and its gathered buffer (n slots of `stride` bytes, rank order)
+  std::vector<uint8_t*> d_send, d_gather;
+  size_t stride = 0; uint32_t cap = 0;
+  std::vector<hipEvent_t> ev_sent, ev_recv;
+  int fold_mode = 0; std::vector<uint8_t*> d_fold;      // GroupFoldState + the record, per rank
+  uint32_t step = 0;         // steps run: the tag of a take-over
+  bool pushed = false;
+};
+
+namespace {
+void shard(uint32_t total, int rank, int n, uint32_t& first, uint32_t& count) {      // parallel.shard_range
+  const uint32_t base = total / uint32_t(n), rem = total % uint32_t(n);
+  count = base + (uint32_t(rank) < rem ? 1u : 0u);
+  first = uint32_t(rank) * base + std::min(uint32_t(rank), rem);
+}
+int group_sync(eg_group* g) {
+  for (int r = 0; r < g->n; ++r) { EG_HIP(hipSetDevice(g->device[r])); EG_HIP(hipDeviceSynchronize()); }
+  return EG_OK;
+}
+void group_free_buffers(eg_group* g) {
+  for (int r = 0; r < g->n; ++r) {
+    (void)hipSetDevice(g->device[r]);
+    if (g->d_send[r]) (void)hipFree(g->d_send[r]);
+    if (g->d_gather[r]) (void)hipFree(g->d_gather[r]);
+    g->d_send[r] = g->d_gather[r] = nullptr;
+  }
+  g->cap = 0; g->stride = 0;
+}
+// messages of up to `cap` results per rank (grown with a synchronisation: the buffers may be in use by the previous step)
+int group_buffers(eg_group* g, uint32_t cap) {
+  if (g->d_send[0] && cap <= g->cap) return EG_OK;
+  int rc = group_sync(g);
+  if (rc != EG_OK) return rc;
+  group_free_buffers(g);
+  const size_t stride = (size_t(EG_PACKET_BYTES) + sizeof(FoldEntry) * cap + 255) & ~size_t(255);
+  for (int r = 0; r < g->n; ++r) {
+    EG_HIP(hipSetDevice(g->device[r]));
+    EG_HIP(hipMalloc((void**)&g->d_send[r], stride));
+    EG_HIP(hipMalloc((void**)&g->d_gather[r], stride * size_t(g->n)));
+    EG_HIP(hipMemset(g->d_send[r], 0, stride));      // the rollout epilogue ADDS to the statistics
+    EG_HIP(hipMemset(g->d_gather[r], 0, stride * size_t(g->n)));
+  }
+  g->cap = cap; g->stride = stride;
+  return EG_OK;
+}
+}  // namespace
+
+eg_group* eg_group_create(const int32_t* devices, int32_t n_ranks, const eg_world* world) {
+  if (!devices || n_ranks < 1 || !world) { set_error("eg_group_create: bad argument"); return nullptr; }
+  const int count = eg_device_count();
+  for (int r = 0; r < n_ranks; ++r)
+    if (devices[r] < 0 || devices[r] >= count) { set_error("eg_group_create: device " + std::to_string(devices[r]) + " does not exist (" + std::to_string(count) + " visible)"); return nullptr; }
+  eg_group* g = new eg_group();
+  g->n = n_ranks;
+  g->device.assign(devices, devices + n_ranks);
+  g->ctx.assign(n_ranks, nullptr); g->d_send.assign(n_ranks, nullptr); g->d_gather.assign(n_ranks, nullptr); g->d_fold.assign(n_ranks, nullptr);
+  g->ev_sent.assign(n_ranks, nullptr); g->ev_recv.assign(n_ranks, nullptr);
+  bool ok = true;
+  for (int r = 0; r < n_ranks && ok; ++r) {
+    g->ctx[r] = eg_create(devices[r], world);
+    if (!g->ctx[r]) { ok = false; break; }
+    g->ctx[r]->group_member = true;
+    if (hipEventCreateWithFlags(&g->ev_sent[r], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&g->ev_recv[r], hipEventDisableTiming) != hipSuccess) { set_error("eg_group_create: hipEventCreate failed"); ok = false; }
+  }
+  // direct access between distinct devices where the platform offers it (the copies work without it, staged)
+  for (int a = 0; a < n_ranks && ok; ++a)
+    for (int b = 0; b < n_ranks; ++b) {
+      if (g->device[a] == g->device[b]) continue;
+      int can = 0;
+      if (hipDeviceCanAccessPeer(&can, g->device[a], g->device[b]) == hipSuccess && can && hipSetDevice(g->device[a]) == hipSuccess)
+        (void)hipDeviceEnablePeerAccess(g->device[b], 0);
+      (void)hipGetLastError();      // (already enabled: not an error)
+    }
+  if (!ok) { const std::string e = g_error; eg_group_destroy(g); set_error(e); return nullptr; }
+  return g;
+}
+
+void eg_group_destroy(eg_group* g) {
+  if (!g) return;
+  (void)group_sync(g);
+  group_free_buffers(g);
+  for (int r = 0; r < g->n; ++r) {
+    (void)hipSetDevice(g->device[r]);
+    if (g->d_fold[r]) (void)hipFree(g->d_fold[r]);
+    if (g->ev_sent[r]) (void)hipEventDestroy(g->ev_sent[r]);
+    if (g->ev_recv[r]) (void)hipEventDestroy(g->ev_recv[r]);
+    eg_destroy(g->ctx[r]);
+  }
+  delete g;
+}
+
+eg_ctx* eg_group_rank(eg_group* g, int32_t rank) {
+  if (!g || rank < 0 || rank >= g->n) { set_error("eg_group_rank: bad argument"); return nullptr; }
+  return g->ctx[rank];
+}
+
+int32_t eg_group_push(eg_group* g, const eg_policy* p, const eg_opts* o) {
+  if (!g || !p) { set_error("eg_group_push: bad argument"); return EG_ERR_BAD_ARG; }
+  for (int r = 0; r < g->n; ++r) {
+    const int rc = eg_policy_push(g->ctx[r], p, o);
+    if (rc != EG_OK) return rc;
+  }
+  g->pushed = true;
+  return EG_OK;
+}
+
+int32_t eg_group_pull(eg_group* g, int32_t rank, eg_policy* p) {
+  if (!g || rank < 0 || rank >= g->n || !p) { set_error("eg_group_pull: bad argument"); return EG_ERR_BAD_ARG; }
+  return eg_policy_pull(g->ctx[rank], p);
+}
+
+int32_t eg_group_replay_hoist(eg_group* g, int32_t on) {
+  if (!g) { set_error("eg_group_replay_hoist: bad argument"); return EG_ERR_BAD_ARG; }
+  for (int r = 0; r < g->n; ++r) {
+    const int rc = eg_replay_hoist(g->ctx[r], on);
+    if (rc != EG_OK) return rc;
+  }
+  return EG_OK;
+}
+
+int32_t eg_group_best_result_track(eg_group* g, int32_t mode) {
+  if (!g || mode < 0 || mode > 2) { set_error("eg_group_best_result_track: bad argument"); return EG_ERR_BAD_ARG; }
+  if (mode != 0)
+    for (int r = 0; r < g->n; ++r) {
+      EG_HIP(hipSetDevice(g->device[r]));
+      if (!g->d_fold[r]) EG_HIP(hipMalloc((void**)&g->d_fold[r], kFoldBytes));
+      EG_HIP(hipMemsetAsync(g->d_fold[r], 0, kFoldBytes, nullptr));      // best_result = None; no record tagged (steps count from 1)
+    }
+  g->fold_mode = mode;
+  return EG_OK;
+}
+
+int32_t eg_group_step(eg_group* g, uint64_t seed, uint64_t first_index, uint32_t n_global, uint32_t replay_period, uint64_t noise_seed) {
+  if (!g || !g->pushed) { set_error("eg_group_step: push a policy first (eg_group_push)"); return EG_ERR_BAD_ARG; }
+  if (n_global == 0) return EG_OK;
+  const int N = g->n;
+  const bool fold = g->fold_mode != 0;
+  int rc = group_buffers(g, n_global / uint32_t(N) + (n_global % uint32_t(N) ? 1u : 0u));
+  if (rc != EG_OK) return rc;
+  g->step += 1;
+  // 1. every rank runs its shard; its message is completed behind the rollout and marked sent
+  for (int r = 0; r < N; ++r) {
+    uint32_t first = 0, n = 0;
+    shard(n_global, r, N, first, n);
+    eg_ctx* c = g->ctx[r];
+    rc = eg_device_rollout(c, seed, first_index + first, n, replay_period, g->d_send[r]);
+    if (rc != EG_OK) return rc;
+    EG_HIP(hipSetDevice(g->device[r]));
+    if (n == 0 || fold) {      // an empty shard's packet still holds the previous step's candidate: it says "none" instead
+      const int lr = launch_fold_pack(c->out, n, g->d_send[r], reinterpret_cast<FoldEntry*>(g->d_send[r] + EG_PACKET_BYTES), nullptr);
+      if (lr != 0) { set_error(std::string("k_fold_pack launch: ") + hipGetErrorString((hipError_t)lr)); return EG_ERR_HIP; }
+    }
+    EG_HIP(hipEventRecord(g->ev_sent[r], nullptr));
+  }
+  // 2. every rank receives every message into slot r of its gathered buffer (read after write: each copy waits for its sender)
+  for (int q = 0; q < N; ++q) {
+    EG_HIP(hipSetDevice(g->device[q]));
+    for (int r = 0; r < N; ++r) {
+      uint32_t first = 0, n = 0;
+      shard(n_global, r, N, first, n);
+      const size_t bytes = size_t(EG_PACKET_BYTES) + (fold ? sizeof(FoldEntry) * n : 0);
+      uint8_t* dst = g->d_gather[q] + size_t(r) * g->stride;
+      EG_HIP(hipStreamWaitEvent(nullptr, g->ev_sent[r], 0));
+      if (g->device[r] == g->device[q]) EG_HIP(hipMemcpyAsync(dst, g->d_send[r], bytes, hipMemcpyDeviceToDevice, nullptr));
+      else EG_HIP(hipMemcpyPeerAsync(dst, g->device[q], g->d_send[r], g->device[r], bytes, nullptr));
+    }
+    EG_HIP(hipEventRecord(g->ev_recv[q], nullptr));
+  }
+  // 3. every rank applies the N packets and folds the N blocks (write after read: not before every peer holds its message)
+  for (int r = 0; r < N; ++r) {
+    EG_HIP(hipSetDevice(g->device[r]));
+    for (int q = 0; q < N; ++q) if (q != r) EG_HIP(hipStreamWaitEvent(nullptr, g->ev_recv[q], 0));
+    eg_ctx* c = g->ctx[r];
+    rc = device_apply(c, g->d_gather[r], N, g->stride, g->d_send[r], noise_seed, false);
+    if (rc != EG_OK) return rc;
+    if (fold) {
+      uint32_t first = 0, n = 0;
+      shard(n_global, r, N, first, n);
+      const int lr = launch_fold_gathered(g->d_gather[r], g->stride, N, n_global, first_index, c->out, first, n, g->fold_mode == 2, g->step,
+                                          g->d_fold[r], nullptr);
+      if (lr != 0) { set_error(std::string("k_fold_gathered launch: ") + hipGetErrorString((hipError_t)lr)); return EG_ERR_HIP; }
+    }
+  }
+  return EG_OK;
+}
+
+int32_t eg_group_fetch_best_result(eg_group* g, eg_episode_out* o, int32_t* state, int64_t* global_index) {
+  if (!g || !o || !state) { set_error("eg_group_fetch_best_result: bad argument"); return EG_ERR_BAD_ARG; }
+  if (!g->d_fold[0] || g->fold_mode == 0) { set_error("eg_group_fetch_best_result: eg_group_best_result_track first"); return EG_ERR_BAD_ARG; }
+  int rc = group_sync(g);
+  if (rc != EG_OK) return rc;
+  std::vector<GroupFoldState> st(g->n);
+  for (int r = 0; r < g->n; ++r) {
+    EG_HIP(hipSetDevice(g->device[r]));
+    EG_HIP(hipMemcpy(&st[r], g->d_fold[r], sizeof(GroupFoldState), hipMemcpyDeviceToHost));
+    if (std::memcmp(st[r].metrics, st[0].metrics, sizeof(st[0].metrics)) != 0 || st[r].index != st[0].index || st[r].has != st[0].has ||
+        st[r].step != st[0].step) { set_error("eg_group_fetch_best_result: the ranks' fold states differ"); return EG_ERR_INTERNAL; }
+  }
+  *state = st[0].has ? 1 : 0;
+  if (global_index) *global_index = st[0].has ? int64_t(st[0].index) : -1;
+  if (!st[0].has) return EG_OK;
+  for (int r = 0; r < g->n; ++r)
+    if (st[r].tag_index == st[0].index && st[r].tag_step == st[0].step) {
+      EG_HIP(hipSetDevice(g->device[r]));
+      return fetch_records(g->d_fold[r] + kFoldRecord, 1, o);
+    }
+  set_error("eg_group_fetch_best_result: no rank holds the record of the held run");
+  return EG_ERR_INTERNAL;
+}
+
 }  // extern "C"
+

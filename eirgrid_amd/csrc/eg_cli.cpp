@@ -45,6 +45,8 @@ struct Args {   // cli/cli.rs:5-59
   uint64_t stop_after = 0;      // leave the loop (as an interrupt would) once this many iterations are done and checkpointed
   std::string dump_world;       // write the loaded world (eirgrid_amd JSON form) there and exit: no device needed
   bool replay_hoist = true;     // the replay iterations of a batch computed once (eg_replay_hoist): the same results, the replay phases 5x faster
+  // --gpus N / --devices LIST: the ranks of a multi-GPU run (eg_group), one device each; empty: the single-device run on --device
+  std::vector<int32_t> ranks; bool device_given = false, gpus_given = false;
 };
 
 void usage() {
@@ -58,7 +60,10 @@ void usage() {
             "engine options:\n      --world <FILE>       world in eirgrid_amd JSON form (default: read <assets-dir> like the reference)\n"
             "      --assets-dir <DIR>   settlements.json, ireland_generators.csv, coastline_points.json [default: aiSimulator/assets]\n"
             "      --batch <B>          iterations per GPU launch [default: 1024]\n      --update <sequential|reduced>  [default: reduced]\n"
-            "      --device <N>         [default: 0]\n      --existing-operational-at-start\n"
+            "      --device <N>         [default: 0]\n"
+            "      --gpus <N>           train on devices 0..N-1, one rank each (--batch stays the global iterations per update)\n"
+            "      --devices <LIST>     train on these devices, one rank each, e.g. 0,1 (repeats: ranks sharing a GPU)\n"
+            "      --existing-operational-at-start\n"
             "      --stop-after <N>     stop like an interrupted run once N iterations are done and checkpointed (resume tests)\n"
             "      --dump-world <FILE>  write the world as loaded (the --world JSON form) and exit; needs no GPU\n"
             "      --no-replay-hoist    run every replay iteration of a batch on its own (default: the replay iterations of a batch —\n"
@@ -95,7 +100,28 @@ bool parse(int argc, char** argv, Args& a) {
     else if (s == "--assets-dir") a.assets_dir = v();
     else if (s == "--batch") a.batch = uint32_t(std::max<uint64_t>(1, std::strtoull(v().c_str(), nullptr, 10)));
     else if (s == "--update") a.update = v();
-    else if (s == "--device") a.device = std::atoi(v().c_str());
+    else if (s == "--device") { a.device = std::atoi(v().c_str()); a.device_given = true; }
+    else if (s == "--gpus" || s == "--devices") {
+      const std::string list = v();
+      const bool gpus = s == "--gpus";
+      if (a.gpus_given || !a.ranks.empty()) { std::fprintf(stderr, "error: --gpus and --devices are given more than once\n"); return false; }
+      a.gpus_given = gpus;
+      // --gpus N: a count >= 1; --devices: comma-separated ordinals >= 0 (digits only)
+      size_t pos = 0;
+      while (true) {
+        const size_t comma = gpus ? std::string::npos : list.find(',', pos);
+        const std::string item = list.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+        if (item.empty() || item.size() > 6 || item.find_first_not_of("0123456789") != std::string::npos) {
+          std::fprintf(stderr, "error: %s needs %s, got '%s'\n", s.c_str(), gpus ? "a number of GPUs" : "a comma-separated list of device numbers", list.c_str());
+          return false;
+        }
+        const int k = std::atoi(item.c_str());
+        if (gpus) { if (k < 1) { std::fprintf(stderr, "error: --gpus needs at least 1\n"); return false; } for (int d = 0; d < k; ++d) a.ranks.push_back(d); }
+        else a.ranks.push_back(k);
+        if (comma == std::string::npos) break;
+        pos = comma + 1;
+      }
+    }
     else if (s == "--existing-operational-at-start") a.existing_operational_at_start = true;
     else if (s == "--stop-after") a.stop_after = std::strtoull(v().c_str(), nullptr, 10);
     else if (s == "--dump-world") a.dump_world = v();
@@ -103,7 +129,14 @@ bool parse(int argc, char** argv, Args& a) {
     else if (s == "-h" || s == "--help") { usage(); std::exit(0); }
     else { std::fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage(); return false; }
   }
-  return a.update == "sequential" || a.update == "reduced";
+  if (a.update != "sequential" && a.update != "reduced") return false;
+  if (!a.ranks.empty() && a.device_given) { std::fprintf(stderr, "error: --device cannot be combined with --gpus / --devices\n"); return false; }
+  if (a.ranks.size() > 1 && a.update == "sequential") {
+    std::fprintf(stderr, "error: --update sequential folds iterations one by one on one device; with more than one rank use --update reduced\n");
+    return false;
+  }
+  if (a.ranks.size() == 1) a.device = a.ranks[0];      // one rank: the single-device run on that device
+  return true;
 }
 
 bool read_file(const std::string& path, std::string& out) {
@@ -241,12 +274,25 @@ int main(int argc, char** argv) {
     return 0;
   }
   const eg_world world = wd.view(a.existing_operational_at_start);
-  eg_ctx* ctx = eg_create(a.device, &world);
-  if (!ctx) { std::fprintf(stderr, "eg_create: %s\n", eg_last_error()); return 1; }
+  // more than one rank: the same reduced-update loop on an eg_group (the exchange between the ranks is inside the library)
+  eg_ctx* ctx = nullptr; eg_group* group = nullptr;
+  if (a.gpus_given && int32_t(a.ranks.size()) > eg_device_count()) {
+    std::fprintf(stderr, "error: --gpus %zu: only %d device(s) visible\n", a.ranks.size(), eg_device_count()); return 2;
+  }
+  if (a.ranks.size() > 1) {
+    group = eg_group_create(a.ranks.data(), int32_t(a.ranks.size()), &world);
+    if (!group) { std::fprintf(stderr, "eg_group_create: %s\n", eg_last_error()); return 1; }
+    std::printf("Ranks: %zu on devices", a.ranks.size());
+    for (int32_t d : a.ranks) std::printf(" %d", d);
+    std::printf(" (%u iterations per update, sharded)\n", a.batch);
+  } else {
+    ctx = eg_create(a.device, &world);
+    if (!ctx) { std::fprintf(stderr, "eg_create: %s\n", eg_last_error()); return 1; }
+  }
   // The reference's replay phases (the last 10 % of a run, --force-full-simulation: core/multi_simulation.rs:38-39, :437-465) run the
   // same replay in every iteration of a batch: computed once unless asked otherwise (worlds the hoist is not sized for: every
   // iteration on its own, silently — the results are the same)
-  if (a.replay_hoist) (void)eg_replay_hoist(ctx, 1);
+  if (a.replay_hoist) (void)(group ? eg_group_replay_hoist(group, 1) : eg_replay_hoist(ctx, 1));
 
   // run directory and resume (multi_simulation.rs:160-165, :210-290, :396-404)
   eg_policy* policy = nullptr; uint64_t start_iteration = 0; std::string run_dir;
@@ -294,8 +340,8 @@ int main(int argc, char** argv) {
   unsigned failed_sequential = 0;      // --update sequential: episodes that did not finish (reduced mode counts them on the device)
   // reduced mode keeps the policy on the device: pushed once, every batch is enqueued without a host round trip and the
   // host copy is refreshed (eg_policy_pull) when a checkpoint or a progress line needs it
-  if (reduced) CHECK(eg_policy_push(ctx, policy, &opts));
-  CHECK(eg_best_result_track(ctx, a.cost_only ? 2 : 1));
+  if (reduced) CHECK(group ? eg_group_push(group, policy, &opts) : eg_policy_push(ctx, policy, &opts));
+  CHECK(group ? eg_group_best_result_track(group, a.cost_only ? 2 : 1) : eg_best_result_track(ctx, a.cost_only ? 2 : 1));
   const uint64_t full_from = a.iterations - std::min(a.iterations, final_full);   // multi_simulation.rs:437-465
   while (done < a.iterations) {
     uint32_t n = uint32_t(std::min<uint64_t>(a.batch, a.iterations - done));
@@ -303,7 +349,8 @@ int main(int argc, char** argv) {
     if (reduced) {
       if (!always_full && done < full_from && done + n > full_from) n = uint32_t(full_from - done);   // a batch never straddles the switch
       const bool full = always_full || done >= full_from;
-      CHECK(eg_device_step(ctx, a.seed, done, n, full ? 1u : 0u, a.seed + done));   // replay (once a best strategy exists) when full
+      if (group) CHECK(eg_group_step(group, a.seed, done, n, full ? 1u : 0u, a.seed + done));
+      else CHECK(eg_device_step(ctx, a.seed, done, n, full ? 1u : 0u, a.seed + done));   // replay (once a best strategy exists) when full
     } else {
       eg_policy_snapshot snap; CHECK(eg_policy_snapshot_view(policy, &snap));
       CHECK(eg_upload_snapshot(ctx, &snap, &opts));
@@ -329,7 +376,7 @@ int main(int argc, char** argv) {
     const auto now = std::chrono::steady_clock::now();
     const bool checkpoint_due = done / a.checkpoint_interval != last_checkpoint || done == a.iterations;
     const bool progress_due = std::chrono::duration<double>(now - last_progress).count() >= double(a.progress_interval) || done == a.iterations;
-    if (reduced && (checkpoint_due || progress_due)) CHECK(eg_policy_pull(ctx, policy));
+    if (reduced && (checkpoint_due || progress_due)) CHECK(group ? eg_group_pull(group, 0, policy) : eg_policy_pull(ctx, policy));
     if (checkpoint_due) {   // multi_simulation.rs:544-567
       last_checkpoint = done / a.checkpoint_interval;
       CHECK(eg_policy_save_json(policy, (run_dir + "/thread_0_weights.json").c_str()));
@@ -352,7 +399,7 @@ int main(int argc, char** argv) {
     if (a.stop_after && done >= a.stop_after && done < a.iterations) {
       if (!checkpoint_due) { std::fprintf(stderr, "error: --stop-after needs a checkpoint at the stop (use -i 1 or a divisor)\n"); return 2; }
       std::printf("Stopped after %llu iterations (--stop-after); resume with the same command\n", (unsigned long long)done);
-      eg_policy_free(policy); eg_destroy(ctx);
+      eg_policy_free(policy); eg_destroy(ctx); eg_group_destroy(group);
       return 0;
     }
   }
@@ -366,7 +413,8 @@ int main(int argc, char** argv) {
     CHECK(eg_policy_export_improvement_csv(policy, (dir + "/improvement_history.csv").c_str()));
   }
   int64_t best_index = -1;
-  { int32_t state = 0; CHECK(eg_fetch_best_result(ctx, &best_run.view, &state, &best_index)); best_run.valid = state == 1; }
+  { int32_t state = 0; CHECK(group ? eg_group_fetch_best_result(group, &best_run.view, &state, &best_index) : eg_fetch_best_result(ctx, &best_run.view, &state, &best_index));
+    best_run.valid = state == 1; }
   if (best_run.valid) {   // multi_simulation.rs:821-850
     const double* bm = best_run.metrics.data();
     std::printf("BEST SIMULATION RESULTS SUMMARY (iteration %lld)\nFinal net emissions: %.2f tonnes\nEmissions Status: %s\nAverage public opinion: %.1f%%\n"
@@ -385,5 +433,6 @@ int main(int argc, char** argv) {
               (unsigned long long)done, run_dir.c_str(), unsigned(eg_policy_get_scalar(policy, 13)) + failed_sequential);
   eg_policy_free(policy);
   eg_destroy(ctx);
+  eg_group_destroy(group);
   return 0;
 }

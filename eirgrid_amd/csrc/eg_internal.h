@@ -334,7 +334,8 @@ int launch_stalled_tables(uint8_t* d_snap, void* stream);
 int launch_rewind(uint8_t* d_snap, const uint8_t* d_held, uint32_t* list_len_out, void* stream);
 // `o`, n_local, first_index: the batch the own packet came from (the winner's record is kept when it is one of them)
 // local_pick: one packet, made by this device's last batch — the candidate record is built inside the kernel
-int launch_apply_update(uint8_t* d_snap, const void* d_packets, int n_packets, long long* d_zero_stats, uint64_t noise_seed,
+// packet_stride: bytes from one packet to the next in d_packets (EG_PACKET_BYTES, or a group's gathered slots, eg_api.cpp eg_group)
+int launch_apply_update(uint8_t* d_snap, const void* d_packets, int n_packets, size_t packet_stride, long long* d_zero_stats, uint64_t noise_seed,
                         const DevOut& o, uint32_t n_local, uint64_t first_index, bool local_pick, uint32_t* list_len_out, void* stream);
 int launch_place(const DevTables& t, int gen_type, int year_index, const uint16_t* d_cells, int n_extra,
                  int32_t* d_out_cell, double* d_out_score, void* stream);
@@ -369,5 +370,20 @@ constexpr size_t kFoldRecord = 64;
 constexpr size_t kFoldBytes = kFoldRecord + rec::stride;
 static_assert(sizeof(FoldState) <= kFoldRecord, "fold state layout");
 int launch_fold_best(const DevOut& o, uint32_t n, uint64_t first_index, bool cost_only, uint8_t* d_fold, void* stream);
+// The same fold over the ranks of a group (eg_api.cpp eg_group; eg_rollout.hip k_fold_pack / k_fold_gathered).  Every rank packs what the
+// fold reads of its shard into a block of FoldEntry behind its update packet; the blocks travel with the packets, and every rank folds
+// all of them in rank order (= global index order).  The state is replicated: identical on every rank.  The record is copied only by
+// the rank whose shard held the winner, which tags it with the winner's global index and the group step of the take-over.
+struct FoldEntry { double net, opinion, cost; int32_t ok, pad; };
+static_assert(sizeof(FoldEntry) == 32, "fold entry");
+struct GroupFoldState { double metrics[4]; long long index; int32_t has; uint32_t step; long long tag_index; uint32_t tag_step, pad; };
+static_assert(sizeof(GroupFoldState) <= kFoldRecord, "group fold state layout");
+// n == 0: marks d_packet as "no candidate" (score -1, index -1) with zero statistics — an empty shard's message; otherwise packs the
+// shard's n results into `block` (may be null: nothing to pack)
+int launch_fold_pack(const DevOut& o, uint32_t n, uint8_t* d_packet, FoldEntry* block, void* stream);
+// gathered: n_ranks slots of slot_stride bytes (packet, then that rank's FoldEntry block), n_global results of the step sharded like
+// parallel.shard_range; own_first / own_n: this rank's shard (its records are in `o`)
+int launch_fold_gathered(const uint8_t* d_gathered, size_t slot_stride, int n_ranks, uint32_t n_global, uint64_t first_index, const DevOut& o,
+                         uint32_t own_first, uint32_t own_n, bool cost_only, uint32_t step, uint8_t* d_fold, void* stream);
 
 }  // namespace eg

@@ -2468,23 +2468,23 @@ __device__ __forceinline__ double fold_impact(const double* cur, const double* n
   if (cost_only) { const double cost_change = x.cost - c.cost; return -cost_change / dmax(dabs(c.cost), 1.0); }      // scoring.rs:52-58
   return evaluate_impact(c, x);
 }
-__global__ void __launch_bounds__(1024) k_fold_best(DevOut O, uint32_t n, unsigned long long first_index, int cost_only, uint8_t* fold) {
+// The speculative windows, shared by k_fold_best (one context) and k_fold_gathered (the ranks of a group): `n` results in index order,
+// `load(i, m)` gives result i's metrics (false: a failed episode, skipped).  The held run is s_best / s_has (in LDS, read and left
+// there); s_win ends as the position (0 .. n-1) of the last take-over, -1 when the held run stays.
+template <typename Load>
+__device__ __forceinline__ void fold_windows(uint32_t n, int cost_only, Load load, double* s_best, int& s_has, int& s_first, int& s_win) {
   constexpr int kPer = 8;      // results per thread and tile, in registers
-  __shared__ double s_best[4];
-  __shared__ int s_has, s_first, s_win;
   const int tid = threadIdx.x;
-  FoldState* st = reinterpret_cast<FoldState*>(fold);
-  if (tid < 4) s_best[tid] = st->metrics[tid];
-  if (tid == 0) { s_has = st->has; s_win = -1; s_first = 0x7FFFFFFF; }
-  __syncthreads();
   for (uint32_t tile = 0; tile < n; tile += kPer * 1024u) {
     double m[kPer][4]; bool ok[kPer];
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {
       const uint32_t i = tile + (uint32_t)k * 1024u + (uint32_t)tid;
-      ok[k] = i < n && *O.status(i) == EG_EP_OK;
+      ok[k] = i < n && load(i, m[k]);
+      if (!ok[k]) {
 #pragma unroll
-      for (int j = 0; j < 4; ++j) m[k][j] = ok[k] ? O.metrics(i)[j] : 0.0;
+        for (int j = 0; j < 4; ++j) m[k][j] = 0.0;
+      }
     }
 #pragma unroll
     for (int k = 0; k < kPer; ++k) {      // window k: results tile + 1024 k + [0, 1024), in index order = thread order
@@ -2510,6 +2510,21 @@ __global__ void __launch_bounds__(1024) k_fold_best(DevOut O, uint32_t n, unsign
     }
   }
   __syncthreads();
+}
+__global__ void __launch_bounds__(1024) k_fold_best(DevOut O, uint32_t n, unsigned long long first_index, int cost_only, uint8_t* fold) {
+  __shared__ double s_best[4];
+  __shared__ int s_has, s_first, s_win;
+  const int tid = threadIdx.x;
+  FoldState* st = reinterpret_cast<FoldState*>(fold);
+  if (tid < 4) s_best[tid] = st->metrics[tid];
+  if (tid == 0) { s_has = st->has; s_win = -1; s_first = 0x7FFFFFFF; }
+  __syncthreads();
+  fold_windows(n, cost_only, [&](uint32_t i, double* m) {
+    if (*O.status(i) != EG_EP_OK) return false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) m[j] = O.metrics(i)[j];
+    return true;
+  }, s_best, s_has, s_first, s_win);
   const int win = s_win;
   if (win < 0) return;      // the held run stays
   const unsigned long long* src = reinterpret_cast<const unsigned long long*>(O.base + (size_t)win * rec::stride);
@@ -2518,6 +2533,67 @@ __global__ void __launch_bounds__(1024) k_fold_best(DevOut O, uint32_t n, unsign
   if (tid == 0) {
     for (int j = 0; j < 4; ++j) st->metrics[j] = s_best[j];
     st->index = (long long)(first_index + (unsigned long long)win); st->has = 1;
+  }
+}
+
+// ---- the same fold over the ranks of a group (eg_api.cpp eg_group_step) -------------------------------------------------
+// k_fold_pack runs behind a rank's rollout: what fold_impact reads of each result of the shard, 32 bytes apart (in the records
+// they are rec::stride = 41.6 KB apart), written into the block that travels behind the rank's update packet.  With n == 0 it
+// makes the packet an empty shard's message instead: eg_device_rollout(n = 0) does not touch the packet, which still holds the
+// previous step's candidate — that must not reach the update again.
+__global__ void __launch_bounds__(256) k_fold_pack(DevOut O, uint32_t n, uint8_t* packet, FoldEntry* block) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (n == 0) {
+    long long* stats = reinterpret_cast<long long*>(packet);
+    for (uint32_t k = threadIdx.x; k < (uint32_t)EG_STATS_LEN; k += 256u) stats[k] = 0;
+    if (threadIdx.x == 0) {
+      UpdateCandidate* c = reinterpret_cast<UpdateCandidate*>(packet + 8 * EG_STATS_LEN);
+      c->score = -1.0; c->index = -1ll;
+    }
+    return;
+  }
+  if (i >= n) return;
+  FoldEntry e;
+  e.ok = *O.status(i) == EG_EP_OK ? 1 : 0; e.pad = 0;
+  const double* m = O.metrics(i);
+  e.net = e.ok ? m[0] : 0.0; e.opinion = e.ok ? m[1] : 0.0; e.cost = e.ok ? m[2] : 0.0;
+  block[i] = e;
+}
+// k_fold_gathered runs on every rank over the gathered blocks of all ranks, in rank order = global index order: the same
+// windows and the same fold_impact as k_fold_best, so the state it leaves is the same on every rank and the same as one
+// context's fold over the whole step.  The winner's record is copied only by the rank whose shard held it, from its own records,
+// and tagged there (index, step); no record crosses devices.
+__global__ void __launch_bounds__(1024) k_fold_gathered(const uint8_t* gathered, unsigned long long slot_stride, int n_ranks, uint32_t n_global,
+                                                       unsigned long long first_index, DevOut O, uint32_t own_first, uint32_t own_n, int cost_only,
+                                                       uint32_t step, uint8_t* fold) {
+  __shared__ double s_best[4];
+  __shared__ int s_has, s_first, s_win;
+  const int tid = threadIdx.x;
+  GroupFoldState* st = reinterpret_cast<GroupFoldState*>(fold);
+  if (tid < 4) s_best[tid] = st->metrics[tid];
+  if (tid == 0) { s_has = st->has; s_win = -1; s_first = 0x7FFFFFFF; }
+  __syncthreads();
+  // parallel.shard_range: the first `rem` ranks hold base + 1 results, the others base
+  const uint32_t base = n_global / (uint32_t)n_ranks, rem = n_global % (uint32_t)n_ranks, big = rem * (base + 1u);
+  fold_windows(n_global, cost_only, [&](uint32_t i, double* m) {
+    const uint32_t r = i < big ? i / (base + 1u) : rem + (i - big) / base;
+    const uint32_t j = i < big ? i - r * (base + 1u) : (i - big) - (r - rem) * base;
+    const FoldEntry* e = reinterpret_cast<const FoldEntry*>(gathered + (size_t)r * slot_stride + EG_PACKET_BYTES) + j;
+    if (e->ok == 0) return false;
+    m[0] = e->net; m[1] = e->opinion; m[2] = e->cost; m[3] = 0.0;
+    return true;
+  }, s_best, s_has, s_first, s_win);
+  const int win = s_win;
+  if (win < 0) return;      // the held run stays
+  if ((uint32_t)win >= own_first && (uint32_t)win - own_first < own_n) {
+    const unsigned long long* src = reinterpret_cast<const unsigned long long*>(O.base + (size_t)((uint32_t)win - own_first) * rec::stride);
+    unsigned long long* dst = reinterpret_cast<unsigned long long*>(fold + kFoldRecord);
+    for (int i = tid; i < (int)(rec::stride / 8); i += 1024) dst[i] = src[i];
+    if (tid == 0) { st->tag_index = (long long)(first_index + (unsigned long long)win); st->tag_step = step; }
+  }
+  if (tid == 0) {
+    for (int j = 0; j < 4; ++j) st->metrics[j] = s_best[j];
+    st->index = (long long)(first_index + (unsigned long long)win); st->has = 1; st->step = step;
   }
 }
 
@@ -2543,9 +2619,9 @@ __device__ void chacha12_block(const uint32_t* key, unsigned long long counter, 
   for (int i = 0; i < 16; ++i) out[i] = x[i] + s[i];
 }
 
-// `packets` = n_packets update packets of EG_PACKET_BYTES (one per rank, in rank order; the gathered copies when N > 1):
+// `packets` = n_packets update packets, packet_stride bytes apart (one per rank, in rank order; the gathered copies when N > 1):
 // the statistics are summed here (integers: any order gives the same sum), the candidate records sit behind them.
-__global__ void __launch_bounds__(1024) k_apply_update(uint8_t* snap_base, const uint8_t* packets, int n_cands, long long* zero_stats,
+__global__ void __launch_bounds__(1024) k_apply_update(uint8_t* snap_base, const uint8_t* packets, int n_cands, unsigned long long packet_stride, long long* zero_stats,
                                                       unsigned long long noise_seed, const uint8_t* out_base, const double* score_list, uint32_t n_local,
                                                       unsigned long long first_index, int local_pick, uint32_t* list_len_out) {
   constexpr int NA = EG_N_ACTIONS, ND = EG_N_DEFICIT, Y = EG_YEARS;
@@ -2573,10 +2649,10 @@ __global__ void __launch_bounds__(1024) k_apply_update(uint8_t* snap_base, const
 
   // serial pieces run on different waves side by side: state + winner + "is it an improvement" on wave 1, the noise key on
   // wave 0
-  const uint8_t* cands = packets + 8 * EG_STATS_LEN;      // record r at cands + r * EG_PACKET_BYTES
+  const uint8_t* cands = packets + 8 * EG_STATS_LEN;      // record r at cands + r * packet_stride
   auto stat = [&](int i) {
     long long v = 0;
-    for (int r = 0; r < n_cands; ++r) v += reinterpret_cast<const long long*>(packets + (size_t)r * EG_PACKET_BYTES)[i];
+    for (int r = 0; r < n_cands; ++r) v += reinterpret_cast<const long long*>(packets + (size_t)r * packet_stride)[i];
     return v;
   };
   // Everything the contrast steps read is requested now and lands while the serial pieces run: the old best lists go to
@@ -2631,14 +2707,14 @@ __global__ void __launch_bounds__(1024) k_apply_update(uint8_t* snap_base, const
     // the batch's candidate: highest score, ties to the lowest global index (eg_policy_apply_packet)
     int win = -1; double ws = 0.0; long long wi = 0;
     for (int r = 0; r < n_cands; ++r) {
-      const UpdateCandidate* c = reinterpret_cast<const UpdateCandidate*>(cands + (size_t)r * EG_PACKET_BYTES);
+      const UpdateCandidate* c = reinterpret_cast<const UpdateCandidate*>(cands + (size_t)r * packet_stride);
       if (c->index < 0) continue;
       if (win < 0 || c->score > ws || (c->score == ws && c->index < wi)) { win = r; ws = c->score; wi = c->index; }
     }
     s_winner = win;
     bool improved = false;
     if (win >= 0 && stat(0) > 0) {
-      const UpdateCandidate* c = reinterpret_cast<const UpdateCandidate*>(cands + (size_t)win * EG_PACKET_BYTES);
+      const UpdateCandidate* c = reinterpret_cast<const UpdateCandidate*>(cands + (size_t)win * packet_stride);
       improved = !st.has_best || rm::score(c->metrics) > rm::score(st.best_metrics);
     }
     s_improved = improved ? 1 : 0;
@@ -2703,7 +2779,7 @@ __global__ void __launch_bounds__(1024) k_apply_update(uint8_t* snap_base, const
     st.failed_total += (uint32_t)stat(1);
     s_randomized_main = randomize_main ? 1 : 0;
     if (improved) {
-      const UpdateCandidate* c = reinterpret_cast<const UpdateCandidate*>(cands + (size_t)s_winner * EG_PACKET_BYTES);
+      const UpdateCandidate* c = reinterpret_cast<const UpdateCandidate*>(cands + (size_t)s_winner * packet_stride);
       DevImprovement* log = reinterpret_cast<DevImprovement*>(snap_base + snap::imp_log) + (st.n_improvements % snap::kImpLogCap);
       log->score = rm::score(c->metrics); log->iteration = st.iteration_count; log->pad = 0;
       for (int k = 0; k < 4; ++k) { log->metrics[k] = c->metrics[k]; st.best_metrics[k] = c->metrics[k]; }
@@ -2724,7 +2800,7 @@ __global__ void __launch_bounds__(1024) k_apply_update(uint8_t* snap_base, const
 #endif
   const bool improved = s_improved != 0;
   if (improved) {      // the candidate's lists become the best lists; the main weights of this moment are kept beside them
-    const UpdateCandidate* c = reinterpret_cast<const UpdateCandidate*>(cands + (size_t)s_winner * EG_PACKET_BYTES);
+    const UpdateCandidate* c = reinterpret_cast<const UpdateCandidate*>(cands + (size_t)s_winner * packet_stride);
     const int nr = s_prefix[0][Y], nd = s_prefix[1][Y];
     for (int i = tid; i < nr && i < (int)snap::kBestCap; i += 1024) best_actions[i] = c->run_log[i];
     for (int i = tid; i < nd && i < (int)snap::kBestCap; i += 1024) bestd_actions[i] = c->def_log[i];
@@ -3036,10 +3112,10 @@ int launch_stalled_tables(uint8_t* d_snap, void* stream) {
   hipLaunchKernelGGL(k_stalled_tables, dim3(EG_YEARS), dim3(kWave), 0, (hipStream_t)stream, d_snap);
   return (int)hipGetLastError();
 }
-int launch_apply_update(uint8_t* d_snap, const void* d_packets, int n_packets, long long* d_zero_stats, uint64_t noise_seed,
+int launch_apply_update(uint8_t* d_snap, const void* d_packets, int n_packets, size_t packet_stride, long long* d_zero_stats, uint64_t noise_seed,
                         const DevOut& o, uint32_t n_local, uint64_t first_index, bool local_pick, uint32_t* list_len_out, void* stream) {
   hipLaunchKernelGGL(k_apply_update, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_snap, (const uint8_t*)d_packets, n_packets,
-                     d_zero_stats, (unsigned long long)noise_seed, (const uint8_t*)o.base, (const double*)o.score_list, n_local, (unsigned long long)first_index,
+                     (unsigned long long)packet_stride, d_zero_stats, (unsigned long long)noise_seed, (const uint8_t*)o.base, (const double*)o.score_list, n_local, (unsigned long long)first_index,
                      local_pick ? 1 : 0, list_len_out);
   return (int)hipGetLastError();
 }
@@ -3051,6 +3127,18 @@ int launch_update_stats(const DevSnapshot& s, const DevOut& o, uint32_t n, long 
 int launch_fold_best(const DevOut& o, uint32_t n, uint64_t first_index, bool cost_only, uint8_t* d_fold, void* stream) {
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_fold_best, dim3(1), dim3(1024), 0, (hipStream_t)stream, o, n, (unsigned long long)first_index, cost_only ? 1 : 0, d_fold);
+  return (int)hipGetLastError();
+}
+int launch_fold_pack(const DevOut& o, uint32_t n, uint8_t* d_packet, FoldEntry* block, void* stream) {
+  if (n > 0 && block == nullptr) return 0;
+  hipLaunchKernelGGL(k_fold_pack, dim3(n > 0 ? (n + 255u) / 256u : 1u), dim3(256), 0, (hipStream_t)stream, o, n, d_packet, block);
+  return (int)hipGetLastError();
+}
+int launch_fold_gathered(const uint8_t* d_gathered, size_t slot_stride, int n_ranks, uint32_t n_global, uint64_t first_index, const DevOut& o,
+                         uint32_t own_first, uint32_t own_n, bool cost_only, uint32_t step, uint8_t* d_fold, void* stream) {
+  if (n_global == 0) return 0;
+  hipLaunchKernelGGL(k_fold_gathered, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_gathered, (unsigned long long)slot_stride, n_ranks, n_global,
+                     (unsigned long long)first_index, o, own_first, own_n, cost_only ? 1 : 0, step, d_fold);
   return (int)hipGetLastError();
 }
 int launch_pick_best(const DevOut& o, uint32_t n, uint64_t first_index, UpdateCandidate* d_cand, void* stream) {

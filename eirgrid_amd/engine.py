@@ -497,3 +497,73 @@ class Engine:
         N.check(N.lib().eg_place(self.h, gen_type, year_index, _p(cells, C.c_uint16) if len(cells) else None, len(cells),
                                  C.byref(cell), C.byref(score)), "eg_place")
         return cell.value, score.value
+
+
+class _Rank(Engine):
+    """A rank's context inside a Group: Engine's per-context queries (fetch, timing, memory report), owned by the group."""
+
+    def __init__(self, handle, world: World):
+        self.h = handle
+        self.world = world
+
+    def close(self):
+        self.h = None      # (eg_group_destroy destroys it)
+
+    __del__ = close
+
+
+class Group:
+    """One eg_group: N ranks (one context each, devices may repeat) driven from this thread; include/eirgrid_hip.h eg_group_*."""
+
+    def __init__(self, world: World, devices=(0, 0)):
+        L = N.lib()
+        if L.eg_device_count() <= 0:
+            raise N.EirgridError("no HIP device visible: eirgrid_amd runs on MI355X (gfx950) only and has no CPU path")
+        w, self._keep = _world_struct(world)
+        self._devices = np.ascontiguousarray(devices, dtype=np.int32)
+        self.h = L.eg_group_create(_p(self._devices, C.c_int32), len(self._devices), C.byref(w))
+        if not self.h:
+            raise N.EirgridError(L.eg_last_error().decode())
+        self.world = world
+        self.ranks = [_Rank(L.eg_group_rank(self.h, r), world) for r in range(len(self._devices))]
+
+    @property
+    def n_ranks(self) -> int:
+        return len(self.ranks)
+
+    def close(self):
+        if getattr(self, "h", None):
+            for r in getattr(self, "ranks", []):
+                r.close()
+            try:
+                N.lib().eg_group_destroy(self.h)
+            except TypeError:      # interpreter shutdown
+                pass
+            self.h = None
+
+    __del__ = close
+
+    def push(self, weights: ActionWeights, enable_energy_sales=True, write_yearly=True):
+        opts = Engine._opts(enable_energy_sales, False, write_yearly)
+        N.check(N.lib().eg_group_push(self.h, weights.h, C.byref(opts)), "eg_group_push")
+
+    def step(self, seed: int, first_episode_index: int, n_global: int, replay_period: int, noise_seed: int):
+        N.check(N.lib().eg_group_step(self.h, C.c_uint64(seed & (2**64 - 1)), C.c_uint64(first_episode_index), n_global,
+                                      replay_period, C.c_uint64(noise_seed & (2**64 - 1))), "eg_group_step")
+
+    def pull(self, rank: int, weights: ActionWeights):
+        N.check(N.lib().eg_group_pull(self.h, rank, weights.h), "eg_group_pull")
+
+    def replay_hoist(self, on: bool = True) -> None:
+        N.check(N.lib().eg_group_replay_hoist(self.h, int(bool(on))), "eg_group_replay_hoist")
+
+    def track_best_result(self, cost_only: bool = False, on: bool = True) -> None:
+        N.check(N.lib().eg_group_best_result_track(self.h, 0 if not on else (2 if cost_only else 1)), "eg_group_best_result_track")
+
+    def fetch_best_result(self):
+        """(global index, record) of the run the reference would summarise and export over every rank's results, or (None, None)."""
+        res = BatchResult.alloc(1)
+        out = res.struct()
+        state = C.c_int32(0); index = C.c_int64(-1)
+        N.check(N.lib().eg_group_fetch_best_result(self.h, C.byref(out), C.byref(state), C.byref(index)), "eg_group_fetch_best_result")
+        return (int(index.value), res) if state.value == 1 else (None, None)

@@ -245,6 +245,38 @@ int32_t eg_best_result_track(eg_ctx *, int32_t mode);
 int32_t eg_fetch_best_result(eg_ctx *, eg_episode_out *out, int32_t *state, int64_t *global_index);
 double eg_evaluate_action_impact(const double current_metrics[4], const double new_metrics[4], int32_t cost_only);
 
+/* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
+ * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
+ * copies, no collective library — and every call enqueues the work of all ranks from the calling thread without synchronising
+ * the host.
+ *   eg_group_create    one context per entry of `devices` (repeats allowed: ranks that share a GPU); NULL + eg_last_error() when a
+ *                      device does not exist
+ *   eg_group_rank      a rank's context, for per-rank queries (eg_fetch, eg_timing_read, eg_memory_report, eg_fetch_best_run, ...);
+ *                      it belongs to the group: never eg_destroy it, and its own best_result fold stays off (eg_best_result_track
+ *                      refuses a rank)
+ *   eg_group_push      eg_policy_push on every rank: every rank holds the same policy
+ *   eg_group_step      one training step over the global batch of n_global episodes [first_episode_index, + n_global): rank r runs
+ *                      the contiguous shard parallel.shard_range gives it (the first ranks take the remainder; shards may be empty),
+ *                      every rank's update packet (and fold block) reaches every rank, and every rank applies the N packets —
+ *                      replicas stay bit-identical, and equal to ONE context's eg_device_step over the same batches.  replay_period
+ *                      and noise_seed as for eg_device_step
+ *   eg_group_pull      eg_policy_pull from one rank (they all hold the same policy)
+ *   eg_group_replay_hoist  eg_replay_hoist on every rank
+ *   eg_group_best_result_track / eg_group_fetch_best_result   the reference's best_result fold (see eg_best_result_track) over the
+ *                      results of ALL ranks in global index order: exactly one context's fold over the same episodes.  The fold's
+ *                      state is kept on every rank; the held run's record only by the rank that ran it, and fetched from there. */
+typedef struct eg_group eg_group;
+eg_group *eg_group_create(const int32_t *devices, int32_t n_ranks, const eg_world *world);
+void eg_group_destroy(eg_group *);
+eg_ctx *eg_group_rank(eg_group *, int32_t rank);
+int32_t eg_group_push(eg_group *, const eg_policy *, const eg_opts *opts);
+int32_t eg_group_step(eg_group *, uint64_t seed, uint64_t first_episode_index, uint32_t n_global, uint32_t replay_period,
+                      uint64_t noise_seed);
+int32_t eg_group_pull(eg_group *, int32_t rank, eg_policy *);
+int32_t eg_group_replay_hoist(eg_group *, int32_t on);
+int32_t eg_group_best_result_track(eg_group *, int32_t mode);
+int32_t eg_group_fetch_best_result(eg_group *, eg_episode_out *out, int32_t *state, int64_t *global_index);
+
 /* Test hook: fills the LDS of every compute unit with `value` and waits.  LDS is not cleared between workgroups, so a
  * kernel that reads a word before writing it sees what the previous tenant left; the parity tests call this with small
  * integers (the values the helper protocol's sequence flags take) before a rollout. */
