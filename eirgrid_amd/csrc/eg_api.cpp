@@ -173,7 +173,7 @@ int collect_timing(eg_ctx* c, int count = -1) {
 // enlarged when a launch brings more of them: a replay episode without a slot falls back to the exact scan, 20-40x slower,
 // and a launch lasts as long as its slowest episode) and the launch has an epoch of its own
 int prepare_heavy(eg_ctx* c, uint32_t n_heavy, bool known_short) {
-  constexpr size_t kSlotBytes = size_t(kRadiusClasses) * 2624 * sizeof(double);
+  constexpr size_t kSlotBytes = size_t(kRadiusClasses) * 2624 * sizeof(double), kTileBytes = size_t(kMaxVariants) * 64 * sizeof(double);
   // No pool while the host KNOWS the best list to be short: replay episodes of a short list never ask for a slot.  (Not by the
   // pinned hint: the host enqueues a free-running loop many batches ahead of the device, the hint is as old as the queue is deep,
   // and a long replay episode without a slot takes the exact scan — 33 instead of 5 ms per batch, measured.)
@@ -188,20 +188,23 @@ int prepare_heavy(eg_ctx* c, uint32_t n_heavy, bool known_short) {
       EG_HIP(hipDeviceSynchronize());
       for (auto it = c->allocs.begin(); it != c->allocs.end(); ++it) if (*it == c->dev.heavy) { c->allocs.erase(it); break; }
       (void)hipFree(c->dev.heavy);
-      c->dev.heavy = nullptr; c->dev.heavy_slots = 0;
+      c->dev.heavy = nullptr; c->dev.heavy_slots = 0; c->dev.heavy_tiles = nullptr;
     }
     if (!c->dev.heavy_claim) {
       void* claim = nullptr;
       if (hipMalloc(&claim, 64) != hipSuccess) { (void)hipGetLastError(); c->heavy_slots_wanted = 0; want = 0; }
       else { EG_HIP(hipMemset(claim, 0xFF, 64)); c->allocs.push_back(claim); c->dev.heavy_claim = static_cast<unsigned*>(claim); }      // 0xFF..: an epoch no launch uses
     }
-    while (want > 0 && hipMalloc(&pool, kSlotBytes * want) != hipSuccess) {      // no memory for that many: fewer; none: heavy episodes take the exact scan
+    while (want > 0 && hipMalloc(&pool, (kSlotBytes + kTileBytes) * want) != hipSuccess) {      // no memory for that many: fewer; none: heavy episodes take the exact scan
       (void)hipGetLastError();
       pool = nullptr;
       want = want > 4096u ? want / 2u : 0u;
       c->heavy_slots_auto = false; c->heavy_slots_wanted = want;
     }
-    if (pool) { c->allocs.push_back(pool); c->dev.heavy = static_cast<uint8_t*>(pool); c->dev.heavy_slots = want; }
+    if (pool) {
+      c->allocs.push_back(pool); c->dev.heavy = static_cast<uint8_t*>(pool); c->dev.heavy_slots = want;
+      c->dev.heavy_tiles = reinterpret_cast<double*>(static_cast<uint8_t*>(pool) + kSlotBytes * want);      // (the fields, then their tile bounds)
+    }
   }
   c->launch_epoch = (c->launch_epoch + 1u) & 0xFFFu;
   if (c->launch_epoch == 0xFFFu) c->launch_epoch = 0u;      // 0xFFF is the "never" epoch the claim word starts with
@@ -401,11 +404,34 @@ eg_ctx* eg_create(int32_t device_ordinal, const eg_world* world) {
         uint32_t* pc = reinterpret_cast<uint32_t*>(blob.data() + tab::pcell) + (size_t(y) * kMaxVariants + v) * kPcStride;
         for (int r = 0; r < kPcStride; ++r) { pb[r] = r < kCells ? base[order[r]] : 0.0; pc[r] = r < kCells ? uint32_t(order[r]) : 0u; }
         std::memcpy(blob.data() + tab::cbase + 8 * (size_t(y) * kMaxVariants + v) * kCells, base.data(), 8 * size_t(kCells));      // the same scores per cell
+        uint16_t* rank = reinterpret_cast<uint16_t*>(blob.data() + tab::crank) + (size_t(y) * kMaxVariants + v) * kCells;      // ... their ranks
+        for (int r = 0; r < kCells; ++r) rank[order[r]] = uint16_t(r);
         for (int r = 0; r < kCells; ++r) {
           list[r].te = te[order[r]]; list[r].cf = marine ? H.coastf[order[r]] : 1.0; list[r].m03 = H.m03[order[r]]; list[r].cell = uint32_t(order[r]);
           list[r].pad = uint32_t(4 * (order[r] / kGrid)) | (uint32_t(4 * (order[r] % kGrid)) << 16);
         }
       }
+  }
+  if (rc == EG_OK) {  // the tile bounds of place_tiles (eg_internal.h tab::ucell): score(y, c) * field(c) = (score(y, c) / u(c)) * (u(c) * field(c)),
+                      // at most the tile's largest ratio times a bound of u * field on the tile (the ratio rounded up by 2^-40: far more than
+                      // the few roundings in between)
+    const double* cb = reinterpret_cast<const double*>(blob.data() + tab::cbase);
+    double* uc = reinterpret_cast<double*>(blob.data() + tab::ucell);
+    double* um = reinterpret_cast<double*>(blob.data() + tab::umax);
+    double* rm = reinterpret_cast<double*>(blob.data() + tab::rmax);
+    auto tile_of = [](int c2) { return (c2 / kGrid / kTileW) * kTileCols + (c2 % kGrid) / kTileW; };
+    for (int v = 0; v < D.n_variants; ++v) {
+      double* u = uc + size_t(v) * kCells;
+      for (int c2 = 0; c2 < kCells; ++c2)
+        for (int y = 0; y < kYears; ++y) u[c2] = std::max(u[c2], cb[(size_t(y) * kMaxVariants + v) * kCells + c2]);
+      for (int c2 = 0; c2 < kCells; ++c2) um[size_t(v) * 64 + tile_of(c2)] = std::max(um[size_t(v) * 64 + tile_of(c2)], u[c2]);
+      for (int y = 0; y < kYears; ++y) {
+        double* r = rm + (size_t(y) * kMaxVariants + v) * 64;
+        for (int c2 = 0; c2 < kCells; ++c2)
+          if (u[c2] >= 1e-300) r[tile_of(c2)] = std::max(r[tile_of(c2)], cb[(size_t(y) * kMaxVariants + v) * kCells + c2] / u[c2]);
+        for (int t = 0; t < kTiles; ++t) r[t] = r[t] * (1.0 + 0x1p-40);
+      }
+    }
   }
   {  // compact factor table (eg_rollout.hip load_factor_table): class k keeps squared distances 0..cap_k, cap_k = the first at which
      // the factor is 1.0 (d >= R); the factor must depend on the squared distance only and reach 1.0 within 12 cells
@@ -520,6 +546,8 @@ eg_ctx* eg_create(int32_t device_ordinal, const eg_world* world) {
     if (const char* rh = std::getenv("EIRGRID_REPLAY_HOIST")) c->hoist_on = c->hoist_supported && rh[0] == '1';
     if (const char* cf = std::getenv("EIRGRID_COOP_FORCE")) c->coop_force = std::atoi(cf);
     if (const char* so = std::getenv("EIRGRID_REPLAY_SOLO")) c->solo_on = so[0] != '0';
+    c->dev.solo_tiles = 1u;      // EIRGRID_SOLO_TILES=0: k_replay_solo searches by rank, as the classic variant does (A/B on one library)
+    if (const char* st = std::getenv("EIRGRID_SOLO_TILES")) c->dev.solo_tiles = st[0] != '0' ? 1u : 0u;
   }
   if (rc != EG_OK) { eg_destroy(c); return nullptr; }
   return c;

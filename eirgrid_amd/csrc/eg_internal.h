@@ -22,6 +22,10 @@ constexpr int kDrCompact = 352;      // doubles of the compact factor table (the
 constexpr int kLdsGens = EG_ONCHIP_GENS;      // generators / offsets of an episode that the kernels keep in LDS; the long-replay variant goes on in the episode's record
 constexpr int kShortReplayMax = 96;   // actions in the best list up to which replay episodes stay on the exact scan (eg_rollout.hip, k_rollout kinds)
 constexpr int kMaxVariants = 12;  // distinct (radius class, marine) pairs over the 15 types (8 for the reference's types)
+constexpr int kTileW = 8;         // the tiles of the spatial bound (tab::ucell / umax / rmax, DevTables::heavy_tiles): 7 x 7 tiles of 8 x 8 cells, edge tiles 3 wide
+constexpr int kTileCols = (kGrid + kTileW - 1) / kTileW;
+constexpr int kTiles = kTileCols * kTileCols;
+static_assert(kTiles <= 64, "a tile per lane");
 constexpr int kPcStride = 48 * 64;  // entries per list of the compact form (tab::pbase / pcell): the 41 chunks, then zeros — the scan requests a round of four chunks
                                     // ahead without asking whether the list has ended
 
@@ -123,7 +127,15 @@ constexpr size_t coastf = a16(te_cell + 8 * size_t(kYears) * kRadiusClasses * kC
 // ... and the unpenalised score (te * cf) * size_factor of every (year, variant) per cell — tab::pbase in cell order: what the hoisted
 // replay's searches multiply the penalty field with (te_cell / coastf: the exact evaluation of tied candidates)
 constexpr size_t cbase = a16(coastf + 8 * size_t(kCells));                                  // f64 [26][kMaxVariants][2601]
-constexpr size_t total = a16(cbase + 8 * size_t(kYears) * kMaxVariants * kCells);
+// the spatial bound of the per-episode replay kernel's searches (eg_rollout.hip place_tiles), the grid in 8 x 8 tiles: per (year,
+// variant) every cell's place in the sorted list (tab::pbase's rank); per variant u(c), the largest unpenalised score of the cell over
+// the years, and its largest value per tile; per (year, variant) and tile the largest ratio score / u (rounded up by 2^-40; cells
+// with u below 1e-300 left out), the same for every cell up to rounding — the years differ by population factors only
+constexpr size_t crank = a16(cbase + 8 * size_t(kYears) * kMaxVariants * kCells);           // u16 [26][kMaxVariants][2601]
+constexpr size_t ucell = a16(crank + 2 * size_t(kYears) * kMaxVariants * kCells);           // f64 [kMaxVariants][2601]
+constexpr size_t umax = a16(ucell + 8 * size_t(kMaxVariants) * kCells);                     // f64 [kMaxVariants][64] (49 tiles, zeros)
+constexpr size_t rmax = a16(umax + 8 * size_t(kMaxVariants) * 64);                          // f64 [26][kMaxVariants][64]
+constexpr size_t total = a16(rmax + 8 * size_t(kYears) * kMaxVariants * 64);
 }  // namespace tab
 
 struct DevTables {
@@ -136,6 +148,10 @@ struct DevTables {
   uint32_t heavy_slots, heavy_epoch;
   uint8_t* heavy;
   unsigned* heavy_claim;
+  // ... and behind the pool, per slot and variant, an upper bound of u(c) * field(c) on every 8 x 8 tile of the grid (tab::ucell):
+  // [kMaxVariants][64] f64 (eg_rollout.hip place_tiles; never read by the classic variant)
+  double* heavy_tiles;
+  uint32_t solo_tiles;      // 1: k_replay_solo searches by tile bounds (place_tiles), 0: by rank (place_heavy; EIRGRID_SOLO_TILES=0)
 #define EG_TAB(name, type) EG_HD const type* name() const { return reinterpret_cast<const type*>(base + tab::name); }
   EG_TAB(usage, double) EG_TAB(population, double)
   EG_TAB(pre_co2, double) EG_TAB(pre_tg, double) EG_TAB(pre_ig, double) EG_TAB(pre_sg, double) EG_TAB(pre_optot, double)
@@ -145,7 +161,7 @@ struct DevTables {
   EG_TAB(dr, double) EG_TAB(m03, double) EG_TAB(t12, double) EG_TAB(offv, double) EG_TAB(offc, double) EG_TAB(cc, double)
   // placement: candidates of every (year, variant) sorted by unpenalised score, descending (ties: ascending cell)
   EG_TAB(ps, PsRec) EG_TAB(pbase, double) EG_TAB(pcell, uint32_t) EG_TAB(hv_lists, uint32_t) EG_TAB(hv_quads, int32_t) EG_TAB(dr_meta, int32_t) EG_TAB(dr_compact, double)
-  EG_TAB(te_cell, double) EG_TAB(coastf, double) EG_TAB(cbase, double)
+  EG_TAB(te_cell, double) EG_TAB(coastf, double) EG_TAB(cbase, double) EG_TAB(crank, uint16_t) EG_TAB(ucell, double) EG_TAB(umax, double) EG_TAB(rmax, double)
 #undef EG_TAB
 };
 

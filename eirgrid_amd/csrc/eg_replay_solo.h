@@ -9,7 +9,8 @@
 //   1. its script (rs::script: actions, logs, counts, the lists' pack words — 64 additional actions at a time),
 //   2. its placements, one after the other, with k_rollout's own searches (place_search / place_heavy / place_exact_long, the penalty
 //      field of the pool, the lists' window in LDS and their tail in the record — the same code, so the same cells and the same
-//      accounting of requested chunks),
+//      accounting of requested chunks) — except that a search of the field goes by tile bounds (place_tiles: the same cell, the same
+//      chunks, fewer instructions; EIRGRID_SOLO_TILES=0: by rank, as k_rollout searches),
 //   3. its yearly rows (rs::books_quad, four years at a time), the running totals, the header and the statistics epilogue.
 // An episode whose script cannot be finished without a seeded draw or a capacity, or that finds no location, publishes nothing:
 // k_rollout<0, kReplayLong>, launched behind this kernel, runs every episode whose word in `done` does not carry the batch's sequence
@@ -117,6 +118,7 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
   const ListTail tail = {(unsigned long long)gen_cell, (unsigned long long)O.gen_pack(e), (unsigned long long)O.off_pack(e)};
   PrefixCache prefix_cache0 = {0.0, -1, 0};
   uint32_t search_seq = 0;
+  int tile_variants = 0;      // variants whose tile bounds (place_tiles) this episode has set up
   int pk_block = 0;
   solo::Entries E;
 #pragma unroll
@@ -137,6 +139,7 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
         const int info = __builtin_amdgcn_readfirstlane(sm.type_info[t]);
         const int hv = info & 15, hrc = (info >> 4) & 15;
         const unsigned long long class_addr = (unsigned long long)T.heavy + (unsigned long long)ep.heavy * slot_bytes + (unsigned long long)(hrc * kFieldStride) * 8ull;
+        const unsigned long long tiles_addr = (unsigned long long)T.heavy_tiles + (unsigned long long)((ep.heavy * kMaxVariants + hv) * 64) * 8ull;
         if (!((ep.heavy_classes >> hrc) & 1)) {      // the first search of this radius class: its field joins
           heavy_build_class<false>(class_addr, tail.gen_cell, lane, hrc, throughput_table(info), (info >> 8) & 15, ep.ngen);
           ep.heavy_classes |= 1 << hrc;
@@ -147,9 +150,17 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
           wave_sync();
           solo::load_entries(E, lane);      // the lane's entries, ready for every field update until the next class joins
         }
-        const size_t yv = (size_t)(yi * kMaxVariants + hv) * kPsStride, yc = (size_t)(yi * kMaxVariants + hv) * kPcStride;
-        const int hr = place_heavy<false>((unsigned long long)(T.ps() + yv), (unsigned long long)(T.pbase() + yc), (unsigned long long)(T.pcell() + yc), class_addr,
-                                          tail.gen_cell, T.size_factor, lane, hrc, throughput_table(info), ep.ngen);
+        int hr = kTilesUndecided;
+        if (T.solo_tiles && !((tile_variants >> hv) & 1)) {      // the variant's first search of the episode: its tile bounds start at the largest u
+          ((GlobalF64)tiles_addr)[lane] = T.umax()[hv * 64 + lane];      // (in flight until place_tiles waits for its stores)
+          tile_variants |= 1 << hv;
+        }
+        if (T.solo_tiles) hr = place_tiles((unsigned long long)T.base, yi * kMaxVariants + hv, class_addr, tiles_addr, tail.gen_cell, T.size_factor, lane, hrc, throughput_table(info), ep.ngen);
+        if (hr == kTilesUndecided) {      // (EIRGRID_SOLO_TILES=0, or ties that place_heavy resolves on its slow path)
+          const size_t yv = (size_t)(yi * kMaxVariants + hv) * kPsStride, yc = (size_t)(yi * kMaxVariants + hv) * kPcStride;
+          hr = place_heavy<false>((unsigned long long)(T.ps() + yv), (unsigned long long)(T.pbase() + yc), (unsigned long long)(T.pcell() + yc), class_addr,
+                                  tail.gen_cell, T.size_factor, lane, hrc, throughput_table(info), ep.ngen);
+        }
         if (hr >= 0) { cell = hr & 0xFFFF; ep.chunks += hr >> 16; placed = true; }
       }
     }
@@ -172,7 +183,11 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
       if (ep.heavy_quads == 3) heavy_add_body<false, 4>(field_addr, hv_list, lane, cell, 8);
       else if (ep.heavy_quads >= 4) heavy_add_body<false, 8>(field_addr, hv_list, lane, cell, 8);
     }
-    if (cell < 0) return;      // EG_EP_NO_LOCATION (or a lost search): the classic path reports it
+    if (cell < 0) {      // EG_EP_NO_LOCATION (or a lost search): the classic path reports it, with the field slot this episode holds
+                         // (tagged with the launch's sequence number; the pool has one slot per replay episode of the launch)
+      if (lane == 0 && ep.heavy >= 0) emap.solo[blockIdx.x] = (emap.solo_seq << 21) | (1ull << 20) | (unsigned long long)ep.heavy;
+      return;
+    }
     if (lane == 0) {
       if (ep.ngen < kLdsGens) { sm.gcell[ep.ngen] = (uint16_t)(cell | (t << 12)); sm.gbm[ep.ngen] = (uint8_t)(yi | (m << 5)); }
       gen_cell[ep.ngen] = (uint16_t)cell;
@@ -228,6 +243,7 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
     for (int i = 0; i < 8; ++i) dbg[i] = cs[i];
 #ifdef EG_STAMPS      // (with -DEG_STAMPS as well: place_heavy's own counters — scan / candidates / exact evaluation cycles; chunks, candidates, searches)
     for (int i = 0; i < 3; ++i) { dbg[8 + i] = sm.hdbg[0][i]; dbg[11 + i] = sm.hdbg[1][i]; }
+    dbg[14] = sm.hdbg[1][3];      // (place_tiles: tiles evaluated)
 #endif
   }
 #endif

@@ -1260,6 +1260,44 @@ __device__ __forceinline__ double exact_product_chain(int rc, int table, int nge
   }
   return s;
 }
+// 3. of a search of the field (place_heavy, place_tiles): the exact scores of the candidates — their ranks in sm.gstage[1], `solo_cell` the
+//    cell of the only one when the approximate pass has it at hand, else -1 — the reference's product in list order, first maximum in
+//    cell order
+template <bool kLatency>
+__device__ __forceinline__ ChunkBest heavy_exact(unsigned long long list_addr, unsigned long long tail_cells, double size_factor, int lane, int rc, int tbl, int ngen_s,
+                                                 int ncand, int solo_cell) {
+  ChunkBest b; b.score = 0.0; b.m03 = 0.0; b.cell = kCells;
+  if (solo_cell >= 0) {      // the usual case: ONE candidate.  It is the arg-max — the arg-max is among the candidates — and nothing
+                             // but its cell is asked for: its exact score (the reference's product over the whole list) need not be
+                             // formed at all.  (It is positive: within 2^-42 of an approximate score of at least 1e-250.)
+    b.cell = solo_cell; b.score = 1.0;
+  } else if (ncand <= 4 || ngen_s > kLdsGens) {      // one at a time, generator-parallel factors and the sequential product (exact_product_chain)
+                                                     // (chunk_product below walks the on-chip window only)
+    for (int k = 0; k < ncand; ++k) {
+      const int rk = __builtin_amdgcn_readfirstlane(sm.gstage[1][k]);
+      const PsRec e = load_rec(list_addr, rk);      // the same record in every lane
+      const double sk = (exact_product_chain<kLatency>(rc, tbl, ngen_s, e.te, (int)e.cell, lane, tail_cells) * e.cf) * size_factor;
+      if (sk > b.score || (sk == b.score && sk > 0.0 && (int)e.cell < b.cell)) { b.score = sk; b.cell = (int)e.cell; b.m03 = e.m03; }
+    }
+  } else {               // many ties: 64 candidates at once (chunk_product)
+    const int r = lane < ncand ? sm.gstage[1][lane] : kCells;
+    PsRec e; e.te = 0.0; e.cf = 1.0; e.m03 = 0.0; e.cell = 0u; e.pad = 0u;
+    if (r < kCells) e = load_rec(list_addr, r);
+    const int table = kLatency ? rc * (kD2Stride * 16) : tbl;
+    const double s = chunk_score<kLatency>(table, size_factor, lane, ngen_s, r, e.te, e.cf, (int)e.cell, (int)e.pad);
+    b = chunk_reduce<false>(s, (int)e.cell, e.m03);
+  }
+  return b;
+}
+// the winner's 0.03 * mean settlement opinion to sm.hres[1].m03; returns cell | chunks requested << 16
+__device__ __forceinline__ int heavy_result(const ChunkBest& b, int lane, int K, int ncand) {
+  wave_sync();
+  if (lane == 0) sm.hres[1].m03 = b.m03;
+  wave_sync();
+  // requested, in units of 2 KB: K chunks of the compact list (64 x 12 B each), K x 64 field entries of 8 B, and — only when several
+  // candidates tie — their full records (the field update that follows bills itself)
+  return b.cell | (((3 * K + 7) / 8 + (K + 3) / 4 + (ncand > 1 ? 1 : 0)) << 16);
+}
 // `list_addr`: the sorted candidate list of (year, variant); `class_addr`: the field of the radius class.
 // returns cell | chunks requested << 16, or kSearchFallback (the winner's 0.03 * mean settlement opinion: the caller reads tab::m03)
 // The scan reads the compact form of the sorted list, `pb_addr` / `pc_addr` = unpenalised score and cell per rank: three registers per
@@ -1352,37 +1390,163 @@ __device__ __noinline__ int place_heavy(unsigned long long list_addr, unsigned l
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const unsigned long long ts2 = __builtin_readcyclecounter();
 #endif
-  ChunkBest b; b.score = 0.0; b.m03 = 0.0; b.cell = kCells;
-  if (ncand == 1 && solo >= 0) {      // the usual case: ONE candidate.  It is the arg-max — the arg-max is among the candidates — and nothing
-                                      // but its cell is asked for: its exact score (the reference's product over the whole list) need not be
-                                      // formed at all.  (It is positive: within 2^-42 of an approximate score of at least 1e-250.)
-    b.cell = __builtin_amdgcn_readlane(lcell, solo); b.score = 1.0;
-  } else if (ncand <= 4 || ngen_s > kLdsGens) {      // one at a time, generator-parallel factors and the sequential product (exact_product_chain)
-                                                     // (chunk_product below walks the on-chip window only)
-    for (int k = 0; k < ncand; ++k) {
-      const int rk = __builtin_amdgcn_readfirstlane(sm.gstage[1][k]);
-      const PsRec e = load_rec(list_addr, rk);      // the same record in every lane
-      const double sk = (exact_product_chain<kLatency>(rc, tbl, ngen_s, e.te, (int)e.cell, lane, tail_cells) * e.cf) * size_factor;
-      if (sk > b.score || (sk == b.score && sk > 0.0 && (int)e.cell < b.cell)) { b.score = sk; b.cell = (int)e.cell; b.m03 = e.m03; }
-    }
-  } else {               // many ties: 64 candidates at once (chunk_product)
-    const int r = lane < ncand ? sm.gstage[1][lane] : kCells;
-    PsRec e; e.te = 0.0; e.cf = 1.0; e.m03 = 0.0; e.cell = 0u; e.pad = 0u;
-    if (r < kCells) e = load_rec(list_addr, r);
-    const int table = kLatency ? rc * (kD2Stride * 16) : tbl;
-    const double s = chunk_score<kLatency>(table, size_factor, lane, ngen_s, r, e.te, e.cf, (int)e.cell, (int)e.pad);
-    b = chunk_reduce<false>(s, (int)e.cell, e.m03);
-  }
+  const ChunkBest b = heavy_exact<kLatency>(list_addr, tail_cells, size_factor, lane, rc, tbl, ngen_s, ncand, ncand == 1 && solo >= 0 ? __builtin_amdgcn_readlane(lcell, solo) : -1);
   if (!(b.score > 0.0)) return kSearchFallback;
 #ifdef EG_STAMPS
   if (lane == 0) { sm.hdbg[0][0] += ts1 - ts0; sm.hdbg[0][1] += ts2 - ts1; sm.hdbg[0][2] += __builtin_readcyclecounter() - ts2; sm.hdbg[1][0] += (unsigned long long)K; sm.hdbg[1][1] += (unsigned long long)ncand; sm.hdbg[1][2] += 1ull; }
 #endif
+  return heavy_result(b, lane, K, ncand);
+}
+
+// ---- the per-episode replay kernel's search: by tile bounds instead of by rank -----------------------------------------------
+// place_heavy walks the candidates in descending unpenalised score.  In a replay the best cells are taken early on, so a search goes
+// 8-9 chunks deep in three dependent rounds of gathers: two thirds of the cycles of a replay episode on k_replay_solo, where a lone
+// wave pays about ten cycles per instruction.  place_tiles finds the same M by WHERE the cells are: the grid in 7 x 7 tiles of 8 x 8
+// cells, and per tile an upper bound of its approximate scores pb(y, c) * field(c).  The unpenalised scores of the years differ by
+// population factors only (tab::te: the distance terms are the same every year), so pb(y, c) = r(y, c) * u(c), u(c) the cell's largest
+// over the years (tab::ucell) and r(y, c) nearly the same on the whole tile: the bound is rmax(y, tile) * g(tile), rmax the tile's
+// largest ratio rounded up (tab::rmax), g an upper bound of u * field on the tile (DevTables::heavy_tiles, per variant).  The field only
+// shrinks (every factor is at most 1, and x * f <= x under round-to-nearest), so a bound once true stays true: a field update leaves g
+// alone, a variant's first search of an episode starts it at the tile's largest u (tab::umax), and a search writes back the present
+// maximum of u * field (rounded up) of every tile it evaluates.  A search
+//   1. takes the bounds of the 49 tiles (a lane each) and evaluates the best two: their 128 cells, two per lane, as rows of tab::cbase
+//      (the unpenalised score per cell: the doubles tab::pbase holds per rank) and of the field, each cell with place_heavy's key — the
+//      high word of pb * field, the low word's six lowest bits replaced by the chunk (rank / 64) its scan meets the cell in;
+//   2. evaluates every other tile whose bound is not below hi(M) * (1 - 2^-29), two at a time, M the largest key so far.  A key exceeds
+//      its score by less than 64 ulp, so every cell place_heavy would keep (key or score at least M * (1 - 2^-30)) is evaluated.
+// What place_heavy's scan reads follows from M.  Its M is the largest key of all cells too (a cell behind the point where it stops has
+// a key below the bound it stopped on, and that bound is below the M it had).  It scans groups of four chunks and stops ahead of group
+// g > 0 when the group's first unpenalised score pb[256 g] is below hi(M) * (1 - 2^-30), hi(M) the largest key of the groups before
+// with its low word cleared.  It cannot stop before group g* = rank(M) / 256 (M itself would be behind the stop), and from the round
+// after g* on its hi(M) is the final M's.  So it stops at g_stop, the first g > g* with pb[256 g] < hi(M) * (1 - 2^-30), or at the end
+// of the list (kGroups), having read K = min(4 g_stop, 41) chunks: ten group boundaries, one load.  Its candidates lie among the
+// cells of rank < 64 K.  It takes its fast path when no lane of its scan (rank % 64) has seen two cells within 2^-30 of M: the
+// candidates are then the lanes' largest keys.  place_tiles keeps per lane of its own the largest key with its rank and cell and the
+// second largest key; when one of its lanes has seen two, or two candidates share a rank % 64 — ties, which place_heavy resolves on
+// its slow path — it returns kTilesUndecided and the caller runs place_heavy.  Otherwise the candidates, their exact evaluation
+// (heavy_exact), the fallbacks and the chunks requested are place_heavy's, bit for bit.
+// `tab_addr`: the tables (DevTables::base), `yv`: year * kMaxVariants + variant, `tiles_addr`: the variant's 49 tile bounds g
+constexpr int kTilesUndecided = -4;
+static_assert(kTileW * kTileW == kWave, "a cell of a tile per lane");
+__device__ __noinline__ int place_tiles(unsigned long long tab_addr, int yv, unsigned long long class_addr, unsigned long long tiles_addr,
+                                        unsigned long long tail_cells, double size_factor, int lane, int rc, int tbl, int ngen) {
+#ifdef EG_STAMPS
+  const unsigned long long ts0 = __builtin_readcyclecounter();
+#endif
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the last field update's and search's stores are in L2 before anything reads them
+  const int ngen_s = __builtin_amdgcn_readfirstlane(ngen);
+  constexpr int kChunks = (kCells + kWave - 1) / kWave, kGroup = 4, kGroups = (kChunks + kGroup - 1) / kGroup;
+  constexpr double kKeep = 1.0 - 0x1p-30, kKeepTile = 1.0 - 0x1p-29;
+  constexpr int kNoTile = 63;      // a tile index with no cell on the grid: the second tile of a round that has only one
+  static_assert(kNoTile >= kTiles && (kNoTile / kTileCols) * kTileW >= kGrid, "kNoTile is off the grid");
+  auto uniform_u64 = [](unsigned long long a) { return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a); };
+  const unsigned long long tab_s = uniform_u64(tab_addr), a_s = uniform_u64(class_addr), t_s = uniform_u64(tiles_addr);
+  const unsigned long long yv_s = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(yv);
+  const unsigned long long cb_s = tab_s + tab::cbase + yv_s * (8ull * kCells), rk_s = tab_s + tab::crank + yv_s * (2ull * kCells);
+  const unsigned long long pb_s = tab_s + tab::pbase + yv_s * (8ull * kPcStride), rm_s = tab_s + tab::rmax + yv_s * (8ull * 64);
+  const unsigned long long uc_s = tab_s + tab::ucell + (yv_s % kMaxVariants) * (8ull * kCells);
+  const GlobalF64 gmax = (GlobalF64)t_s;
+  auto field_at = [&](int cell) { return __hip_atomic_load((GlobalF64)(a_s + (unsigned long long)((unsigned)cell * 8u)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  auto cb_at = [&](int cell) { return *(GlobalF64c)(cb_s + (unsigned long long)((unsigned)cell * 8u)); };
+  auto uc_at = [&](int cell) { return *(GlobalF64c)(uc_s + (unsigned long long)((unsigned)cell * 8u)); };
+  auto rk_at = [&](int cell) { return (int)*(const uint16_t __attribute__((address_space(1)))*)(rk_s + (unsigned long long)((unsigned)cell * 2u)); };
+  // the group boundaries of the sorted list (what place_heavy's stop rule reads), requested now, needed at the end
+  const double gb = lane >= 1 && lane < kGroups ? *(GlobalF64c)(pb_s + (unsigned long long)((unsigned)(lane * kGroup * kWave) * 8u)) : 0.0;
+  // 1. the bounds, and the two best tiles
+  const double bound = lane < kTiles ? *(GlobalF64c)(rm_s + (unsigned long long)((unsigned)lane * 8u)) * field_load(gmax + lane) : 0.0;
+  unsigned long long left = __ballot(bound > 0.0);      // tiles not evaluated yet that may hold a positive score
+  if (left == 0ull) return kSearchFallback;             // (place_heavy's M: below 1e-250)
+  const unsigned hb = (unsigned)__double2hiint(bound);
+  const unsigned h1 = wave_max_u32(hb);
+  int ta = __ffsll((long long)(left & __ballot(hb == h1))) - 1, tb = kNoTile;
+  {
+    const unsigned long long rest = left & ~(1ull << ta);
+    const unsigned h2 = wave_max_u32(lane == ta ? 0u : hb);
+    const unsigned long long second = rest & __ballot(hb == h2);
+    if (rest != 0ull) tb = __ffsll((long long)(second != 0ull ? second : rest)) - 1;
+  }
+  // 2. the tiles, two at a time: per lane the largest key (with its rank and cell) and the second largest
+  double lm = 0.0, l2 = 0.0;
+  int lrank = 0, lcell = -1;
+#ifdef EG_STAMPS
+  int tiles = 0;
+#endif
+  auto fold = [&](double v, int r, int c) {
+    const double key = __hiloint2double(__double2hiint(v), (__double2loint(v) & ~63) | (r >> 6));
+    const bool larger = key > lm;
+    l2 = vmax64(l2, vmin64(lm, key));      // (scores: not negative, finite)
+    lm = vmax64(lm, key);
+    lrank = larger ? r : lrank; lcell = larger ? c : lcell;
+  };
+#pragma nounroll
+  for (;;) {
+    left &= ~(1ull << ta) & ~(1ull << tb);
+    const int ia = (ta / kTileCols) * kTileW + (lane >> 3), ja = (ta % kTileCols) * kTileW + (lane & 7);
+    const int ib = (tb / kTileCols) * kTileW + (lane >> 3), jb = (tb % kTileCols) * kTileW + (lane & 7);
+    const bool ina = ia < kGrid && ja < kGrid, inb = ib < kGrid && jb < kGrid;
+    const int ca = ina ? ia * kGrid + ja : 0, cb = inb ? ib * kGrid + jb : 0;      // (a lane off the grid reads cell 0 and scores 0)
+    const double fa = field_at(ca), fb = field_at(cb), pa = cb_at(ca), pb = cb_at(cb), ua = uc_at(ca), ub = uc_at(cb);
+    const int ra = rk_at(ca), rb = rk_at(cb);
+    fold(ina ? pa * fa : 0.0, ra, ca);
+    fold(inb ? pb * fb : 0.0, rb, cb);
+    // the tiles' present maxima of u * field, rounded up within their high word: their g from now on
+    const unsigned gha = wave_max_u32(ina ? (unsigned)__double2hiint(ua * fa) : 0u), ghb = wave_max_u32(inb ? (unsigned)__double2hiint(ub * fb) : 0u);
+    if (lane == 0) {
+      gmax[ta] = __hiloint2double((int)gha, -1);
+      if (tb < kTiles) gmax[tb] = __hiloint2double((int)ghb, -1);
+    }
+#ifdef EG_STAMPS
+    tiles += tb < kTiles ? 2 : 1;
+#endif
+    const double m_lo = __hiloint2double((int)wave_max_u32((unsigned)__double2hiint(lm)), 0);      // (a lower bound of M)
+    left &= __ballot(bound >= m_lo * kKeepTile);
+    if (left == 0ull) break;
+    ta = __ffsll((long long)left) - 1;
+    const unsigned long long rest = left & (left - 1ull);
+    tb = rest != 0ull ? __ffsll((long long)rest) - 1 : kNoTile;
+  }
+  const double M = wave_max_f64(lm);
+  if (!(M >= 1e-250)) return kSearchFallback;      // (nothing placeable, or subnormal territory: the exact scan decides)
+#ifdef EG_STAMPS
+  const unsigned long long ts1 = __builtin_readcyclecounter();
+#endif
+  const double thr = M * kKeep;
+  if (__ballot(l2 >= thr) != 0ull) return kTilesUndecided;
+  // the chunks place_heavy's scan reads (see above)
+  const int gstar = (__double2loint(M) & 63) / kGroup;
+  const double m_hi = __hiloint2double(__double2hiint(M), 0);
+  const unsigned long long stops = __ballot(lane > gstar && lane < kGroups && !(gb >= m_hi * kKeep));
+  const int g_stop = stops != 0ull ? __ffsll((long long)stops) - 1 : kGroups;
+  const int K = kGroup * g_stop < kChunks ? kGroup * g_stop : kChunks;
+  // the candidates: the lanes' largest keys within 2^-30 of M, among the ranks the scan reads — their ranks in sm.gstage[1]
+  const unsigned long long m1 = __ballot(lm >= thr && lrank < K * kWave);
+  const int ncand = __popcll(m1);
+  if (ncand == 0) return kTilesUndecided;      // (M's own cell is one)
+  if (ncand > 1) {      // two in one lane of place_heavy's scan: its slow path
+    unsigned long long seen = 0ull;
+    for (unsigned long long m = m1; m != 0ull; m &= m - 1ull) {
+      const unsigned long long bit = 1ull << (__builtin_amdgcn_readlane(lrank, __ffsll((long long)m) - 1) & 63);
+      if (seen & bit) return kTilesUndecided;
+      seen |= bit;
+    }
+  }
+  if ((m1 >> lane) & 1ull) sm.gstage[1][__popcll(m1 & ((1ull << lane) - 1ull))] = lrank;
   wave_sync();
-  if (lane == 0) sm.hres[1].m03 = b.m03;
-  wave_sync();
-  // requested, in units of 2 KB: K chunks of the compact list (64 x 12 B each), K x 64 field entries of 8 B, and — only when several
-  // candidates tie — their full records (the field update that follows bills itself)
-  return b.cell | (((3 * K + 7) / 8 + (K + 3) / 4 + (ncand > 1 ? 1 : 0)) << 16);
+#ifdef EG_STAMPS
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const unsigned long long ts2 = __builtin_readcyclecounter();
+#endif
+  // 3. exact scores of the candidates, as place_heavy evaluates them
+  const unsigned long long list_addr = tab_s + tab::ps + yv_s * (sizeof(PsRec) * (unsigned long long)kPsStride);
+  const ChunkBest b = heavy_exact<false>(list_addr, tail_cells, size_factor, lane, rc, tbl, ngen_s, ncand, ncand == 1 ? __builtin_amdgcn_readlane(lcell, __ffsll((long long)m1) - 1) : -1);
+  if (!(b.score > 0.0)) return kSearchFallback;
+#ifdef EG_STAMPS
+  if (lane == 0) {
+    sm.hdbg[0][0] += ts1 - ts0; sm.hdbg[0][1] += ts2 - ts1; sm.hdbg[0][2] += __builtin_readcyclecounter() - ts2;
+    sm.hdbg[1][0] += (unsigned long long)K; sm.hdbg[1][1] += (unsigned long long)ncand; sm.hdbg[1][2] += 1ull; sm.hdbg[1][3] += (unsigned long long)tiles;
+  }
+#endif
+  return heavy_result(b, lane, K, ncand);
 }
 
 // The exact scan for a list that has outgrown the on-chip window (long-replay variant; reached when the field path cannot
@@ -1684,7 +1848,8 @@ struct EpisodeMap {
   unsigned long long hoist_seq;
   uint32_t stats_rep;         // 1: `stats` is kStatsReplicas copies of the statistics array (entry-major); this workgroup adds to copy (index % kStatsReplicas)
   // per-episode replay kernel (eg_replay_solo.h): word b carries solo_seq when k_replay_solo has completed workgroup b's episode — the
-  // long-replay variant, launched behind it, then has nothing to do for that episode (0 / null: no such kernel in this launch)
+  // long-replay variant, launched behind it, then has nothing to do for that episode (0 / null: no such kernel in this launch) —, and
+  // solo_seq << 21 | 1 << 20 | slot when it gave the episode up holding field slot `slot`: the long-replay variant runs it in that slot
   unsigned long long* solo;
   unsigned long long solo_seq;
 };
@@ -1799,6 +1964,10 @@ __global__ void __launch_bounds__(kWave * (1 + kHelpers), kKind == kReplayLong ?
 
   Episode ep;
   ep.ngen = 0; ep.noff = 0; ep.run_pos = 0; ep.def_pos = 0; ep.act_pos = 0; ep.status = EG_EP_OK; ep.bytes = 32ull; ep.chunks = 0; ep.heavy = -1; ep.heavy_classes = 0; ep.heavy_quads = 0;
+  if constexpr (kHeavy) if (emap.solo_seq != 0ull) {      // k_replay_solo gave this episode up after it had claimed a field slot: the same slot
+    const unsigned long long w = emap.solo[blockIdx.x];
+    if ((w >> 21) == emap.solo_seq && ((w >> 20) & 1ull)) ep.heavy = (int)(w & 0xFFFFFull);
+  }
   uint8_t* run_log = O.run_log(e);
   uint8_t* def_log = O.def_log(e);
   uint8_t* act_log = O.act_log(e);

@@ -34,5 +34,7 @@ for name, col, per in (("set-up", 0, 1), ("script", 1, 1), ("placements: list en
     print(f"  {name:40s} {st[:, col].mean():12.0f} cycles {100 * st[:, col].mean() / tot:5.1f} %   ({st[:, col].mean() / per:.0f} each)")
 if full[:, 13].mean() > 0:      # built with -DEG_STAMPS as well: place_heavy's own counters
     n = full[:, 13].mean()
-    print(f"  place_heavy: {n:.0f} searches per episode: scan {full[:, 8].mean() / n:.0f} cycles, candidates {full[:, 9].mean() / n:.0f}, exact evaluation + rest {full[:, 10].mean() / n:.0f}; "
+    print(f"  place_heavy / place_tiles: {n:.0f} searches per episode: scan / tiles {full[:, 8].mean() / n:.0f} cycles, candidates {full[:, 9].mean() / n:.0f}, exact evaluation + rest {full[:, 10].mean() / n:.0f}; "
           f"chunks scanned per search {full[:, 11].mean() / n:.1f}, candidates {full[:, 12].mean() / n:.2f}")
+    if full[:, 14].mean() > 0:      # place_tiles (EIRGRID_SOLO_TILES=1, the default): tiles evaluated
+        print(f"  place_tiles: tiles evaluated per search {full[:, 14].mean() / n:.2f} (the searches that place_heavy decided count as none)")
