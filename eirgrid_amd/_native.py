@@ -11,6 +11,7 @@ import os
 YEARS, N_ACTIONS, N_DEFICIT, N_COUNTS, N_TYPES = 26, 61, 15, 21, 15
 GRID, CELLS, YEARLY_FIELDS = 51, 2601, 21
 MAX_GENS, MAX_OFFSETS, RUN_CAP, DEF_CAP, ACT_CAP, ONCHIP_GENS = 4096, 4096, 4096, 4096, 4096, 512
+TOPK_MAX = 64      # EG_TOPK_MAX: entries a top-K archive holds at most
 STATS_LEN = 8 + 2 * YEARS * N_ACTIONS + YEARS * N_DEFICIT
 CANDIDATE_BYTES = 8 + 8 + 32 + 4 * YEARS + 4 * YEARS + RUN_CAP + DEF_CAP
 PACKET_BYTES = 8 * STATS_LEN + CANDIDATE_BYTES
@@ -62,7 +63,8 @@ EXPORTS = [
     "eg_fetch_episode_lists", "eg_fetch_record", "eg_fetch_best_run", "eg_best_result_track", "eg_fetch_best_result", "eg_evaluate_action_impact", "eg_place", "eg_find_suitable_location", "eg_debug_fill_lds", "eg_debug_occupy", "eg_policy_apply_reduced", "eg_policy_apply_packet", "eg_train_step",
     "eg_policy_push", "eg_device_rollout", "eg_device_apply", "eg_device_step", "eg_policy_pull",
     "eg_group_create", "eg_group_destroy", "eg_group_rank", "eg_group_push", "eg_group_step", "eg_group_pull", "eg_group_replay_hoist",
-    "eg_group_best_result_track", "eg_group_fetch_best_result",
+    "eg_group_best_result_track", "eg_group_fetch_best_result", "eg_top_k_track", "eg_fetch_top_k", "eg_rank_score",
+    "eg_group_top_k_track", "eg_group_fetch_top_k",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -191,6 +193,16 @@ def lib():
     L.eg_best_result_track.argtypes = [C.c_void_p, C.c_int32]
     L.eg_fetch_best_result.restype = C.c_int32
     L.eg_fetch_best_result.argtypes = [C.c_void_p, C.POINTER(EgEpisodeOut), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.eg_top_k_track.restype = C.c_int32
+    L.eg_top_k_track.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    L.eg_fetch_top_k.restype = C.c_int32
+    L.eg_fetch_top_k.argtypes = [C.c_void_p, C.POINTER(EgEpisodeOut), C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int64)]
+    L.eg_group_top_k_track.restype = C.c_int32
+    L.eg_group_top_k_track.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+    L.eg_group_fetch_top_k.restype = C.c_int32
+    L.eg_group_fetch_top_k.argtypes = [C.c_void_p, C.POINTER(EgEpisodeOut), C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int64)]
+    L.eg_rank_score.restype = C.c_double
+    L.eg_rank_score.argtypes = [_dp, C.c_int32]
     L.eg_evaluate_action_impact.restype = C.c_double
     L.eg_evaluate_action_impact.argtypes = [_dp, _dp, C.c_int32]
     L.eg_fetch_best_run.restype = C.c_int32

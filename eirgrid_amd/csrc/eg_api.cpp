@@ -63,6 +63,10 @@ struct eg_ctx {
   // the reference's best_result fold (multi_simulation.rs:613-620): 0 = not tracked, 1 = optimization_mode None, 2 = cost_only
   int fold_mode = 0; uint8_t* d_fold = nullptr;
   bool group_member = false;      // owned by an eg_group: the group folds its ranks' results (eg_group_best_result_track), never the context itself
+  // the top-K archive of distinct scenarios (eg_top_k_track; eg_topk.h): 0 = not tracked, 1 = mode None, 2 = cost_only; d_topk: TopKState
+  // and the record slots; per batch, the rank score and key of every episode and one block per chunk (also a group rank's scratch)
+  int topk_mode = 0, topk_k = 0; uint8_t* d_topk = nullptr;
+  double* d_tk_score = nullptr; unsigned long long* d_tk_key = nullptr; TopKBlock* d_tk_blocks = nullptr; uint32_t tk_cap = 0;
   // Is the best list long (the replay episodes run the heavy-capable variant and are the batch's long pole)?  `list_exact`: the host
   // KNOWS the list the next launch will find on the device (it uploaded, rewound or pulled it and no on-device update has been
   // enqueued since): the replay variant that has nothing to do is then not launched at all.  Otherwise the device may have replaced
@@ -211,6 +215,26 @@ int prepare_heavy(eg_ctx* c, uint32_t n_heavy, bool known_short) {
   c->dev.heavy_epoch = c->launch_epoch;
   return EG_OK;
 }
+// The top-K fold's first two steps over the n results of the last batch in c->out (global indices first_index..): rank scores and keys
+// against the archive at d_state, then every chunk's top-k distinct entries into c->d_tk_blocks (ceil(n / kTopKChunk) blocks).
+int topk_select(eg_ctx* c, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state, int k) {
+  if (n > c->tk_cap) {      // (grown like the records: hipFree waits for the launches that may still use the old buffers)
+    if (c->d_tk_score) (void)hipFree(c->d_tk_score);
+    if (c->d_tk_key) (void)hipFree(c->d_tk_key);
+    if (c->d_tk_blocks) (void)hipFree(c->d_tk_blocks);
+    c->d_tk_score = nullptr; c->d_tk_key = nullptr; c->d_tk_blocks = nullptr; c->tk_cap = 0;
+    EG_HIP(hipMalloc((void**)&c->d_tk_score, sizeof(double) * n));
+    EG_HIP(hipMalloc((void**)&c->d_tk_key, sizeof(unsigned long long) * n));
+    EG_HIP(hipMalloc((void**)&c->d_tk_blocks, sizeof(TopKBlock) * ((n + kTopKChunk - 1u) / kTopKChunk)));
+    c->tk_cap = n;
+  }
+  int lr = launch_topk_keys(c->out, n, first_index, mode, use_score_list, d_state, c->d_tk_score, c->d_tk_key, nullptr);
+  if (lr == 0) lr = launch_topk_select(c->out, n, first_index, c->d_tk_score, c->d_tk_key, k, c->d_tk_blocks, nullptr);
+  if (lr != 0) { set_error(std::string("k_topk_keys / k_topk_select launch: ") + hipGetErrorString((hipError_t)lr)); return EG_ERR_HIP; }
+  return EG_OK;
+}
+uint32_t topk_chunks(uint32_t n) { return (n + kTopKChunk - 1u) / kTopKChunk; }
+
 // One batch = up to three grids of k_rollout (eg_internal.h RolloutPlan): the episodes that replay the best strategy on the
 // two replay variants (one of which returns at once), the others on the lean one, on two streams side by side.  `host_mask` (n bytes, may be NULL):
 // which episodes replay; otherwise `period` (0: none): episode i replays when (first_index + i) % period == 0.
@@ -309,6 +333,13 @@ int launch_batch(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, con
   if (c->fold_mode != 0) {      // behind the batch on the null stream: its results are in iteration order in the records
     const int fr = launch_fold_best(c->out, n, first_index, c->fold_mode == 2, c->d_fold, nullptr);
     if (fr != 0) { set_error(std::string("k_fold_best launch: ") + hipGetErrorString((hipError_t)fr)); return EG_ERR_HIP; }
+  }
+  if (c->topk_mode != 0) {      // the top-K archive, behind the batch as well (the epilogue's scores are the rank scores in mode 1)
+    rc = topk_select(c, n, first_index, c->topk_mode, d_stats != nullptr && c->topk_mode == 1, c->d_topk, c->topk_k);
+    if (rc != EG_OK) return rc;
+    const int mr = launch_topk_merge(c->d_topk, reinterpret_cast<const uint8_t*>(c->d_tk_blocks), int(topk_chunks(n)), sizeof(TopKBlock), nullptr,
+                                     c->topk_k, c->out, first_index, n, 0u, nullptr);
+    if (mr != 0) { set_error(std::string("k_topk_merge launch: ") + hipGetErrorString((hipError_t)mr)); return EG_ERR_HIP; }
   }
   c->ev_used[slot] = uint8_t((plan.n_heavy > 0 ? 1 : 0) | (plan.n_lean > 0 ? 2 : 0));
   c->ring_head = (c->ring_head + 1) % eg_ctx::kTimingRing; c->ring_pending += 1;
@@ -561,6 +592,10 @@ void eg_destroy(eg_ctx* c) {
   if (c->d_snap) (void)hipFree(c->d_snap);
   if (c->d_snap_held) (void)hipFree(c->d_snap_held);
   if (c->d_fold) (void)hipFree(c->d_fold);
+  if (c->d_topk) (void)hipFree(c->d_topk);
+  if (c->d_tk_score) (void)hipFree(c->d_tk_score);
+  if (c->d_tk_key) (void)hipFree(c->d_tk_key);
+  if (c->d_tk_blocks) (void)hipFree(c->d_tk_blocks);
   if (c->d_hoist) (void)hipFree(c->d_hoist);
   if (c->d_stats_rep) (void)hipFree(c->d_stats_rep);
   if (c->d_solo) (void)hipFree(c->d_solo);
@@ -846,6 +881,64 @@ int32_t eg_fetch_best_result(eg_ctx* c, eg_episode_out* o, int32_t* state, int64
   if (!st.has) return EG_OK;
   return fetch_records(c->d_fold + kFoldRecord, 1, o);
 }
+
+namespace {
+// row r of a caller's episode-major buffers
+eg_episode_out out_row(const eg_episode_out* o, size_t r) {
+  eg_episode_out x = *o;
+#define EG_ROW(field, count) if (x.field) x.field += r * size_t(count)
+  EG_ROW(metrics, 4); EG_ROW(yearly, EG_YEARS * EG_YEARLY_FIELDS); EG_ROW(status, 1); EG_ROW(n_run, EG_YEARS); EG_ROW(n_def, EG_YEARS);
+  EG_ROW(n_act, EG_YEARS); EG_ROW(run_log, EG_RUN_CAP); EG_ROW(def_log, EG_DEF_CAP); EG_ROW(act_log, EG_ACT_CAP); EG_ROW(n_gens, 1);
+  EG_ROW(gen_cell, EG_MAX_GENS); EG_ROW(gen_pack, EG_MAX_GENS); EG_ROW(n_offsets, 1); EG_ROW(off_pack, EG_MAX_OFFSETS); EG_ROW(n_draws, 1);
+  EG_ROW(bytes_moved, 1); EG_ROW(n_chunks, 1);
+#undef EG_ROW
+  return x;
+}
+// a fresh archive of k entries (mode 1 / 2), stream-ordered behind everything enqueued before
+int topk_reset(uint8_t* d_state, int k, int mode) {
+  static_assert(sizeof(TopKState) <= kTopKRecords, "top-k state layout");
+  TopKState st{};
+  st.k = k; st.mode = mode;
+  EG_HIP(hipMemcpy(d_state, &st, sizeof(st), hipMemcpyHostToDevice));
+  return EG_OK;
+}
+}  // namespace
+
+int32_t eg_top_k_track(eg_ctx* c, int32_t k, int32_t mode) {
+  if (!c || mode < 0 || mode > 2 || (mode != 0 && (k < 1 || k > EG_TOPK_MAX))) { set_error("eg_top_k_track: bad argument (1 <= k <= EG_TOPK_MAX, mode 0..2)"); return EG_ERR_BAD_ARG; }
+  if (c->group_member && mode != 0) { set_error("eg_top_k_track: the context is a rank of an eg_group (use eg_group_top_k_track)"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  if (mode != 0) {
+    if (!c->d_topk) EG_HIP(hipMalloc((void**)&c->d_topk, kTopKBytes));
+    const int rc = topk_reset(c->d_topk, k, mode);
+    if (rc != EG_OK) return rc;
+    c->topk_k = k;
+  }
+  c->topk_mode = mode;
+  return EG_OK;
+}
+
+int32_t eg_fetch_top_k(eg_ctx* c, eg_episode_out* o, int32_t* n_held, double* scores, int64_t* global_index) {
+  if (!c || !o || !n_held) { set_error("eg_fetch_top_k: bad argument"); return EG_ERR_BAD_ARG; }
+  if (!c->d_topk) { set_error("eg_fetch_top_k: eg_top_k_track first"); return EG_ERR_BAD_ARG; }
+  int rc = eg_sync(c);
+  if (rc != EG_OK) return rc;
+  TopKState st{};
+  EG_HIP(hipMemcpy(&st, c->d_topk, sizeof(st), hipMemcpyDeviceToHost));
+  if (st.n_held < 0 || st.n_held > st.k || st.k > EG_TOPK_MAX) { set_error("eg_fetch_top_k: the archive's state is corrupt"); return EG_ERR_INTERNAL; }
+  *n_held = st.n_held;
+  for (int r = 0; r < st.n_held; ++r) {
+    if (scores) scores[r] = st.e[r].score;
+    if (global_index) global_index[r] = st.e[r].index;
+    if (st.e[r].slot < 0 || st.e[r].slot >= st.k) { set_error("eg_fetch_top_k: the archive's state is corrupt"); return EG_ERR_INTERNAL; }
+    eg_episode_out row = out_row(o, size_t(r));
+    rc = fetch_records(c->d_topk + kTopKRecords + size_t(st.e[r].slot) * rec::stride, 1, &row);
+    if (rc != EG_OK) return rc;
+  }
+  return EG_OK;
+}
+
+double eg_rank_score(const double m[4], int32_t mode) { return m ? rm::rank_score(m, mode) : std::nan(""); }
 
 namespace { int ensure_packet(eg_ctx* c); }
 int32_t eg_train_step(eg_ctx* c, eg_policy* p, const eg_opts* o, uint64_t seed, uint64_t first_index, uint32_t n,
@@ -1168,7 +1261,8 @@ int32_t eg_find_suitable_location(eg_ctx* c, int32_t year_index, int32_t gen_typ
 
 // ---- eg_group: N ranks, one context each, driven from one host thread --------------------------------------------------
 // A step shards the global batch (parallel.shard_range), runs every rank's shard, exchanges one message per rank — its update
-// packet, followed by its fold block when the best_result fold is tracked — into every rank's gathered buffer, and applies the N
+// packet, followed by its fold block when the best_result fold is tracked and, at the fixed offset topk_off behind the fold block's
+// room, its top-K block when the top-K archive is — into every rank's gathered buffer, and applies the N
 // packets on every rank (the statistics are integer sums, the candidate choice is order-free: every rank makes the same update).
 // Nothing synchronises the host inside a step; the order comes from events, on the legacy null stream of each rank's device:
 //   ev_sent[r]  recorded by rank r behind its rollout and its message (fold block / empty-shard packet);
@@ -1183,11 +1277,13 @@ struct eg_group {
   int n = 0;
   std::vector<eg_ctx*> ctx;
   std::vector<int> device;
-  // rank r's message (update packet, then FoldEntry[cap]) and its gathered buffer (n slots of `stride` bytes, rank order)
+  // rank r's message (update packet, then FoldEntry[cap], then a TopKBlock at topk_off) and its gathered buffer (n slots of `stride`
+  // bytes, rank order)
   std::vector<uint8_t*> d_send, d_gather;
-  size_t stride = 0; uint32_t cap = 0;
+  size_t stride = 0, topk_off = 0; uint32_t cap = 0;
   std::vector<hipEvent_t> ev_sent, ev_recv;
   int fold_mode = 0; std::vector<uint8_t*> d_fold;      // GroupFoldState + the record, per rank
+  int topk_mode = 0, topk_k = 0; std::vector<uint8_t*> d_topk;      // the top-K archive per rank: replicated state, the records this rank ran
   uint32_t step = 0;         // steps run: the tag of a take-over
   bool pushed = false;
 };
@@ -1217,7 +1313,8 @@ int group_buffers(eg_group* g, uint32_t cap) {
   int rc = group_sync(g);
   if (rc != EG_OK) return rc;
   group_free_buffers(g);
-  const size_t stride = (size_t(EG_PACKET_BYTES) + sizeof(FoldEntry) * cap + 255) & ~size_t(255);
+  const size_t topk_off = (size_t(EG_PACKET_BYTES) + sizeof(FoldEntry) * cap + 255) & ~size_t(255);
+  const size_t stride = (topk_off + sizeof(TopKBlock) + 255) & ~size_t(255);
   for (int r = 0; r < g->n; ++r) {
     EG_HIP(hipSetDevice(g->device[r]));
     EG_HIP(hipMalloc((void**)&g->d_send[r], stride));
@@ -1225,7 +1322,7 @@ int group_buffers(eg_group* g, uint32_t cap) {
     EG_HIP(hipMemset(g->d_send[r], 0, stride));      // the rollout epilogue ADDS to the statistics
     EG_HIP(hipMemset(g->d_gather[r], 0, stride * size_t(g->n)));
   }
-  g->cap = cap; g->stride = stride;
+  g->cap = cap; g->stride = stride; g->topk_off = topk_off;
   return EG_OK;
 }
 }  // namespace
@@ -1239,6 +1336,7 @@ eg_group* eg_group_create(const int32_t* devices, int32_t n_ranks, const eg_worl
   g->n = n_ranks;
   g->device.assign(devices, devices + n_ranks);
   g->ctx.assign(n_ranks, nullptr); g->d_send.assign(n_ranks, nullptr); g->d_gather.assign(n_ranks, nullptr); g->d_fold.assign(n_ranks, nullptr);
+  g->d_topk.assign(n_ranks, nullptr);
   g->ev_sent.assign(n_ranks, nullptr); g->ev_recv.assign(n_ranks, nullptr);
   bool ok = true;
   for (int r = 0; r < n_ranks && ok; ++r) {
@@ -1268,6 +1366,7 @@ void eg_group_destroy(eg_group* g) {
   for (int r = 0; r < g->n; ++r) {
     (void)hipSetDevice(g->device[r]);
     if (g->d_fold[r]) (void)hipFree(g->d_fold[r]);
+    if (g->d_topk[r]) (void)hipFree(g->d_topk[r]);
     if (g->ev_sent[r]) (void)hipEventDestroy(g->ev_sent[r]);
     if (g->ev_recv[r]) (void)hipEventDestroy(g->ev_recv[r]);
     eg_destroy(g->ctx[r]);
@@ -1316,11 +1415,26 @@ int32_t eg_group_best_result_track(eg_group* g, int32_t mode) {
   return EG_OK;
 }
 
+int32_t eg_group_top_k_track(eg_group* g, int32_t k, int32_t mode) {
+  if (!g || mode < 0 || mode > 2 || (mode != 0 && (k < 1 || k > EG_TOPK_MAX))) { set_error("eg_group_top_k_track: bad argument (1 <= k <= EG_TOPK_MAX, mode 0..2)"); return EG_ERR_BAD_ARG; }
+  if (mode != 0) {
+    for (int r = 0; r < g->n; ++r) {
+      EG_HIP(hipSetDevice(g->device[r]));
+      if (!g->d_topk[r]) EG_HIP(hipMalloc((void**)&g->d_topk[r], kTopKBytes));
+      const int rc = topk_reset(g->d_topk[r], k, mode);      // (no slot tagged: steps count from 1)
+      if (rc != EG_OK) return rc;
+    }
+    g->topk_k = k;
+  }
+  g->topk_mode = mode;
+  return EG_OK;
+}
+
 int32_t eg_group_step(eg_group* g, uint64_t seed, uint64_t first_index, uint32_t n_global, uint32_t replay_period, uint64_t noise_seed) {
   if (!g || !g->pushed) { set_error("eg_group_step: push a policy first (eg_group_push)"); return EG_ERR_BAD_ARG; }
   if (n_global == 0) return EG_OK;
   const int N = g->n;
-  const bool fold = g->fold_mode != 0;
+  const bool fold = g->fold_mode != 0, topk = g->topk_mode != 0;
   int rc = group_buffers(g, n_global / uint32_t(N) + (n_global % uint32_t(N) ? 1u : 0u));
   if (rc != EG_OK) return rc;
   g->step += 1;
@@ -1336,6 +1450,12 @@ int32_t eg_group_step(eg_group* g, uint64_t seed, uint64_t first_index, uint32_t
       const int lr = launch_fold_pack(c->out, n, g->d_send[r], reinterpret_cast<FoldEntry*>(g->d_send[r] + EG_PACKET_BYTES), nullptr);
       if (lr != 0) { set_error(std::string("k_fold_pack launch: ") + hipGetErrorString((hipError_t)lr)); return EG_ERR_HIP; }
     }
+    if (topk) {      // the shard's own top-k distinct entries (against this rank's replica of the archive); an empty shard: none
+      if (n > 0) { rc = topk_select(c, n, first_index + first, g->topk_mode, g->topk_mode == 1, g->d_topk[r], g->topk_k); if (rc != EG_OK) return rc; }
+      const int lr = launch_topk_merge(nullptr, reinterpret_cast<const uint8_t*>(c->d_tk_blocks), n > 0 ? int(topk_chunks(n)) : 0, sizeof(TopKBlock),
+                                       reinterpret_cast<TopKBlock*>(g->d_send[r] + g->topk_off), g->topk_k, c->out, 0, 0, 0u, nullptr);
+      if (lr != 0) { set_error(std::string("k_topk_merge launch: ") + hipGetErrorString((hipError_t)lr)); return EG_ERR_HIP; }
+    }
     EG_HIP(hipEventRecord(g->ev_sent[r], nullptr));
   }
   // 2. every rank receives every message into slot r of its gathered buffer (read after write: each copy waits for its sender)
@@ -1349,6 +1469,11 @@ int32_t eg_group_step(eg_group* g, uint64_t seed, uint64_t first_index, uint32_t
       EG_HIP(hipStreamWaitEvent(nullptr, g->ev_sent[r], 0));
       if (g->device[r] == g->device[q]) EG_HIP(hipMemcpyAsync(dst, g->d_send[r], bytes, hipMemcpyDeviceToDevice, nullptr));
       else EG_HIP(hipMemcpyPeerAsync(dst, g->device[q], g->d_send[r], g->device[r], bytes, nullptr));
+      if (topk) {
+        uint8_t* tdst = dst + g->topk_off; const uint8_t* tsrc = g->d_send[r] + g->topk_off;
+        if (g->device[r] == g->device[q]) EG_HIP(hipMemcpyAsync(tdst, tsrc, sizeof(TopKBlock), hipMemcpyDeviceToDevice, nullptr));
+        else EG_HIP(hipMemcpyPeerAsync(tdst, g->device[q], tsrc, g->device[r], sizeof(TopKBlock), nullptr));
+      }
     }
     EG_HIP(hipEventRecord(g->ev_recv[q], nullptr));
   }
@@ -1365,6 +1490,13 @@ int32_t eg_group_step(eg_group* g, uint64_t seed, uint64_t first_index, uint32_t
       const int lr = launch_fold_gathered(g->d_gather[r], g->stride, N, n_global, first_index, c->out, first, n, g->fold_mode == 2, g->step,
                                           g->d_fold[r], nullptr);
       if (lr != 0) { set_error(std::string("k_fold_gathered launch: ") + hipGetErrorString((hipError_t)lr)); return EG_ERR_HIP; }
+    }
+    if (topk) {      // the N blocks into this rank's replica; the records of new entries its own shard ran are copied and tagged here
+      uint32_t first = 0, n = 0;
+      shard(n_global, r, N, first, n);
+      const int lr = launch_topk_merge(g->d_topk[r], g->d_gather[r] + g->topk_off, N, g->stride, nullptr, g->topk_k, c->out, first_index + first, n,
+                                       g->step, nullptr);
+      if (lr != 0) { set_error(std::string("k_topk_merge launch: ") + hipGetErrorString((hipError_t)lr)); return EG_ERR_HIP; }
     }
   }
   return EG_OK;
@@ -1392,6 +1524,40 @@ int32_t eg_group_fetch_best_result(eg_group* g, eg_episode_out* o, int32_t* stat
     }
   set_error("eg_group_fetch_best_result: no rank holds the record of the held run");
   return EG_ERR_INTERNAL;
+}
+
+int32_t eg_group_fetch_top_k(eg_group* g, eg_episode_out* o, int32_t* n_held, double* scores, int64_t* global_index) {
+  if (!g || !o || !n_held) { set_error("eg_group_fetch_top_k: bad argument"); return EG_ERR_BAD_ARG; }
+  if (!g->d_topk[0]) { set_error("eg_group_fetch_top_k: eg_group_top_k_track first"); return EG_ERR_BAD_ARG; }
+  int rc = group_sync(g);
+  if (rc != EG_OK) return rc;
+  std::vector<TopKState> st(g->n);
+  for (int r = 0; r < g->n; ++r) {
+    EG_HIP(hipSetDevice(g->device[r]));
+    EG_HIP(hipMemcpy(&st[r], g->d_topk[r], sizeof(TopKState), hipMemcpyDeviceToHost));
+    if (st[r].n_held != st[0].n_held || st[r].k != st[0].k ||
+        std::memcmp(st[r].e, st[0].e, sizeof(TopKEntry) * size_t(std::max(0, std::min(st[0].n_held, EG_TOPK_MAX)))) != 0) {
+      set_error("eg_group_fetch_top_k: the ranks' archives differ"); return EG_ERR_INTERNAL;
+    }
+  }
+  const TopKState& s0 = st[0];
+  if (s0.n_held < 0 || s0.n_held > s0.k || s0.k > EG_TOPK_MAX) { set_error("eg_group_fetch_top_k: the archive's state is corrupt"); return EG_ERR_INTERNAL; }
+  *n_held = s0.n_held;
+  for (int i = 0; i < s0.n_held; ++i) {
+    const TopKEntry& e = s0.e[i];
+    if (e.slot < 0 || e.slot >= s0.k) { set_error("eg_group_fetch_top_k: the archive's state is corrupt"); return EG_ERR_INTERNAL; }
+    if (scores) scores[i] = e.score;
+    if (global_index) global_index[i] = e.index;
+    int owner = -1;
+    for (int r = 0; r < g->n && owner < 0; ++r)
+      if (st[r].tag_index[e.slot] == e.index && st[r].tag_step[e.slot] == e.step) owner = r;
+    if (owner < 0) { set_error("eg_group_fetch_top_k: no rank holds the record of entry " + std::to_string(i)); return EG_ERR_INTERNAL; }
+    EG_HIP(hipSetDevice(g->device[owner]));
+    eg_episode_out row = out_row(o, size_t(i));
+    rc = fetch_records(g->d_topk[owner] + kTopKRecords + size_t(e.slot) * rec::stride, 1, &row);
+    if (rc != EG_OK) return rc;
+  }
+  return EG_OK;
 }
 
 }  // extern "C"

@@ -47,6 +47,7 @@ struct Args {   // cli/cli.rs:5-59
   bool replay_hoist = true;     // the replay iterations of a batch computed once (eg_replay_hoist): the same results, the replay phases 5x faster
   // --gpus N / --devices LIST: the ranks of a multi-GPU run (eg_group), one device each; empty: the single-device run on --device
   std::vector<int32_t> ranks; bool device_given = false, gpus_given = false;
+  int32_t top_k = 0;            // --top-k K: keep the K best distinct scenarios of the run (eg_top_k_track) and export them; 0: off
 };
 
 void usage() {
@@ -67,7 +68,9 @@ void usage() {
             "      --stop-after <N>     stop like an interrupted run once N iterations are done and checkpointed (resume tests)\n"
             "      --dump-world <FILE>  write the world as loaded (the --world JSON form) and exit; needs no GPU\n"
             "      --no-replay-hoist    run every replay iteration of a batch on its own (default: the replay iterations of a batch —\n"
-            "                           one and the same computation — are computed once; identical results either way)");
+            "                           one and the same computation — are computed once; identical results either way)\n"
+            "      --top-k <K>          keep the K best distinct scenarios of the run (0..64, ranked by score_metrics in the run's mode)\n"
+            "                           and write them to enhanced_csv/<stamp>/top_k/ [default: 0 = off]");
 }
 
 bool parse(int argc, char** argv, Args& a) {
@@ -126,6 +129,14 @@ bool parse(int argc, char** argv, Args& a) {
     else if (s == "--stop-after") a.stop_after = std::strtoull(v().c_str(), nullptr, 10);
     else if (s == "--dump-world") a.dump_world = v();
     else if (s == "--no-replay-hoist") a.replay_hoist = false;
+    else if (s == "--top-k") {
+      const std::string k = v();
+      if (k.empty() || k.size() > 3 || k.find_first_not_of("0123456789") != std::string::npos || std::atoi(k.c_str()) > EG_TOPK_MAX) {
+        std::fprintf(stderr, "error: --top-k needs a number from 0 to %d, got '%s'\n", EG_TOPK_MAX, k.c_str());
+        return false;
+      }
+      a.top_k = std::atoi(k.c_str());
+    }
     else if (s == "-h" || s == "--help") { usage(); std::exit(0); }
     else { std::fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage(); return false; }
   }
@@ -342,6 +353,8 @@ int main(int argc, char** argv) {
   // host copy is refreshed (eg_policy_pull) when a checkpoint or a progress line needs it
   if (reduced) CHECK(group ? eg_group_push(group, policy, &opts) : eg_policy_push(ctx, policy, &opts));
   CHECK(group ? eg_group_best_result_track(group, a.cost_only ? 2 : 1) : eg_best_result_track(ctx, a.cost_only ? 2 : 1));
+  // --top-k: the K best distinct scenarios of this process's iterations, ranked in the run's mode, kept on the device behind every batch
+  if (a.top_k > 0) CHECK(group ? eg_group_top_k_track(group, a.top_k, a.cost_only ? 2 : 1) : eg_top_k_track(ctx, a.top_k, a.cost_only ? 2 : 1));
   const uint64_t full_from = a.iterations - std::min(a.iterations, final_full);   // multi_simulation.rs:437-465
   while (done < a.iterations) {
     uint32_t n = uint32_t(std::min<uint64_t>(a.batch, a.iterations - done));
@@ -405,13 +418,13 @@ int main(int argc, char** argv) {
   }
   CHECK(eg_policy_save_json(policy, (run_dir + "/best_weights.json").c_str()));   // multi_simulation.rs:1160-1164
   char stamp[32]; std::string dir;
-  if (a.enable_csv_export) {   // multi_simulation.rs:852-859, :912-921; csv_export.rs:114-127 (directory named after the time of export)
+  if (a.enable_csv_export || a.top_k > 0) {   // multi_simulation.rs:852-859, :912-921; csv_export.rs:114-127 (directory named after the time of export)
     std::time_t t = std::time(nullptr); std::tm tmv; localtime_r(&t, &tmv);
     std::strftime(stamp, sizeof(stamp), "%Y%m%d_%H%M%S", &tmv);
     dir = run_dir + "/enhanced_csv/" + stamp;
     mkdirs(dir);
-    CHECK(eg_policy_export_improvement_csv(policy, (dir + "/improvement_history.csv").c_str()));
   }
+  if (a.enable_csv_export) CHECK(eg_policy_export_improvement_csv(policy, (dir + "/improvement_history.csv").c_str()));
   int64_t best_index = -1;
   { int32_t state = 0; CHECK(group ? eg_group_fetch_best_result(group, &best_run.view, &state, &best_index) : eg_fetch_best_result(ctx, &best_run.view, &state, &best_index));
     best_run.valid = state == 1; }
@@ -428,6 +441,38 @@ int main(int argc, char** argv) {
       for (const std::string& n : wd.names) names.push_back(n.c_str());
       CHECK(eg_export_run_details(&world, names.size() == wd.sx.size() ? names.data() : nullptr, &best_run.view, dir.c_str(), a.seed));
     } else std::puts("note: no iteration finished in this run; simulation_summary.csv and the detail files not written");
+  }
+  if (a.top_k > 0) {      // top_k/index.csv: rank, score, iteration, metrics; with the CSV export one directory per entry, like the best run's
+    const size_t K = size_t(a.top_k);
+    std::vector<double> metrics_k(K * 4), yearly_k(K * EG_YEARS * EG_YEARLY_FIELDS), score_k(K);
+    std::vector<int32_t> n_act_k(K * EG_YEARS), n_gens_k(K); std::vector<uint8_t> act_k(K * EG_ACT_CAP); std::vector<uint16_t> pack_k(K * EG_MAX_GENS);
+    std::vector<int64_t> index_k(K);
+    eg_episode_out out{}; out.metrics = metrics_k.data(); out.yearly = yearly_k.data(); out.n_act = n_act_k.data(); out.act_log = act_k.data();
+    out.n_gens = n_gens_k.data(); out.gen_pack = pack_k.data();
+    int32_t held = 0;
+    CHECK(group ? eg_group_fetch_top_k(group, &out, &held, score_k.data(), index_k.data()) : eg_fetch_top_k(ctx, &out, &held, score_k.data(), index_k.data()));
+    const std::string tk = dir + "/top_k";
+    mkdirs(tk);
+    std::ofstream f(tk + "/index.csv");
+    f << "rank,score,iteration,final_net_emissions,average_public_opinion,total_cost,power_reliability\n";
+    std::vector<const char*> names;
+    for (const std::string& n : wd.names) names.push_back(n.c_str());
+    for (int32_t r = 0; r < held; ++r) {
+      char line[512]; const double* m = &metrics_k[size_t(r) * 4];
+      std::snprintf(line, sizeof(line), "%d,%.17g,%lld,%.17g,%.17g,%.17g,%.17g\n", r + 1, score_k[size_t(r)], (long long)index_k[size_t(r)], m[0], m[1], m[2], m[3]);
+      f << line;
+      if (!a.enable_csv_export) continue;
+      char sub[16]; std::snprintf(sub, sizeof(sub), "/%02d", r + 1);
+      const std::string ed = tk + sub;
+      mkdirs(ed);
+      eg_episode_out one{}; one.metrics = &metrics_k[size_t(r) * 4]; one.yearly = &yearly_k[size_t(r) * EG_YEARS * EG_YEARLY_FIELDS];
+      one.n_act = &n_act_k[size_t(r) * EG_YEARS]; one.act_log = &act_k[size_t(r) * EG_ACT_CAP]; one.n_gens = &n_gens_k[size_t(r)];
+      one.gen_pack = &pack_k[size_t(r) * EG_MAX_GENS];
+      CHECK(eg_export_summary_csv(&one, (ed + "/simulation_summary.csv").c_str(), stamp));
+      CHECK(eg_export_run_details(&world, names.size() == wd.sx.size() ? names.data() : nullptr, &one, ed.c_str(), a.seed));
+    }
+    if (!f) { std::fprintf(stderr, "error: cannot write %s/index.csv\n", tk.c_str()); return 1; }
+    std::printf("Top %d distinct scenarios (%d held) written to %s\n", a.top_k, held, tk.c_str());
   }
   std::printf("Done: %llu iterations in %s (%u episodes failed); best_weights.json, latest_weights.json, checkpoint_iteration.txt written\n",
               (unsigned long long)done, run_dir.c_str(), unsigned(eg_policy_get_scalar(policy, 13)) + failed_sequential);

@@ -401,5 +401,28 @@ int launch_fold_pack(const DevOut& o, uint32_t n, uint8_t* d_packet, FoldEntry* 
 // parallel.shard_range; own_first / own_n: this rank's shard (its records are in `o`)
 int launch_fold_gathered(const uint8_t* d_gathered, size_t slot_stride, int n_ranks, uint32_t n_global, uint64_t first_index, const DevOut& o,
                          uint32_t own_first, uint32_t own_n, bool cost_only, uint32_t step, uint8_t* d_fold, void* stream);
+// The top-K archive of distinct scenarios (include/eirgrid_hip.h eg_top_k_track; eg_topk.h).  An entry is what ranks and identifies a
+// scenario; the archive is a TopKState (entries in rank order, each naming the record slot that holds its episode) followed by
+// EG_TOPK_MAX record slots (rec:: layout).  A slot never moves while its entry is held; a new entry's record goes to a free one.
+// tag_index / tag_step: in a group, the entry whose record this rank copied into the slot (global index, admission step).
+struct TopKEntry { double score; long long index; double metrics[4]; unsigned long long key; int32_t slot; uint32_t step; };
+static_assert(sizeof(TopKEntry) == 64, "top-k entry");
+struct TopKBlock { int32_t n, pad[15]; TopKEntry e[EG_TOPK_MAX]; };      // up to k entries in rank order (a chunk's, a rank's message)
+struct TopKState { int32_t k, n_held, mode, pad; TopKEntry e[EG_TOPK_MAX]; long long tag_index[EG_TOPK_MAX]; uint32_t tag_step[EG_TOPK_MAX]; };
+constexpr size_t kTopKRecords = (sizeof(TopKState) + 255) & ~size_t(255);
+constexpr size_t kTopKBytes = kTopKRecords + size_t(EG_TOPK_MAX) * rec::stride;
+constexpr uint32_t kTopKChunk = 1024;      // episodes per workgroup of k_topk_select
+// k_topk_keys: rank score and key of every episode of the batch that can still enter the archive at d_state (else score -inf);
+// use_score_list: the statistics epilogue ran for this batch (mode 1 only: its scores are the rank scores)
+int launch_topk_keys(const DevOut& o, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state,
+                     double* d_score, unsigned long long* d_key, void* stream);
+// k_topk_select: the top-k distinct entries of every chunk of kTopKChunk episodes, one TopKBlock per chunk
+int launch_topk_select(const DevOut& o, uint32_t n, uint64_t first_index, const double* d_score, const unsigned long long* d_key, int k,
+                       TopKBlock* d_blocks, void* stream);
+// k_topk_merge: the top-k distinct entries of n_blocks blocks (block_stride bytes apart) — d_state != null: together with the archive's
+// held entries, into the archive (records of new entries copied from `o` when their global index lies in [own_first, own_first + own_n),
+// tagged with `step`); otherwise into the block d_pack (a rank's message)
+int launch_topk_merge(uint8_t* d_state, const uint8_t* d_blocks, int n_blocks, size_t block_stride, TopKBlock* d_pack, int k, const DevOut& o,
+                      uint64_t own_first, uint32_t own_n, uint32_t step, void* stream);
 
 }  // namespace eg

@@ -40,6 +40,14 @@ EG_RM double score(const double* m) {
   const double cost_weight = normalized_cost > 8.0 ? 0.8 : 0.5;
   return 1.0 + (cost_score * cost_weight + m[1] * (1.0 - cost_weight));
 }
+// ai/metrics/scoring.rs:7-15 (optimization_mode "cost_only") with the same logarithm: 2.0 up to the acceptable cost, falling with
+// log(cost) to 1.0 at 100 times it and beyond
+EG_RM double score_cost_only(const double* m) {
+  const double normalized_cost = dmaxd(m[2] / kMaxCost, 1.0);
+  return 2.0 - dmind(eg_detlog(normalized_cost) / eg_detlog(kMaxCost * 100.0 / kMaxCost), 1.0);
+}
+// the rank score of the top-K archive (eg_topk.h, eg_rank_score): mode 2 = cost_only, any other = optimization_mode None
+EG_RM double rank_score(const double* m, int mode) { return mode == 2 ? score_cost_only(m) : score(m); }
 
 // Everything a rollout / statistics kernel needs that depends only on the policy's scalars (learning.rs:37-55, :82,
 // :131-180; sampling.rs:425-427), evaluated wherever the policy changes: on the host at upload, on the device after an

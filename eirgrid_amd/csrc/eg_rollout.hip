@@ -2503,6 +2503,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 
 #ifndef EG_TU_THROUGHPUT      // (everything from here to the launchers lives in eg_rollout.o only)
 #include "eg_replay_coop.h"      // k_replay_coop, k_replay_broadcast: the replay episodes of a batch, computed once
+#include "eg_topk.h"             // k_topk_keys, k_topk_select, k_topk_merge: the top-K archive of distinct scenarios
 
 // ---- B2: a single placement search, for parity tests of the arg-max --------------------------------------------
 __global__ void __launch_bounds__(kWave) k_place(DevTables T, int type, int yi, const uint16_t* __restrict__ cells,
@@ -3308,6 +3309,26 @@ int launch_fold_gathered(const uint8_t* d_gathered, size_t slot_stride, int n_ra
   if (n_global == 0) return 0;
   hipLaunchKernelGGL(k_fold_gathered, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_gathered, (unsigned long long)slot_stride, n_ranks, n_global,
                      (unsigned long long)first_index, o, own_first, own_n, cost_only ? 1 : 0, step, d_fold);
+  return (int)hipGetLastError();
+}
+int launch_topk_keys(const DevOut& o, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state,
+                     double* d_score, unsigned long long* d_key, void* stream) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_topk_keys, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, o, n, (unsigned long long)first_index, mode,
+                     use_score_list ? 1 : 0, reinterpret_cast<const TopKState*>(d_state), d_score, d_key);
+  return (int)hipGetLastError();
+}
+int launch_topk_select(const DevOut& o, uint32_t n, uint64_t first_index, const double* d_score, const unsigned long long* d_key, int k,
+                       TopKBlock* d_blocks, void* stream) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_topk_select, dim3((n + kTopKChunk - 1u) / kTopKChunk), dim3(1024), 0, (hipStream_t)stream, o, n,
+                     (unsigned long long)first_index, d_score, d_key, k, d_blocks);
+  return (int)hipGetLastError();
+}
+int launch_topk_merge(uint8_t* d_state, const uint8_t* d_blocks, int n_blocks, size_t block_stride, TopKBlock* d_pack, int k, const DevOut& o,
+                      uint64_t own_first, uint32_t own_n, uint32_t step, void* stream) {
+  hipLaunchKernelGGL(k_topk_merge, dim3(1), dim3(1024), 0, (hipStream_t)stream, reinterpret_cast<TopKState*>(d_state), d_blocks, n_blocks,
+                     (unsigned long long)block_stride, d_pack, k, o, (unsigned long long)own_first, own_n, step);
   return (int)hipGetLastError();
 }
 int launch_pick_best(const DevOut& o, uint32_t n, uint64_t first_index, UpdateCandidate* d_cand, void* stream) {

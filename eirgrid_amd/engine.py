@@ -8,7 +8,7 @@ marshals numpy buffers.
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, fields
 
 import numpy as np
 
@@ -178,6 +178,24 @@ def evaluate_action_impact(current_metrics, new_metrics, cost_only: bool = False
 def score_metrics(metrics, cost_only: bool = False) -> float:
     m = np.ascontiguousarray(metrics, dtype=np.float64)
     return N.lib().eg_score_metrics(_p(m, C.c_double), int(cost_only))
+
+
+def rank_score(metrics, cost_only: bool = False) -> float:
+    """The top-K archive's rank score (eg_rank_score): score_metrics with the library's own logarithm, the bits the device uses."""
+    m = np.ascontiguousarray(metrics, dtype=np.float64)
+    return N.lib().eg_rank_score(_p(m, C.c_double), 2 if cost_only else 1)
+
+
+def _fetch_top_k(fn, handle, what):
+    """(BatchResult of the n_held entries in rank order, scores [n_held], global indices [n_held]) of a top-K archive."""
+    res = BatchResult.alloc(N.TOPK_MAX)
+    out = res.struct()
+    held = C.c_int32(0)
+    scores = np.zeros(N.TOPK_MAX); index = np.zeros(N.TOPK_MAX, np.int64)
+    N.check(fn(handle, C.byref(out), C.byref(held), _p(scores, C.c_double), _p(index, C.c_int64)), what)
+    n = held.value
+    rows = BatchResult(*[np.ascontiguousarray(getattr(res, f.name)[:n]) for f in fields(BatchResult)])
+    return rows, scores[:n].copy(), index[:n].copy()
 
 
 @dataclass
@@ -463,6 +481,15 @@ class Engine:
         N.check(N.lib().eg_fetch_best_result(self.h, C.byref(out), C.byref(state), C.byref(index)), "eg_fetch_best_result")
         return (int(index.value), res) if state.value == 1 else (None, None)
 
+    def track_top_k(self, k: int, cost_only: bool = False) -> None:
+        """Start an empty top-K archive of the k best distinct scenarios (eg_top_k_track); every batch launched from now on is folded
+        into it on the device.  k = 0 stops tracking (the archive stays fetchable)."""
+        N.check(N.lib().eg_top_k_track(self.h, int(k), 0 if k == 0 else (2 if cost_only else 1)), "eg_top_k_track")
+
+    def fetch_top_k(self):
+        """(BatchResult of the n_held entries in rank order, their rank scores, their global indices)."""
+        return _fetch_top_k(N.lib().eg_fetch_top_k, self.h, "eg_fetch_top_k")
+
     def fetch_scores(self, n_episodes: int) -> np.ndarray:
         s = np.zeros(n_episodes)
         N.check(N.lib().eg_fetch_scores(self.h, _p(s, C.c_double)), "eg_fetch_scores")
@@ -567,3 +594,11 @@ class Group:
         state = C.c_int32(0); index = C.c_int64(-1)
         N.check(N.lib().eg_group_fetch_best_result(self.h, C.byref(out), C.byref(state), C.byref(index)), "eg_group_fetch_best_result")
         return (int(index.value), res) if state.value == 1 else (None, None)
+
+    def track_top_k(self, k: int, cost_only: bool = False) -> None:
+        """The top-K archive over every rank's results (eg_group_top_k_track): one context's archive over the same episodes."""
+        N.check(N.lib().eg_group_top_k_track(self.h, int(k), 0 if k == 0 else (2 if cost_only else 1)), "eg_group_top_k_track")
+
+    def fetch_top_k(self):
+        """(BatchResult of the n_held entries in rank order, their rank scores, their global indices), records from the ranks that ran them."""
+        return _fetch_top_k(N.lib().eg_group_fetch_top_k, self.h, "eg_group_fetch_top_k")

@@ -245,6 +245,31 @@ int32_t eg_best_result_track(eg_ctx *, int32_t mode);
 int32_t eg_fetch_best_result(eg_ctx *, eg_episode_out *out, int32_t *state, int64_t *global_index);
 double eg_evaluate_action_impact(const double current_metrics[4], const double new_metrics[4], int32_t cost_only);
 
+/* Top-K archive of distinct scenarios (no counterpart in the reference, whose author collected the "Top 10 optimized scenarios" of
+ * README.md / mapData/top10/ by hand).  eg_top_k_track(ctx, k, mode) starts an empty archive of 1 <= k <= EG_TOPK_MAX entries (mode 1:
+ * optimization_mode None, 2: "cost_only" (--cost-only), 0: stop tracking; the archive stays fetchable); from then on every batch
+ * launched on this context is folded into it on the device behind its rollout, where the best_result fold runs.  The archive holds
+ * the k highest-ranked DISTINCT SCENARIOS among all episodes folded since tracking started:
+ *   rank score   eg_rank_score(metrics, mode): score_metrics of ai/metrics/scoring.rs:5-45 (mode 2: its cost_only branch, :7-15),
+ *                evaluated with the shared IEEE-only logarithm of csrc/eg_reduced_math.h, the same bits on the host and the device;
+ *   order        score descending, ties to the lower global index;
+ *   failures     episodes with status != EG_EP_OK (and a NaN score) are skipped;
+ *   identity     two episodes are the same scenario when the bit patterns of their 4 metrics AND their 64-bit keys are equal; the key
+ *                covers n_act[26] as little-endian int32 followed by act_log[0 .. sum n_act), zero-padded to a multiple of 8 bytes,
+ *                read as little-endian 8-byte words w_i:  key = sum_i splitmix64(w_i + i * 0x9E3779B97F4A7C15) mod 2^64, with
+ *                splitmix64(z) = z ^ z >> 31 after z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB.
+ *                (A collision of keys together with equal metrics would merge two scenarios into one.);
+ *   occurrence   a scenario is held once, at its earliest global index, with that episode's whole record (replay episodes of the best
+ *                strategy are one scenario, however many batches carry them).
+ * The result depends only on the set of episodes folded, not on how they were split into batches, ranks or hoisted replays.  Like
+ * best_result the archive lives as long as the context: it is not part of any checkpoint.  eg_fetch_top_k copies the *n_held <= k
+ * entries in rank order: `out` rows (sized for k episodes), scores[k] and global_index[k] (either may be NULL).  eg_top_k_track
+ * refuses a rank of an eg_group: eg_group_top_k_track folds the ranks' results. */
+#define EG_TOPK_MAX 64
+int32_t eg_top_k_track(eg_ctx *, int32_t k, int32_t mode);
+int32_t eg_fetch_top_k(eg_ctx *, eg_episode_out *out, int32_t *n_held, double *scores, int64_t *global_index);
+double eg_rank_score(const double metrics[4], int32_t mode);   /* mode 2: cost_only; 0 or 1: optimization_mode None */
+
 /* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
  * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
  * copies, no collective library — and every call enqueues the work of all ranks from the calling thread without synchronising
@@ -264,7 +289,11 @@ double eg_evaluate_action_impact(const double current_metrics[4], const double n
  *   eg_group_replay_hoist  eg_replay_hoist on every rank
  *   eg_group_best_result_track / eg_group_fetch_best_result   the reference's best_result fold (see eg_best_result_track) over the
  *                      results of ALL ranks in global index order: exactly one context's fold over the same episodes.  The fold's
- *                      state is kept on every rank; the held run's record only by the rank that ran it, and fetched from there. */
+ *                      state is kept on every rank; the held run's record only by the rank that ran it, and fetched from there.
+ *   eg_group_top_k_track / eg_group_fetch_top_k   the top-K archive (see eg_top_k_track) over the results of ALL ranks: exactly one
+ *                      context's archive over the same episodes.  Each rank sends its shard's own top-k distinct entries behind its
+ *                      message; every rank merges the N blocks into its replica of the archive; an entry's record is kept by the rank
+ *                      that ran it, and fetched from there. */
 typedef struct eg_group eg_group;
 eg_group *eg_group_create(const int32_t *devices, int32_t n_ranks, const eg_world *world);
 void eg_group_destroy(eg_group *);
@@ -276,6 +305,8 @@ int32_t eg_group_pull(eg_group *, int32_t rank, eg_policy *);
 int32_t eg_group_replay_hoist(eg_group *, int32_t on);
 int32_t eg_group_best_result_track(eg_group *, int32_t mode);
 int32_t eg_group_fetch_best_result(eg_group *, eg_episode_out *out, int32_t *state, int64_t *global_index);
+int32_t eg_group_top_k_track(eg_group *, int32_t k, int32_t mode);
+int32_t eg_group_fetch_top_k(eg_group *, eg_episode_out *out, int32_t *n_held, double *scores, int64_t *global_index);
 
 /* Test hook: fills the LDS of every compute unit with `value` and waits.  LDS is not cleared between workgroups, so a
  * kernel that reads a word before writing it sees what the previous tenant left; the parity tests call this with small
