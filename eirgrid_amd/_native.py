@@ -56,6 +56,12 @@ class EgEpisodeOut(C.Structure):
                 ("n_chunks", _u32p)]
 
 
+class EgPlanSet(C.Structure):
+    _fields_ = [("n_plans", C.c_int32), ("best_count", _i32p), ("best_actions", _u8p), ("best_deficit_count", _i32p),
+                ("best_deficit_actions", _u8p), ("best_actions_len", C.c_int64), ("best_deficit_actions_len", C.c_int64),
+                ("names", C.POINTER(C.c_char_p))]
+
+
 # every symbol include/eirgrid_hip.h declares
 EXPORTS = [
     "eg_build_hash", "eg_last_error", "eg_device_count", "eg_create", "eg_destroy", "eg_rollout_batch", "eg_upload_snapshot",
@@ -64,7 +70,7 @@ EXPORTS = [
     "eg_policy_push", "eg_device_rollout", "eg_device_apply", "eg_device_step", "eg_policy_pull",
     "eg_group_create", "eg_group_destroy", "eg_group_rank", "eg_group_push", "eg_group_step", "eg_group_pull", "eg_group_replay_hoist",
     "eg_group_best_result_track", "eg_group_fetch_best_result", "eg_top_k_track", "eg_fetch_top_k", "eg_rank_score",
-    "eg_group_top_k_track", "eg_group_fetch_top_k",
+    "eg_group_top_k_track", "eg_group_fetch_top_k", "eg_plans_validate", "eg_evaluate_plans", "eg_plans_load", "eg_plans_free",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -201,6 +207,14 @@ def lib():
     L.eg_group_top_k_track.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.eg_group_fetch_top_k.restype = C.c_int32
     L.eg_group_fetch_top_k.argtypes = [C.c_void_p, C.POINTER(EgEpisodeOut), C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int64)]
+    L.eg_plans_validate.restype = C.c_int32
+    L.eg_plans_validate.argtypes = [C.POINTER(EgPlanSet)]
+    L.eg_evaluate_plans.restype = C.c_int32
+    L.eg_evaluate_plans.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.c_uint64, C.c_uint64,
+                                    C.POINTER(EgEpisodeOut)]
+    L.eg_plans_load.restype = C.POINTER(EgPlanSet)
+    L.eg_plans_load.argtypes = [C.c_char_p]
+    L.eg_plans_free.argtypes = [C.POINTER(EgPlanSet)]
     L.eg_rank_score.restype = C.c_double
     L.eg_rank_score.argtypes = [_dp, C.c_int32]
     L.eg_evaluate_action_impact.restype = C.c_double

@@ -389,3 +389,144 @@ eg_policy* eg_policy_load_json(const char* path) {   // ai/learning/weights/seri
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- plans (include/eirgrid_hip.h eg_plans_load / eg_plans_validate)
+namespace {
+
+struct PlanSet : eg_plan_set {      // what eg_plans_load hands out: the C view and the storage behind it
+  std::vector<int32_t> cnt, dcnt;
+  std::vector<uint8_t> act, dact;
+  std::vector<std::string> name_store;
+  std::vector<const char*> name_ptrs;
+};
+
+// One plan's two year-keyed lists from an object of the checkpoint schema (the lists of eg_policy_load_json's load_lists: an action the
+// canonical table cannot represent is dropped as there, an unknown action type or generator type is an error).  `where` prefixes the
+// problems, appended to `problems`.
+bool plan_from_json(const Json& root, const std::string& where, PlanSet& ps, std::string& problems) {
+  const size_t problems_before = problems.size();
+  auto bad = [&](const std::string& m) { problems += (problems.empty() ? "" : "\n") + where + ": " + m; };
+  if (root.kind != Json::Obj) { bad("not a JSON object"); return false; }
+  const char* keys[2] = {"best_actions", "best_deficit_actions"};
+  std::array<ActionList, Y> lists[2];
+  for (int w = 0; w < 2; ++w) {
+    const Json* t = root.get(keys[w]);
+    if (!t) { bad(std::string("missing \"") + keys[w] + "\""); continue; }
+    if (t->kind == Json::Null) continue;      // (a checkpoint of a policy without a best strategy: empty lists)
+    if (t->kind != Json::Obj) { bad(std::string(keys[w]) + ": not an object keyed by year"); continue; }
+    size_t total = 0;
+    for (auto& kv : t->obj) {
+      const int y = std::atoi(kv.first.c_str()) - 2025;
+      if (y < 0 || y >= Y) { bad(std::string(keys[w]) + ": year \"" + kv.first + "\" outside 2025..2050"); continue; }
+      if (kv.second.kind != Json::Arr) { bad(std::string(keys[w]) + "[\"" + kv.first + "\"]: not a list"); continue; }
+      lists[w][y].clear();
+      for (size_t i = 0; i < kv.second.arr.size(); ++i) {
+        const int idx = kv.second.arr[i].kind == Json::Obj ? action_index(kv.second.arr[i]) : -2;
+        if (idx == -2) { bad(std::string(keys[w]) + "[\"" + kv.first + "\"] entry " + std::to_string(i) + ": unknown action"); continue; }
+        if (idx >= 0) lists[w][y].push_back(uint8_t(idx));
+      }
+    }
+    for (int y = 0; y < Y; ++y) total += lists[w][y].size();
+    if (total > eg::snap::kBestCap) bad(std::string(keys[w]) + ": " + std::to_string(total) + " entries (at most " + std::to_string(eg::snap::kBestCap) + ")");
+  }
+  std::string name;
+  if (const Json* n = root.get("name"); n && n->kind != Json::Null) {
+    if (n->kind == Json::Str) name = n->str;
+    else bad("name: not a string");
+  }
+  if (problems.size() != problems_before) return false;
+  for (int y = 0; y < Y; ++y) {
+    ps.cnt.push_back(int32_t(lists[0][y].size())); ps.act.insert(ps.act.end(), lists[0][y].begin(), lists[0][y].end());
+    ps.dcnt.push_back(int32_t(lists[1][y].size())); ps.dact.insert(ps.dact.end(), lists[1][y].begin(), lists[1][y].end());
+  }
+  ps.name_store.push_back(name);
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t eg_plans_validate(const eg_plan_set* p) {
+  auto fail = [](const std::string& m) { eg::set_error("eg_plans_validate: " + m); return EG_ERR_BAD_ARG; };
+  if (!p) return fail("NULL plan set");
+  if (p->n_plans < 1) return fail("n_plans = " + std::to_string(p->n_plans) + " (at least 1)");
+  if (!p->best_count || !p->best_deficit_count) return fail("NULL best_count / best_deficit_count");
+  const char* field[2] = {"best_actions", "best_deficit_actions"};
+  const int32_t* count[2] = {p->best_count, p->best_deficit_count};
+  const uint8_t* flat[2] = {p->best_actions, p->best_deficit_actions};
+  const int64_t len[2] = {p->best_actions_len, p->best_deficit_actions_len};
+  for (int w = 0; w < 2; ++w) {
+    if (len[w] < 0) return fail(std::string(field[w]) + "_len = " + std::to_string(len[w]));
+    if (len[w] > 0 && !flat[w]) return fail(std::string("NULL ") + field[w]);
+    int64_t pos = 0;
+    for (int32_t j = 0; j < p->n_plans; ++j) {
+      const std::string who = "plan " + std::to_string(j) + (p->names && p->names[j] && p->names[j][0] ? std::string(" (\"") + p->names[j] + "\")" : std::string());
+      int64_t n = 0;
+      for (int y = 0; y < Y; ++y) {
+        const int32_t k = count[w][size_t(j) * Y + y];
+        if (k < 0) return fail(who + ": " + field[w] + " year " + std::to_string(2025 + y) + ": count " + std::to_string(k) + " < 0");
+        n += k;
+      }
+      if (n > int64_t(eg::snap::kBestCap)) return fail(who + ": " + field[w] + ": " + std::to_string(n) + " entries (at most " + std::to_string(eg::snap::kBestCap) + ")");
+      if (pos + n > len[w]) return fail(who + ": the " + field[w] + " counts add up to more than " + field[w] + "_len = " + std::to_string(len[w]));
+      int64_t i = pos;
+      for (int y = 0; y < Y; ++y)
+        for (int32_t k = 0; k < count[w][size_t(j) * Y + y]; ++k, ++i)
+          if (flat[w][i] >= EG_N_ACTIONS)
+            return fail(who + ": " + field[w] + " year " + std::to_string(2025 + y) + " entry " + std::to_string(k) + ": " + std::to_string(int(flat[w][i])) + " >= " + std::to_string(EG_N_ACTIONS));
+      pos += n;
+    }
+    if (pos != len[w]) return fail(std::string("the ") + field[w] + " counts add up to " + std::to_string(pos) + " entries, " + field[w] + "_len = " + std::to_string(len[w]));
+  }
+  return EG_OK;
+}
+
+eg_plan_set* eg_plans_load(const char* path) {
+  if (!path) { eg::set_error("eg_plans_load: NULL path"); return nullptr; }
+  std::ifstream f(path, std::ios::binary);
+  if (!f) { eg::set_error(std::string("eg_plans_load: cannot open ") + path); return nullptr; }
+  std::stringstream ss; ss << f.rdbuf();
+  const std::string text = ss.str();
+  std::unique_ptr<PlanSet> ps(new PlanSet());
+  std::string problems;
+  {  // one JSON document (a checkpoint) ...
+    JsonParser jp{text.data(), text.data() + text.size(), {}};
+    Json root;
+    if (jp.value(root)) {
+      jp.ws();
+      if (jp.p == jp.end) plan_from_json(root, "line 1", *ps, problems);
+      else root.kind = Json::Null;
+    }
+    if (root.kind == Json::Null) {      // ... or JSON Lines: one object per non-blank line
+      size_t at = 0;
+      for (int line = 1; at <= text.size(); ++line) {
+        size_t nl = text.find('\n', at);
+        if (nl == std::string::npos) nl = text.size();
+        JsonParser lp{text.data() + at, text.data() + nl, {}};
+        lp.ws();
+        if (lp.p != lp.end) {
+          const std::string where = "line " + std::to_string(line);
+          Json obj;
+          if (!lp.value(obj)) problems += (problems.empty() ? "" : "\n") + where + ": " + lp.err;
+          else if (lp.ws(), lp.p != lp.end) problems += (problems.empty() ? "" : "\n") + where + ": trailing characters after the object";
+          else plan_from_json(obj, where, *ps, problems);
+        }
+        at = nl + 1;
+      }
+    }
+  }
+  if (problems.empty() && ps->name_store.empty()) problems = "no plans";
+  if (!problems.empty()) { eg::set_error(std::string("eg_plans_load: ") + path + ":\n" + problems); return nullptr; }
+  for (auto& n : ps->name_store) ps->name_ptrs.push_back(n.c_str());
+  ps->n_plans = int32_t(ps->name_store.size());
+  ps->best_count = ps->cnt.data(); ps->best_deficit_count = ps->dcnt.data();
+  ps->best_actions = ps->act.data(); ps->best_deficit_actions = ps->dact.data();
+  ps->best_actions_len = int64_t(ps->act.size()); ps->best_deficit_actions_len = int64_t(ps->dact.size());
+  ps->names = ps->name_ptrs.data();
+  return ps.release();
+}
+
+void eg_plans_free(eg_plan_set* p) { delete static_cast<PlanSet*>(p); }
+
+}  // extern "C"

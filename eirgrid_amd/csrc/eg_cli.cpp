@@ -48,6 +48,8 @@ struct Args {   // cli/cli.rs:5-59
   // --gpus N / --devices LIST: the ranks of a multi-GPU run (eg_group), one device each; empty: the single-device run on --device
   std::vector<int32_t> ranks; bool device_given = false, gpus_given = false;
   int32_t top_k = 0;            // --top-k K: keep the K best distinct scenarios of the run (eg_top_k_track) and export them; 0: off
+  std::string evaluate;         // --evaluate FILE: score the plans of FILE (eg_evaluate_plans) and exit; no training
+  std::string evaluate_policy;  // --evaluate-policy CKPT: the policy the plans are evaluated under (default: ActionWeights::new)
 };
 
 void usage() {
@@ -70,7 +72,12 @@ void usage() {
             "      --no-replay-hoist    run every replay iteration of a batch on its own (default: the replay iterations of a batch —\n"
             "                           one and the same computation — are computed once; identical results either way)\n"
             "      --top-k <K>          keep the K best distinct scenarios of the run (0..64, ranked by score_metrics in the run's mode)\n"
-            "                           and write them to enhanced_csv/<stamp>/top_k/ [default: 0 = off]");
+            "                           and write them to enhanced_csv/<stamp>/top_k/ [default: 0 = off]\n"
+            "      --evaluate <FILE>    score the plans of FILE (a checkpoint, or JSON Lines of best_actions / best_deficit_actions with an\n"
+            "                           optional name) and exit: plan j replays as iteration j of --seed [default 0], --batch plans per\n"
+            "                           launch; writes <checkpoint-dir>/<stamp>/plans/index.csv, with --top-k K also the K best plans'\n"
+            "                           exports in plans/top_k/; no training runs\n"
+            "      --evaluate-policy <CKPT>  the policy the plans are evaluated under [default: a fresh one]");
 }
 
 bool parse(int argc, char** argv, Args& a) {
@@ -137,6 +144,8 @@ bool parse(int argc, char** argv, Args& a) {
       }
       a.top_k = std::atoi(k.c_str());
     }
+    else if (s == "--evaluate") a.evaluate = v();
+    else if (s == "--evaluate-policy") a.evaluate_policy = v();
     else if (s == "-h" || s == "--help") { usage(); std::exit(0); }
     else { std::fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage(); return false; }
   }
@@ -147,6 +156,8 @@ bool parse(int argc, char** argv, Args& a) {
     return false;
   }
   if (a.ranks.size() == 1) a.device = a.ranks[0];      // one rank: the single-device run on that device
+  if (!a.evaluate_policy.empty() && a.evaluate.empty()) { std::fprintf(stderr, "error: --evaluate-policy needs --evaluate\n"); return false; }
+  if (!a.evaluate.empty() && a.ranks.size() > 1) { std::fprintf(stderr, "error: --evaluate runs on one device (no --gpus / --devices)\n"); return false; }
   return true;
 }
 
@@ -246,12 +257,109 @@ std::string newest_run_dir(const std::string& base) {   // multi_simulation.rs:2
 
 #define CHECK(call) do { int32_t rc_ = (call); if (rc_ < 0) { std::fprintf(stderr, "%s failed (%d): %s\n", #call, rc_, eg_last_error()); return 1; } } while (0)
 
+std::string time_stamp(const char* fmt) { char buf[32]; std::time_t t = std::time(nullptr); std::tm tmv; localtime_r(&t, &tmv); std::strftime(buf, sizeof(buf), fmt, &tmv); return buf; }
+
+// --evaluate: every plan of `plans` scored under one policy (eg_evaluate_plans), plan j as iteration j of the run's seed, --batch plans
+// per launch.  <checkpoint-dir>/<stamp>/plans/index.csv gets a row per plan; --top-k K exports the K best plans like top_k/ exports an
+// entry (score descending, ties to the lower plan index; failed plans are not ranked).
+int run_evaluate(const Args& a, const WorldData& wd, const eg_world& world, const eg_plan_set& plans) {
+  eg_policy* policy = a.evaluate_policy.empty() ? eg_policy_new() : eg_policy_load_json(a.evaluate_policy.c_str());
+  if (!policy) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
+  eg_ctx* ctx = eg_create(a.device, &world);
+  if (!ctx) { std::fprintf(stderr, "eg_create: %s\n", eg_last_error()); eg_policy_free(policy); return 1; }
+  const uint32_t n = uint32_t(plans.n_plans);
+  const int mode = a.cost_only ? 2 : 1;
+  eg_opts opts{a.enable_energy_sales ? 1 : 0, 0, 1};
+  eg_policy_snapshot snap; CHECK(eg_policy_snapshot_view(policy, &snap));
+  // where plan j's entries start in the flat lists
+  std::vector<int64_t> pos(n + 1, 0), dpos(n + 1, 0);
+  for (uint32_t j = 0; j < n; ++j) {
+    int64_t k = 0, dk = 0;
+    for (int y = 0; y < EG_YEARS; ++y) { k += plans.best_count[size_t(j) * EG_YEARS + y]; dk += plans.best_deficit_count[size_t(j) * EG_YEARS + y]; }
+    pos[j + 1] = pos[j] + k; dpos[j + 1] = dpos[j] + dk;
+  }
+  auto subset = [&](uint32_t j0, uint32_t m) {      // plans [j0, j0 + m) as a set of their own
+    eg_plan_set s = plans;
+    s.n_plans = int32_t(m);
+    s.best_count = plans.best_count + size_t(j0) * EG_YEARS; s.best_deficit_count = plans.best_deficit_count + size_t(j0) * EG_YEARS;
+    s.best_actions = plans.best_actions + pos[j0]; s.best_deficit_actions = plans.best_deficit_actions + dpos[j0];
+    s.best_actions_len = pos[j0 + m] - pos[j0]; s.best_deficit_actions_len = dpos[j0 + m] - dpos[j0];
+    s.names = plans.names ? plans.names + j0 : nullptr;
+    return s;
+  };
+  std::vector<double> metrics(size_t(n) * 4); std::vector<int32_t> status(n), n_gens(n);
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint32_t j0 = 0; j0 < n; j0 += a.batch) {
+    const uint32_t m = std::min(a.batch, n - j0);
+    const eg_plan_set s = subset(j0, m);
+    eg_episode_out out{}; out.metrics = &metrics[size_t(j0) * 4]; out.status = &status[j0]; out.n_gens = &n_gens[j0];
+    CHECK(eg_evaluate_plans(ctx, &snap, &opts, &s, a.seed, j0, &out));
+  }
+  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  std::vector<double> score(n);
+  std::vector<uint32_t> order;
+  for (uint32_t j = 0; j < n; ++j) {
+    score[j] = status[j] == EG_EP_OK ? eg_rank_score(&metrics[size_t(j) * 4], mode) : std::nan("");
+    if (status[j] == EG_EP_OK) order.push_back(j);
+  }
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return score[x] > score[y]; });
+  const std::string stamp = time_stamp("%Y%m%d_%H%M%S"), dir = a.checkpoint_dir + "/" + stamp + "/plans";
+  mkdirs(dir);
+  auto name_of = [&](uint32_t j) { return std::string(plans.names && plans.names[j] ? plans.names[j] : ""); };
+  {
+    std::ofstream f(dir + "/index.csv");
+    f << "plan,name,status,score,final_net_emissions,average_public_opinion,total_cost,power_reliability,n_generators\n";
+    for (uint32_t j = 0; j < n; ++j) {
+      std::string name = name_of(j);      // (a name with a comma, a quote or a line break is quoted, CSV style)
+      if (name.find_first_of(",\"\n") != std::string::npos) {
+        std::string q = "\"";
+        for (char ch : name) { if (ch == '"') q += '"'; q += ch; }
+        name = q + "\"";
+      }
+      const double* m = &metrics[size_t(j) * 4];
+      char line[512];
+      std::snprintf(line, sizeof(line), ",%d,%.17g,%.17g,%.17g,%.17g,%.17g,%d\n", status[j], score[j], m[0], m[1], m[2], m[3], n_gens[j]);
+      f << j << ',' << name << line;
+    }
+    if (!f) { std::fprintf(stderr, "error: cannot write %s/index.csv\n", dir.c_str()); return 1; }
+  }
+  if (a.top_k > 0) {      // the K best plans, each evaluated once more on its own (the same episode: same policy, seed and index)
+    std::vector<double> m1(4), yearly(size_t(EG_YEARS) * EG_YEARLY_FIELDS);
+    std::vector<int32_t> n_act(EG_YEARS); std::vector<uint8_t> act(EG_ACT_CAP); std::vector<uint16_t> pack(EG_MAX_GENS); int32_t g = 0, st = 0;
+    std::vector<const char*> names;
+    for (const std::string& nm : wd.names) names.push_back(nm.c_str());
+    const std::string tk = dir + "/top_k";
+    for (size_t r = 0; r < order.size() && r < size_t(a.top_k); ++r) {
+      const uint32_t j = order[r];
+      const eg_plan_set s = subset(j, 1);
+      eg_episode_out one{}; one.metrics = m1.data(); one.yearly = yearly.data(); one.n_act = n_act.data(); one.act_log = act.data();
+      one.n_gens = &g; one.gen_pack = pack.data(); one.status = &st;
+      CHECK(eg_evaluate_plans(ctx, &snap, &opts, &s, a.seed, j, &one));
+      char sub[24]; std::snprintf(sub, sizeof(sub), "/%02zu", r + 1);
+      const std::string ed = tk + sub;
+      mkdirs(ed);
+      CHECK(eg_export_summary_csv(&one, (ed + "/simulation_summary.csv").c_str(), stamp.c_str()));
+      CHECK(eg_export_run_details(&world, names.size() == wd.sx.size() ? names.data() : nullptr, &one, ed.c_str(), a.seed));
+    }
+  }
+  if (order.empty()) std::printf("Evaluated %u plans in %.3f s (%.0f plans/s); no plan finished\n", n, secs, double(n) / std::max(secs, 1e-9));
+  else {
+    const std::string best = name_of(order[0]).empty() ? std::string() : " (" + name_of(order[0]) + ")";
+    std::printf("Evaluated %u plans in %.3f s (%.0f plans/s); best plan %u%s score %.6f; written to %s\n", n, secs, double(n) / std::max(secs, 1e-9),
+                order[0], best.c_str(), score[order[0]], dir.c_str());
+  }
+  eg_policy_free(policy);
+  eg_destroy(ctx);
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
   Args a;
   if (!parse(argc, argv, a)) return 2;
   std::puts("EirGrid Power System Simulator (2025-2050) — MI355X rollout engine");
+  eg_plan_set* plans = nullptr;      // --evaluate: every invalid line is reported before a device is touched
+  if (!a.evaluate.empty() && !(plans = eg_plans_load(a.evaluate.c_str()))) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
   if (a.enable_construction_delays) { std::fprintf(stderr, "error: --enable-construction-delays is not implemented on the device (DESIGN.md §6)\n"); return 2; }
 
   WorldData wd;
@@ -285,6 +393,7 @@ int main(int argc, char** argv) {
     return 0;
   }
   const eg_world world = wd.view(a.existing_operational_at_start);
+  if (plans) { const int rc = run_evaluate(a, wd, world, *plans); eg_plans_free(plans); return rc; }
   // more than one rank: the same reduced-update loop on an eg_group (the exchange between the ranks is inside the library)
   eg_ctx* ctx = nullptr; eg_group* group = nullptr;
   if (a.gpus_given && int32_t(a.ranks.size()) > eg_device_count()) {

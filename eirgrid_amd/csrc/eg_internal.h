@@ -211,6 +211,9 @@ constexpr size_t bestd_off = best_off + 4 * 28;
 constexpr size_t best_actions = bestd_off + 4 * 28;                         // u8 [kBestCap]
 constexpr size_t bestd_actions = best_actions + kBestCap;
 constexpr size_t state = (bestd_actions + kBestCap + 15) & ~size_t(15);     // DevState
+// A plan block (eg_evaluate_plans): the list section [best_mask, state) on its own, one per plan of a plan batch, same layout
+constexpr size_t kPlanStride = state - best_mask;
+static_assert(kPlanStride == 8832 && kPlanStride % 64 == 0, "plan block layout");
 constexpr size_t upload_bytes = state + sizeof(DevState);                   // what eg_upload_snapshot copies
 // device-resident policy only (on-device updates, eg_policy_pull):
 constexpr int kImpLogCap = 256;
@@ -242,12 +245,20 @@ struct DevSnapshot {
   double boost_others, boost_noop;   // 1 + lr * 0.1, 1 + lr * 0.2 (learning.rs:74-87, deficit.rs:118-127)
   double eps_main;                   // exploration rate of sample_action, stall-scaled (sampling.rs:150-157)
   double scaled_power;               // 1 + 2 * min(stall / 1000, 3) (sampling.rs:193-195)
+  // Where the episode's best lists live (the six list accessors below): base + snap::best_mask (load_state), or in a plan batch
+  // (eg_evaluate_plans) the episode's own plan block, plan_pool + e * snap::kPlanStride.  plan_pool is the host's: null outside plan batches.
+  const uint8_t* lists;
+  const uint8_t* plan_pool;
 #define EG_SNAP(name, type) EG_HD const type* name() const { return reinterpret_cast<const type*>(base + snap::name); }
+#define EG_LIST(name, type) EG_HD const type* name() const { return reinterpret_cast<const type*>(lists + (snap::name - snap::best_mask)); }
   EG_SNAP(pol, double) EG_SNAP(scaled, double) EG_SNAP(scaled_perm, uint8_t)
-  EG_SNAP(best_mask, unsigned long long) EG_SNAP(bestd_mask, unsigned long long)
-  EG_SNAP(best_off, int32_t) EG_SNAP(bestd_off, int32_t) EG_SNAP(best_actions, uint8_t) EG_SNAP(bestd_actions, uint8_t)
+  EG_LIST(best_mask, unsigned long long) EG_LIST(bestd_mask, unsigned long long)
+  EG_LIST(best_off, int32_t) EG_LIST(bestd_off, int32_t) EG_LIST(best_actions, uint8_t) EG_LIST(bestd_actions, uint8_t)
   EG_SNAP(state, DevState)
+#undef EG_LIST
 #undef EG_SNAP
+  // the resident list's total length (best_off()[EG_YEARS] before load_state has set `lists`)
+  EG_HD int32_t resident_list_len() const { return reinterpret_cast<const int32_t*>(base + snap::best_off)[EG_YEARS]; }
 };
 
 // Per-batch outputs in HBM: one record per episode (everything an episode writes is contiguous), fixed layout.
@@ -324,6 +335,11 @@ struct RolloutPlan {
   // has completed in d_solo (a word per workgroup of the replay grid)
   unsigned long long solo_seq;
   unsigned long long* d_solo;
+  // a plan batch (eg_evaluate_plans): no lean grid and no hoist; the short-replay variant runs over the n_short episodes d_index lists, the
+  // long-replay one (with k_replay_solo ahead of it) over the n_heavy - n_short that d_index_long lists
+  bool plans;
+  uint32_t n_short;
+  const uint32_t* d_index_long;
 };
 constexpr int kStatsReplicas = 64;
 int launch_fold_stats(long long* d_rep, long long* d_stats, void* stream);

@@ -81,12 +81,13 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
                                                                        EpisodeMap emap) {
   const int lane = threadIdx.x;
   if (blockIdx.x >= emap.count) return;
-  if (!(S_in.state()->has_lists && S_in.best_off()[EG_YEARS] > kShortReplayMax)) return;      // (uniform for the whole grid: the short variant's)
+  if (S_in.plan_pool == nullptr && !(S_in.state()->has_lists && S_in.resident_list_len() > kShortReplayMax)) return;      // (uniform for the whole grid: the short variant's; a plan batch launches it over its long plans only)
   if (emap.hoist_seq != 0ull && *emap.hoist == emap.hoist_seq) return;                        // served by the replay hoist
   const uint32_t e = map_episode(emap, blockIdx.x);
   if (e >= n_episodes) return;
   DevSnapshot S = S_in;
   load_state(S);
+  plan_lists(S, e);
   const bool replay = replay_mask != nullptr ? replay_mask[e] != 0 : (replay_period != 0u && S.has_best_actions && (first_index + e) % replay_period == 0ull);
   if (!replay || !S.has_best_actions) return;      // an ordinary episode, or a flagged one without lists (fallback draws from the first action on)
 #ifdef EG_SOLO_STAMPS      // diagnostic build (make ab AB=solostamps ABFLAGS=-DEG_SOLO_STAMPS; scripts/solo_stamps.py): cycles of the phases

@@ -1727,6 +1727,11 @@ __device__ __forceinline__ void load_state(DevSnapshot& S) {
   S.heur_min = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.heur_min); S.heur_max = (uint32_t)__builtin_amdgcn_readfirstlane((int)st.heur_max);
   S.boost_others = uniform_f64(st.boost_others); S.boost_noop = uniform_f64(st.boost_noop);
   S.eps_main = uniform_f64(st.eps_main); S.scaled_power = uniform_f64(st.scaled_power);
+  S.lists = S.base + snap::best_mask;      // the resident list (a plan batch's replay kernels then point it at the episode's plan block)
+}
+// A plan batch (eg_evaluate_plans): episode e replays plan block e.  `e` is wave-uniform, so the list reads stay scalar loads.
+__device__ __forceinline__ void plan_lists(DevSnapshot& S, uint32_t e) {
+  if (S.plan_pool != nullptr) S.lists = S.plan_pool + (size_t)e * snap::kPlanStride;
 }
 
 // One wave adds the contributions of episode e (its outputs must be visible in memory).
@@ -1898,8 +1903,9 @@ __global__ void __launch_bounds__(kWave * (1 + kHelpers), kKind == kReplayLong ?
   const int lane = threadIdx.x & (kWave - 1);
   if (blockIdx.x >= emap.count) return;
   if constexpr (kReplay) {      // (uniform for the whole grid)
-    const bool long_list = S_in.state()->has_lists && S_in.best_off()[EG_YEARS] > kShortReplayMax;
-    if (long_list != kHeavy) return;
+    // (a plan batch launches each variant over exactly the plans it serves: eg_api.cpp launch_plans)
+    const bool long_list = S_in.state()->has_lists && S_in.resident_list_len() > kShortReplayMax;
+    if (S_in.plan_pool == nullptr && long_list != kHeavy) return;
     if (emap.hoist_seq != 0ull && *emap.hoist == emap.hoist_seq) return;      // served by k_replay_coop / k_replay_broadcast
     if constexpr (kHeavy) if (emap.solo_seq != 0ull && emap.solo[blockIdx.x] == emap.solo_seq) return;      // done by k_replay_solo
   }
@@ -1936,6 +1942,7 @@ __global__ void __launch_bounds__(kWave * (1 + kHelpers), kKind == kReplayLong ?
   }
   DevSnapshot S = S_in;
   load_state(S);
+  if constexpr (kReplay) plan_lists(S, e);
   // iteration.rs:34-42: which episodes replay the best strategy comes from the caller's mask or, when the policy lives on
   // the device (the host cannot know whether a best strategy exists yet), from a period over the global episode index
   // (Replay episodes always run the heavy-capable variant — the launch plan sends them there, eg_api.cpp launch_batch —, so
@@ -3131,6 +3138,17 @@ int launch_rollout(const DevTables& t, const DevSnapshot& s, const DevOut& o, ui
   // into the packet)
   const bool rep = d_stats_packet != nullptr && p.d_stats_rep != nullptr;
   long long* d_stats = rep ? p.d_stats_rep : d_stats_packet;
+  if (p.plans) {      // each replay variant over exactly its plans (the kernels then skip their grid-uniform list-length test)
+    EpisodeMap ms{}, ml{};
+    ms.count = p.n_short; ms.mode = 1u; ms.index = p.d_index;
+    ml.count = p.n_heavy - p.n_short; ml.mode = 1u; ml.index = p.d_index_long;
+    if (!p.helper_waves && p.solo_seq != 0ull) { ml.solo = p.d_solo; ml.solo_seq = p.solo_seq; }
+    if (ms.count > 0) launch_variant<kReplayShort>(p.helper_waves, t, s, o, seed, first_index, n, d_replay_mask, replay_period, d_stats, ms, p.stream_heavy, p.ev[0],
+                                                   ml.count > 0 ? nullptr : p.ev[1]);
+    else (void)hipEventRecord((hipEvent_t)p.ev[0], (hipStream_t)p.stream_heavy);      // (k_replay_solo runs first: the start is a marker)
+    if (ml.count > 0) launch_variant<kReplayLong>(p.helper_waves, t, s, o, seed, first_index, n, d_replay_mask, replay_period, d_stats, ml, p.stream_heavy, nullptr, p.ev[1]);
+    return (int)hipGetLastError();
+  }
   if (p.n_heavy > 0) {      // first, so that the long episodes start first: both replay variants, one of which returns at once
     EpisodeMap m{};
     m.count = p.n_heavy; m.stats_rep = rep ? 1u : 0u;

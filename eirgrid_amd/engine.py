@@ -186,6 +186,73 @@ def rank_score(metrics, cost_only: bool = False) -> float:
     return N.lib().eg_rank_score(_p(m, C.c_double), 2 if cost_only else 1)
 
 
+class Plan:
+    """A strategy to score (eg_evaluate_plans): per year the best_actions list and the best_deficit_actions list, canonical action
+    indices 0..60 — what update_best_strategy installs and a replay episode reads."""
+
+    def __init__(self, best_actions, best_deficit_actions, name: str = ""):
+        self.best_actions = [list(map(int, best_actions[y])) for y in range(N.YEARS)]
+        self.best_deficit_actions = [list(map(int, best_deficit_actions[y])) for y in range(N.YEARS)]
+        self.name = name
+        assert len(best_actions) == N.YEARS and len(best_deficit_actions) == N.YEARS
+
+    def __len__(self) -> int:
+        """Entries of the best_actions list (what routes a plan to the short or the long replay path)."""
+        return sum(len(l) for l in self.best_actions)
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Plan) and (self.best_actions, self.best_deficit_actions) == (other.best_actions, other.best_deficit_actions)
+
+    def __repr__(self) -> str:
+        return f"Plan({self.name!r}, {len(self)} actions, {sum(len(l) for l in self.best_deficit_actions)} deficit actions)"
+
+    @staticmethod
+    def load(path: str) -> "list[Plan]":
+        """Plans of a file in the checkpoint schema: one checkpoint (one plan) or JSON Lines with optional names (eg_plans_load)."""
+        L = N.lib()
+        ps = L.eg_plans_load(str(path).encode())
+        if not ps:
+            raise N.EirgridError(L.eg_last_error().decode())
+        try:
+            s = ps.contents
+            out, pos, dpos = [], 0, 0
+            for j in range(s.n_plans):
+                run, dfc = [], []
+                for y in range(N.YEARS):
+                    k, dk = s.best_count[j * N.YEARS + y], s.best_deficit_count[j * N.YEARS + y]
+                    run.append(list(s.best_actions[pos:pos + k])); dfc.append(list(s.best_deficit_actions[dpos:dpos + dk]))
+                    pos += k; dpos += dk
+                out.append(Plan(run, dfc, s.names[j].decode() if s.names else ""))
+            return out
+        finally:
+            L.eg_plans_free(ps)
+
+    @staticmethod
+    def from_policy(weights: "ActionWeights", name: str = "") -> "Plan":
+        """The policy's current best lists (empty when it has none)."""
+        return Plan(weights.lists(0), weights.lists(1), name)
+
+    @staticmethod
+    def from_result(res: "BatchResult", e: int, name: str = "") -> "Plan":
+        """The lists update_best_strategy would install from episode e: its current_run_actions / current_deficit_actions by year
+        (ai/learning/strategy.rs)."""
+        return Plan(res.lists(e, "run"), res.lists(e, "def"), name)
+
+
+class PlanSet:
+    """Plans as one eg_plan_set (the arrays stay alive as long as this object)."""
+
+    def __init__(self, plans):
+        plans = list(plans)
+        self.count = np.array([[len(l) for l in p.best_actions] for p in plans], np.int32).reshape(len(plans), N.YEARS)
+        self.dcount = np.array([[len(l) for l in p.best_deficit_actions] for p in plans], np.int32).reshape(len(plans), N.YEARS)
+        self.act = np.array([a for p in plans for l in p.best_actions for a in l] or [0], np.uint8)
+        self.dact = np.array([a for p in plans for l in p.best_deficit_actions for a in l] or [0], np.uint8)
+        self.names = (C.c_char_p * max(len(plans), 1))(*[p.name.encode() for p in plans])
+        self.s = N.EgPlanSet(len(plans), _p(self.count, C.c_int32), _p(self.act, C.c_uint8), _p(self.dcount, C.c_int32),
+                             _p(self.dact, C.c_uint8), int(self.count.sum()), int(self.dcount.sum()), self.names)
+
+
 def _fetch_top_k(fn, handle, what):
     """(BatchResult of the n_held entries in rank order, scores [n_held], global indices [n_held]) of a top-K archive."""
     res = BatchResult.alloc(N.TOPK_MAX)
@@ -338,6 +405,20 @@ class Engine:
         """Single-episode form with the reference's argument order (core/iteration.rs:10-20)."""
         mask = np.array([1 if replay_best_strategy else 0], dtype=np.uint8)
         return self.rollout_batch(weights, seed, 1, iteration, mask, enable_energy_sales, enable_construction_delays)
+
+    def evaluate_plans(self, weights: ActionWeights, plans, seed: int, first_episode_index: int = 0, enable_energy_sales=True,
+                       write_yearly=True) -> BatchResult:
+        """Score given plans (eg_evaluate_plans): plan j is the replay episode at global index first_episode_index + j under `weights`,
+        with has_best = 1 and the plan as its best lists.  Trains nothing and leaves the resident policy alone; rank the results with
+        rank_score(res.metrics[j], cost_only)."""
+        ps = plans if isinstance(plans, PlanSet) else PlanSet(plans)
+        res = BatchResult.alloc(ps.s.n_plans)
+        snap = weights.snapshot()
+        opts = self._opts(enable_energy_sales, False, write_yearly)
+        out = res.struct()
+        N.check(N.lib().eg_evaluate_plans(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.c_uint64(seed & (2**64 - 1)),
+                                          C.c_uint64(first_episode_index), C.byref(out)), "eg_evaluate_plans")
+        return res
 
     # device-resident path used by bench.py
     def upload_snapshot(self, weights: ActionWeights, enable_energy_sales=True, write_yearly=True):

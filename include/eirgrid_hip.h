@@ -270,6 +270,41 @@ int32_t eg_top_k_track(eg_ctx *, int32_t k, int32_t mode);
 int32_t eg_fetch_top_k(eg_ctx *, eg_episode_out *out, int32_t *n_held, double *scores, int64_t *global_index);
 double eg_rank_score(const double metrics[4], int32_t mode);   /* mode 2: cost_only; 0 or 1: optimization_mode None */
 
+/* Plan evaluation: what does a given strategy score?  A PLAN is what update_best_strategy installs and a replay episode reads
+ * (ai/learning/strategy.rs; sampling.rs:76-145, :240-270): per year a list of canonical action indices 0..60 (best_actions) and the
+ * deficit actions, also as canonical indices (best_deficit_actions: an AddGenerator at 100 % or DoNothing), each flat list at most
+ * 4 096 entries.  eg_evaluate_plans(ctx, policy, opts, plans, seed, first_episode_index, out) runs plan j as global episode
+ * first_episode_index + j: exactly the replay episode (replay_mask = 1) that eg_rollout_batch runs at that index under a snapshot
+ * equal to `policy`, except that has_best = 1 and the replay lists are plan j's (both present).  Every other field of the policy is
+ * used as given, best_metrics included.  So a replay applies its deficit actions twice; when a year's list runs out the
+ * episode goes on with seeded draws from the policy's tables (seed + first_episode_index + j); in-episode nudges are discarded.
+ * An evaluation is not training: no statistics, no update packet, no best_result or top-K fold, and the context's resident policy
+ * (eg_policy_push / eg_device_step state, eg_fetch_best_run's record, the improvement log) is untouched — the policy goes to a device
+ * snapshot of its own.  What it leaves behind is the last batch: eg_last_batch_size() = n_plans and eg_fetch / eg_fetch_record
+ * return the plans' records (also copied into `out` when it is not NULL).  Evaluate between whole training steps, never between
+ * eg_device_rollout and eg_device_apply.  EG_ERR_BAD_ARG (with a message naming the plan and the field) for n_plans < 1, a NULL
+ * pointer, a negative count, counts that do not add up to the *_len of the flat data, an entry >= 61, a list over 4 096 entries;
+ * eg_plans_validate runs these checks alone.  A rank of an eg_group is refused (plan batches on a group are not supported).
+ *
+ * eg_plans_load reads plans from a file in the checkpoint schema (eg_policy_load_json: year-keyed best_actions /
+ * best_deficit_actions of SerializableAction; null = empty lists): one JSON document (a checkpoint: one plan) or JSON Lines (one
+ * object per non-blank line carrying both keys, optionally "name").  NULL + eg_last_error() on malformed input; the message names
+ * every bad line and field.  names[j] is "" when a line has none.  Free with eg_plans_free. */
+typedef struct {
+  int32_t n_plans;
+  const int32_t *best_count;            /* [n][26] */
+  const uint8_t *best_actions;          /* plan-major, then year-major: sum(best_count) entries */
+  const int32_t *best_deficit_count;    /* [n][26] */
+  const uint8_t *best_deficit_actions;  /* sum(best_deficit_count) entries */
+  int64_t best_actions_len, best_deficit_actions_len;   /* entries of the two flat arrays */
+  const char *const *names;             /* [n] or NULL */
+} eg_plan_set;
+int32_t eg_plans_validate(const eg_plan_set *);
+int32_t eg_evaluate_plans(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts *, const eg_plan_set *, uint64_t seed,
+                          uint64_t first_episode_index, eg_episode_out *out /* may be NULL */);
+eg_plan_set *eg_plans_load(const char *path);
+void eg_plans_free(eg_plan_set *);
+
 /* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
  * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
  * copies, no collective library — and every call enqueues the work of all ranks from the calling thread without synchronising
