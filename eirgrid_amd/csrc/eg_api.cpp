@@ -117,6 +117,9 @@ struct eg_ctx {
   uint64_t hoist_batches = 0;      // batches launched with the hoist armed (eg_replay_hoist_stats)
   int coop_force = 0;              // EIRGRID_COOP_FORCE (test hook): the hoisted searches' rarely-run paths
   long long* d_stats_rep = nullptr;      // kStatsReplicas copies of the statistics array (RolloutPlan::d_stats_rep); EIRGRID_STATS_REPLICAS=0: none
+  // set from a launch that adds to the copies until k_fold_stats (which clears them) is enqueued behind it: a batch that failed in
+  // between left partial sums there, and the next batch that uses the copies clears them first
+  bool stats_rep_dirty = false;
   // per-episode replay kernel (eg_replay_solo.h; EIRGRID_REPLAY_SOLO=0: off): a word per replay episode of a launch, the launches' sequence
   unsigned long long* d_solo = nullptr; uint32_t solo_cap = 0; unsigned long long solo_seq = 0;
   bool solo_on = true;
@@ -295,6 +298,11 @@ int launch_batch(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, con
     // (small batches add directly: a few hundred episodes do not queue up in L2, and the fold is a launch of its own — configs[1],
     //  1 024 episodes: 0.257 ms per batch without it, 0.264 with)
     plan.d_stats_rep = (off || n < 4096u) ? nullptr : c->d_stats_rep;
+    if (plan.d_stats_rep != nullptr && c->stats_rep_dirty) {      // (on the null stream, ahead of the fork to the replay stream;
+      if (c->stream_heavy) EG_HIP(hipStreamSynchronize(c->stream_heavy));      //  replay grids of that batch that were never joined end first)
+      EG_HIP(hipMemsetAsync(c->d_stats_rep, 0, sizeof(long long) * size_t(kStatsReplicas) * EG_STATS_LEN, nullptr));
+      c->stats_rep_dirty = false;
+    }
   }
   // long replay episodes: script / placements / rows, each on its own wave (eg_replay_solo.h) — unless the batch's replays are computed
   // once anyway (what ends that script ends this one as well: the classic variant alone is the fallback then)
@@ -325,6 +333,7 @@ int launch_batch(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, con
     // (the hoisted replay is one workgroup that needs a whole CU: it is dispatched ahead of the lean grid in any case)
     if (list_long || plan.hoist_seq != 0ull) plan.go_event = c->ev_go[slot];
   }
+  if (plan.d_stats_rep != nullptr) c->stats_rep_dirty = true;      // until the fold is enqueued: every return before it leaves them dirty
   const int lr = launch_rollout(c->dev, c->snap, c->out, seed, first_index, n, d_mask, period, d_stats, plan);
   if (lr != 0) { set_error(std::string("k_rollout launch: ") + hipGetErrorString((hipError_t)lr)); return EG_ERR_HIP; }
   if (split) {
@@ -334,6 +343,7 @@ int launch_batch(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, con
   if (d_stats != nullptr && plan.d_stats_rep != nullptr) {
     const int fs = launch_fold_stats(plan.d_stats_rep, d_stats, nullptr);
     if (fs != 0) { set_error(std::string("k_fold_stats launch: ") + hipGetErrorString((hipError_t)fs)); return EG_ERR_HIP; }
+    c->stats_rep_dirty = false;
   }
   if (c->fold_mode != 0) {      // behind the batch on the null stream: its results are in iteration order in the records
     const int fr = launch_fold_best(c->out, n, first_index, c->fold_mode == 2, c->d_fold, nullptr);

@@ -270,3 +270,85 @@ def test_cli_top_k_row_one_is_the_best_weights_metrics(built, tmp_path):
     assert got == [bm["final_net_emissions"], bm["average_public_opinion"], bm["total_cost"], bm["power_reliability"]]
     scores = [float(r[1]) for r in rows[1:]]
     assert scores == sorted(scores, reverse=True)
+
+
+def _block_entries(res, k, cost_only, spans):
+    """What k_topk_merge reads from a batch folded into an archive that is not full yet (every successful episode passes k_topk_keys),
+    restated: per span of episodes — a chunk of k_topk_select, or a rank's shard — its distinct scenarios (metrics bits, key) with a
+    rank score, at most k of them."""
+    from eirgrid_amd.engine import rank_score
+    key = keys(res.n_act, res.act_log)
+    total = 0
+    for lo, hi in spans:
+        ids = set()
+        for e in range(lo, hi):
+            s = rank_score(res.metrics[e], cost_only)
+            if res.status[e] == 0 and s == s:
+                ids.add((res.metrics[e].tobytes(), int(key[e])))
+        total += min(k, len(ids))
+    return total
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cost_only", [False, True])
+@pytest.mark.parametrize("k", [63, 64])
+def test_archive_at_production_size_is_the_host_restatement(world, k, cost_only):
+    """Four batches of 16 384 (configs[2]'s size: 16 blocks of k_topk_select) with the device update between them: the first batch's
+    blocks hold more than k_topk_merge's 512 list entries, so the merge compacts its list between blocks; after every batch the archive
+    is the restatement's, entries and records."""
+    from eirgrid_amd.engine import ActionWeights, Engine
+    eng = Engine(world, device=0)
+    try:
+        eng.push(ActionWeights())
+        eng.track_top_k(k, cost_only=cost_only)
+        ref = Archive(k, cost_only)
+        first, seed, n = 0, 4242, 16384
+        for b in range(4):
+            eng.device_step(seed, first, n, 10, seed + first)
+            res = eng.fetch(n)
+            if b == 0:
+                entries = _block_entries(res, k, cost_only, [(c, min(c + 1024, n)) for c in range(0, n, 1024)])
+                assert entries > 512, entries
+            want = ref.feed(eng, res, first)
+            assert_archive(eng.fetch_top_k(), want, ref.records, (k, cost_only, b))
+            first += n
+        assert len(want) == k
+        print(f"k {k} cost_only {cost_only}: the first batch's blocks hold {entries} entries")
+    finally:
+        eng.close()
+
+
+@pytest.mark.gpu
+def test_group_of_eight_ranks_archive_equals_one_context(world):
+    """Eight ranks on device 0 with K = 64.  A first step of 5 episodes leaves a few entries held, so that in the next one (16 384) the
+    archive is not full, every rank's block is full and each rank's merge reads held + 8 x 64 > 512 entries: it compacts its list
+    before the last block.  Steps whose global batch is smaller than eight leave shards empty.  After every step the archive equals one
+    context's, and that one the restatement's: one context runs the same merge kernel, and a fault in it can give both the same wrong
+    archive."""
+    from eirgrid_amd.engine import ActionWeights, Engine, Group
+    g = Group(world, devices=(0,) * 8)
+    single = Engine(world, device=0)
+    try:
+        w = ActionWeights()
+        g.push(w); single.push(w)
+        g.track_top_k(64); single.track_top_k(64)
+        ref = Archive(64, False)
+        first, seed = 0, 808
+        held = 0
+        for step, n in enumerate((5, 16384, 3, 16384, 8191, 4096)):
+            g.step(seed, first, n, 10, seed + first)
+            single.device_step(seed, first, n, 10, seed + first)
+            res = single.fetch(n)
+            if step == 1:
+                spans = [(o, o + c) for o, c in (_shard(n, r, 8) for r in range(8))]
+                entries = held + _block_entries(res, 64, False, spans)
+                assert 0 < held < 64 and entries > 512, (held, entries)
+            got, want = g.fetch_top_k(), single.fetch_top_k()
+            assert_same_archive(got, want, n)
+            assert_archive(want, ref.feed(single, res, first), ref.records, ("eight ranks", step))      # (and got == want)
+            held = len(want[2])
+            first += n
+        print(f"eight ranks: the 16 384-episode step's merges read {entries} entries")
+        assert len(got[2]) == 64
+    finally:
+        g.close(); single.close()

@@ -209,11 +209,13 @@ def _policy_state(w):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("devices,sizes", [((0, 0), [700, 513, None, 1, 300, 1]), ((0, 0, 0), [700, 512, None, 2, 301, 2])])
+@pytest.mark.parametrize("devices,sizes", [((0, 0), [700, 513, None, 1, 300, 1]), ((0, 0, 0), [700, 512, None, 2, 301, 2]),
+                                           ((0, 0), [8191, 8192, 1, 16385])])
 def test_group_replicas_equal_one_context(world, devices, sizes):
     """Every rank's policy is bit-identical to every other rank's and to one context's eg_device_step over the same global
     batches — also across steps whose shards are empty (n_global < N).  None in `sizes`: a fresh policy is pushed to both
-    sides, after which an empty shard's packet would still hold its candidate from before the push, were it sent as it is."""
+    sides, after which an empty shard's packet would still hold its candidate from before the push, were it sent as it is.  8 191 across
+    two ranks: one shard of 4 096 (replicated statistics) and one of 4 095 (added directly)."""
     from eirgrid_amd.engine import ActionWeights, Engine, Group
     g = Group(world, devices=devices)
     single = Engine(world, device=0)
