@@ -1,0 +1,164 @@
+// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_plans / eg_place / eg_group .cpp): owned buffers, the
+// error macros, the context and the helpers that cross units.  Host only: the kernels include eg_internal.h, never this.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <functional>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "eg_internal.h"
+
+#define EG_HIP(call) \
+  do { const hipError_t e_ = (call); if (e_ != hipSuccess) { eg::set_error(std::string(#call) + ": " + hipGetErrorString(e_)); return EG_ERR_HIP; } } while (0)
+// a launcher of eg_rollout.hip (they return the launch's hipError_t as an int): "k_x launch: <what HIP says>"
+#define EG_LAUNCH_AS(what, call) \
+  do { const int lr_ = (call); if (lr_ != 0) { eg::set_error(std::string(what ": ") + hipGetErrorString((hipError_t)lr_)); return EG_ERR_HIP; } } while (0)
+#define EG_LAUNCH(name, call) EG_LAUNCH_AS(name " launch", call)
+// a call that returns EG_OK or an error code with the error text set
+#define EG_TRY(call) do { const int rc_ = (call); if (rc_ != EG_OK) return rc_; } while (0)
+
+namespace eg {
+// An owned allocation of `count` elements of T in device memory (Pinned: in pinned host memory).  Move-only; converts to T*.
+template <typename T, bool Pinned = false>
+struct DevBuf {
+  T* ptr = nullptr; size_t count = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept { std::swap(ptr, o.ptr); std::swap(count, o.count); }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(ptr, o.ptr); std::swap(count, o.count); return *this; }
+  ~DevBuf() { release(); }
+  operator T*() const { return ptr; }
+  void release() { if (ptr) (void)(Pinned ? hipHostFree(ptr) : hipFree(ptr)); ptr = nullptr; count = 0; }
+  // Room for n elements: a new allocation of exactly n only when n exceeds what is held (what is held is what eg_memory_report tells),
+  // the old one freed first — hipFree waits for the launches that may still use it.  *fresh: whether the buffer is a new one (its
+  // contents undefined: the callers that rely on zeros clear it).  After a failure nothing is held.  `flags`: of hipHostMalloc.
+  hipError_t reserve(size_t n, bool* fresh = nullptr, unsigned flags = 0) {
+    if (fresh) *fresh = n > count;
+    if (n <= count) return hipSuccess;
+    release();
+    const hipError_t e = Pinned ? hipHostMalloc((void**)&ptr, sizeof(T) * n, flags) : hipMalloc((void**)&ptr, sizeof(T) * n);
+    if (e != hipSuccess) ptr = nullptr; else count = n;
+    return e;
+  }
+  // the same for callers that carry on without the buffer when memory is short: the sticky HIP error is cleared
+  bool try_reserve(size_t n, unsigned flags = 0) {
+    if (reserve(n, nullptr, flags) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+  }
+};
+template <typename T> using PinBuf = DevBuf<T, true>;
+}  // namespace eg
+
+struct eg_host_tables {
+  eg::HostTables H;
+  std::map<std::string, std::pair<const double*, int64_t>> f64;
+  std::map<std::string, std::pair<const int32_t*, int64_t>> i32;
+  void index();
+};
+
+struct eg_ctx {
+  int device = 0;
+  eg_host_tables tables;
+  eg::DevBuf<uint8_t> d_tables;      // the table blob (dev.base)
+  eg::DevTables dev{};
+  // snapshot in HBM: the whole snapshot lives in ONE device buffer filled by ONE copy from a pinned staging buffer
+  eg::DevBuf<uint8_t> d_snap; eg::PinBuf<uint8_t> h_snap;
+  eg::DevBuf<uint8_t> d_snap_held;      // eg_policy_hold / eg_policy_rewind
+  // the reference's best_result fold (multi_simulation.rs:613-620): 0 = not tracked, 1 = optimization_mode None, 2 = cost_only
+  int fold_mode = 0; eg::DevBuf<uint8_t> d_fold;
+  bool group_member = false;      // owned by an eg_group: the group folds its ranks' results (eg_group_best_result_track), never the context itself
+  // the top-K archive of distinct scenarios (eg_top_k_track; eg_topk.h): 0 = not tracked, 1 = mode None, 2 = cost_only; d_topk: TopKState
+  // and the record slots; per batch, the rank score and key of every episode and one block per chunk (also a group rank's scratch)
+  int topk_mode = 0, topk_k = 0; eg::DevBuf<uint8_t> d_topk;
+  eg::DevBuf<double> d_tk_score; eg::DevBuf<unsigned long long> d_tk_key; eg::DevBuf<eg::TopKBlock> d_tk_blocks;
+  // Is the best list long (the replay episodes run the heavy-capable variant and are the batch's long pole)?  `list_exact`: the host
+  // KNOWS the list the next launch will find on the device (it uploaded, rewound or pulled it and no on-device update has been
+  // enqueued since): the replay variant that has nothing to do is then not launched at all.  Otherwise the device may have replaced
+  // the list since the host last looked — both variants are launched and decide for themselves — and the hint only orders the
+  // launches; it follows the device through `h_list_len`, a pinned host word that k_apply_update and k_rewind write the list's
+  // length to (read without synchronising: as old as the launch queue is deep).
+  bool long_list_hint = false, long_list_hint_held = false, list_exact = false, list_exact_held = false;
+  eg::PinBuf<uint32_t> h_list_len; uint32_t* d_list_len = nullptr;      // the same pinned word, host and device address
+  eg::DevSnapshot snap{};
+  bool snap_valid = false;
+  // outputs: the records and the score list in one buffer (ensure_outputs); `out` points into it
+  eg::DevBuf<uint8_t> d_out; eg::DevOut out{};
+  uint32_t last_n = 0;
+  uint64_t last_first = 0;      // global index of the first episode of the last batch
+  eg::DevBuf<uint8_t> d_mask;
+  // timing: a ring of event pairs riding on the rollout dispatches.  A pair is only waited for when the ring comes round to
+  // it again (kTimingRing launches later: long finished) or when the caller reads the timing — never inside a training step.
+  static constexpr int kTimingRing = 256;
+  hipEvent_t ev[kTimingRing][4] = {};       // start / stop of the heavy grid, start / stop of the lean grid (eg_internal.h RolloutPlan)
+  uint8_t ev_used[kTimingRing] = {};        // bit 0: the heavy pair was recorded, bit 1: the lean pair
+  hipStream_t stream_heavy = nullptr;   // the replay grids of a split batch run beside the lean grid (which stays on the null stream)
+  hipEvent_t ev_fork[kTimingRing] = {}, ev_go[kTimingRing] = {}, ev_join[kTimingRing] = {};
+  eg::DevBuf<uint32_t> d_index;         // replay / other episode indices of a host-masked batch
+  int ring_head = 0, ring_pending = 0;      // next pair to use; pairs recorded and not yet collected (the oldest is head - pending)
+  double total_ms = 0.0; int32_t n_launches = 0;
+  double grids_ms = 0.0;      // the same launches, every grid's own duration added up (== total_ms when a batch is one grid)
+  // eg_place / eg_find_suitable_location: device buffers kept between calls (d_place_xy: the x, then the y, half the buffer each)
+  eg::DevBuf<uint16_t> d_place_cells; eg::DevBuf<int32_t> d_place_cell; eg::DevBuf<double> d_place_score, d_place_xy;
+  uint32_t push_iteration_count = 0;     // iteration counter written into the device state by the next upload
+  uint32_t push_failed = 0;              // ... and the failed-episode counter
+  uint32_t pulled_improvements = 0;      // on-device improvement log entries already appended to a host policy
+  // eg_train_step / eg_device_step: library-owned update packet (device) and its pinned host copy
+  eg::DevBuf<uint8_t> d_packet; eg::PinBuf<uint8_t> h_packet;
+  // batches of at most this many episodes run the helper-wave kernel (three waves per episode, all resident at once)
+  uint32_t helper_max_episodes = 0;
+  // heavy episodes (eg_rollout.hip place_heavy): pool of penalty fields, one slot per episode that outgrows kHeavyGens (d_heavy, d_heavy_claim: what dev.heavy* point to)
+  // EIRGRID_HEAVY_POOL_GB (default 64): what the pool may grow to, 126 KB per replay episode of a launch; 131 072 replay episodes
+  // (an all-replay batch of configs[3]'s size) want 16 GB.  eg_memory_report tells what is held.
+  eg::DevBuf<uint8_t> d_heavy; eg::DevBuf<unsigned> d_heavy_claim;
+  uint32_t heavy_slots_max = 0, heavy_slots_wanted = 4096, launch_epoch = 0;
+  bool heavy_slots_auto = true;      // (EIRGRID_HEAVY_SLOTS fixes the pool size instead)
+  // replay hoist (eg_replay_coop.h; eg_replay_hoist / EIRGRID_REPLAY_HOIST=1): the replay episodes of a batch computed once.
+  // d_hoist: HoistInfo {u64 sequence number of the last batch whose hoist succeeded, i32 lengths[5]}; d_coop: the scratch record.
+  bool hoist_on = false, hoist_supported = false;
+  unsigned long long hoist_seq = 0;
+  eg::DevBuf<uint8_t> d_hoist, d_coop;
+  uint64_t hoist_batches = 0;      // batches launched with the hoist armed (eg_replay_hoist_stats)
+  int coop_force = 0;              // EIRGRID_COOP_FORCE (test hook): the hoisted searches' rarely-run paths
+  eg::DevBuf<long long> d_stats_rep;      // kStatsReplicas copies of the statistics array (RolloutPlan::d_stats_rep); EIRGRID_STATS_REPLICAS=0: none
+  // set from a launch that adds to the copies until k_fold_stats (which clears them) is enqueued behind it: a batch that failed in
+  // between left partial sums there, and the next batch that uses the copies clears them first
+  bool stats_rep_dirty = false;
+  // per-episode replay kernel (eg_replay_solo.h; EIRGRID_REPLAY_SOLO=0: off): a word per replay episode of a launch, the launches' sequence
+  eg::DevBuf<unsigned long long> d_solo; unsigned long long solo_seq = 0;
+  bool solo_on = true;
+  // plan batches (eg_evaluate_plans): the evaluated policy's own snapshot (the resident one in d_snap stays untouched), the plan blocks
+  // (snap::kPlanStride bytes each) and the index lists of the short and the long plans
+  eg::DevBuf<uint8_t> d_eval_snap, d_plans;
+  eg::DevBuf<uint32_t> d_plan_index;
+};
+
+namespace eg {
+// the two process-wide switches, read from the environment at first use (eg_api.cpp, next to the context's options)
+bool stats_replicas_off();      // EIRGRID_STATS_REPLICAS=0
+bool fetch_full();              // EIRGRID_FETCH_FULL=1
+// eg_api.cpp
+int ensure_outputs(eg_ctx* c, uint32_t n);
+int prepare_heavy(eg_ctx* c, uint32_t n_heavy, bool known_short);
+int ring_take(eg_ctx* c, RolloutPlan& plan, int& slot);
+void ring_commit(eg_ctx* c, int slot, int ev_used);
+int arm_solo(eg_ctx* c, RolloutPlan& plan, uint32_t n);
+int device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, size_t packet_stride, void* d_own_packet, uint64_t noise_seed, bool local_pick);
+// eg_plans.cpp
+int check_policy(const eg_policy_snapshot* s, const eg_opts* o, const char* who);
+void stage_policy(eg_ctx* c, const eg_policy_snapshot* s, bool have_lists, uint8_t* h);
+DevSnapshot snapshot_of(uint8_t* d_base, const eg_opts* o);
+// eg_fetch.cpp
+int fetch_records(const uint8_t* d_base, size_t N, eg_episode_out* o);
+int fold_reset(DevBuf<uint8_t>& d_fold);
+int topk_reset(DevBuf<uint8_t>& d_topk, int k, int mode);
+int topk_select(eg_ctx* c, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state, int k);
+inline uint32_t topk_chunks(uint32_t n) { return (n + kTopKChunk - 1u) / kTopKChunk; }
+// The entries of the archive state `st` into the caller's rows: archive_of(i, entry) is the device archive (TopKState, then the record
+// slots) that holds entry i's record, made current on its device — or NULL with the error text set.  `who` names the entry point.
+int fetch_topk_rows(const char* who, const TopKState& st, const std::function<const uint8_t*(int, const TopKEntry&)>& archive_of,
+                    eg_episode_out* o, int32_t* n_held, double* scores, int64_t* global_index);
+
+}  // namespace eg

@@ -366,7 +366,7 @@ int launch_stalled_tables(uint8_t* d_snap, void* stream);
 int launch_rewind(uint8_t* d_snap, const uint8_t* d_held, uint32_t* list_len_out, void* stream);
 // `o`, n_local, first_index: the batch the own packet came from (the winner's record is kept when it is one of them)
 // local_pick: one packet, made by this device's last batch — the candidate record is built inside the kernel
-// packet_stride: bytes from one packet to the next in d_packets (EG_PACKET_BYTES, or a group's gathered slots, eg_api.cpp eg_group)
+// packet_stride: bytes from one packet to the next in d_packets (EG_PACKET_BYTES, or a group's gathered slots, eg_group.cpp)
 int launch_apply_update(uint8_t* d_snap, const void* d_packets, int n_packets, size_t packet_stride, long long* d_zero_stats, uint64_t noise_seed,
                         const DevOut& o, uint32_t n_local, uint64_t first_index, bool local_pick, uint32_t* list_len_out, void* stream);
 int launch_place(const DevTables& t, int gen_type, int year_index, const uint16_t* d_cells, int n_extra,
@@ -402,7 +402,7 @@ constexpr size_t kFoldRecord = 64;
 constexpr size_t kFoldBytes = kFoldRecord + rec::stride;
 static_assert(sizeof(FoldState) <= kFoldRecord, "fold state layout");
 int launch_fold_best(const DevOut& o, uint32_t n, uint64_t first_index, bool cost_only, uint8_t* d_fold, void* stream);
-// The same fold over the ranks of a group (eg_api.cpp eg_group; eg_rollout.hip k_fold_pack / k_fold_gathered).  Every rank packs what the
+// The same fold over the ranks of a group (eg_group.cpp; eg_rollout.hip k_fold_pack / k_fold_gathered).  Every rank packs what the
 // fold reads of its shard into a block of FoldEntry behind its update packet; the blocks travel with the packets, and every rank folds
 // all of them in rank order (= global index order).  The state is replicated: identical on every rank.  The record is copied only by
 // the rank whose shard held the winner, which tags it with the winner's global index and the group step of the take-over.

@@ -1,0 +1,155 @@
+// eg_plans.cpp — a policy in snapshot layout (shared with eg_upload_snapshot) and plan batches: eg_evaluate_plans, launch_plans.
+#include <algorithm>
+#include <cstring>
+
+#include "eg_host.h"
+#define EG_RM static inline
+#include "eg_reduced_math.h"
+
+using namespace eg;
+
+// What eg_upload_snapshot and eg_evaluate_plans refuse in a policy snapshot (the pointers are checked by the caller)
+int eg::check_policy(const eg_policy_snapshot* s, const eg_opts* o, const char* who) {
+  if (o && o->enable_construction_delays) { set_error("enable_construction_delays is not implemented on the device (SURVEY §8(f) N4)"); return EG_ERR_UNSUPPORTED; }
+  // the device walks rely on strictly positive weights (the reference clamps every weight to [1e-4, 0.999])
+  for (int i = 0; i < EG_YEARS * EG_N_ACTIONS; ++i) if (!(s->weights[i] > 0.0)) { set_error(std::string(who) + ": weights must be > 0"); return EG_ERR_BAD_ARG; }
+  for (int i = 0; i < EG_YEARS * EG_N_DEFICIT; ++i) if (!(s->deficit_weights[i] > 0.0)) { set_error(std::string(who) + ": deficit weights must be > 0"); return EG_ERR_BAD_ARG; }
+  return EG_OK;
+}
+namespace {
+// The list section of a snapshot at `dst` (snap::best_mask .. snap::state; a plan block has the same layout): per year the masks
+// (bit a: a occurs in best(y) or best_deficit(y) / in best_deficit(y)), the prefix offsets and the two lists.  count == NULL: none.
+// The lists' total lengths are the caller's to check (<= snap::kBestCap).
+void write_lists(uint8_t* dst, const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact) {
+  constexpr size_t b = snap::best_mask;
+  int32_t off[28] = {0}, offd[28] = {0};
+  unsigned long long mask[26] = {0}, dmask[26] = {0};
+  if (count)
+    for (int y = 0; y < EG_YEARS; ++y) {
+      off[y + 1] = off[y] + count[y]; offd[y + 1] = offd[y] + dcount[y];
+      for (int i = off[y]; i < off[y + 1]; ++i) if (act[i] < 64) mask[y] |= 1ull << act[i];
+      for (int i = offd[y]; i < offd[y + 1]; ++i) if (dact[i] < 64) { mask[y] |= 1ull << dact[i]; dmask[y] |= 1ull << dact[i]; }
+    }
+  std::memcpy(dst + (snap::best_mask - b), mask, sizeof(mask)); std::memcpy(dst + (snap::bestd_mask - b), dmask, sizeof(dmask));
+  std::memcpy(dst + (snap::best_off - b), off, sizeof(off)); std::memcpy(dst + (snap::bestd_off - b), offd, sizeof(offd));
+  if (count) { std::memcpy(dst + (snap::best_actions - b), act, size_t(off[26])); std::memcpy(dst + (snap::bestd_actions - b), dact, size_t(offd[26])); }
+}
+}  // namespace
+// The policy `s` in snapshot layout into the staging buffer h (snap::upload_bytes): packed rows, list section, scalars
+void eg::stage_policy(eg_ctx* c, const eg_policy_snapshot* s, bool have_lists, uint8_t* h) {
+  {  // packed policy rows; sampling.rs:182, :352-355, :406: the sums the samplers start from, folded in table order
+    double* pol = reinterpret_cast<double*>(h + snap::pol);
+    std::memset(pol, 0, sizeof(double) * EG_YEARS * snap::kPolRow);
+    for (int y = 0; y < EG_YEARS; ++y) {
+      double* row = pol + y * snap::kPolRow;
+      double a = 0.0, b = 0.0, c2 = 0.0;
+      for (int i = 0; i < EG_N_ACTIONS; ++i) { row[i] = s->weights[y * EG_N_ACTIONS + i]; a += row[i]; }
+      for (int i = 0; i < EG_N_DEFICIT; ++i) row[snap::kPolDw + i] = s->deficit_weights[y * EG_N_DEFICIT + i];
+      for (int i = 0; i < 14; ++i) b += s->deficit_weights[y * EG_N_DEFICIT + i];
+      if (s->count_weights) for (int i = 0; i < EG_N_COUNTS; ++i) { row[snap::kPolCw + i] = s->count_weights[y * EG_N_COUNTS + i]; c2 += row[snap::kPolCw + i]; }
+      row[snap::kPolTotMain] = a; row[snap::kPolTotDeficit] = b; row[snap::kPolTotCount] = c2;
+      const HostTables& H = c->tables.H;      // the year's world scalars ride along (eg_internal.h, snap::kPolYear)
+      double* ys = row + snap::kPolYear;
+      ys[0] = H.pre_co2[y]; ys[1] = H.pre_tg[y]; ys[2] = H.pre_ig[y]; ys[3] = H.pre_sg[y]; ys[4] = H.pre_optot[y];
+      ys[5] = H.usage[y]; ys[6] = H.population[y]; ys[7] = H.inflation[y]; ys[8] = H.carbon_price[y]; ys[9] = double(H.pre_opcnt[y]);
+    }
+  }
+  if (have_lists) write_lists(h + snap::best_mask, s->best_count, s->best_actions, s->best_deficit_count, s->best_deficit_actions);
+  else write_lists(h + snap::best_mask, nullptr, nullptr, nullptr, nullptr);
+  {  // the policy's scalars as the kernels read them (snap::state)
+    DevState st{};
+    st.learning_rate = s->learning_rate; st.exploration_rate = s->exploration_rate;
+    for (int i = 0; i < 4; ++i) st.best_metrics[i] = s->has_best ? s->best_metrics[i] : 0.0;
+    st.stall = s->iterations_without_improvement; st.iteration_count = c->push_iteration_count; st.failed_total = c->push_failed;
+    st.has_best = s->has_best ? 1 : 0; st.has_cw = s->count_weights ? 1 : 0; st.has_lists = have_lists ? 1 : 0;
+    rm::derive_state(st);
+    std::memcpy(h + snap::state, &st, sizeof(st));
+  }
+}
+// what the kernels get of a snapshot at d_base and the caller's options (none: the defaults)
+DevSnapshot eg::snapshot_of(uint8_t* d_base, const eg_opts* o) {
+  DevSnapshot S{};
+  S.base = d_base;
+  S.enable_energy_sales = o ? (o->enable_energy_sales ? 1 : 0) : 1;
+  S.write_yearly = o ? (o->write_yearly ? 1 : 0) : 1;
+  return S;
+}
+
+namespace {
+// A plan batch (eg_evaluate_plans) over the n episodes of c->out: c->d_plan_index lists the n_short short plans (<= kShortReplayMax
+// actions), then the long ones.  The short-replay variant runs over exactly the short ones; the long ones go to k_replay_solo and the
+// long-replay variant, in launches of at most as many episodes as the penalty-field pool has slots (a long replay claims one per
+// launch epoch).  The hoist, the statistics epilogue and the best_result / top-K folds do not run.
+int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short) {
+  const uint32_t n_long = n - n_short;
+  const bool helper = n <= c->helper_max_episodes;
+  uint32_t done = 0;
+  for (bool first = true; first || done < n_long; first = false) {
+    uint32_t chunk = n_long - done;
+    EG_TRY(prepare_heavy(c, chunk, chunk == 0));
+    if (c->dev.heavy && chunk > c->dev.heavy_slots) chunk = c->dev.heavy_slots;
+    RolloutPlan plan{};
+    plan.plans = true; plan.helper_waves = helper;
+    plan.n_short = first ? n_short : 0u;
+    plan.n_heavy = plan.n_short + chunk; plan.n_lean = 0; plan.mode = 1u;
+    plan.d_index = c->d_plan_index; plan.d_index_long = c->d_plan_index + n_short + done;
+    if (chunk > 0 && !helper) EG_TRY(arm_solo(c, plan, chunk));
+    int slot = 0;
+    EG_TRY(ring_take(c, plan, slot));
+    EG_LAUNCH_AS("k_rollout launch (plan batch)", launch_rollout(c->dev, S, c->out, seed, first_index, n, nullptr, 1u, nullptr, plan));
+    ring_commit(c, slot, 1);
+    done += chunk;
+  }
+  c->last_n = n; c->last_first = first_index;
+  return EG_OK;
+}
+}  // namespace
+
+extern "C" int32_t eg_evaluate_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* p, uint64_t seed, uint64_t first_index,
+                          eg_episode_out* out) {
+  if (!c || !s || !s->weights || !s->deficit_weights) { set_error("eg_evaluate_plans: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->group_member) { set_error("eg_evaluate_plans: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_plans_validate(p));
+  EG_TRY(check_policy(s, o, "eg_evaluate_plans"));
+  EG_HIP(hipSetDevice(c->device));
+  const uint32_t n = uint32_t(p->n_plans);
+  EG_TRY(ensure_outputs(c, n));
+  // the plan blocks (the list section's layout, one per plan) and the routing: the short plans' indices first, then the long ones'
+  std::vector<uint8_t> blocks(size_t(n) * snap::kPlanStride, 0);
+  std::vector<uint32_t> idx(n);
+  uint32_t n_short = 0;
+  {
+    std::vector<uint32_t> longs;
+    int64_t pos = 0, dpos = 0;
+    for (uint32_t j = 0; j < n; ++j) {
+      const int32_t* cnt = p->best_count + size_t(j) * EG_YEARS;
+      const int32_t* dcnt = p->best_deficit_count + size_t(j) * EG_YEARS;
+      int64_t len = 0, dlen = 0;
+      for (int y = 0; y < EG_YEARS; ++y) { len += cnt[y]; dlen += dcnt[y]; }
+      write_lists(blocks.data() + size_t(j) * snap::kPlanStride, cnt, p->best_actions + pos, dcnt, p->best_deficit_actions + dpos);
+      pos += len; dpos += dlen;
+      if (len > kShortReplayMax) longs.push_back(j); else idx[n_short++] = j;
+    }
+    std::copy(longs.begin(), longs.end(), idx.begin() + n_short);
+  }
+  EG_HIP(c->d_plans.reserve(blocks.size()));
+  EG_HIP(c->d_plan_index.reserve(n));
+  EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+  // then the policy, in a device snapshot of its own: has_best = 1 and lists present (empty: every episode reads its plan block instead).
+  // (Last before the launches: a launch's start event takes the time the stream's previous command ended — with the snapshot staged
+  //  first, eg_timing_read counted the host building the plan blocks.)
+  eg_policy_snapshot ps = *s;
+  static const int32_t kNoCounts[EG_YEARS] = {};
+  static const uint8_t kNoActions[1] = {0};
+  ps.has_best = 1; ps.best_count = kNoCounts; ps.best_deficit_count = kNoCounts; ps.best_actions = kNoActions; ps.best_deficit_actions = kNoActions;
+  EG_HIP(c->d_eval_snap.reserve(snap::upload_bytes));
+  EG_HIP(hipStreamSynchronize(nullptr));   // the pinned staging buffer may still feed the previous copy
+  stage_policy(c, &ps, true, c->h_snap);
+  EG_HIP(hipMemcpyAsync(c->d_eval_snap, c->h_snap, snap::upload_bytes, hipMemcpyHostToDevice, nullptr));
+  EG_LAUNCH("k_stalled_tables", launch_stalled_tables(c->d_eval_snap, nullptr));      // sampling.rs:190-220, as at upload
+  DevSnapshot S = snapshot_of(c->d_eval_snap, o);
+  S.plan_pool = c->d_plans;
+  EG_TRY(launch_plans(c, S, seed, first_index, n, n_short));
+  return out ? eg_fetch(c, out) : EG_OK;
+}

@@ -1,4 +1,4 @@
-// eg_reduced_math.h — scalar formulas of the batch ("reduced") update, shared by the host (eg_policy.cpp, eg_api.cpp)
+// eg_reduced_math.h — scalar formulas of the batch ("reduced") update, shared by the host (eg_policy.cpp, eg_plans.cpp, eg_fetch.cpp)
 // and the device (k_apply_update, the statistics epilogue).  Every transcendental goes through include/eg_detpow.h
 // (IEEE + - * / and bit operations only, no FMA contraction), so the host and the device compute the same bits and a
 // policy that is updated on the device stays identical to one updated on the host from the same packets.

@@ -50,7 +50,7 @@ constexpr int kPer = (kCells + kThreads - 1) / kThreads;      // candidate cells
 constexpr int kEnt = 1024 / kThreads;                         // entries of the field update per lane: 2
 constexpr double kKeepCoop = 1.0 - 0x1p-30;
 constexpr int kVariants = 8;                                  // (radius class, marine) pairs whose scores a lane keeps in registers — the reference's
-                                                              // fifteen types make eight; a world with more is not hoisted (eg_api.cpp)
+                                                              // fifteen types make eight; a world with more is not hoisted (eg_device_tables.cpp)
 constexpr int kSpare = kFieldStride - 2;                      // where a field update that falls off the grid goes (class-relative; never a candidate)
 static_assert(kPer <= 16 && (kPer - 1) * kThreads < kCells && kFieldStride >= kCells + 2, "cell slots of a lane; padding of a class's field");
 

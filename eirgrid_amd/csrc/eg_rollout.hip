@@ -317,7 +317,7 @@ __device__ __forceinline__ void load_static_tables(const DevTables& T, int lane,
 // ---- placement: arg-max over the 51x51 distinct candidates (Q10) -------------------------------------------
 // Reference (metal_location_search.rs:110-176): score(c) = ((te[c] * prod_{g in list order, d<R} d/R) * coast(c)) * 0.9,
 // keep the first strictly greater score in (i, j) order, i.e. the maximum with ties to the lowest cell index.
-// Here the candidates of (year, radius class, marine) come pre-sorted by their unpenalised score (host, eg_api.cpp).
+// Here the candidates of (year, radius class, marine) come pre-sorted by their unpenalised score (host, eg_device_tables.cpp).
 // Every penalty factor is in [0, 1] and IEEE multiplication is monotone, so score(c) <= base(c): the scan takes 64
 // candidates at a time (one per lane, each lane folding the generator list in order for its own cell) and stops as
 // soon as the next chunk's largest base score is below the best score found — the same winner, bit for bit, as the
@@ -1098,7 +1098,7 @@ __device__ __forceinline__ int heavy_claim(const DevTables& T, int lane) {
   return __builtin_amdgcn_readfirstlane(slot);
 }
 // field[rc][c] *= d/R of a generator at `cell`, for every class and every cell closer than the class radius.  The cells
-// concerned are the same for every generator up to a translation: the host lists them once (eg_api.cpp, tab::hv_box: 978
+// concerned are the same for every generator up to a translation: the host lists them once (eg_device_tables.cpp, tab::hv_box: 978
 // entries {di, dj, squared distance, class} for the reference's six radii, padded to 1024 = 16 per lane) and the heavy
 // variant keeps the list in LDS.  One memory round trip: every lane requests its 16 field entries, then multiplies and
 // stores.  Entries are distinct, so the order is free.
@@ -1903,7 +1903,7 @@ __global__ void __launch_bounds__(kWave * (1 + kHelpers), kKind == kReplayLong ?
   const int lane = threadIdx.x & (kWave - 1);
   if (blockIdx.x >= emap.count) return;
   if constexpr (kReplay) {      // (uniform for the whole grid)
-    // (a plan batch launches each variant over exactly the plans it serves: eg_api.cpp launch_plans)
+    // (a plan batch launches each variant over exactly the plans it serves: eg_plans.cpp launch_plans)
     const bool long_list = S_in.state()->has_lists && S_in.resident_list_len() > kShortReplayMax;
     if (S_in.plan_pool == nullptr && long_list != kHeavy) return;
     if (emap.hoist_seq != 0ull && *emap.hoist == emap.hoist_seq) return;      // served by k_replay_coop / k_replay_broadcast
@@ -2713,7 +2713,7 @@ __global__ void __launch_bounds__(1024) k_fold_best(DevOut O, uint32_t n, unsign
   }
 }
 
-// ---- the same fold over the ranks of a group (eg_api.cpp eg_group_step) -------------------------------------------------
+// ---- the same fold over the ranks of a group (eg_group.cpp eg_group_step) -------------------------------------------------
 // k_fold_pack runs behind a rank's rollout: what fold_impact reads of each result of the shard, 32 bytes apart (in the records
 // they are rec::stride = 41.6 KB apart), written into the block that travels behind the rank's update packet.  With n == 0 it
 // makes the packet an empty shard's message instead: eg_device_rollout(n = 0) does not touch the packet, which still holds the

@@ -1,4 +1,4 @@
-"""GPU: plan evaluation (include/eirgrid_hip.h eg_evaluate_plans; csrc/eg_api.cpp launch_plans; the per-episode list base of the
+"""GPU: plan evaluation (include/eirgrid_hip.h eg_evaluate_plans; csrc/eg_plans.cpp launch_plans; the per-episode list base of the
 replay kernels).  Plan j under policy P is the replay episode at global index first + j under a snapshot equal to P with has_best = 1
 and the plan as its best lists.  Bar: every record bit-identical to the tabled oracle and to the replay batches the library already
 runs; an evaluation leaves the training state of its context untouched."""
