@@ -62,6 +62,13 @@ class EgPlanSet(C.Structure):
                 ("names", C.POINTER(C.c_char_p))]
 
 
+class EgPlanEdit(C.Structure):
+    _fields_ = [("kind", C.c_uint8), ("list", C.c_uint8), ("year", C.c_uint16), ("pos", C.c_uint32), ("action", C.c_uint8)]
+
+
+EDIT_NONE, EDIT_DELETE, EDIT_REPLACE, EDIT_INSERT = 0, 1, 2, 3
+PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
+
 # every symbol include/eirgrid_hip.h declares
 EXPORTS = [
     "eg_build_hash", "eg_last_error", "eg_device_count", "eg_create", "eg_destroy", "eg_rollout_batch", "eg_upload_snapshot",
@@ -71,6 +78,7 @@ EXPORTS = [
     "eg_group_create", "eg_group_destroy", "eg_group_rank", "eg_group_push", "eg_group_step", "eg_group_pull", "eg_group_replay_hoist",
     "eg_group_best_result_track", "eg_group_fetch_best_result", "eg_top_k_track", "eg_fetch_top_k", "eg_rank_score",
     "eg_group_top_k_track", "eg_group_fetch_top_k", "eg_plans_validate", "eg_evaluate_plans", "eg_plans_load", "eg_plans_free",
+    "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -212,6 +220,16 @@ def lib():
     L.eg_evaluate_plans.restype = C.c_int32
     L.eg_evaluate_plans.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.c_uint64, C.c_uint64,
                                     C.POINTER(EgEpisodeOut)]
+    # EIRGRID_LIB names another build of the library for an A/B measurement (scripts/plan_edit_probe.py times the host path of a build of
+    # the parent commit, which has no plan edits): such a build may lack these symbols and still loads.  The shipped library must have them.
+    if hasattr(L, "eg_evaluate_plan_edits") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_plan_edits_validate.restype = C.c_int32
+        L.eg_plan_edits_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgPlanEdit), C.c_int32]
+        L.eg_debug_fetch_plan_block.restype = C.c_int32
+        L.eg_debug_fetch_plan_block.argtypes = [C.c_void_p, C.c_uint32, _u8p]
+        L.eg_evaluate_plan_edits.restype = C.c_int32
+        L.eg_evaluate_plan_edits.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgPlanEdit),
+                                             C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(EgEpisodeOut)]
     L.eg_plans_load.restype = C.POINTER(EgPlanSet)
     L.eg_plans_load.argtypes = [C.c_char_p]
     L.eg_plans_free.argtypes = [C.POINTER(EgPlanSet)]

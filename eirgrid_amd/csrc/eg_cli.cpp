@@ -50,6 +50,8 @@ struct Args {   // cli/cli.rs:5-59
   int32_t top_k = 0;            // --top-k K: keep the K best distinct scenarios of the run (eg_top_k_track) and export them; 0: off
   std::string evaluate;         // --evaluate FILE: score the plans of FILE (eg_evaluate_plans) and exit; no training
   std::string evaluate_policy;  // --evaluate-policy CKPT: the policy the plans are evaluated under (default: ActionWeights::new)
+  std::string sensitivity;      // --sensitivity FILE: score every one-entry edit of FILE's first plan (eg_evaluate_plan_edits) and exit
+  std::vector<uint8_t> sensitivity_replace;      // --sensitivity-replace a,b,...: also every best_actions entry replaced by each of these
 };
 
 void usage() {
@@ -77,7 +79,12 @@ void usage() {
             "                           optional name) and exit: plan j replays as iteration j of --seed [default 0], --batch plans per\n"
             "                           launch; writes <checkpoint-dir>/<stamp>/plans/index.csv, with --top-k K also the K best plans'\n"
             "                           exports in plans/top_k/; no training runs\n"
-            "      --evaluate-policy <CKPT>  the policy the plans are evaluated under [default: a fresh one]");
+            "      --evaluate-policy <CKPT>  the policy the plans (or the edits of --sensitivity) are evaluated under [default: a fresh one]\n"
+            "      --sensitivity <FILE> which actions of a plan matter: the first plan of FILE (as --evaluate reads it) is scored as it is and\n"
+            "                           with every entry of its two lists deleted in turn, all as iteration 0 of --seed [default 0] on one\n"
+            "                           device; writes <checkpoint-dir>/<stamp>/sensitivity/index.csv (metrics, score and their\n"
+            "                           differences from the unedited plan, one row per edit) and exits; no training runs\n"
+            "      --sensitivity-replace <a,b,...>  also every best_actions entry replaced by each of these canonical actions (0..60)");
 }
 
 bool parse(int argc, char** argv, Args& a) {
@@ -146,6 +153,20 @@ bool parse(int argc, char** argv, Args& a) {
     }
     else if (s == "--evaluate") a.evaluate = v();
     else if (s == "--evaluate-policy") a.evaluate_policy = v();
+    else if (s == "--sensitivity") a.sensitivity = v();
+    else if (s == "--sensitivity-replace") {
+      const std::string list = v();
+      for (size_t pos = 0; pos <= list.size();) {
+        const size_t comma = std::min(list.find(',', pos), list.size());
+        const std::string item = list.substr(pos, comma - pos);
+        if (item.empty() || item.size() > 2 || item.find_first_not_of("0123456789") != std::string::npos || std::atoi(item.c_str()) >= EG_N_ACTIONS) {
+          std::fprintf(stderr, "error: --sensitivity-replace needs a comma-separated list of canonical actions 0..%d, got '%s'\n", EG_N_ACTIONS - 1, list.c_str());
+          return false;
+        }
+        a.sensitivity_replace.push_back(uint8_t(std::atoi(item.c_str())));
+        pos = comma + 1;
+      }
+    }
     else if (s == "-h" || s == "--help") { usage(); std::exit(0); }
     else { std::fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage(); return false; }
   }
@@ -156,7 +177,10 @@ bool parse(int argc, char** argv, Args& a) {
     return false;
   }
   if (a.ranks.size() == 1) a.device = a.ranks[0];      // one rank: the single-device run on that device
-  if (!a.evaluate_policy.empty() && a.evaluate.empty()) { std::fprintf(stderr, "error: --evaluate-policy needs --evaluate\n"); return false; }
+  if (!a.evaluate_policy.empty() && a.evaluate.empty() && a.sensitivity.empty()) { std::fprintf(stderr, "error: --evaluate-policy needs --evaluate or --sensitivity\n"); return false; }
+  if (!a.sensitivity_replace.empty() && a.sensitivity.empty()) { std::fprintf(stderr, "error: --sensitivity-replace needs --sensitivity\n"); return false; }
+  if (!a.sensitivity.empty() && !a.evaluate.empty()) { std::fprintf(stderr, "error: --sensitivity and --evaluate are separate runs\n"); return false; }
+  if (!a.sensitivity.empty() && a.ranks.size() > 1) { std::fprintf(stderr, "error: --sensitivity runs on one device (no --gpus / --devices)\n"); return false; }
   if (!a.evaluate.empty() && a.ranks.size() > 1) { std::fprintf(stderr, "error: --evaluate runs on one device (no --gpus / --devices)\n"); return false; }
   return true;
 }
@@ -352,6 +376,86 @@ int run_evaluate(const Args& a, const WorldData& wd, const eg_world& world, cons
   eg_destroy(ctx);
   return 0;
 }
+
+// --sensitivity: the first plan of `plans` as it is and with every one-entry edit of the canonical order (include/eirgrid_hip.h
+// eg_evaluate_plan_edits; the order of Engine.plan_sensitivity): none; every best_actions entry deleted, in (year, position) order; every
+// best_deficit_actions entry deleted; with --sensitivity-replace, every best_actions entry replaced by each listed action.  All variants
+// run as iteration 0 of the run's seed (same_index), --batch edits per launch.  <checkpoint-dir>/<stamp>/sensitivity/index.csv gets a row
+// per edit: the calendar year, the canonical actions before and after, metrics and score as plans/index.csv writes them, and their
+// differences from row 0 (NaN where either variant failed).
+int run_sensitivity(const Args& a, const eg_world& world, const eg_plan_set& plans) {
+  eg_plan_set base = plans;
+  base.n_plans = 1; base.names = nullptr;
+  base.best_actions_len = 0; base.best_deficit_actions_len = 0;
+  for (int y = 0; y < EG_YEARS; ++y) { base.best_actions_len += plans.best_count[y]; base.best_deficit_actions_len += plans.best_deficit_count[y]; }
+  std::vector<eg_plan_edit> edits(1, eg_plan_edit{EG_EDIT_NONE, 0, 0, 0, 0});
+  std::vector<int> before(1, -1);
+  const int32_t* count[2] = {base.best_count, base.best_deficit_count};
+  const uint8_t* flat[2] = {base.best_actions, base.best_deficit_actions};
+  for (int w = 0; w < 2; ++w) {
+    int64_t at = 0;
+    for (int y = 0; y < EG_YEARS; ++y)
+      for (int32_t i = 0; i < count[w][y]; ++i, ++at) { edits.push_back(eg_plan_edit{EG_EDIT_DELETE, uint8_t(w), uint16_t(y), uint32_t(i), 0}); before.push_back(flat[w][at]); }
+  }
+  if (!a.sensitivity_replace.empty()) {
+    int64_t at = 0;
+    for (int y = 0; y < EG_YEARS; ++y)
+      for (int32_t i = 0; i < count[0][y]; ++i, ++at)
+        for (uint8_t act : a.sensitivity_replace) { edits.push_back(eg_plan_edit{EG_EDIT_REPLACE, 0, uint16_t(y), uint32_t(i), act}); before.push_back(flat[0][at]); }
+  }
+  const uint32_t n = uint32_t(edits.size());
+  CHECK(eg_plan_edits_validate(&base, edits.data(), int32_t(n)));
+  struct Owned {      // released on every way out
+    eg_policy* policy = nullptr; eg_ctx* ctx = nullptr;
+    ~Owned() { if (policy) eg_policy_free(policy); if (ctx) eg_destroy(ctx); }
+  } own;
+  eg_policy* policy = own.policy = a.evaluate_policy.empty() ? eg_policy_new() : eg_policy_load_json(a.evaluate_policy.c_str());
+  if (!policy) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
+  eg_ctx* ctx = own.ctx = eg_create(a.device, &world);
+  if (!ctx) { std::fprintf(stderr, "eg_create: %s\n", eg_last_error()); return 1; }
+  const int mode = a.cost_only ? 2 : 1;
+  eg_opts opts{a.enable_energy_sales ? 1 : 0, 0, 1};
+  eg_policy_snapshot snap; CHECK(eg_policy_snapshot_view(policy, &snap));
+  std::vector<double> metrics(size_t(n) * 4); std::vector<int32_t> status(n);
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint32_t j0 = 0; j0 < n; j0 += a.batch) {
+    const uint32_t m = std::min(a.batch, n - j0);
+    eg_episode_out out{}; out.metrics = &metrics[size_t(j0) * 4]; out.status = &status[j0];
+    CHECK(eg_evaluate_plan_edits(ctx, &snap, &opts, &base, &edits[j0], int32_t(m), a.seed, 0, 1, &out));
+  }
+  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  const std::string stamp = time_stamp("%Y%m%d_%H%M%S"), dir = a.checkpoint_dir + "/" + stamp + "/sensitivity";
+  mkdirs(dir);
+  std::vector<double> score(n);
+  for (uint32_t j = 0; j < n; ++j) score[j] = status[j] == EG_EP_OK ? eg_rank_score(&metrics[size_t(j) * 4], mode) : std::nan("");
+  {
+    static const char* kKind[4] = {"none", "delete", "replace", "insert"};
+    std::ofstream f(dir + "/index.csv");
+    f << "edit,kind,list,year,pos,action_before,action_after,status,net_emissions,public_opinion,total_cost,power_reliability,score,"
+         "d_net_emissions,d_public_opinion,d_total_cost,d_score\n";
+    const bool base_ok = status[0] == EG_EP_OK;
+    for (uint32_t j = 0; j < n; ++j) {
+      const eg_plan_edit& e = edits[j];
+      const double* m = &metrics[size_t(j) * 4];
+      char line[640];
+      int k = std::snprintf(line, sizeof(line), "%u,%s,", j, kKind[e.kind]);
+      if (e.kind == EG_EDIT_NONE) k += std::snprintf(line + k, sizeof(line) - k, ",,,,,");
+      else {
+        k += std::snprintf(line + k, sizeof(line) - k, "%s,%d,%u,%d,", e.list ? "best_deficit_actions" : "best_actions", 2025 + int(e.year), e.pos, before[j]);
+        if (e.kind == EG_EDIT_DELETE) k += std::snprintf(line + k, sizeof(line) - k, ",");
+        else k += std::snprintf(line + k, sizeof(line) - k, "%d,", int(e.action));
+      }
+      const bool both = base_ok && status[j] == EG_EP_OK;
+      const double nan = std::nan("");
+      std::snprintf(line + k, sizeof(line) - k, "%d,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", status[j], m[0], m[1], m[2], m[3], score[j],
+                    both ? m[0] - metrics[0] : nan, both ? m[1] - metrics[1] : nan, both ? m[2] - metrics[2] : nan, both ? score[j] - score[0] : nan);
+      f << line;
+    }
+    if (!f) { std::fprintf(stderr, "error: cannot write %s/index.csv\n", dir.c_str()); return 1; }
+  }
+  std::printf("Evaluated %u edits in %.3f s (%.0f edits/s); written to %s\n", n, secs, double(n) / std::max(secs, 1e-9), dir.c_str());
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -359,7 +463,8 @@ int main(int argc, char** argv) {
   if (!parse(argc, argv, a)) return 2;
   std::puts("EirGrid Power System Simulator (2025-2050) — MI355X rollout engine");
   eg_plan_set* plans = nullptr;      // --evaluate: every invalid line is reported before a device is touched
-  if (!a.evaluate.empty() && !(plans = eg_plans_load(a.evaluate.c_str()))) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
+  const std::string& plans_file = a.evaluate.empty() ? a.sensitivity : a.evaluate;      // (--sensitivity reads its base plan the same way)
+  if (!plans_file.empty() && !(plans = eg_plans_load(plans_file.c_str()))) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
   if (a.enable_construction_delays) { std::fprintf(stderr, "error: --enable-construction-delays is not implemented on the device (DESIGN.md §6)\n"); return 2; }
 
   WorldData wd;
@@ -393,7 +498,7 @@ int main(int argc, char** argv) {
     return 0;
   }
   const eg_world world = wd.view(a.existing_operational_at_start);
-  if (plans) { const int rc = run_evaluate(a, wd, world, *plans); eg_plans_free(plans); return rc; }
+  if (plans) { const int rc = a.sensitivity.empty() ? run_evaluate(a, wd, world, *plans) : run_sensitivity(a, world, *plans); eg_plans_free(plans); return rc; }
   // more than one rank: the same reduced-update loop on an eg_group (the exchange between the ranks is inside the library)
   eg_ctx* ctx = nullptr; eg_group* group = nullptr;
   if (a.gpus_given && int32_t(a.ranks.size()) > eg_device_count()) {

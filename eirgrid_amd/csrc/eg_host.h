@@ -133,6 +133,9 @@ struct eg_ctx {
   // (snap::kPlanStride bytes each) and the index lists of the short and the long plans
   eg::DevBuf<uint8_t> d_eval_snap, d_plans;
   eg::DevBuf<uint32_t> d_plan_index;
+  // plan-edit batches (eg_evaluate_plan_edits): the base plan's block followed by the packed edits, 8 bytes each — what k_plan_edits reads
+  eg::DevBuf<uint8_t> d_plan_edit_in;
+  size_t n_plan_blocks = 0;      // blocks of the last plan or plan-edit batch in d_plans (eg_debug_fetch_plan_block)
 };
 
 namespace eg {

@@ -340,6 +340,8 @@ struct RolloutPlan {
   bool plans;
   uint32_t n_short;
   const uint32_t* d_index_long;
+  // a plan-edit batch with same_index (eg_evaluate_plan_edits): every episode of the plan batch runs as global episode first_index
+  bool same_index;
 };
 constexpr int kStatsReplicas = 64;
 int launch_fold_stats(long long* d_rep, long long* d_stats, void* stream);
@@ -428,6 +430,9 @@ struct TopKState { int32_t k, n_held, mode, pad; TopKEntry e[EG_TOPK_MAX]; long 
 constexpr size_t kTopKRecords = (sizeof(TopKState) + 255) & ~size_t(255);
 constexpr size_t kTopKBytes = kTopKRecords + size_t(EG_TOPK_MAX) * rec::stride;
 constexpr uint32_t kTopKChunk = 1024;      // episodes per workgroup of k_topk_select
+// k_plan_edits (eg_plan_edits.h): the n plan blocks of a plan-edit batch into d_pool (snap::kPlanStride bytes each) from the base
+// plan's block d_base and n packed edits (8 bytes each: kind | list << 8 | year << 16 | action << 24, then pos)
+int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream);
 // k_topk_keys: rank score and key of every episode of the batch that can still enter the archive at d_state (else score -inf);
 // use_score_list: the statistics epilogue ran for this batch (mode 1 only: its scores are the rank scores)
 int launch_topk_keys(const DevOut& o, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state,

@@ -1,4 +1,5 @@
-// eg_plans.cpp — a policy in snapshot layout (shared with eg_upload_snapshot) and plan batches: eg_evaluate_plans, launch_plans.
+// eg_plans.cpp — a policy in snapshot layout (shared with eg_upload_snapshot) and plan batches: eg_evaluate_plans, eg_evaluate_plan_edits,
+// launch_plans.
 #include <algorithm>
 #include <cstring>
 
@@ -80,7 +81,7 @@ namespace {
 // actions), then the long ones.  The short-replay variant runs over exactly the short ones; the long ones go to k_replay_solo and the
 // long-replay variant, in launches of at most as many episodes as the penalty-field pool has slots (a long replay claims one per
 // launch epoch).  The hoist, the statistics epilogue and the best_result / top-K folds do not run.
-int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short) {
+int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index) {
   const uint32_t n_long = n - n_short;
   const bool helper = n <= c->helper_max_episodes;
   uint32_t done = 0;
@@ -89,7 +90,7 @@ int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_
     EG_TRY(prepare_heavy(c, chunk, chunk == 0));
     if (c->dev.heavy && chunk > c->dev.heavy_slots) chunk = c->dev.heavy_slots;
     RolloutPlan plan{};
-    plan.plans = true; plan.helper_waves = helper;
+    plan.plans = true; plan.helper_waves = helper; plan.same_index = same_index;
     plan.n_short = first ? n_short : 0u;
     plan.n_heavy = plan.n_short + chunk; plan.n_lean = 0; plan.mode = 1u;
     plan.d_index = c->d_plan_index; plan.d_index_long = c->d_plan_index + n_short + done;
@@ -102,6 +103,28 @@ int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_
   }
   c->last_n = n; c->last_first = first_index;
   return EG_OK;
+}
+// The rest of a plan batch whose routing is in c->d_plan_index: the policy into a device snapshot of its own — has_best = 1 and lists
+// present (empty: every episode reads its plan block instead) —, then the launches.  `edits`: a plan-edit batch, whose blocks
+// k_plan_edits writes on the launches' stream from c->d_plan_edit_in (the base block, then the packed edits).
+// (The snapshot is staged last before the launches: a launch's start event takes the time the stream's previous command ended — with
+//  the snapshot staged first, eg_timing_read counted the host building the plan blocks.)
+int stage_and_launch_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short,
+                           bool edits, bool same_index) {
+  eg_policy_snapshot ps = *s;
+  static const int32_t kNoCounts[EG_YEARS] = {};
+  static const uint8_t kNoActions[1] = {0};
+  ps.has_best = 1; ps.best_count = kNoCounts; ps.best_deficit_count = kNoCounts; ps.best_actions = kNoActions; ps.best_deficit_actions = kNoActions;
+  EG_HIP(c->d_eval_snap.reserve(snap::upload_bytes));
+  EG_HIP(hipStreamSynchronize(nullptr));   // the pinned staging buffer may still feed the previous copy
+  stage_policy(c, &ps, true, c->h_snap);
+  EG_HIP(hipMemcpyAsync(c->d_eval_snap, c->h_snap, snap::upload_bytes, hipMemcpyHostToDevice, nullptr));
+  EG_LAUNCH("k_stalled_tables", launch_stalled_tables(c->d_eval_snap, nullptr));      // sampling.rs:190-220, as at upload
+  if (edits) EG_LAUNCH("k_plan_edits", launch_plan_edits(c->d_plan_edit_in, c->d_plan_edit_in + snap::kPlanStride, n, c->d_plans, nullptr));
+  DevSnapshot S = snapshot_of(c->d_eval_snap, o);
+  S.plan_pool = c->d_plans;
+  c->n_plan_blocks = n;
+  return launch_plans(c, S, seed, first_index, n, n_short, same_index);
 }
 }  // namespace
 
@@ -136,20 +159,85 @@ extern "C" int32_t eg_evaluate_plans(eg_ctx* c, const eg_policy_snapshot* s, con
   EG_HIP(c->d_plan_index.reserve(n));
   EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
   EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  // then the policy, in a device snapshot of its own: has_best = 1 and lists present (empty: every episode reads its plan block instead).
-  // (Last before the launches: a launch's start event takes the time the stream's previous command ended — with the snapshot staged
-  //  first, eg_timing_read counted the host building the plan blocks.)
-  eg_policy_snapshot ps = *s;
-  static const int32_t kNoCounts[EG_YEARS] = {};
-  static const uint8_t kNoActions[1] = {0};
-  ps.has_best = 1; ps.best_count = kNoCounts; ps.best_deficit_count = kNoCounts; ps.best_actions = kNoActions; ps.best_deficit_actions = kNoActions;
-  EG_HIP(c->d_eval_snap.reserve(snap::upload_bytes));
-  EG_HIP(hipStreamSynchronize(nullptr));   // the pinned staging buffer may still feed the previous copy
-  stage_policy(c, &ps, true, c->h_snap);
-  EG_HIP(hipMemcpyAsync(c->d_eval_snap, c->h_snap, snap::upload_bytes, hipMemcpyHostToDevice, nullptr));
-  EG_LAUNCH("k_stalled_tables", launch_stalled_tables(c->d_eval_snap, nullptr));      // sampling.rs:190-220, as at upload
-  DevSnapshot S = snapshot_of(c->d_eval_snap, o);
-  S.plan_pool = c->d_plans;
-  EG_TRY(launch_plans(c, S, seed, first_index, n, n_short));
+  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, false, false));
   return out ? eg_fetch(c, out) : EG_OK;
+}
+
+// ---------------------------------------------------------------- plan edits (include/eirgrid_hip.h eg_evaluate_plan_edits)
+extern "C" int32_t eg_plan_edits_validate(const eg_plan_set* base, const eg_plan_edit* edits, int32_t n_edits) {
+  auto fail = [](const std::string& m) { set_error("eg_plan_edits_validate: " + m); return EG_ERR_BAD_ARG; };
+  EG_TRY(eg_plans_validate(base));
+  if (base->n_plans != 1) return fail("the base holds " + std::to_string(base->n_plans) + " plans (exactly 1)");
+  if (n_edits < 1) return fail("n_edits = " + std::to_string(n_edits) + " (at least 1)");
+  if (!edits) return fail("NULL edits");
+  const char* field[2] = {"best_actions", "best_deficit_actions"};
+  const int32_t* count[2] = {base->best_count, base->best_deficit_count};
+  int64_t total[2] = {0, 0};
+  for (int w = 0; w < 2; ++w) for (int y = 0; y < EG_YEARS; ++y) total[w] += count[w][y];
+  for (int32_t j = 0; j < n_edits; ++j) {
+    const eg_plan_edit& e = edits[j];
+    const std::string who = "edit " + std::to_string(j) + ": ";
+    if (e.kind > EG_EDIT_INSERT) return fail(who + "kind " + std::to_string(int(e.kind)) + " (0 none, 1 delete, 2 replace, 3 insert)");
+    if (e.kind == EG_EDIT_NONE) continue;      // (the base plan itself: the other fields are not read)
+    if (e.list > 1) return fail(who + "list " + std::to_string(int(e.list)) + " (0 best_actions, 1 best_deficit_actions)");
+    if (e.year >= EG_YEARS) return fail(who + "year " + std::to_string(int(e.year)) + " (a year index 0.." + std::to_string(EG_YEARS - 1) + ")");
+    const int64_t len = count[e.list][e.year];
+    const std::string where = std::string(field[e.list]) + " year " + std::to_string(2025 + int(e.year)) + " (" + std::to_string(len) + " entries)";
+    if (e.kind == EG_EDIT_INSERT ? int64_t(e.pos) > len : int64_t(e.pos) >= len)
+      return fail(who + "pos " + std::to_string(e.pos) + " outside " + where + (e.kind == EG_EDIT_INSERT ? ": an insert takes 0..len" : ": 0..len-1"));
+    if (e.kind == EG_EDIT_INSERT && total[e.list] + 1 > int64_t(snap::kBestCap))
+      return fail(who + "the insert makes " + field[e.list] + " " + std::to_string(total[e.list] + 1) + " entries (at most " + std::to_string(snap::kBestCap) + ")");
+    if (e.kind != EG_EDIT_DELETE && e.action >= EG_N_ACTIONS)
+      return fail(who + "action " + std::to_string(int(e.action)) + " >= " + std::to_string(EG_N_ACTIONS));
+  }
+  return EG_OK;
+}
+
+extern "C" int32_t eg_evaluate_plan_edits(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* base, const eg_plan_edit* edits,
+                                          int32_t n_edits, uint64_t seed, uint64_t first_index, int32_t same_index, eg_episode_out* out) {
+  if (!c || !s || !s->weights || !s->deficit_weights) { set_error("eg_evaluate_plan_edits: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->group_member) { set_error("eg_evaluate_plan_edits: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_plan_edits_validate(base, edits, n_edits));
+  EG_TRY(check_policy(s, o, "eg_evaluate_plan_edits"));
+  EG_HIP(hipSetDevice(c->device));
+  const uint32_t n = uint32_t(n_edits);
+  EG_TRY(ensure_outputs(c, n));
+  // what goes up: the base plan's block and 8 bytes per variant (eg_plan_edits.h unpack), and the routing — a variant's best_actions
+  // list is the base's, one entry longer or shorter: the short variants' indices first, then the long ones'
+  std::vector<uint8_t> in(snap::kPlanStride + size_t(n) * 8, 0);
+  write_lists(in.data(), base->best_count, base->best_actions, base->best_deficit_count, base->best_deficit_actions);
+  int64_t base_len = 0;
+  for (int y = 0; y < EG_YEARS; ++y) base_len += base->best_count[y];
+  std::vector<uint32_t> idx(n);
+  uint32_t n_short = 0;
+  {
+    std::vector<uint32_t> longs;
+    uint32_t* packed = reinterpret_cast<uint32_t*>(in.data() + snap::kPlanStride);
+    for (uint32_t j = 0; j < n; ++j) {
+      const eg_plan_edit& e = edits[j];
+      const bool none = e.kind == EG_EDIT_NONE;
+      packed[2 * j] = none ? 0u : uint32_t(e.kind) | uint32_t(e.list) << 8 | uint32_t(e.year) << 16 | uint32_t(e.kind == EG_EDIT_DELETE ? 0 : e.action) << 24;
+      packed[2 * j + 1] = none ? 0u : e.pos;
+      const int64_t len = base_len + (!none && e.list == 0 ? (e.kind == EG_EDIT_INSERT ? 1 : e.kind == EG_EDIT_DELETE ? -1 : 0) : 0);
+      if (len > kShortReplayMax) longs.push_back(j); else idx[n_short++] = j;
+    }
+    std::copy(longs.begin(), longs.end(), idx.begin() + n_short);
+  }
+  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
+  EG_HIP(c->d_plan_index.reserve(n));
+  EG_HIP(c->d_plan_edit_in.reserve(in.size()));
+  EG_HIP(hipMemcpy(c->d_plan_edit_in, in.data(), in.size(), hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, true, same_index != 0));
+  return out ? eg_fetch(c, out) : EG_OK;
+}
+
+extern "C" int32_t eg_debug_fetch_plan_block(eg_ctx* c, uint32_t plan, uint8_t* out) {
+  static_assert(EG_PLAN_BLOCK_BYTES == snap::kPlanStride, "plan block size is part of the C ABI");
+  if (!c || !out) { set_error("eg_debug_fetch_plan_block: bad argument"); return EG_ERR_BAD_ARG; }
+  if (!c->d_plans.ptr || size_t(plan) >= c->n_plan_blocks) { set_error("eg_debug_fetch_plan_block: plan " + std::to_string(plan) + " is not in the last plan batch (" + std::to_string(c->n_plan_blocks) + " plans)"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  EG_HIP(hipDeviceSynchronize());
+  EG_HIP(hipMemcpy(out, c->d_plans + size_t(plan) * snap::kPlanStride, snap::kPlanStride, hipMemcpyDeviceToHost));
+  return EG_OK;
 }

@@ -1852,6 +1852,10 @@ struct EpisodeMap {
   const unsigned long long* hoist;
   unsigned long long hoist_seq;
   uint32_t stats_rep;         // 1: `stats` is kStatsReplicas copies of the statistics array (entry-major); this workgroup adds to copy (index % kStatsReplicas)
+  // a plan-edit batch with same_index (eg_evaluate_plan_edits): 1 = every episode of this plan batch draws from the stream of global
+  // episode first_index.  Read by the replay variants in a plan batch only.  (In the four bytes of padding in front of `solo`: the
+  // argument block of every k_rollout keeps its layout.)
+  uint32_t same_index;
   // per-episode replay kernel (eg_replay_solo.h): word b carries solo_seq when k_replay_solo has completed workgroup b's episode — the
   // long-replay variant, launched behind it, then has nothing to do for that episode (0 / null: no such kernel in this launch) —, and
   // solo_seq << 21 | 1 << 20 | slot when it gave the episode up holding field slot `slot`: the long-replay variant runs it in that slot
@@ -1966,7 +1970,10 @@ __global__ void __launch_bounds__(kWave * (1 + kHelpers), kKind == kReplayLong ?
                                                  T.pre_tg()[lane] == T.pre_tg()[lane - 1] && T.pre_ig()[lane] == T.pre_ig()[lane - 1] &&
                                                  T.pre_sg()[lane] == T.pre_sg()[lane - 1]);
   Rng rng;
-  rng_seed(rng, seed + first_index + (unsigned long long)e, lane);   // simulation.rs:50-53, one stream per episode
+  // (a plan-edit batch with same_index runs every variant as global episode first_index: the same fallback draws for all of them)
+  unsigned long long stream_e = (unsigned long long)e;
+  if constexpr (kReplay) if (S_in.plan_pool != nullptr && emap.same_index != 0u) stream_e = 0ull;
+  rng_seed(rng, seed + first_index + stream_e, lane);   // simulation.rs:50-53, one stream per episode
   EG_MARKG(16);
 
   Episode ep;
@@ -2511,6 +2518,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #ifndef EG_TU_THROUGHPUT      // (everything from here to the launchers lives in eg_rollout.o only)
 #include "eg_replay_coop.h"      // k_replay_coop, k_replay_broadcast: the replay episodes of a batch, computed once
 #include "eg_topk.h"             // k_topk_keys, k_topk_select, k_topk_merge: the top-K archive of distinct scenarios
+#include "eg_plan_edits.h"       // k_plan_edits: the plan blocks of a plan-edit batch from one base block and an edit per variant
 
 // ---- B2: a single placement search, for parity tests of the arg-max --------------------------------------------
 __global__ void __launch_bounds__(kWave) k_place(DevTables T, int type, int yi, const uint16_t* __restrict__ cells,
@@ -3091,14 +3099,14 @@ __global__ void __launch_bounds__(1024) k_apply_update(uint8_t* snap_base, const
 int launch_rollout_throughput(int kind, const DevTables& t, const DevSnapshot& s, const DevOut& o, uint64_t seed, uint64_t first_index, uint32_t n,
                               const uint8_t* d_replay_mask, uint32_t replay_period, long long* d_stats, uint32_t count, uint32_t mode,
                               const uint32_t* index, uint32_t off, uint32_t period, const unsigned long long* hoist, unsigned long long hoist_seq,
-                              uint32_t stats_rep, unsigned long long* solo, unsigned long long solo_seq, void* stream, void* ev0, void* ev1);
+                              uint32_t stats_rep, uint32_t same_index, unsigned long long* solo, unsigned long long solo_seq, void* stream, void* ev0, void* ev1);
 #ifdef EG_TU_THROUGHPUT
 int launch_rollout_throughput(int kind, const DevTables& t, const DevSnapshot& s, const DevOut& o, uint64_t seed, uint64_t first_index, uint32_t n,
                               const uint8_t* d_replay_mask, uint32_t replay_period, long long* d_stats, uint32_t count, uint32_t mode,
                               const uint32_t* index, uint32_t off, uint32_t period, const unsigned long long* hoist, unsigned long long hoist_seq,
-                              uint32_t stats_rep, unsigned long long* solo, unsigned long long solo_seq, void* stream, void* ev0, void* ev1) {
+                              uint32_t stats_rep, uint32_t same_index, unsigned long long* solo, unsigned long long solo_seq, void* stream, void* ev0, void* ev1) {
   EpisodeMap map{};
-  map.count = count; map.mode = mode; map.index = index; map.off = off; map.period = period; map.hoist = hoist; map.hoist_seq = hoist_seq; map.stats_rep = stats_rep;
+  map.count = count; map.mode = mode; map.index = index; map.off = off; map.period = period; map.hoist = hoist; map.hoist_seq = hoist_seq; map.stats_rep = stats_rep; map.same_index = same_index;
   map.solo = solo; map.solo_seq = solo_seq;
   // the timing events ride on the dispatch packet itself (no separate barrier packets around the kernel)
 #define EG_LAUNCH_TP(kKind) hipExtLaunchKernelGGL((k_rollout<0, kKind>), dim3(map.count), dim3(kWave), 0, (hipStream_t)stream, (hipEvent_t)ev0, (hipEvent_t)ev1, 0, \
@@ -3127,7 +3135,7 @@ void launch_variant(bool helper_waves, const DevTables& t, const DevSnapshot& s,
                           d_replay_mask, replay_period, d_stats, map);
   else
     (void)launch_rollout_throughput(kKind, t, s, o, seed, first_index, n, d_replay_mask, replay_period, d_stats, map.count, map.mode, map.index, map.off, map.period,
-                                    map.hoist, map.hoist_seq, map.stats_rep, map.solo, map.solo_seq, stream, ev0, ev1);
+                                    map.hoist, map.hoist_seq, map.stats_rep, map.same_index, map.solo, map.solo_seq, stream, ev0, ev1);
 }
 }  // namespace
 
@@ -3142,6 +3150,7 @@ int launch_rollout(const DevTables& t, const DevSnapshot& s, const DevOut& o, ui
     EpisodeMap ms{}, ml{};
     ms.count = p.n_short; ms.mode = 1u; ms.index = p.d_index;
     ml.count = p.n_heavy - p.n_short; ml.mode = 1u; ml.index = p.d_index_long;
+    ms.same_index = ml.same_index = p.same_index ? 1u : 0u;      // (k_rollout: every episode draws from the stream of first_index)
     if (!p.helper_waves && p.solo_seq != 0ull) { ml.solo = p.d_solo; ml.solo_seq = p.solo_seq; }
     if (ms.count > 0) launch_variant<kReplayShort>(p.helper_waves, t, s, o, seed, first_index, n, d_replay_mask, replay_period, d_stats, ms, p.stream_heavy, p.ev[0],
                                                    ml.count > 0 ? nullptr : p.ev[1]);
@@ -3347,6 +3356,12 @@ int launch_topk_merge(uint8_t* d_state, const uint8_t* d_blocks, int n_blocks, s
                       uint64_t own_first, uint32_t own_n, uint32_t step, void* stream) {
   hipLaunchKernelGGL(k_topk_merge, dim3(1), dim3(1024), 0, (hipStream_t)stream, reinterpret_cast<TopKState*>(d_state), d_blocks, n_blocks,
                      (unsigned long long)block_stride, d_pack, k, o, (unsigned long long)own_first, own_n, step);
+  return (int)hipGetLastError();
+}
+static_assert(sizeof(EpisodeMap) == 64 && offsetof(EpisodeMap, solo) == 48, "EpisodeMap: same_index sits in what was padding");
+int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_plan_edits, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_base, reinterpret_cast<const uint2*>(d_edits), n, d_pool);
   return (int)hipGetLastError();
 }
 int launch_pick_best(const DevOut& o, uint32_t n, uint64_t first_index, UpdateCandidate* d_cand, void* stream) {

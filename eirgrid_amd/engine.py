@@ -253,6 +253,68 @@ class PlanSet:
                              _p(self.dact, C.c_uint8), int(self.count.sum()), int(self.dcount.sum()), self.names)
 
 
+@dataclass(frozen=True)
+class PlanEdit:
+    """One edit of a plan (eg_plan_edit): kind "none" (the plan itself), "delete", "replace" or "insert" (in front of `pos`; pos = len
+    appends); list 0 = best_actions, 1 = best_deficit_actions; year: the year index 0..25; pos: a position in that year's list; action:
+    the canonical index replace / insert put there."""
+    kind: str = "none"
+    list: int = 0
+    year: int = 0
+    pos: int = 0
+    action: int = 0
+
+    KINDS = ("none", "delete", "replace", "insert")
+
+    def struct(self) -> N.EgPlanEdit:
+        return N.EgPlanEdit(self.KINDS.index(self.kind), self.list, self.year, self.pos, self.action)
+
+    def apply(self, plan: "Plan") -> "Plan":
+        """The edited plan (a copy), as the device builds it."""
+        lists = ([list(l) for l in plan.best_actions], [list(l) for l in plan.best_deficit_actions])
+        l = lists[self.list][self.year]
+        if self.kind == "delete":
+            del l[self.pos]
+        elif self.kind == "replace":
+            l[self.pos] = self.action
+        elif self.kind == "insert":
+            l.insert(self.pos, self.action)
+        return Plan(lists[0], lists[1], plan.name)
+
+
+def _edit_array(edits):
+    edits = list(edits)
+    arr = (N.EgPlanEdit * max(len(edits), 1))()
+    for j, e in enumerate(edits):
+        arr[j] = e.struct() if isinstance(e, PlanEdit) else e
+    return arr, len(edits)
+
+
+@dataclass
+class Sensitivity:
+    """Engine.plan_sensitivity: per edit (row 0: the base plan) the record's status, the four metrics, the rank score (NaN for a variant
+    that failed) and their differences from row 0 (NaN where the base or the variant failed)."""
+    edits: list
+    result: "BatchResult"
+    status: np.ndarray        # [n]
+    metrics: np.ndarray       # [n,4]
+    score: np.ndarray         # [n]
+    d_metrics: np.ndarray     # [n,4]
+    d_score: np.ndarray       # [n]
+
+
+def sensitivity_edits(base: "Plan", replace_with=None) -> "list[PlanEdit]":
+    """The canonical edit order of a sensitivity run: the base itself; every best_actions entry in (year, position) order as a delete;
+    every best_deficit_actions entry likewise; then, per best_actions entry, a replace by each action of `replace_with`."""
+    edits = [PlanEdit()]
+    for which, lists in enumerate((base.best_actions, base.best_deficit_actions)):
+        edits += [PlanEdit("delete", which, y, i) for y, l in enumerate(lists) for i in range(len(l))]
+    for a in (replace_with or ()):
+        assert 0 <= int(a) < N.N_ACTIONS, a
+    edits += [PlanEdit("replace", 0, y, i, int(a)) for y, l in enumerate(base.best_actions) for i in range(len(l)) for a in (replace_with or ())]
+    return edits
+
+
 def _fetch_top_k(fn, handle, what):
     """(BatchResult of the n_held entries in rank order, scores [n_held], global indices [n_held]) of a top-K archive."""
     res = BatchResult.alloc(N.TOPK_MAX)
@@ -419,6 +481,40 @@ class Engine:
         N.check(N.lib().eg_evaluate_plans(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.c_uint64(seed & (2**64 - 1)),
                                           C.c_uint64(first_episode_index), C.byref(out)), "eg_evaluate_plans")
         return res
+
+    def evaluate_plan_edits(self, weights: ActionWeights, base: "Plan", edits, seed: int, first_index: int = 0, same_index: bool = True,
+                            enable_energy_sales=True, write_yearly=True) -> BatchResult:
+        """Score edits of one plan (eg_evaluate_plan_edits): variant j is `base` with edits[j] (PlanEdit) applied, evaluated as
+        evaluate_plans would evaluate it — at global index first_index for every variant (same_index: the same fallback draws), or at
+        first_index + j.  The variants' plan blocks are built on the device."""
+        ps = PlanSet([base])
+        arr, n = _edit_array(edits)
+        res = BatchResult.alloc(max(n, 1))
+        snap = weights.snapshot()
+        opts = self._opts(enable_energy_sales, False, write_yearly)
+        out = res.struct()
+        N.check(N.lib().eg_evaluate_plan_edits(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), arr, n, C.c_uint64(seed & (2**64 - 1)),
+                                               C.c_uint64(first_index), int(bool(same_index)), C.byref(out)), "eg_evaluate_plan_edits")
+        return res
+
+    def debug_fetch_plan_block(self, plan: int) -> np.ndarray:
+        """Test hook (eg_debug_fetch_plan_block): the bytes of plan block `plan` of the last plan or plan-edit batch."""
+        out = np.zeros(N.PLAN_BLOCK_BYTES, np.uint8)
+        N.check(N.lib().eg_debug_fetch_plan_block(self.h, int(plan), _p(out, C.c_uint8)), "eg_debug_fetch_plan_block")
+        return out
+
+    def plan_sensitivity(self, weights: ActionWeights, base: "Plan", seed: int, mode: int = 1, replace_with=None) -> Sensitivity:
+        """Which actions of `base` matter: the edits of sensitivity_edits(base, replace_with), all at global index 0 of `seed`; per edit
+        the metrics, eg_rank_score in `mode` (1: optimization_mode None, 2: cost_only) and their differences from the base's."""
+        edits = sensitivity_edits(base, replace_with)
+        res = self.evaluate_plan_edits(weights, base, edits, seed, 0, True)
+        L = N.lib()
+        score = np.array([L.eg_rank_score(_p(np.ascontiguousarray(res.metrics[j]), C.c_double), int(mode)) if res.status[j] == N.EG_EP_OK else np.nan
+                          for j in range(len(edits))])
+        # (differences are NaN where the base or the variant failed, as the CLI writes them)
+        both = (res.status == N.EG_EP_OK) & (res.status[0] == N.EG_EP_OK)
+        d_metrics = np.where(both[:, None], res.metrics - res.metrics[0], np.nan)
+        return Sensitivity(edits, res, res.status.copy(), res.metrics.copy(), score, d_metrics, np.where(both, score - score[0], np.nan))
 
     # device-resident path used by bench.py
     def upload_snapshot(self, weights: ActionWeights, enable_energy_sales=True, write_yearly=True):

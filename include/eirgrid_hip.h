@@ -305,6 +305,38 @@ int32_t eg_evaluate_plans(eg_ctx *, const eg_policy_snapshot *policy, const eg_o
 eg_plan_set *eg_plans_load(const char *path);
 void eg_plans_free(eg_plan_set *);
 
+/* Plan edits: which actions of a plan matter?  eg_evaluate_plan_edits(ctx, policy, opts, base, edits, n_edits, seed,
+ * first_episode_index, same_index, out) evaluates n_edits VARIANTS of one base plan (a plan set of exactly one plan), variant j being the
+ * base with edit j applied to one year's list of one of its two lists:
+ *   kind    EG_EDIT_NONE: the base plan itself (no other field is read), EG_EDIT_DELETE: entry `pos` removed, EG_EDIT_REPLACE: entry `pos`
+ *           becomes `action`, EG_EDIT_INSERT: `action` inserted in front of entry `pos`
+ *   list    0 = best_actions, 1 = best_deficit_actions
+ *   year    the year index 0..25
+ *   pos     a position in that year's list: 0..len-1 for delete and replace, 0..len for insert (len: append)
+ *   action  replace and insert: a canonical index 0..60 (what eg_plans_validate accepts in either list)
+ * Variant j is evaluated exactly as eg_evaluate_plans evaluates the edited plan as plan j — the same replay semantics, seeded draws when
+ * a list runs out, no statistics, update or folds, the resident policy untouched, the batch left behind for eg_fetch / eg_fetch_record,
+ * ranks of a group refused — at global episode first_episode_index + j (same_index = 0), or with same_index = 1 every variant at global
+ * episode first_episode_index: all variants then see the same fallback draws and differ by their edit only.  The host uploads the base
+ * plan's block once and 8 bytes per variant; the variants' plan blocks are written on the device (csrc/eg_plan_edits.h).
+ * eg_plan_edits_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the edit and the field for a position out of range,
+ * an insert that would make a list longer than 4 096 entries, an action >= 61, a year >= 26, an unknown kind or list, n_edits < 1, or a
+ * base that is not exactly one valid plan. */
+#define EG_EDIT_NONE 0
+#define EG_EDIT_DELETE 1
+#define EG_EDIT_REPLACE 2
+#define EG_EDIT_INSERT 3
+typedef struct { uint8_t kind, list; uint16_t year; uint32_t pos; uint8_t action; } eg_plan_edit;
+int32_t eg_plan_edits_validate(const eg_plan_set *base, const eg_plan_edit *edits, int32_t n_edits);
+int32_t eg_evaluate_plan_edits(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts *, const eg_plan_set *base /* n_plans == 1 */,
+                               const eg_plan_edit *edits, int32_t n_edits, uint64_t seed, uint64_t first_episode_index, int32_t same_index,
+                               eg_episode_out *out /* may be NULL */);
+/* Test hook: the plan block of plan / variant `plan` of the last plan or plan-edit batch as the replay kernels read it
+ * (EG_PLAN_BLOCK_BYTES: per-year masks, prefix offsets, the two flat lists; csrc/eg_internal.h snap::kPlanStride), after the device has
+ * finished that batch.  A plan-edit batch's blocks must equal, byte for byte, the blocks eg_evaluate_plans builds for the edited plans. */
+#define EG_PLAN_BLOCK_BYTES 8832
+int32_t eg_debug_fetch_plan_block(eg_ctx *, uint32_t plan, uint8_t *out /* EG_PLAN_BLOCK_BYTES */);
+
 /* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
  * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
  * copies, no collective library — and every call enqueues the work of all ranks from the calling thread without synchronising
