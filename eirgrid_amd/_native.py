@@ -66,7 +66,19 @@ class EgPlanEdit(C.Structure):
     _fields_ = [("kind", C.c_uint8), ("list", C.c_uint8), ("year", C.c_uint16), ("pos", C.c_uint32), ("action", C.c_uint8)]
 
 
+class EgRefineOpts(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("max_rounds", C.c_int32), ("n_replace", C.c_int32), ("replace_with", _u8p),
+                ("n_append", C.c_int32), ("append_with", _u8p)]
+
+
+class EgRefineStep(C.Structure):
+    _fields_ = [("edit", EgPlanEdit), ("variant", C.c_int32), ("n_variants", C.c_int32), ("n_failed", C.c_int32), ("score", C.c_double),
+                ("metrics", C.c_double * 4)]
+
+
 EDIT_NONE, EDIT_DELETE, EDIT_REPLACE, EDIT_INSERT = 0, 1, 2, 3
+REFINE_LOCAL_OPTIMUM, REFINE_MAX_ROUNDS, REFINE_BASE_FAILED = 0, 1, 2
+REFINE_MAX_VARIANTS = 16384      # EG_REFINE_MAX_VARIANTS
 PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
 
 # every symbol include/eirgrid_hip.h declares
@@ -78,7 +90,7 @@ EXPORTS = [
     "eg_group_create", "eg_group_destroy", "eg_group_rank", "eg_group_push", "eg_group_step", "eg_group_pull", "eg_group_replay_hoist",
     "eg_group_best_result_track", "eg_group_fetch_best_result", "eg_top_k_track", "eg_fetch_top_k", "eg_rank_score",
     "eg_group_top_k_track", "eg_group_fetch_top_k", "eg_plans_validate", "eg_evaluate_plans", "eg_plans_load", "eg_plans_free",
-    "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block",
+    "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block", "eg_plans_save", "eg_refine_validate", "eg_refine_plan",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -230,6 +242,16 @@ def lib():
         L.eg_evaluate_plan_edits.restype = C.c_int32
         L.eg_evaluate_plan_edits.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgPlanEdit),
                                              C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(EgEpisodeOut)]
+    # (likewise: scripts/refine_probe.py times the Python loop on a build of the parent commit, which has no refinement)
+    if hasattr(L, "eg_refine_plan") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_plans_save.restype = C.c_int32
+        L.eg_plans_save.argtypes = [C.POINTER(EgPlanSet), C.c_char_p]
+        L.eg_refine_validate.restype = C.c_int32
+        L.eg_refine_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts)]
+        L.eg_refine_plan.restype = C.c_int32
+        L.eg_refine_plan.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts),
+                                     C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgRefineStep), _i32p, _i32p, _dp,
+                                     C.POINTER(EgEpisodeOut)]
     L.eg_plans_load.restype = C.POINTER(EgPlanSet)
     L.eg_plans_load.argtypes = [C.c_char_p]
     L.eg_plans_free.argtypes = [C.POINTER(EgPlanSet)]

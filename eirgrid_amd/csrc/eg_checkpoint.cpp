@@ -57,7 +57,8 @@ std::string fmt_display(double v) {      // Rust `{}` of an f64: shortest digits
 }
 struct Writer {
   std::string out; int depth = 0;
-  void nl() { out += '\n'; out.append(size_t(depth) * 2, ' '); }
+  bool compact = false;      // one line (JSON Lines: eg_plans_save)
+  void nl() { if (compact) return; out += '\n'; out.append(size_t(depth) * 2, ' '); }
   void action(int a) {   // SerializableAction::from (serializable_action.rs:15-66)
     const char* type; std::string gen = "null", id = "null", pct = "null", off = "null", mult = "null";
     if (a < 45) { type = "AddGenerator"; gen = std::string("\"") + kTypeName[a / 3] + "\""; mult = std::to_string(kMultPercent[a % 3]); }
@@ -445,6 +446,23 @@ bool plan_from_json(const Json& root, const std::string& where, PlanSet& ps, std
 
 }  // namespace
 
+eg_plan_set* eg::make_plan_set(const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact, const char* name) {
+  std::unique_ptr<PlanSet> ps(new PlanSet());
+  ps->cnt.assign(count, count + Y); ps->dcnt.assign(dcount, dcount + Y);
+  int64_t n = 0, dn = 0;
+  for (int y = 0; y < Y; ++y) { n += count[y]; dn += dcount[y]; }
+  ps->act.assign(act, act + n); ps->dact.assign(dact, dact + dn);
+  ps->act.reserve(1); ps->dact.reserve(1);      // (data() of an empty list is not NULL)
+  ps->name_store.push_back(name ? name : "");
+  ps->name_ptrs.push_back(ps->name_store[0].c_str());
+  ps->n_plans = 1;
+  ps->best_count = ps->cnt.data(); ps->best_deficit_count = ps->dcnt.data();
+  ps->best_actions = ps->act.data(); ps->best_deficit_actions = ps->dact.data();
+  ps->best_actions_len = n; ps->best_deficit_actions_len = dn;
+  ps->names = ps->name_ptrs.data();
+  return ps.release();
+}
+
 extern "C" {
 
 int32_t eg_plans_validate(const eg_plan_set* p) {
@@ -528,5 +546,35 @@ eg_plan_set* eg_plans_load(const char* path) {
 }
 
 void eg_plans_free(eg_plan_set* p) { delete static_cast<PlanSet*>(p); }
+
+int32_t eg_plans_save(const eg_plan_set* p, const char* path) {
+  if (!path) { eg::set_error("eg_plans_save: NULL path"); return EG_ERR_BAD_ARG; }
+  if (const int32_t rc = eg_plans_validate(p); rc != EG_OK) return rc;
+  Writer w;
+  w.compact = true;
+  int64_t pos[2] = {0, 0};
+  for (int32_t j = 0; j < p->n_plans; ++j) {
+    const int32_t* count[2] = {p->best_count + size_t(j) * Y, p->best_deficit_count + size_t(j) * Y};
+    const uint8_t* flat[2] = {p->best_actions, p->best_deficit_actions};
+    const char* keys[2] = {"best_actions", "best_deficit_actions"};
+    w.out += '{';
+    for (int k = 0; k < 2; ++k) {
+      std::array<ActionList, Y> lists;
+      for (int y = 0; y < Y; ++y) { lists[y].assign(flat[k] + pos[k], flat[k] + pos[k] + count[k][y]); pos[k] += count[k][y]; }
+      w.out += std::string("\"") + keys[k] + "\": "; w.lists(lists); w.out += ", ";
+    }
+    w.out += "\"name\": \"";
+    for (const char* ch = p->names && p->names[j] ? p->names[j] : ""; *ch; ++ch) {
+      if (*ch == '"' || *ch == '\\') w.out += '\\';
+      if ((unsigned char)*ch >= 0x20) w.out += *ch;      // (control characters are dropped: a name is a label)
+    }
+    w.out += "\"}\n";
+  }
+  std::ofstream f(path, std::ios::binary | std::ios::trunc);
+  if (!f) { eg::set_error(std::string("eg_plans_save: cannot open ") + path); return EG_ERR_BAD_ARG; }
+  f << w.out;
+  if (!f.good()) { eg::set_error(std::string("eg_plans_save: cannot write ") + path); return EG_ERR_BAD_ARG; }
+  return EG_OK;
+}
 
 }  // extern "C"

@@ -52,6 +52,9 @@ struct Args {   // cli/cli.rs:5-59
   std::string evaluate_policy;  // --evaluate-policy CKPT: the policy the plans are evaluated under (default: ActionWeights::new)
   std::string sensitivity;      // --sensitivity FILE: score every one-entry edit of FILE's first plan (eg_evaluate_plan_edits) and exit
   std::vector<uint8_t> sensitivity_replace;      // --sensitivity-replace a,b,...: also every best_actions entry replaced by each of these
+  std::string refine;           // --refine FILE: apply the best one-entry edit of FILE's plan round after round (eg_refine_plan) and exit
+  int32_t refine_rounds = 64; bool refine_rounds_given = false;      // --refine-rounds N: at most N applied edits
+  std::vector<uint8_t> refine_replace, refine_append;      // --refine-replace / --refine-append a,b,...: the moves beside the deletes
 };
 
 void usage() {
@@ -84,7 +87,14 @@ void usage() {
             "                           with every entry of its two lists deleted in turn, all as iteration 0 of --seed [default 0] on one\n"
             "                           device; writes <checkpoint-dir>/<stamp>/sensitivity/index.csv (metrics, score and their\n"
             "                           differences from the unedited plan, one row per edit) and exits; no training runs\n"
-            "      --sensitivity-replace <a,b,...>  also every best_actions entry replaced by each of these canonical actions (0..60)");
+            "      --sensitivity-replace <a,b,...>  also every best_actions entry replaced by each of these canonical actions (0..60)\n"
+            "      --refine <FILE>      improve a plan greedily: FILE holds one plan (as --evaluate reads it); round after round every one-entry\n"
+            "                           edit of it is scored as iteration 0 of --seed [default 0] on one device and the best one applied, until\n"
+            "                           none improves the score (--cost-only: the cost score); writes <checkpoint-dir>/<stamp>/refine/\n"
+            "                           trajectory.csv (a row per applied edit) and refined.jsonl (the plan, for --evaluate) and exits\n"
+            "      --refine-rounds <N>  apply at most N edits [default: 64]\n"
+            "      --refine-replace <a,b,...>  besides deleting an entry, try it replaced by each of these canonical actions (0..60)\n"
+            "      --refine-append <a,b,...>   ... and each of these actions appended to each year's best_actions list");
 }
 
 bool parse(int argc, char** argv, Args& a) {
@@ -154,18 +164,28 @@ bool parse(int argc, char** argv, Args& a) {
     else if (s == "--evaluate") a.evaluate = v();
     else if (s == "--evaluate-policy") a.evaluate_policy = v();
     else if (s == "--sensitivity") a.sensitivity = v();
-    else if (s == "--sensitivity-replace") {
+    else if (s == "--sensitivity-replace" || s == "--refine-replace" || s == "--refine-append") {
       const std::string list = v();
+      std::vector<uint8_t>& into = s == "--sensitivity-replace" ? a.sensitivity_replace : s == "--refine-replace" ? a.refine_replace : a.refine_append;
       for (size_t pos = 0; pos <= list.size();) {
         const size_t comma = std::min(list.find(',', pos), list.size());
         const std::string item = list.substr(pos, comma - pos);
         if (item.empty() || item.size() > 2 || item.find_first_not_of("0123456789") != std::string::npos || std::atoi(item.c_str()) >= EG_N_ACTIONS) {
-          std::fprintf(stderr, "error: --sensitivity-replace needs a comma-separated list of canonical actions 0..%d, got '%s'\n", EG_N_ACTIONS - 1, list.c_str());
+          std::fprintf(stderr, "error: %s needs a comma-separated list of canonical actions 0..%d, got '%s'\n", s.c_str(), EG_N_ACTIONS - 1, list.c_str());
           return false;
         }
-        a.sensitivity_replace.push_back(uint8_t(std::atoi(item.c_str())));
+        into.push_back(uint8_t(std::atoi(item.c_str())));
         pos = comma + 1;
       }
+    }
+    else if (s == "--refine") a.refine = v();
+    else if (s == "--refine-rounds") {
+      const std::string k = v();
+      if (k.empty() || k.size() > 6 || k.find_first_not_of("0123456789") != std::string::npos || std::atoi(k.c_str()) < 1) {
+        std::fprintf(stderr, "error: --refine-rounds needs a number from 1 to 999999, got '%s'\n", k.c_str());
+        return false;
+      }
+      a.refine_rounds = std::atoi(k.c_str()); a.refine_rounds_given = true;
     }
     else if (s == "-h" || s == "--help") { usage(); std::exit(0); }
     else { std::fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage(); return false; }
@@ -177,7 +197,12 @@ bool parse(int argc, char** argv, Args& a) {
     return false;
   }
   if (a.ranks.size() == 1) a.device = a.ranks[0];      // one rank: the single-device run on that device
-  if (!a.evaluate_policy.empty() && a.evaluate.empty() && a.sensitivity.empty()) { std::fprintf(stderr, "error: --evaluate-policy needs --evaluate or --sensitivity\n"); return false; }
+  if (!a.evaluate_policy.empty() && a.evaluate.empty() && a.sensitivity.empty() && a.refine.empty()) { std::fprintf(stderr, "error: --evaluate-policy needs --evaluate, --sensitivity or --refine\n"); return false; }
+  if (a.refine.empty() && (a.refine_rounds_given || !a.refine_replace.empty() || !a.refine_append.empty())) {
+    std::fprintf(stderr, "error: --refine-rounds, --refine-replace and --refine-append need --refine\n"); return false;
+  }
+  if (!a.refine.empty() && (!a.evaluate.empty() || !a.sensitivity.empty())) { std::fprintf(stderr, "error: --refine, --sensitivity and --evaluate are separate runs\n"); return false; }
+  if (!a.refine.empty() && a.ranks.size() > 1) { std::fprintf(stderr, "error: --refine runs on one device (no --gpus / --devices)\n"); return false; }
   if (!a.sensitivity_replace.empty() && a.sensitivity.empty()) { std::fprintf(stderr, "error: --sensitivity-replace needs --sensitivity\n"); return false; }
   if (!a.sensitivity.empty() && !a.evaluate.empty()) { std::fprintf(stderr, "error: --sensitivity and --evaluate are separate runs\n"); return false; }
   if (!a.sensitivity.empty() && a.ranks.size() > 1) { std::fprintf(stderr, "error: --sensitivity runs on one device (no --gpus / --devices)\n"); return false; }
@@ -456,6 +481,58 @@ int run_sensitivity(const Args& a, const eg_world& world, const eg_plan_set& pla
   std::printf("Evaluated %u edits in %.3f s (%.0f edits/s); written to %s\n", n, secs, double(n) / std::max(secs, 1e-9), dir.c_str());
   return 0;
 }
+
+// --refine: the plan of `plans` improved greedily on the device (include/eirgrid_hip.h eg_refine_plan): per round every one-entry edit —
+// the deletes, with --refine-replace the replaces, with --refine-append the appends — as iteration 0 of the run's seed, the best one
+// applied while it improves the score.  <checkpoint-dir>/<stamp>/refine/trajectory.csv: row 0 the start, then a row per applied edit
+// (the round, the edit with its calendar year, its place among the round's variants, how many of them failed, score and metrics as
+// plans/index.csv writes them), a last line with the stop reason; refine/refined.jsonl: the refined plan, as --evaluate reads it.
+int run_refine(const Args& a, const eg_world& world, const eg_plan_set& plans) {
+  eg_refine_opts ro{a.cost_only ? 2 : 1, a.refine_rounds, int32_t(a.refine_replace.size()), a.refine_replace.empty() ? nullptr : a.refine_replace.data(),
+                    int32_t(a.refine_append.size()), a.refine_append.empty() ? nullptr : a.refine_append.data()};
+  CHECK(eg_refine_validate(&plans, &ro));
+  struct Owned {      // released on every way out
+    eg_policy* policy = nullptr; eg_ctx* ctx = nullptr; eg_plan_set* refined = nullptr;
+    ~Owned() { if (policy) eg_policy_free(policy); if (ctx) eg_destroy(ctx); if (refined) eg_plans_free(refined); }
+  } own;
+  eg_policy* policy = own.policy = a.evaluate_policy.empty() ? eg_policy_new() : eg_policy_load_json(a.evaluate_policy.c_str());
+  if (!policy) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
+  eg_ctx* ctx = own.ctx = eg_create(a.device, &world);
+  if (!ctx) { std::fprintf(stderr, "eg_create: %s\n", eg_last_error()); return 1; }
+  eg_opts opts{a.enable_energy_sales ? 1 : 0, 0, 1};
+  eg_policy_snapshot snap; CHECK(eg_policy_snapshot_view(policy, &snap));
+  std::vector<eg_refine_step> steps(size_t(a.refine_rounds));
+  int32_t n_steps = 0, stop = 0; double start = 0.0;
+  const auto t0 = std::chrono::steady_clock::now();
+  CHECK(eg_refine_plan(ctx, &snap, &opts, &plans, &ro, a.seed, 0, &own.refined, steps.data(), &n_steps, &stop, &start, nullptr));
+  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  const std::string stamp = time_stamp("%Y%m%d_%H%M%S"), dir = a.checkpoint_dir + "/" + stamp + "/refine";
+  mkdirs(dir);
+  static const char* kStop[3] = {"local_optimum", "max_rounds", "base_failed"};
+  {
+    static const char* kKind[4] = {"none", "delete", "replace", "insert"};
+    std::ofstream f(dir + "/trajectory.csv");
+    f << "round,kind,list,year,pos,action,variant,n_variants,n_failed,score,net_emissions,public_opinion,total_cost,power_reliability\n";
+    char line[640];
+    std::snprintf(line, sizeof(line), "start,none,,,,,0,,,%.17g,,,,\n", start);
+    f << line;
+    for (int32_t r = 0; r < n_steps; ++r) {
+      const eg_refine_step& st = steps[size_t(r)];
+      const eg_plan_edit& e = st.edit;
+      int k = std::snprintf(line, sizeof(line), "%d,%s,%s,%d,%u,", r, kKind[e.kind & 3], e.list ? "best_deficit_actions" : "best_actions", 2025 + int(e.year), e.pos);
+      if (e.kind != EG_EDIT_DELETE) k += std::snprintf(line + k, sizeof(line) - k, "%d", int(e.action));
+      std::snprintf(line + k, sizeof(line) - k, ",%d,%d,%d,%.17g,%.17g,%.17g,%.17g,%.17g\n", st.variant, st.n_variants, st.n_failed, st.score, st.metrics[0], st.metrics[1],
+                    st.metrics[2], st.metrics[3]);
+      f << line;
+    }
+    f << "# stop: " << kStop[stop] << " after " << n_steps << " steps\n";
+    if (!f) { std::fprintf(stderr, "error: cannot write %s/trajectory.csv\n", dir.c_str()); return 1; }
+  }
+  CHECK(eg_plans_save(own.refined, (dir + "/refined.jsonl").c_str()));
+  std::printf("Refined the plan in %d steps (%.3f s): score %.6f -> %.6f, stop: %s; written to %s\n", n_steps, secs, start,
+              n_steps > 0 ? steps[size_t(n_steps) - 1].score : start, kStop[stop], dir.c_str());
+  return 0;
+}
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -463,8 +540,9 @@ int main(int argc, char** argv) {
   if (!parse(argc, argv, a)) return 2;
   std::puts("EirGrid Power System Simulator (2025-2050) — MI355X rollout engine");
   eg_plan_set* plans = nullptr;      // --evaluate: every invalid line is reported before a device is touched
-  const std::string& plans_file = a.evaluate.empty() ? a.sensitivity : a.evaluate;      // (--sensitivity reads its base plan the same way)
+  const std::string& plans_file = !a.evaluate.empty() ? a.evaluate : !a.sensitivity.empty() ? a.sensitivity : a.refine;      // (--sensitivity and --refine read their base plan the same way)
   if (!plans_file.empty() && !(plans = eg_plans_load(plans_file.c_str()))) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
+  if (!a.refine.empty() && plans->n_plans != 1) { std::fprintf(stderr, "error: --refine needs a file with one plan, %s holds %d\n", a.refine.c_str(), plans->n_plans); eg_plans_free(plans); return 2; }
   if (a.enable_construction_delays) { std::fprintf(stderr, "error: --enable-construction-delays is not implemented on the device (DESIGN.md §6)\n"); return 2; }
 
   WorldData wd;
@@ -498,7 +576,11 @@ int main(int argc, char** argv) {
     return 0;
   }
   const eg_world world = wd.view(a.existing_operational_at_start);
-  if (plans) { const int rc = a.sensitivity.empty() ? run_evaluate(a, wd, world, *plans) : run_sensitivity(a, world, *plans); eg_plans_free(plans); return rc; }
+  if (plans) {
+    const int rc = !a.refine.empty() ? run_refine(a, world, *plans) : a.sensitivity.empty() ? run_evaluate(a, wd, world, *plans) : run_sensitivity(a, world, *plans);
+    eg_plans_free(plans);
+    return rc;
+  }
   // more than one rank: the same reduced-update loop on an eg_group (the exchange between the ranks is inside the library)
   eg_ctx* ctx = nullptr; eg_group* group = nullptr;
   if (a.gpus_given && int32_t(a.ranks.size()) > eg_device_count()) {

@@ -1,4 +1,4 @@
-// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_plans / eg_place / eg_group .cpp): owned buffers, the
+// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_plans / eg_refine / eg_place / eg_group .cpp): owned buffers, the
 // error macros, the context and the helpers that cross units.  Host only: the kernels include eg_internal.h, never this.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -136,6 +136,8 @@ struct eg_ctx {
   // plan-edit batches (eg_evaluate_plan_edits): the base plan's block followed by the packed edits, 8 bytes each — what k_plan_edits reads
   eg::DevBuf<uint8_t> d_plan_edit_in;
   size_t n_plan_blocks = 0;      // blocks of the last plan or plan-edit batch in d_plans (eg_debug_fetch_plan_block)
+  // plan refinement (eg_refine_plan): the step log k_refine_pick writes, a ring of kRefineLog entries of kRefineEntryStride bytes
+  eg::DevBuf<uint8_t> d_refine_log;
 };
 
 namespace eg {
@@ -153,6 +155,10 @@ int device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, size_t pac
 int check_policy(const eg_policy_snapshot* s, const eg_opts* o, const char* who);
 void stage_policy(eg_ctx* c, const eg_policy_snapshot* s, bool have_lists, uint8_t* h);
 DevSnapshot snapshot_of(uint8_t* d_base, const eg_opts* o);
+void write_lists(uint8_t* dst, const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact);
+int stage_eval_snapshot(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, DevSnapshot* S);
+void pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len, uint32_t* packed, uint32_t* idx, uint32_t* n_short);
+int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index);
 // eg_fetch.cpp
 int fetch_records(const uint8_t* d_base, size_t N, eg_episode_out* o);
 int fold_reset(DevBuf<uint8_t>& d_fold);

@@ -433,6 +433,23 @@ constexpr uint32_t kTopKChunk = 1024;      // episodes per workgroup of k_topk_s
 // k_plan_edits (eg_plan_edits.h): the n plan blocks of a plan-edit batch into d_pool (snap::kPlanStride bytes each) from the base
 // plan's block d_base and n packed edits (8 bytes each: kind | list << 8 | year << 16 | action << 24, then pos)
 int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream);
+// k_refine_pick (eg_refine.h): the best candidate of the n variants of a refinement round (eg_refine_plan) — status EG_EP_OK and a rank
+// score that is not NaN; the largest score, ties to the lowest variant — into one entry of the step log, and, when it is not variant 0,
+// its plan block (d_pool + winner * snap::kPlanStride) over the base block d_base.  d_edits: the round's packed edits.
+struct RefineEntry {
+  int32_t winner, n_failed;        // -1: variant 0 is no candidate (nothing copied); variants that are no candidates
+  uint32_t edit[2];                // the winner's packed edit
+  double score, metrics[4];        // the winner's
+  int32_t off26, offd26;           // the two list totals of the winner's block
+  int32_t base_ok, n;              // variant 0 is a candidate; variants looked at
+  double base_score, base_metrics[4];
+};
+constexpr size_t kRefineEntryStride = 128;
+constexpr int kRefineLog = 256;
+static_assert(sizeof(RefineEntry) <= kRefineEntryStride, "refine entry");
+int launch_refine_pick(const DevOut& o, uint32_t n, int mode, const void* d_edits, const uint8_t* d_pool, uint8_t* d_base, void* d_entry, void* stream);
+// eg_checkpoint.cpp: one plan as a set eg_plans_free releases (counts [26], the flat lists)
+eg_plan_set* make_plan_set(const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact, const char* name);
 // k_topk_keys: rank score and key of every episode of the batch that can still enter the archive at d_state (else score -inf);
 // use_score_list: the statistics epilogue ran for this batch (mode 1 only: its scores are the rank scores)
 int launch_topk_keys(const DevOut& o, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state,

@@ -1,5 +1,5 @@
 // eg_plans.cpp — a policy in snapshot layout (shared with eg_upload_snapshot) and plan batches: eg_evaluate_plans, eg_evaluate_plan_edits,
-// launch_plans.
+// launch_plans (eg_refine.cpp loops over the same pieces).
 #include <algorithm>
 #include <cstring>
 
@@ -17,11 +17,10 @@ int eg::check_policy(const eg_policy_snapshot* s, const eg_opts* o, const char* 
   for (int i = 0; i < EG_YEARS * EG_N_DEFICIT; ++i) if (!(s->deficit_weights[i] > 0.0)) { set_error(std::string(who) + ": deficit weights must be > 0"); return EG_ERR_BAD_ARG; }
   return EG_OK;
 }
-namespace {
 // The list section of a snapshot at `dst` (snap::best_mask .. snap::state; a plan block has the same layout): per year the masks
 // (bit a: a occurs in best(y) or best_deficit(y) / in best_deficit(y)), the prefix offsets and the two lists.  count == NULL: none.
 // The lists' total lengths are the caller's to check (<= snap::kBestCap).
-void write_lists(uint8_t* dst, const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact) {
+void eg::write_lists(uint8_t* dst, const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact) {
   constexpr size_t b = snap::best_mask;
   int32_t off[28] = {0}, offd[28] = {0};
   unsigned long long mask[26] = {0}, dmask[26] = {0};
@@ -35,7 +34,6 @@ void write_lists(uint8_t* dst, const int32_t* count, const uint8_t* act, const i
   std::memcpy(dst + (snap::best_off - b), off, sizeof(off)); std::memcpy(dst + (snap::bestd_off - b), offd, sizeof(offd));
   if (count) { std::memcpy(dst + (snap::best_actions - b), act, size_t(off[26])); std::memcpy(dst + (snap::bestd_actions - b), dact, size_t(offd[26])); }
 }
-}  // namespace
 // The policy `s` in snapshot layout into the staging buffer h (snap::upload_bytes): packed rows, list section, scalars
 void eg::stage_policy(eg_ctx* c, const eg_policy_snapshot* s, bool have_lists, uint8_t* h) {
   {  // packed policy rows; sampling.rs:182, :352-355, :406: the sums the samplers start from, folded in table order
@@ -76,12 +74,11 @@ DevSnapshot eg::snapshot_of(uint8_t* d_base, const eg_opts* o) {
   return S;
 }
 
-namespace {
 // A plan batch (eg_evaluate_plans) over the n episodes of c->out: c->d_plan_index lists the n_short short plans (<= kShortReplayMax
 // actions), then the long ones.  The short-replay variant runs over exactly the short ones; the long ones go to k_replay_solo and the
 // long-replay variant, in launches of at most as many episodes as the penalty-field pool has slots (a long replay claims one per
 // launch epoch).  The hoist, the statistics epilogue and the best_result / top-K folds do not run.
-int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index) {
+int eg::launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index) {
   const uint32_t n_long = n - n_short;
   const bool helper = n <= c->helper_max_episodes;
   uint32_t done = 0;
@@ -104,13 +101,9 @@ int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_
   c->last_n = n; c->last_first = first_index;
   return EG_OK;
 }
-// The rest of a plan batch whose routing is in c->d_plan_index: the policy into a device snapshot of its own — has_best = 1 and lists
-// present (empty: every episode reads its plan block instead) —, then the launches.  `edits`: a plan-edit batch, whose blocks
-// k_plan_edits writes on the launches' stream from c->d_plan_edit_in (the base block, then the packed edits).
-// (The snapshot is staged last before the launches: a launch's start event takes the time the stream's previous command ended — with
-//  the snapshot staged first, eg_timing_read counted the host building the plan blocks.)
-int stage_and_launch_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short,
-                           bool edits, bool same_index) {
+// The policy a plan batch is evaluated under into a device snapshot of its own (c->d_eval_snap) — has_best = 1 and lists present
+// (empty: every episode reads its plan block instead) — with its stalled-sampler tables; *S: what the launches get, the plan pool set.
+int eg::stage_eval_snapshot(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, DevSnapshot* S) {
   eg_policy_snapshot ps = *s;
   static const int32_t kNoCounts[EG_YEARS] = {};
   static const uint8_t kNoActions[1] = {0};
@@ -120,9 +113,36 @@ int stage_and_launch_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts
   stage_policy(c, &ps, true, c->h_snap);
   EG_HIP(hipMemcpyAsync(c->d_eval_snap, c->h_snap, snap::upload_bytes, hipMemcpyHostToDevice, nullptr));
   EG_LAUNCH("k_stalled_tables", launch_stalled_tables(c->d_eval_snap, nullptr));      // sampling.rs:190-220, as at upload
+  *S = snapshot_of(c->d_eval_snap, o);
+  S->plan_pool = c->d_plans;
+  return EG_OK;
+}
+// What a plan-edit batch uploads behind the base block, 8 bytes per variant (eg_plan_edits.h unpack), and its routing — a variant's
+// best_actions list is the base's (base_len entries), one entry longer or shorter: the short variants' indices first, then the long ones'
+void eg::pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len, uint32_t* packed, uint32_t* idx, uint32_t* n_short) {
+  std::vector<uint32_t> longs;
+  uint32_t ns = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    const eg_plan_edit& e = edits[j];
+    const bool none = e.kind == EG_EDIT_NONE;
+    packed[2 * j] = none ? 0u : uint32_t(e.kind) | uint32_t(e.list) << 8 | uint32_t(e.year) << 16 | uint32_t(e.kind == EG_EDIT_DELETE ? 0 : e.action) << 24;
+    packed[2 * j + 1] = none ? 0u : e.pos;
+    const int64_t len = base_len + (!none && e.list == 0 ? (e.kind == EG_EDIT_INSERT ? 1 : e.kind == EG_EDIT_DELETE ? -1 : 0) : 0);
+    if (len > kShortReplayMax) longs.push_back(j); else idx[ns++] = j;
+  }
+  std::copy(longs.begin(), longs.end(), idx + ns);
+  *n_short = ns;
+}
+namespace {
+// The rest of a plan batch whose routing is in c->d_plan_index: the policy into its device snapshot, then the launches.  `edits`: a
+// plan-edit batch, whose blocks k_plan_edits writes on the launches' stream from c->d_plan_edit_in (the base block, then the packed edits).
+// (The snapshot is staged last before the launches: a launch's start event takes the time the stream's previous command ended — with
+//  the snapshot staged first, eg_timing_read counted the host building the plan blocks.)
+int stage_and_launch_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short,
+                           bool edits, bool same_index) {
+  DevSnapshot S{};
+  EG_TRY(stage_eval_snapshot(c, s, o, &S));
   if (edits) EG_LAUNCH("k_plan_edits", launch_plan_edits(c->d_plan_edit_in, c->d_plan_edit_in + snap::kPlanStride, n, c->d_plans, nullptr));
-  DevSnapshot S = snapshot_of(c->d_eval_snap, o);
-  S.plan_pool = c->d_plans;
   c->n_plan_blocks = n;
   return launch_plans(c, S, seed, first_index, n, n_short, same_index);
 }
@@ -202,27 +222,14 @@ extern "C" int32_t eg_evaluate_plan_edits(eg_ctx* c, const eg_policy_snapshot* s
   EG_HIP(hipSetDevice(c->device));
   const uint32_t n = uint32_t(n_edits);
   EG_TRY(ensure_outputs(c, n));
-  // what goes up: the base plan's block and 8 bytes per variant (eg_plan_edits.h unpack), and the routing — a variant's best_actions
-  // list is the base's, one entry longer or shorter: the short variants' indices first, then the long ones'
+  // what goes up: the base plan's block, the packed edits and the routing (pack_plan_edits)
   std::vector<uint8_t> in(snap::kPlanStride + size_t(n) * 8, 0);
   write_lists(in.data(), base->best_count, base->best_actions, base->best_deficit_count, base->best_deficit_actions);
   int64_t base_len = 0;
   for (int y = 0; y < EG_YEARS; ++y) base_len += base->best_count[y];
   std::vector<uint32_t> idx(n);
   uint32_t n_short = 0;
-  {
-    std::vector<uint32_t> longs;
-    uint32_t* packed = reinterpret_cast<uint32_t*>(in.data() + snap::kPlanStride);
-    for (uint32_t j = 0; j < n; ++j) {
-      const eg_plan_edit& e = edits[j];
-      const bool none = e.kind == EG_EDIT_NONE;
-      packed[2 * j] = none ? 0u : uint32_t(e.kind) | uint32_t(e.list) << 8 | uint32_t(e.year) << 16 | uint32_t(e.kind == EG_EDIT_DELETE ? 0 : e.action) << 24;
-      packed[2 * j + 1] = none ? 0u : e.pos;
-      const int64_t len = base_len + (!none && e.list == 0 ? (e.kind == EG_EDIT_INSERT ? 1 : e.kind == EG_EDIT_DELETE ? -1 : 0) : 0);
-      if (len > kShortReplayMax) longs.push_back(j); else idx[n_short++] = j;
-    }
-    std::copy(longs.begin(), longs.end(), idx.begin() + n_short);
-  }
+  pack_plan_edits(edits, n, base_len, reinterpret_cast<uint32_t*>(in.data() + snap::kPlanStride), idx.data(), &n_short);
   EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
   EG_HIP(c->d_plan_index.reserve(n));
   EG_HIP(c->d_plan_edit_in.reserve(in.size()));

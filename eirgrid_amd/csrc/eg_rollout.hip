@@ -2519,6 +2519,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_replay_coop.h"      // k_replay_coop, k_replay_broadcast: the replay episodes of a batch, computed once
 #include "eg_topk.h"             // k_topk_keys, k_topk_select, k_topk_merge: the top-K archive of distinct scenarios
 #include "eg_plan_edits.h"       // k_plan_edits: the plan blocks of a plan-edit batch from one base block and an edit per variant
+#include "eg_refine.h"           // k_refine_pick: the winner of a refinement round, its block made the next round's base
 
 // ---- B2: a single placement search, for parity tests of the arg-max --------------------------------------------
 __global__ void __launch_bounds__(kWave) k_place(DevTables T, int type, int yi, const uint16_t* __restrict__ cells,
@@ -3362,6 +3363,12 @@ static_assert(sizeof(EpisodeMap) == 64 && offsetof(EpisodeMap, solo) == 48, "Epi
 int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream) {
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_plan_edits, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_base, reinterpret_cast<const uint2*>(d_edits), n, d_pool);
+  return (int)hipGetLastError();
+}
+int launch_refine_pick(const DevOut& o, uint32_t n, int mode, const void* d_edits, const uint8_t* d_pool, uint8_t* d_base, void* d_entry, void* stream) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_refine_pick, dim3(1), dim3(refine::kThreads), 0, (hipStream_t)stream, o, n, mode, reinterpret_cast<const uint2*>(d_edits), d_pool, d_base,
+                     reinterpret_cast<RefineEntry*>(d_entry));
   return (int)hipGetLastError();
 }
 int launch_pick_best(const DevOut& o, uint32_t n, uint64_t first_index, UpdateCandidate* d_cand, void* stream) {

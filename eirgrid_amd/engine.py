@@ -207,6 +207,18 @@ class Plan:
         return f"Plan({self.name!r}, {len(self)} actions, {sum(len(l) for l in self.best_deficit_actions)} deficit actions)"
 
     @staticmethod
+    def _from_set(s) -> "list[Plan]":
+        out, pos, dpos = [], 0, 0
+        for j in range(s.n_plans):
+            run, dfc = [], []
+            for y in range(N.YEARS):
+                k, dk = s.best_count[j * N.YEARS + y], s.best_deficit_count[j * N.YEARS + y]
+                run.append(list(s.best_actions[pos:pos + k])); dfc.append(list(s.best_deficit_actions[dpos:dpos + dk]))
+                pos += k; dpos += dk
+            out.append(Plan(run, dfc, s.names[j].decode() if s.names else ""))
+        return out
+
+    @staticmethod
     def load(path: str) -> "list[Plan]":
         """Plans of a file in the checkpoint schema: one checkpoint (one plan) or JSON Lines with optional names (eg_plans_load)."""
         L = N.lib()
@@ -214,18 +226,15 @@ class Plan:
         if not ps:
             raise N.EirgridError(L.eg_last_error().decode())
         try:
-            s = ps.contents
-            out, pos, dpos = [], 0, 0
-            for j in range(s.n_plans):
-                run, dfc = [], []
-                for y in range(N.YEARS):
-                    k, dk = s.best_count[j * N.YEARS + y], s.best_deficit_count[j * N.YEARS + y]
-                    run.append(list(s.best_actions[pos:pos + k])); dfc.append(list(s.best_deficit_actions[dpos:dpos + dk]))
-                    pos += k; dpos += dk
-                out.append(Plan(run, dfc, s.names[j].decode() if s.names else ""))
-            return out
+            return Plan._from_set(ps.contents)
         finally:
             L.eg_plans_free(ps)
+
+    @staticmethod
+    def save(path: str, plans) -> None:
+        """The plans as JSON Lines in the checkpoint schema (eg_plans_save): what Plan.load and --evaluate read."""
+        ps = plans if isinstance(plans, PlanSet) else PlanSet(plans)
+        N.check(N.lib().eg_plans_save(C.byref(ps.s), str(path).encode()), "eg_plans_save")
 
     @staticmethod
     def from_policy(weights: "ActionWeights", name: str = "") -> "Plan":
@@ -313,6 +322,39 @@ def sensitivity_edits(base: "Plan", replace_with=None) -> "list[PlanEdit]":
         assert 0 <= int(a) < N.N_ACTIONS, a
     edits += [PlanEdit("replace", 0, y, i, int(a)) for y, l in enumerate(base.best_actions) for i in range(len(l)) for a in (replace_with or ())]
     return edits
+
+
+def refine_edits(base: "Plan", replace_with=None, append_with=None) -> "list[PlanEdit]":
+    """The variants of one round of Engine.refine_plan, in order: sensitivity_edits(base, replace_with), then per year and action of
+    `append_with` that action appended to the year's best_actions list — no appends while best_actions holds 4 096 entries."""
+    edits = sensitivity_edits(base, replace_with)
+    for a in (append_with or ()):
+        assert 0 <= int(a) < N.N_ACTIONS, a
+    if len(base) < N.RUN_CAP:
+        edits += [PlanEdit("insert", 0, y, len(l), int(a)) for y, l in enumerate(base.best_actions) for a in (append_with or ())]
+    return edits
+
+
+@dataclass
+class RefineStep:
+    """One applied edit of Engine.refine_plan (eg_refine_step): the edit against the plan of its round, its place among the round's
+    n_variants variants, how many of them were no candidates, and the score and metrics it reached."""
+    edit: "PlanEdit"
+    variant: int
+    n_variants: int
+    n_failed: int
+    score: float
+    metrics: np.ndarray
+
+
+REFINE_STOP = ("local_optimum", "max_rounds", "base_failed")
+
+
+def _refine_opts(mode, max_rounds, replace_with, append_with):
+    """(eg_refine_opts, the arrays it points into)"""
+    rep = np.array(list(replace_with or []), np.uint8); app = np.array(list(append_with or []), np.uint8)
+    opts = N.EgRefineOpts(int(mode), int(max_rounds), len(rep), _p(rep, C.c_uint8) if len(rep) else None, len(app), _p(app, C.c_uint8) if len(app) else None)
+    return opts, (rep, app)
 
 
 def _fetch_top_k(fn, handle, what):
@@ -515,6 +557,35 @@ class Engine:
         both = (res.status == N.EG_EP_OK) & (res.status[0] == N.EG_EP_OK)
         d_metrics = np.where(both[:, None], res.metrics - res.metrics[0], np.nan)
         return Sensitivity(edits, res, res.status.copy(), res.metrics.copy(), score, d_metrics, np.where(both, score - score[0], np.nan))
+
+    def refine_plan(self, weights: ActionWeights, base: "Plan", seed: int, index: int = 0, mode: int = 1, max_rounds: int = 64, replace_with=None,
+                    append_with=None, enable_energy_sales=True, write_yearly=True):
+        """Greedy refinement of `base` on the device (eg_refine_plan): per round the variants of refine_edits(plan, replace_with,
+        append_with), all at global index `index` of `seed`; the best candidate by eg_rank_score in `mode` (ties: the lowest variant, so
+        only a strict improvement moves the plan) becomes the next round's plan.  Returns (refined Plan, [RefineStep], stop reason — one of
+        REFINE_STOP —, the base's score (NaN when it failed), the refined plan's record as a BatchResult of one episode, or None when the
+        base failed)."""
+        ps = PlanSet([base])
+        ro, keep = _refine_opts(mode, max_rounds, replace_with, append_with)
+        steps = (N.EgRefineStep * max(int(max_rounds), 1))()
+        n_steps, stop = C.c_int32(0), C.c_int32(0)
+        start = C.c_double(float("nan"))
+        refined = C.POINTER(N.EgPlanSet)()
+        res = BatchResult.alloc(1)
+        snap = weights.snapshot()
+        opts = self._opts(enable_energy_sales, False, write_yearly)
+        out = res.struct()
+        L = N.lib()
+        N.check(L.eg_refine_plan(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(ro), C.c_uint64(seed & (2**64 - 1)), C.c_uint64(index),
+                                 C.byref(refined), steps, C.byref(n_steps), C.byref(stop), C.byref(start), C.byref(out)), "eg_refine_plan")
+        try:
+            plan = Plan._from_set(refined.contents)[0]
+        finally:
+            L.eg_plans_free(refined)
+        rows = [RefineStep(PlanEdit(PlanEdit.KINDS[s.edit.kind], s.edit.list, s.edit.year, s.edit.pos, s.edit.action), s.variant, s.n_variants, s.n_failed,
+                           s.score, np.array(s.metrics[:])) for s in steps[:n_steps.value]]
+        reason = REFINE_STOP[stop.value]
+        return plan, rows, reason, start.value, (None if reason == "base_failed" else res)
 
     # device-resident path used by bench.py
     def upload_snapshot(self, weights: ActionWeights, enable_energy_sales=True, write_yearly=True):

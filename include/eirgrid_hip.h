@@ -304,6 +304,9 @@ int32_t eg_evaluate_plans(eg_ctx *, const eg_policy_snapshot *policy, const eg_o
                           uint64_t first_episode_index, eg_episode_out *out /* may be NULL */);
 eg_plan_set *eg_plans_load(const char *path);
 void eg_plans_free(eg_plan_set *);
+/* Writes the plans as JSON Lines in the same schema, one object per line with its name: what eg_plans_load reads back.  The set is
+ * validated first (eg_plans_validate). */
+int32_t eg_plans_save(const eg_plan_set *, const char *path);
 
 /* Plan edits: which actions of a plan matter?  eg_evaluate_plan_edits(ctx, policy, opts, base, edits, n_edits, seed,
  * first_episode_index, same_index, out) evaluates n_edits VARIANTS of one base plan (a plan set of exactly one plan), variant j being the
@@ -336,6 +339,45 @@ int32_t eg_evaluate_plan_edits(eg_ctx *, const eg_policy_snapshot *policy, const
  * finished that batch.  A plan-edit batch's blocks must equal, byte for byte, the blocks eg_evaluate_plans builds for the edited plans. */
 #define EG_PLAN_BLOCK_BYTES 8832
 int32_t eg_debug_fetch_plan_block(eg_ctx *, uint32_t plan, uint8_t *out /* EG_PLAN_BLOCK_BYTES */);
+
+/* Greedy plan refinement: apply the best one-entry edit of a plan, again and again, without leaving the device.
+ * eg_refine_plan(ctx, policy, opts, base, refine_opts, seed, episode_index, ...) starts from the base plan B_0 (a plan set of exactly one
+ * plan).  In round r the VARIANTS of B_r are, in this order:
+ *   1. the base itself (EG_EDIT_NONE); every best_actions entry deleted, in (year, position) order; every best_deficit_actions entry
+ *      deleted likewise; every best_actions entry, in the same order, replaced by each action of replace_with in the given order — the
+ *      order of the CLI's --sensitivity table;
+ *   2. for every year 0..25 and each action of append_with in the given order, that action inserted behind the last entry of the
+ *      year's best_actions list (an empty year: at position 0).  No appends while best_actions holds 4 096 entries.
+ * All variants are evaluated as eg_evaluate_plan_edits(..., first_episode_index = episode_index, same_index = 1) evaluates them.
+ * Variant j is a CANDIDATE when its status is EG_EP_OK and s_j = eg_rank_score(metrics_j, mode) is not NaN; the WINNER is the candidate
+ * with the largest s_j, ties to the lowest j — variant 0 is the base, so only a strict improvement moves the plan.
+ *   variant 0 is no candidate   stop with EG_REFINE_BASE_FAILED; B_r is returned, no step is recorded for the round
+ *   the winner is variant 0     stop with EG_REFINE_LOCAL_OPTIMUM
+ *   otherwise                   B_{r+1} is the winner's plan and a step is recorded: its edit (against B_r), its variant index, the round's
+ *                               variant count, how many variants were no candidates, its score and metrics
+ *   after max_rounds steps      stop with EG_REFINE_MAX_ROUNDS
+ * The winner is picked on the device (csrc/eg_refine.h k_refine_pick) and its plan block becomes the next round's base there; per round
+ * the host uploads 12 bytes per variant and reads one entry of at most 128 bytes back.  The policy is checked, staged and uploaded once
+ * per call.  Everything else is the contract of eg_evaluate_plan_edits: no statistics, update or folds, the resident policy untouched, a
+ * rank of a group refused; the last round's variants stay behind as the last batch for eg_fetch / eg_fetch_record.
+ * *refined: the final plan (free with eg_plans_free); steps[max_rounds], *n_steps, *stop_reason; *start_score: s_0 of round 0 (NaN when
+ * the base failed); `out` (one episode, may be NULL): the refined plan's record — variant 0 of the last round on LOCAL_OPTIMUM, the last
+ * winner on MAX_ROUNDS, not written on BASE_FAILED.  A round that would enumerate more than EG_REFINE_MAX_VARIANTS variants is refused
+ * (EG_ERR_BAD_ARG naming the round and the count): round 0 by eg_refine_validate, later rounds when they are reached.
+ * eg_refine_validate runs the checks alone: mode 1 or 2, max_rounds >= 1, actions 0..60, no NULL list with a count, a base of exactly
+ * one valid plan. */
+#define EG_REFINE_LOCAL_OPTIMUM 0
+#define EG_REFINE_MAX_ROUNDS 1
+#define EG_REFINE_BASE_FAILED 2
+#define EG_REFINE_MAX_VARIANTS 16384
+typedef struct { int32_t mode /* 1 | 2 */, max_rounds; int32_t n_replace; const uint8_t *replace_with;
+                 int32_t n_append; const uint8_t *append_with; } eg_refine_opts;
+typedef struct { eg_plan_edit edit; int32_t variant, n_variants, n_failed; double score; double metrics[4]; } eg_refine_step;
+int32_t eg_refine_validate(const eg_plan_set *base, const eg_refine_opts *);
+int32_t eg_refine_plan(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, const eg_plan_set *base /* 1 plan */,
+                       const eg_refine_opts *, uint64_t seed, uint64_t episode_index,
+                       eg_plan_set **refined /* eg_plans_free */, eg_refine_step *steps /* max_rounds */,
+                       int32_t *n_steps, int32_t *stop_reason, double *start_score, eg_episode_out *out /* 1 episode or NULL */);
 
 /* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
  * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
