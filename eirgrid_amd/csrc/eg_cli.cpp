@@ -13,49 +13,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <ctime>
-#include <fstream>
 #include <random>
-#include <sstream>
-#include <string>
-#include <vector>
 
 #include <dirent.h>
-#include <sys/stat.h>
 
+#include "eg_cli.h"
 #include "eg_json.h"
-#include "eirgrid_hip.h"
 
 namespace {
-
-struct Args {   // cli/cli.rs:5-59
-  uint64_t iterations = 1000; bool parallel = true; bool no_continue = false; std::string checkpoint_dir = "checkpoints";
-  uint64_t checkpoint_interval = 5; uint64_t progress_interval = 10; std::string cache_dir = "cache";
-  bool force_full_simulation = false, enable_timing = false; bool has_seed = false; uint64_t seed = 0;
-  bool verbose_state_logging = false, cost_only = false, enable_energy_sales = true, enable_csv_export = true;
-  bool debug_logging = false, debug_weights = false, enable_construction_delays = false, track_weight_history = false;
-  // engine-specific
-  std::string world_json, assets_dir = "aiSimulator/assets"; uint32_t batch = 1024; std::string update = "reduced"; int device = 0;
-  bool existing_operational_at_start = false;
-  uint64_t stop_after = 0;      // leave the loop (as an interrupt would) once this many iterations are done and checkpointed
-  std::string dump_world;       // write the loaded world (eirgrid_amd JSON form) there and exit: no device needed
-  bool replay_hoist = true;     // the replay iterations of a batch computed once (eg_replay_hoist): the same results, the replay phases 5x faster
-  // --gpus N / --devices LIST: the ranks of a multi-GPU run (eg_group), one device each; empty: the single-device run on --device
-  std::vector<int32_t> ranks; bool device_given = false, gpus_given = false;
-  int32_t top_k = 0;            // --top-k K: keep the K best distinct scenarios of the run (eg_top_k_track) and export them; 0: off
-  std::string evaluate;         // --evaluate FILE: score the plans of FILE (eg_evaluate_plans) and exit; no training
-  std::string evaluate_policy;  // --evaluate-policy CKPT: the policy the plans are evaluated under (default: ActionWeights::new)
-  std::string sensitivity;      // --sensitivity FILE: score every one-entry edit of FILE's first plan (eg_evaluate_plan_edits) and exit
-  std::vector<uint8_t> sensitivity_replace;      // --sensitivity-replace a,b,...: also every best_actions entry replaced by each of these
-  std::string refine;           // --refine FILE: apply the best one-entry edit of FILE's plan round after round (eg_refine_plan) and exit
-  int32_t refine_rounds = 64; bool refine_rounds_given = false;      // --refine-rounds N: at most N applied edits
-  std::vector<uint8_t> refine_replace, refine_append;      // --refine-replace / --refine-append a,b,...: the moves beside the deletes
-};
 
 void usage() {
   std::puts("Usage: eirgrid-hip [OPTIONS]\n"
@@ -97,6 +63,24 @@ void usage() {
             "      --refine-append <a,b,...>   ... and each of these actions appended to each year's best_actions list");
 }
 
+// digits only, at most max_digits of them, lo <= value <= hi: every number of the command line that is checked at all
+bool parse_uint(const std::string& text, size_t max_digits, int lo, int hi, int32_t* out) {
+  if (text.empty() || text.size() > max_digits || text.find_first_not_of("0123456789") != std::string::npos) return false;
+  *out = std::atoi(text.c_str());
+  return *out >= lo && *out <= hi;
+}
+// a comma-separated list of such numbers, appended to `out`; an empty item is refused
+template <class T> bool parse_list(const std::string& list, size_t max_digits, int hi, std::vector<T>& out) {
+  for (size_t pos = 0; pos <= list.size();) {
+    const size_t comma = std::min(list.find(',', pos), list.size());
+    int32_t k;
+    if (!parse_uint(list.substr(pos, comma - pos), max_digits, 0, hi, &k)) return false;
+    out.push_back(T(k));
+    pos = comma + 1;
+  }
+  return true;
+}
+
 bool parse(int argc, char** argv, Args& a) {
   auto need = [&](int& i) -> const char* { if (i + 1 >= argc) { std::fprintf(stderr, "error: %s needs a value\n", argv[i]); std::exit(2); } return argv[++i]; };
   for (int i = 1; i < argc; ++i) {
@@ -134,20 +118,13 @@ bool parse(int argc, char** argv, Args& a) {
       if (a.gpus_given || !a.ranks.empty()) { std::fprintf(stderr, "error: --gpus and --devices are given more than once\n"); return false; }
       a.gpus_given = gpus;
       // --gpus N: a count >= 1; --devices: comma-separated ordinals >= 0 (digits only)
-      size_t pos = 0;
-      while (true) {
-        const size_t comma = gpus ? std::string::npos : list.find(',', pos);
-        const std::string item = list.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
-        if (item.empty() || item.size() > 6 || item.find_first_not_of("0123456789") != std::string::npos) {
-          std::fprintf(stderr, "error: %s needs %s, got '%s'\n", s.c_str(), gpus ? "a number of GPUs" : "a comma-separated list of device numbers", list.c_str());
-          return false;
-        }
-        const int k = std::atoi(item.c_str());
-        if (gpus) { if (k < 1) { std::fprintf(stderr, "error: --gpus needs at least 1\n"); return false; } for (int d = 0; d < k; ++d) a.ranks.push_back(d); }
-        else a.ranks.push_back(k);
-        if (comma == std::string::npos) break;
-        pos = comma + 1;
+      int32_t k = 0;
+      if (gpus ? !parse_uint(list, 6, 0, 999999, &k) : !parse_list(list, 6, 999999, a.ranks)) {
+        std::fprintf(stderr, "error: %s needs %s, got '%s'\n", s.c_str(), gpus ? "a number of GPUs" : "a comma-separated list of device numbers", list.c_str());
+        return false;
       }
+      if (gpus && k < 1) { std::fprintf(stderr, "error: --gpus needs at least 1\n"); return false; }
+      for (int32_t d = 0; d < k; ++d) a.ranks.push_back(d);
     }
     else if (s == "--existing-operational-at-start") a.existing_operational_at_start = true;
     else if (s == "--stop-after") a.stop_after = std::strtoull(v().c_str(), nullptr, 10);
@@ -155,37 +132,23 @@ bool parse(int argc, char** argv, Args& a) {
     else if (s == "--no-replay-hoist") a.replay_hoist = false;
     else if (s == "--top-k") {
       const std::string k = v();
-      if (k.empty() || k.size() > 3 || k.find_first_not_of("0123456789") != std::string::npos || std::atoi(k.c_str()) > EG_TOPK_MAX) {
-        std::fprintf(stderr, "error: --top-k needs a number from 0 to %d, got '%s'\n", EG_TOPK_MAX, k.c_str());
-        return false;
-      }
-      a.top_k = std::atoi(k.c_str());
+      if (!parse_uint(k, 3, 0, EG_TOPK_MAX, &a.top_k)) { std::fprintf(stderr, "error: --top-k needs a number from 0 to %d, got '%s'\n", EG_TOPK_MAX, k.c_str()); return false; }
     }
     else if (s == "--evaluate") a.evaluate = v();
     else if (s == "--evaluate-policy") a.evaluate_policy = v();
     else if (s == "--sensitivity") a.sensitivity = v();
     else if (s == "--sensitivity-replace" || s == "--refine-replace" || s == "--refine-append") {
       const std::string list = v();
-      std::vector<uint8_t>& into = s == "--sensitivity-replace" ? a.sensitivity_replace : s == "--refine-replace" ? a.refine_replace : a.refine_append;
-      for (size_t pos = 0; pos <= list.size();) {
-        const size_t comma = std::min(list.find(',', pos), list.size());
-        const std::string item = list.substr(pos, comma - pos);
-        if (item.empty() || item.size() > 2 || item.find_first_not_of("0123456789") != std::string::npos || std::atoi(item.c_str()) >= EG_N_ACTIONS) {
-          std::fprintf(stderr, "error: %s needs a comma-separated list of canonical actions 0..%d, got '%s'\n", s.c_str(), EG_N_ACTIONS - 1, list.c_str());
-          return false;
-        }
-        into.push_back(uint8_t(std::atoi(item.c_str())));
-        pos = comma + 1;
+      if (!parse_list(list, 2, EG_N_ACTIONS - 1, s == "--sensitivity-replace" ? a.sensitivity_replace : s == "--refine-replace" ? a.refine_replace : a.refine_append)) {
+        std::fprintf(stderr, "error: %s needs a comma-separated list of canonical actions 0..%d, got '%s'\n", s.c_str(), EG_N_ACTIONS - 1, list.c_str());
+        return false;
       }
     }
     else if (s == "--refine") a.refine = v();
     else if (s == "--refine-rounds") {
       const std::string k = v();
-      if (k.empty() || k.size() > 6 || k.find_first_not_of("0123456789") != std::string::npos || std::atoi(k.c_str()) < 1) {
-        std::fprintf(stderr, "error: --refine-rounds needs a number from 1 to 999999, got '%s'\n", k.c_str());
-        return false;
-      }
-      a.refine_rounds = std::atoi(k.c_str()); a.refine_rounds_given = true;
+      a.refine_rounds_given = true;
+      if (!parse_uint(k, 6, 1, 999999, &a.refine_rounds)) { std::fprintf(stderr, "error: --refine-rounds needs a number from 1 to 999999, got '%s'\n", k.c_str()); return false; }
     }
     else if (s == "-h" || s == "--help") { usage(); std::exit(0); }
     else { std::fprintf(stderr, "error: unexpected argument '%s'\n", argv[i]); usage(); return false; }
@@ -210,22 +173,6 @@ bool parse(int argc, char** argv, Args& a) {
   return true;
 }
 
-bool read_file(const std::string& path, std::string& out) {
-  std::ifstream f(path, std::ios::binary); if (!f) return false;
-  std::stringstream ss; ss << f.rdbuf(); out = ss.str(); return true;
-}
-bool exists(const std::string& p) { struct stat st; return ::stat(p.c_str(), &st) == 0; }
-void mkdirs(const std::string& p) { std::string cur; for (size_t i = 0; i <= p.size(); ++i) { if (i == p.size() || p[i] == '/') { if (!cur.empty()) ::mkdir(cur.c_str(), 0755); } if (i < p.size()) cur += p[i]; } }
-
-struct WorldData {
-  std::vector<double> sx, sy; std::vector<uint32_t> spop; std::vector<double> gx, gy, gcap; std::vector<int32_t> gtype; std::vector<double> cx, cy;
-  std::vector<std::string> names;      // settlement names (settlements.csv of the export); empty: "Settlement_<i>"
-  eg_world view(bool at_start) const {
-    eg_world w{}; w.n_settlements = int32_t(sx.size()); w.settlement_x = sx.data(); w.settlement_y = sy.data(); w.settlement_pop = spop.data();
-    w.n_existing = int32_t(gx.size()); w.existing_x = gx.data(); w.existing_y = gy.data(); w.existing_type = gtype.data(); w.existing_capacity_mw = gcap.data();
-    w.n_coast = int32_t(cx.size()); w.coast_x = cx.data(); w.coast_y = cy.data(); w.existing_operational_at_start = at_start ? 1 : 0; return w;
-  }
-};
 bool parse_json(const std::string& path, eg::Json& root) {
   std::string text; if (!read_file(path, text)) return false;
   eg::JsonParser ps{text.data(), text.data() + text.size(), {}};
@@ -304,285 +251,39 @@ std::string newest_run_dir(const std::string& base) {   // multi_simulation.rs:2
   return best.empty() ? best : base + "/" + best;
 }
 
-#define CHECK(call) do { int32_t rc_ = (call); if (rc_ < 0) { std::fprintf(stderr, "%s failed (%d): %s\n", #call, rc_, eg_last_error()); return 1; } } while (0)
-
-std::string time_stamp(const char* fmt) { char buf[32]; std::time_t t = std::time(nullptr); std::tm tmv; localtime_r(&t, &tmv); std::strftime(buf, sizeof(buf), fmt, &tmv); return buf; }
-
-// --evaluate: every plan of `plans` scored under one policy (eg_evaluate_plans), plan j as iteration j of the run's seed, --batch plans
-// per launch.  <checkpoint-dir>/<stamp>/plans/index.csv gets a row per plan; --top-k K exports the K best plans like top_k/ exports an
-// entry (score descending, ties to the lower plan index; failed plans are not ranked).
-int run_evaluate(const Args& a, const WorldData& wd, const eg_world& world, const eg_plan_set& plans) {
-  eg_policy* policy = a.evaluate_policy.empty() ? eg_policy_new() : eg_policy_load_json(a.evaluate_policy.c_str());
-  if (!policy) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
-  eg_ctx* ctx = eg_create(a.device, &world);
-  if (!ctx) { std::fprintf(stderr, "eg_create: %s\n", eg_last_error()); eg_policy_free(policy); return 1; }
-  const uint32_t n = uint32_t(plans.n_plans);
-  const int mode = a.cost_only ? 2 : 1;
-  eg_opts opts{a.enable_energy_sales ? 1 : 0, 0, 1};
-  eg_policy_snapshot snap; CHECK(eg_policy_snapshot_view(policy, &snap));
-  // where plan j's entries start in the flat lists
-  std::vector<int64_t> pos(n + 1, 0), dpos(n + 1, 0);
-  for (uint32_t j = 0; j < n; ++j) {
-    int64_t k = 0, dk = 0;
-    for (int y = 0; y < EG_YEARS; ++y) { k += plans.best_count[size_t(j) * EG_YEARS + y]; dk += plans.best_deficit_count[size_t(j) * EG_YEARS + y]; }
-    pos[j + 1] = pos[j] + k; dpos[j + 1] = dpos[j] + dk;
-  }
-  auto subset = [&](uint32_t j0, uint32_t m) {      // plans [j0, j0 + m) as a set of their own
-    eg_plan_set s = plans;
-    s.n_plans = int32_t(m);
-    s.best_count = plans.best_count + size_t(j0) * EG_YEARS; s.best_deficit_count = plans.best_deficit_count + size_t(j0) * EG_YEARS;
-    s.best_actions = plans.best_actions + pos[j0]; s.best_deficit_actions = plans.best_deficit_actions + dpos[j0];
-    s.best_actions_len = pos[j0 + m] - pos[j0]; s.best_deficit_actions_len = dpos[j0 + m] - dpos[j0];
-    s.names = plans.names ? plans.names + j0 : nullptr;
-    return s;
-  };
-  std::vector<double> metrics(size_t(n) * 4); std::vector<int32_t> status(n), n_gens(n);
-  const auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t j0 = 0; j0 < n; j0 += a.batch) {
-    const uint32_t m = std::min(a.batch, n - j0);
-    const eg_plan_set s = subset(j0, m);
-    eg_episode_out out{}; out.metrics = &metrics[size_t(j0) * 4]; out.status = &status[j0]; out.n_gens = &n_gens[j0];
-    CHECK(eg_evaluate_plans(ctx, &snap, &opts, &s, a.seed, j0, &out));
-  }
-  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  std::vector<double> score(n);
-  std::vector<uint32_t> order;
-  for (uint32_t j = 0; j < n; ++j) {
-    score[j] = status[j] == EG_EP_OK ? eg_rank_score(&metrics[size_t(j) * 4], mode) : std::nan("");
-    if (status[j] == EG_EP_OK) order.push_back(j);
-  }
-  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return score[x] > score[y]; });
-  const std::string stamp = time_stamp("%Y%m%d_%H%M%S"), dir = a.checkpoint_dir + "/" + stamp + "/plans";
-  mkdirs(dir);
-  auto name_of = [&](uint32_t j) { return std::string(plans.names && plans.names[j] ? plans.names[j] : ""); };
-  {
-    std::ofstream f(dir + "/index.csv");
-    f << "plan,name,status,score,final_net_emissions,average_public_opinion,total_cost,power_reliability,n_generators\n";
-    for (uint32_t j = 0; j < n; ++j) {
-      std::string name = name_of(j);      // (a name with a comma, a quote or a line break is quoted, CSV style)
-      if (name.find_first_of(",\"\n") != std::string::npos) {
-        std::string q = "\"";
-        for (char ch : name) { if (ch == '"') q += '"'; q += ch; }
-        name = q + "\"";
-      }
-      const double* m = &metrics[size_t(j) * 4];
-      char line[512];
-      std::snprintf(line, sizeof(line), ",%d,%.17g,%.17g,%.17g,%.17g,%.17g,%d\n", status[j], score[j], m[0], m[1], m[2], m[3], n_gens[j]);
-      f << j << ',' << name << line;
-    }
-    if (!f) { std::fprintf(stderr, "error: cannot write %s/index.csv\n", dir.c_str()); return 1; }
-  }
-  if (a.top_k > 0) {      // the K best plans, each evaluated once more on its own (the same episode: same policy, seed and index)
-    std::vector<double> m1(4), yearly(size_t(EG_YEARS) * EG_YEARLY_FIELDS);
-    std::vector<int32_t> n_act(EG_YEARS); std::vector<uint8_t> act(EG_ACT_CAP); std::vector<uint16_t> pack(EG_MAX_GENS); int32_t g = 0, st = 0;
-    std::vector<const char*> names;
-    for (const std::string& nm : wd.names) names.push_back(nm.c_str());
-    const std::string tk = dir + "/top_k";
-    for (size_t r = 0; r < order.size() && r < size_t(a.top_k); ++r) {
-      const uint32_t j = order[r];
-      const eg_plan_set s = subset(j, 1);
-      eg_episode_out one{}; one.metrics = m1.data(); one.yearly = yearly.data(); one.n_act = n_act.data(); one.act_log = act.data();
-      one.n_gens = &g; one.gen_pack = pack.data(); one.status = &st;
-      CHECK(eg_evaluate_plans(ctx, &snap, &opts, &s, a.seed, j, &one));
-      char sub[24]; std::snprintf(sub, sizeof(sub), "/%02zu", r + 1);
-      const std::string ed = tk + sub;
-      mkdirs(ed);
-      CHECK(eg_export_summary_csv(&one, (ed + "/simulation_summary.csv").c_str(), stamp.c_str()));
-      CHECK(eg_export_run_details(&world, names.size() == wd.sx.size() ? names.data() : nullptr, &one, ed.c_str(), a.seed));
-    }
-  }
-  if (order.empty()) std::printf("Evaluated %u plans in %.3f s (%.0f plans/s); no plan finished\n", n, secs, double(n) / std::max(secs, 1e-9));
-  else {
-    const std::string best = name_of(order[0]).empty() ? std::string() : " (" + name_of(order[0]) + ")";
-    std::printf("Evaluated %u plans in %.3f s (%.0f plans/s); best plan %u%s score %.6f; written to %s\n", n, secs, double(n) / std::max(secs, 1e-9),
-                order[0], best.c_str(), score[order[0]], dir.c_str());
-  }
-  eg_policy_free(policy);
-  eg_destroy(ctx);
-  return 0;
-}
-
-// --sensitivity: the first plan of `plans` as it is and with every one-entry edit of the canonical order (include/eirgrid_hip.h
-// eg_evaluate_plan_edits; the order of Engine.plan_sensitivity): none; every best_actions entry deleted, in (year, position) order; every
-// best_deficit_actions entry deleted; with --sensitivity-replace, every best_actions entry replaced by each listed action.  All variants
-// run as iteration 0 of the run's seed (same_index), --batch edits per launch.  <checkpoint-dir>/<stamp>/sensitivity/index.csv gets a row
-// per edit: the calendar year, the canonical actions before and after, metrics and score as plans/index.csv writes them, and their
-// differences from row 0 (NaN where either variant failed).
-int run_sensitivity(const Args& a, const eg_world& world, const eg_plan_set& plans) {
-  eg_plan_set base = plans;
-  base.n_plans = 1; base.names = nullptr;
-  base.best_actions_len = 0; base.best_deficit_actions_len = 0;
-  for (int y = 0; y < EG_YEARS; ++y) { base.best_actions_len += plans.best_count[y]; base.best_deficit_actions_len += plans.best_deficit_count[y]; }
-  std::vector<eg_plan_edit> edits(1, eg_plan_edit{EG_EDIT_NONE, 0, 0, 0, 0});
-  std::vector<int> before(1, -1);
-  const int32_t* count[2] = {base.best_count, base.best_deficit_count};
-  const uint8_t* flat[2] = {base.best_actions, base.best_deficit_actions};
-  for (int w = 0; w < 2; ++w) {
-    int64_t at = 0;
-    for (int y = 0; y < EG_YEARS; ++y)
-      for (int32_t i = 0; i < count[w][y]; ++i, ++at) { edits.push_back(eg_plan_edit{EG_EDIT_DELETE, uint8_t(w), uint16_t(y), uint32_t(i), 0}); before.push_back(flat[w][at]); }
-  }
-  if (!a.sensitivity_replace.empty()) {
-    int64_t at = 0;
-    for (int y = 0; y < EG_YEARS; ++y)
-      for (int32_t i = 0; i < count[0][y]; ++i, ++at)
-        for (uint8_t act : a.sensitivity_replace) { edits.push_back(eg_plan_edit{EG_EDIT_REPLACE, 0, uint16_t(y), uint32_t(i), act}); before.push_back(flat[0][at]); }
-  }
-  const uint32_t n = uint32_t(edits.size());
-  CHECK(eg_plan_edits_validate(&base, edits.data(), int32_t(n)));
-  struct Owned {      // released on every way out
-    eg_policy* policy = nullptr; eg_ctx* ctx = nullptr;
-    ~Owned() { if (policy) eg_policy_free(policy); if (ctx) eg_destroy(ctx); }
-  } own;
-  eg_policy* policy = own.policy = a.evaluate_policy.empty() ? eg_policy_new() : eg_policy_load_json(a.evaluate_policy.c_str());
-  if (!policy) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
-  eg_ctx* ctx = own.ctx = eg_create(a.device, &world);
-  if (!ctx) { std::fprintf(stderr, "eg_create: %s\n", eg_last_error()); return 1; }
-  const int mode = a.cost_only ? 2 : 1;
-  eg_opts opts{a.enable_energy_sales ? 1 : 0, 0, 1};
-  eg_policy_snapshot snap; CHECK(eg_policy_snapshot_view(policy, &snap));
-  std::vector<double> metrics(size_t(n) * 4); std::vector<int32_t> status(n);
-  const auto t0 = std::chrono::steady_clock::now();
-  for (uint32_t j0 = 0; j0 < n; j0 += a.batch) {
-    const uint32_t m = std::min(a.batch, n - j0);
-    eg_episode_out out{}; out.metrics = &metrics[size_t(j0) * 4]; out.status = &status[j0];
-    CHECK(eg_evaluate_plan_edits(ctx, &snap, &opts, &base, &edits[j0], int32_t(m), a.seed, 0, 1, &out));
-  }
-  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  const std::string stamp = time_stamp("%Y%m%d_%H%M%S"), dir = a.checkpoint_dir + "/" + stamp + "/sensitivity";
-  mkdirs(dir);
-  std::vector<double> score(n);
-  for (uint32_t j = 0; j < n; ++j) score[j] = status[j] == EG_EP_OK ? eg_rank_score(&metrics[size_t(j) * 4], mode) : std::nan("");
-  {
-    static const char* kKind[4] = {"none", "delete", "replace", "insert"};
-    std::ofstream f(dir + "/index.csv");
-    f << "edit,kind,list,year,pos,action_before,action_after,status,net_emissions,public_opinion,total_cost,power_reliability,score,"
-         "d_net_emissions,d_public_opinion,d_total_cost,d_score\n";
-    const bool base_ok = status[0] == EG_EP_OK;
-    for (uint32_t j = 0; j < n; ++j) {
-      const eg_plan_edit& e = edits[j];
-      const double* m = &metrics[size_t(j) * 4];
-      char line[640];
-      int k = std::snprintf(line, sizeof(line), "%u,%s,", j, kKind[e.kind]);
-      if (e.kind == EG_EDIT_NONE) k += std::snprintf(line + k, sizeof(line) - k, ",,,,,");
-      else {
-        k += std::snprintf(line + k, sizeof(line) - k, "%s,%d,%u,%d,", e.list ? "best_deficit_actions" : "best_actions", 2025 + int(e.year), e.pos, before[j]);
-        if (e.kind == EG_EDIT_DELETE) k += std::snprintf(line + k, sizeof(line) - k, ",");
-        else k += std::snprintf(line + k, sizeof(line) - k, "%d,", int(e.action));
-      }
-      const bool both = base_ok && status[j] == EG_EP_OK;
-      const double nan = std::nan("");
-      std::snprintf(line + k, sizeof(line) - k, "%d,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g,%.17g\n", status[j], m[0], m[1], m[2], m[3], score[j],
-                    both ? m[0] - metrics[0] : nan, both ? m[1] - metrics[1] : nan, both ? m[2] - metrics[2] : nan, both ? score[j] - score[0] : nan);
-      f << line;
-    }
-    if (!f) { std::fprintf(stderr, "error: cannot write %s/index.csv\n", dir.c_str()); return 1; }
-  }
-  std::printf("Evaluated %u edits in %.3f s (%.0f edits/s); written to %s\n", n, secs, double(n) / std::max(secs, 1e-9), dir.c_str());
-  return 0;
-}
-
-// --refine: the plan of `plans` improved greedily on the device (include/eirgrid_hip.h eg_refine_plan): per round every one-entry edit —
-// the deletes, with --refine-replace the replaces, with --refine-append the appends — as iteration 0 of the run's seed, the best one
-// applied while it improves the score.  <checkpoint-dir>/<stamp>/refine/trajectory.csv: row 0 the start, then a row per applied edit
-// (the round, the edit with its calendar year, its place among the round's variants, how many of them failed, score and metrics as
-// plans/index.csv writes them), a last line with the stop reason; refine/refined.jsonl: the refined plan, as --evaluate reads it.
-int run_refine(const Args& a, const eg_world& world, const eg_plan_set& plans) {
-  eg_refine_opts ro{a.cost_only ? 2 : 1, a.refine_rounds, int32_t(a.refine_replace.size()), a.refine_replace.empty() ? nullptr : a.refine_replace.data(),
-                    int32_t(a.refine_append.size()), a.refine_append.empty() ? nullptr : a.refine_append.data()};
-  CHECK(eg_refine_validate(&plans, &ro));
-  struct Owned {      // released on every way out
-    eg_policy* policy = nullptr; eg_ctx* ctx = nullptr; eg_plan_set* refined = nullptr;
-    ~Owned() { if (policy) eg_policy_free(policy); if (ctx) eg_destroy(ctx); if (refined) eg_plans_free(refined); }
-  } own;
-  eg_policy* policy = own.policy = a.evaluate_policy.empty() ? eg_policy_new() : eg_policy_load_json(a.evaluate_policy.c_str());
-  if (!policy) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
-  eg_ctx* ctx = own.ctx = eg_create(a.device, &world);
-  if (!ctx) { std::fprintf(stderr, "eg_create: %s\n", eg_last_error()); return 1; }
-  eg_opts opts{a.enable_energy_sales ? 1 : 0, 0, 1};
-  eg_policy_snapshot snap; CHECK(eg_policy_snapshot_view(policy, &snap));
-  std::vector<eg_refine_step> steps(size_t(a.refine_rounds));
-  int32_t n_steps = 0, stop = 0; double start = 0.0;
-  const auto t0 = std::chrono::steady_clock::now();
-  CHECK(eg_refine_plan(ctx, &snap, &opts, &plans, &ro, a.seed, 0, &own.refined, steps.data(), &n_steps, &stop, &start, nullptr));
-  const double secs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  const std::string stamp = time_stamp("%Y%m%d_%H%M%S"), dir = a.checkpoint_dir + "/" + stamp + "/refine";
-  mkdirs(dir);
-  static const char* kStop[3] = {"local_optimum", "max_rounds", "base_failed"};
-  {
-    static const char* kKind[4] = {"none", "delete", "replace", "insert"};
-    std::ofstream f(dir + "/trajectory.csv");
-    f << "round,kind,list,year,pos,action,variant,n_variants,n_failed,score,net_emissions,public_opinion,total_cost,power_reliability\n";
-    char line[640];
-    std::snprintf(line, sizeof(line), "start,none,,,,,0,,,%.17g,,,,\n", start);
-    f << line;
-    for (int32_t r = 0; r < n_steps; ++r) {
-      const eg_refine_step& st = steps[size_t(r)];
-      const eg_plan_edit& e = st.edit;
-      int k = std::snprintf(line, sizeof(line), "%d,%s,%s,%d,%u,", r, kKind[e.kind & 3], e.list ? "best_deficit_actions" : "best_actions", 2025 + int(e.year), e.pos);
-      if (e.kind != EG_EDIT_DELETE) k += std::snprintf(line + k, sizeof(line) - k, "%d", int(e.action));
-      std::snprintf(line + k, sizeof(line) - k, ",%d,%d,%d,%.17g,%.17g,%.17g,%.17g,%.17g\n", st.variant, st.n_variants, st.n_failed, st.score, st.metrics[0], st.metrics[1],
-                    st.metrics[2], st.metrics[3]);
-      f << line;
-    }
-    f << "# stop: " << kStop[stop] << " after " << n_steps << " steps\n";
-    if (!f) { std::fprintf(stderr, "error: cannot write %s/trajectory.csv\n", dir.c_str()); return 1; }
-  }
-  CHECK(eg_plans_save(own.refined, (dir + "/refined.jsonl").c_str()));
-  std::printf("Refined the plan in %d steps (%.3f s): score %.6f -> %.6f, stop: %s; written to %s\n", n_steps, secs, start,
-              n_steps > 0 ? steps[size_t(n_steps) - 1].score : start, kStop[stop], dir.c_str());
-  return 0;
-}
-}  // namespace
-
-int main(int argc, char** argv) {
-  Args a;
-  if (!parse(argc, argv, a)) return 2;
-  std::puts("EirGrid Power System Simulator (2025-2050) — MI355X rollout engine");
-  eg_plan_set* plans = nullptr;      // --evaluate: every invalid line is reported before a device is touched
-  const std::string& plans_file = !a.evaluate.empty() ? a.evaluate : !a.sensitivity.empty() ? a.sensitivity : a.refine;      // (--sensitivity and --refine read their base plan the same way)
-  if (!plans_file.empty() && !(plans = eg_plans_load(plans_file.c_str()))) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
-  if (!a.refine.empty() && plans->n_plans != 1) { std::fprintf(stderr, "error: --refine needs a file with one plan, %s holds %d\n", a.refine.c_str(), plans->n_plans); eg_plans_free(plans); return 2; }
-  if (a.enable_construction_delays) { std::fprintf(stderr, "error: --enable-construction-delays is not implemented on the device (DESIGN.md §6)\n"); return 2; }
-
-  WorldData wd;
+int load_world(const Args& a, WorldData& wd) {      // --world, or the reference's assets; what was loaded goes to stdout
   if (!a.world_json.empty()) { if (!load_world_json(a.world_json, wd)) { std::fprintf(stderr, "error: cannot read world %s\n", a.world_json.c_str()); return 1; } }
   else if (!load_reference_assets(a.assets_dir, wd)) { std::fprintf(stderr, "error: cannot read %s/{settlements.json,ireland_generators.csv} (use --world or --assets-dir)\n", a.assets_dir.c_str()); return 1; }
   std::printf("World: %zu settlements, %zu existing generators, %zu coastline points\n", wd.sx.size(), wd.gx.size(), wd.cx.size());
-  {  // the fuel mix as data/generators_loader.rs:47-57 maps it (gas -> GasCombinedCycle, oil -> GasPeaker, ...)
-    static const char* kTypeName[EG_N_TYPES] = {"OnshoreWind", "OffshoreWind", "DomesticSolar", "CommercialSolar", "UtilitySolar", "Nuclear", "CoalPlant",
-                                                "GasCombinedCycle", "GasPeaker", "Biomass", "HydroDam", "PumpedStorage", "BatteryStorage", "TidalGenerator", "WaveEnergy"};
-    int count[EG_N_TYPES] = {0};
-    for (int32_t t : wd.gtype) if (t >= 0 && t < EG_N_TYPES) count[t] += 1;
-    std::string mix;
-    for (int t = 0; t < EG_N_TYPES; ++t) if (count[t]) mix += (mix.empty() ? "" : ", ") + std::string(kTypeName[t]) + " " + std::to_string(count[t]);
-    std::printf("Existing generators by type: %s\n", mix.c_str());
-  }
-  if (!a.dump_world.empty()) {
-    std::ofstream f(a.dump_world);
-    if (!f) { std::fprintf(stderr, "error: cannot write %s\n", a.dump_world.c_str()); return 1; }
-    auto arr = [&](const char* key, const std::vector<double>& v, bool last = false) {
-      f << "\"" << key << "\": [";
-      char buf[40];
-      for (size_t i = 0; i < v.size(); ++i) { std::snprintf(buf, sizeof(buf), "%.17g", v[i]); f << (i ? ", " : "") << buf; }
-      f << "]" << (last ? "" : ", ");
-    };
-    f << "{";
-    arr("settlement_x", wd.sx); arr("settlement_y", wd.sy); arr("settlement_pop", std::vector<double>(wd.spop.begin(), wd.spop.end()));
-    arr("existing_x", wd.gx); arr("existing_y", wd.gy); arr("existing_type", std::vector<double>(wd.gtype.begin(), wd.gtype.end()));
-    arr("existing_capacity", wd.gcap); arr("coast_x", wd.cx); arr("coast_y", wd.cy);
-    f << "\"existing_operational_at_start\": " << (a.existing_operational_at_start ? "true" : "false") << "}\n";
-    std::printf("World written to %s\n", a.dump_world.c_str());
-    return 0;
-  }
-  const eg_world world = wd.view(a.existing_operational_at_start);
-  if (plans) {
-    const int rc = !a.refine.empty() ? run_refine(a, world, *plans) : a.sensitivity.empty() ? run_evaluate(a, wd, world, *plans) : run_sensitivity(a, world, *plans);
-    eg_plans_free(plans);
-    return rc;
-  }
-  // more than one rank: the same reduced-update loop on an eg_group (the exchange between the ranks is inside the library)
-  eg_ctx* ctx = nullptr; eg_group* group = nullptr;
+  // the fuel mix as data/generators_loader.rs:47-57 maps it (gas -> GasCombinedCycle, oil -> GasPeaker, ...)
+  static const char* kTypeName[EG_N_TYPES] = {"OnshoreWind", "OffshoreWind", "DomesticSolar", "CommercialSolar", "UtilitySolar", "Nuclear", "CoalPlant",
+                                              "GasCombinedCycle", "GasPeaker", "Biomass", "HydroDam", "PumpedStorage", "BatteryStorage", "TidalGenerator", "WaveEnergy"};
+  int count[EG_N_TYPES] = {0};
+  for (int32_t t : wd.gtype) if (t >= 0 && t < EG_N_TYPES) count[t] += 1;
+  std::string mix;
+  for (int t = 0; t < EG_N_TYPES; ++t) if (count[t]) mix += (mix.empty() ? "" : ", ") + std::string(kTypeName[t]) + " " + std::to_string(count[t]);
+  std::printf("Existing generators by type: %s\n", mix.c_str());
+  return 0;
+}
+
+int dump_world(const Args& a, const WorldData& wd) {      // --dump-world: the world as loaded, in the --world JSON form
+  std::ofstream f(a.dump_world);
+  if (!f) { std::fprintf(stderr, "error: cannot write %s\n", a.dump_world.c_str()); return 1; }
+  auto arr = [&](const char* key, const std::vector<double>& v) { f << "\"" << key << "\": [" << csv17(v.data(), int(v.size()), ", ") << "], "; };
+  f << "{";
+  arr("settlement_x", wd.sx); arr("settlement_y", wd.sy); arr("settlement_pop", std::vector<double>(wd.spop.begin(), wd.spop.end()));
+  arr("existing_x", wd.gx); arr("existing_y", wd.gy); arr("existing_type", std::vector<double>(wd.gtype.begin(), wd.gtype.end()));
+  arr("existing_capacity", wd.gcap); arr("coast_x", wd.cx); arr("coast_y", wd.cy);
+  f << "\"existing_operational_at_start\": " << (a.existing_operational_at_start ? "true" : "false") << "}\n";
+  std::printf("World written to %s\n", a.dump_world.c_str());
+  return 0;
+}
+
+// The training run: --iterations iterations in batches on one device or, with more than one rank, the same reduced-update loop on an
+// eg_group (the exchange between the ranks is inside the library); checkpoints, progress lines and the best run's export as the header says.
+int run_training(Args& a, const WorldData& wd, const eg_world& world) {
+  Session own;
+  eg_ctx*& ctx = own.ctx; eg_group*& group = own.group; eg_policy*& policy = own.policy;
   if (a.gpus_given && int32_t(a.ranks.size()) > eg_device_count()) {
     std::fprintf(stderr, "error: --gpus %zu: only %d device(s) visible\n", a.ranks.size(), eg_device_count()); return 2;
   }
@@ -592,17 +293,14 @@ int main(int argc, char** argv) {
     std::printf("Ranks: %zu on devices", a.ranks.size());
     for (int32_t d : a.ranks) std::printf(" %d", d);
     std::printf(" (%u iterations per update, sharded)\n", a.batch);
-  } else {
-    ctx = eg_create(a.device, &world);
-    if (!ctx) { std::fprintf(stderr, "eg_create: %s\n", eg_last_error()); return 1; }
-  }
+  } else if (int rc = own.create(a, world)) return rc;
   // The reference's replay phases (the last 10 % of a run, --force-full-simulation: core/multi_simulation.rs:38-39, :437-465) run the
   // same replay in every iteration of a batch: computed once unless asked otherwise (worlds the hoist is not sized for: every
   // iteration on its own, silently — the results are the same)
   if (a.replay_hoist) (void)(group ? eg_group_replay_hoist(group, 1) : eg_replay_hoist(ctx, 1));
 
   // run directory and resume (multi_simulation.rs:160-165, :210-290, :396-404)
-  eg_policy* policy = nullptr; uint64_t start_iteration = 0; std::string run_dir;
+  uint64_t start_iteration = 0; std::string run_dir;
   if (!a.no_continue) {
     run_dir = newest_run_dir(a.checkpoint_dir);
     if (!run_dir.empty()) {
@@ -614,11 +312,7 @@ int main(int argc, char** argv) {
     }
   }
   if (!policy) policy = eg_policy_new();
-  if (run_dir.empty()) {
-    char buf[32]; std::time_t t = std::time(nullptr); std::tm tmv; localtime_r(&t, &tmv);
-    std::strftime(buf, sizeof(buf), "%m%d_%H%M%S", &tmv);
-    run_dir = a.checkpoint_dir + "/2024" + buf;   // the literal "2024" of multi_simulation.rs:162 (Q17)
-  }
+  if (run_dir.empty()) run_dir = a.checkpoint_dir + "/2024" + time_stamp("%m%d_%H%M%S");   // the literal "2024" of multi_simulation.rs:162 (Q17)
   mkdirs(run_dir);
   if (!a.has_seed) { std::random_device rd; a.seed = (uint64_t(rd()) << 32) | rd(); }
   const bool cache_loaded = exists(a.cache_dir + "/location_analysis.json");   // multi_simulation.rs:150-154
@@ -629,19 +323,12 @@ int main(int argc, char** argv) {
   // The run that is summarised and exported at the end: the reference's `best_result`, a fold over this process's iterations in
   // iteration order that starts at None (core/multi_simulation.rs:384, :613-620; --cost-only reaches it as optimization_mode).
   // The library folds every batch on the device behind its rollout (eg_best_result_track) and keeps the held run's record.
-  struct BestRun {
-    std::vector<double> metrics = std::vector<double>(4), yearly = std::vector<double>(size_t(EG_YEARS) * EG_YEARLY_FIELDS);
-    std::vector<int32_t> n_act = std::vector<int32_t>(EG_YEARS); std::vector<uint8_t> act_log = std::vector<uint8_t>(EG_ACT_CAP);
-    std::vector<uint16_t> gen_pack = std::vector<uint16_t>(EG_MAX_GENS); int32_t n_gens = 0;
-    eg_episode_out view{}; bool valid = false;
-    BestRun() { view.metrics = metrics.data(); view.yearly = yearly.data(); view.n_act = n_act.data(); view.act_log = act_log.data();
-                view.n_gens = &n_gens; view.gen_pack = gen_pack.data(); }
-  } best_run;
+  Records best_run(1);
   std::vector<uint8_t> mask;
   std::vector<double> metrics; std::vector<int32_t> n_run, n_def; std::vector<uint8_t> run_log, def_log;
   eg_opts opts{a.enable_energy_sales ? 1 : 0, 0, a.enable_csv_export ? 1 : 0};   // the export needs the best episode's yearly rows
   const uint64_t final_full = a.iterations * 10 / 100;   // FULL_RUN_PERCENTAGE, multi_simulation.rs:38, :437
-  auto t0 = std::chrono::steady_clock::now(); auto last_progress = t0;
+  const auto t0 = Clock::now(); auto last_progress = t0;
   uint64_t done = start_iteration, last_checkpoint = start_iteration / a.checkpoint_interval;
   const bool reduced = a.update == "reduced";
   unsigned failed_sequential = 0;      // --update sequential: episodes that did not finish (reduced mode counts them on the device)
@@ -682,7 +369,7 @@ int main(int argc, char** argv) {
                                         &n_def[size_t(i) * EG_YEARS], &def_log[size_t(i) * EG_DEF_CAP], a.seed + done + i));
     }
     done += n;
-    const auto now = std::chrono::steady_clock::now();
+    const auto now = Clock::now();
     const bool checkpoint_due = done / a.checkpoint_interval != last_checkpoint || done == a.iterations;
     const bool progress_due = std::chrono::duration<double>(now - last_progress).count() >= double(a.progress_interval) || done == a.iterations;
     if (reduced && (checkpoint_due || progress_due)) CHECK(group ? eg_group_pull(group, 0, policy) : eg_policy_pull(ctx, policy));
@@ -708,72 +395,66 @@ int main(int argc, char** argv) {
     if (a.stop_after && done >= a.stop_after && done < a.iterations) {
       if (!checkpoint_due) { std::fprintf(stderr, "error: --stop-after needs a checkpoint at the stop (use -i 1 or a divisor)\n"); return 2; }
       std::printf("Stopped after %llu iterations (--stop-after); resume with the same command\n", (unsigned long long)done);
-      eg_policy_free(policy); eg_destroy(ctx); eg_group_destroy(group);
       return 0;
     }
   }
   CHECK(eg_policy_save_json(policy, (run_dir + "/best_weights.json").c_str()));   // multi_simulation.rs:1160-1164
-  char stamp[32]; std::string dir;
+  std::string stamp, dir;
   if (a.enable_csv_export || a.top_k > 0) {   // multi_simulation.rs:852-859, :912-921; csv_export.rs:114-127 (directory named after the time of export)
-    std::time_t t = std::time(nullptr); std::tm tmv; localtime_r(&t, &tmv);
-    std::strftime(stamp, sizeof(stamp), "%Y%m%d_%H%M%S", &tmv);
-    dir = run_dir + "/enhanced_csv/" + stamp;
-    mkdirs(dir);
+    stamp = time_stamp(kStamp);
+    dir = mkdirs(run_dir + "/enhanced_csv/" + stamp);
   }
   if (a.enable_csv_export) CHECK(eg_policy_export_improvement_csv(policy, (dir + "/improvement_history.csv").c_str()));
-  int64_t best_index = -1;
-  { int32_t state = 0; CHECK(group ? eg_group_fetch_best_result(group, &best_run.view, &state, &best_index) : eg_fetch_best_result(ctx, &best_run.view, &state, &best_index));
-    best_run.valid = state == 1; }
-  if (best_run.valid) {   // multi_simulation.rs:821-850
+  int64_t best_index = -1; int32_t state = 0;      // (state 1: an iteration finished and its record is held)
+  eg_episode_out best_view = best_run.view();
+  CHECK(group ? eg_group_fetch_best_result(group, &best_view, &state, &best_index) : eg_fetch_best_result(ctx, &best_view, &state, &best_index));
+  if (state == 1) {   // multi_simulation.rs:821-850
     const double* bm = best_run.metrics.data();
     std::printf("BEST SIMULATION RESULTS SUMMARY (iteration %lld)\nFinal net emissions: %.2f tonnes\nEmissions Status: %s\nAverage public opinion: %.1f%%\n"
                 "Total cost: EUR %.2f billion accumulated\nPower reliability: %.1f%%\n", (long long)best_index, bm[0],
                 bm[0] <= 0.0 ? "NET ZERO ACHIEVED" : "NET ZERO NOT ACHIEVED", bm[1] * 100.0, bm[2] / 1e9, bm[3] * 100.0);
   }
   if (a.enable_csv_export) {
-    if (best_run.valid) {
-      CHECK(eg_export_summary_csv(&best_run.view, (dir + "/simulation_summary.csv").c_str(), stamp));
-      std::vector<const char*> names;
-      for (const std::string& n : wd.names) names.push_back(n.c_str());
-      CHECK(eg_export_run_details(&world, names.size() == wd.sx.size() ? names.data() : nullptr, &best_run.view, dir.c_str(), a.seed));
-    } else std::puts("note: no iteration finished in this run; simulation_summary.csv and the detail files not written");
+    if (state == 1) { if (int rc = export_entry(world, wd, best_view, dir, stamp, a.seed)) return rc; }
+    else std::puts("note: no iteration finished in this run; simulation_summary.csv and the detail files not written");
   }
   if (a.top_k > 0) {      // top_k/index.csv: rank, score, iteration, metrics; with the CSV export one directory per entry, like the best run's
-    const size_t K = size_t(a.top_k);
-    std::vector<double> metrics_k(K * 4), yearly_k(K * EG_YEARS * EG_YEARLY_FIELDS), score_k(K);
-    std::vector<int32_t> n_act_k(K * EG_YEARS), n_gens_k(K); std::vector<uint8_t> act_k(K * EG_ACT_CAP); std::vector<uint16_t> pack_k(K * EG_MAX_GENS);
-    std::vector<int64_t> index_k(K);
-    eg_episode_out out{}; out.metrics = metrics_k.data(); out.yearly = yearly_k.data(); out.n_act = n_act_k.data(); out.act_log = act_k.data();
-    out.n_gens = n_gens_k.data(); out.gen_pack = pack_k.data();
-    int32_t held = 0;
+    Records top(size_t(a.top_k));
+    std::vector<double> score_k(size_t(a.top_k)); std::vector<int64_t> index_k(size_t(a.top_k));
+    eg_episode_out out = top.view(); int32_t held = 0;
     CHECK(group ? eg_group_fetch_top_k(group, &out, &held, score_k.data(), index_k.data()) : eg_fetch_top_k(ctx, &out, &held, score_k.data(), index_k.data()));
-    const std::string tk = dir + "/top_k";
-    mkdirs(tk);
+    const std::string tk = mkdirs(dir + "/top_k");
     std::ofstream f(tk + "/index.csv");
     f << "rank,score,iteration,final_net_emissions,average_public_opinion,total_cost,power_reliability\n";
-    std::vector<const char*> names;
-    for (const std::string& n : wd.names) names.push_back(n.c_str());
     for (int32_t r = 0; r < held; ++r) {
-      char line[512]; const double* m = &metrics_k[size_t(r) * 4];
-      std::snprintf(line, sizeof(line), "%d,%.17g,%lld,%.17g,%.17g,%.17g,%.17g\n", r + 1, score_k[size_t(r)], (long long)index_k[size_t(r)], m[0], m[1], m[2], m[3]);
-      f << line;
+      f << r + 1 << ',' << csv17(&score_k[size_t(r)], 1) << ',' << index_k[size_t(r)] << ',' << csv17(&top.metrics[size_t(r) * 4], 4) << '\n';
       if (!a.enable_csv_export) continue;
       char sub[16]; std::snprintf(sub, sizeof(sub), "/%02d", r + 1);
-      const std::string ed = tk + sub;
-      mkdirs(ed);
-      eg_episode_out one{}; one.metrics = &metrics_k[size_t(r) * 4]; one.yearly = &yearly_k[size_t(r) * EG_YEARS * EG_YEARLY_FIELDS];
-      one.n_act = &n_act_k[size_t(r) * EG_YEARS]; one.act_log = &act_k[size_t(r) * EG_ACT_CAP]; one.n_gens = &n_gens_k[size_t(r)];
-      one.gen_pack = &pack_k[size_t(r) * EG_MAX_GENS];
-      CHECK(eg_export_summary_csv(&one, (ed + "/simulation_summary.csv").c_str(), stamp));
-      CHECK(eg_export_run_details(&world, names.size() == wd.sx.size() ? names.data() : nullptr, &one, ed.c_str(), a.seed));
+      if (int rc = export_entry(world, wd, top.view(size_t(r)), tk + sub, stamp, a.seed)) return rc;
     }
     if (!f) { std::fprintf(stderr, "error: cannot write %s/index.csv\n", tk.c_str()); return 1; }
     std::printf("Top %d distinct scenarios (%d held) written to %s\n", a.top_k, held, tk.c_str());
   }
   std::printf("Done: %llu iterations in %s (%u episodes failed); best_weights.json, latest_weights.json, checkpoint_iteration.txt written\n",
               (unsigned long long)done, run_dir.c_str(), unsigned(eg_policy_get_scalar(policy, 13)) + failed_sequential);
-  eg_policy_free(policy);
-  eg_destroy(ctx);
-  eg_group_destroy(group);
   return 0;
+}
+}  // namespace
+
+int main(int argc, char** argv) {
+  Args a;
+  if (!parse(argc, argv, a)) return 2;
+  std::puts("EirGrid Power System Simulator (2025-2050) — MI355X rollout engine");
+  Session loaded;      // the plans of --evaluate, --sensitivity or --refine (they read their file the same way): every invalid line is reported before a device is touched
+  const std::string& plans_file = !a.evaluate.empty() ? a.evaluate : !a.sensitivity.empty() ? a.sensitivity : a.refine;
+  if (!plans_file.empty() && !(loaded.plans = eg_plans_load(plans_file.c_str()))) { std::fprintf(stderr, "error: %s\n", eg_last_error()); return 1; }
+  if (!a.refine.empty() && loaded.plans->n_plans != 1) { std::fprintf(stderr, "error: --refine needs a file with one plan, %s holds %d\n", a.refine.c_str(), loaded.plans->n_plans); return 2; }
+  if (a.enable_construction_delays) { std::fprintf(stderr, "error: --enable-construction-delays is not implemented on the device (DESIGN.md §6)\n"); return 2; }
+  WorldData wd;
+  if (int rc = load_world(a, wd)) return rc;
+  if (!a.dump_world.empty()) return dump_world(a, wd);
+  const eg_world world = wd.view(a.existing_operational_at_start);
+  if (!loaded.plans) return run_training(a, wd, world);
+  if (!a.refine.empty()) return run_refine(a, world, *loaded.plans);
+  return a.sensitivity.empty() ? run_evaluate(a, wd, world, *loaded.plans) : run_sensitivity(a, world, *loaded.plans);
 }

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "eg_edit_order.h"
 #include "eg_host.h"
 
 using namespace eg;
@@ -20,18 +21,11 @@ struct Mirror {
 int64_t n_variants(int64_t len0, int64_t len1, const eg_refine_opts& o) {
   return 1 + len0 + len1 + int64_t(o.n_replace) * len0 + (len0 < int64_t(snap::kBestCap) ? int64_t(EG_YEARS) * o.n_append : 0);
 }
-void enumerate(const Mirror& m, const eg_refine_opts& o, std::vector<eg_plan_edit>& edits) {
-  edits.clear();
-  edits.push_back(eg_plan_edit{EG_EDIT_NONE, 0, 0, 0, 0});
+void enumerate(const Mirror& m, const eg_refine_opts& o, std::vector<eg_plan_edit>& edits) {      // the round's edits, in the canonical order
+  int32_t count[2][EG_YEARS];
   for (int w = 0; w < 2; ++w)
-    for (int y = 0; y < EG_YEARS; ++y)
-      for (size_t i = 0; i < m.l[w][y].size(); ++i) edits.push_back(eg_plan_edit{EG_EDIT_DELETE, uint8_t(w), uint16_t(y), uint32_t(i), 0});
-  for (int y = 0; y < EG_YEARS; ++y)
-    for (size_t i = 0; i < m.l[0][y].size(); ++i)
-      for (int32_t k = 0; k < o.n_replace; ++k) edits.push_back(eg_plan_edit{EG_EDIT_REPLACE, 0, uint16_t(y), uint32_t(i), o.replace_with[k]});
-  if (m.total(0) < int64_t(snap::kBestCap))
-    for (int y = 0; y < EG_YEARS; ++y)
-      for (int32_t k = 0; k < o.n_append; ++k) edits.push_back(eg_plan_edit{EG_EDIT_INSERT, 0, uint16_t(y), uint32_t(m.l[0][y].size()), o.append_with[k]});
+    for (int y = 0; y < EG_YEARS; ++y) count[w][y] = int32_t(m.l[w][y].size());
+  enumerate_edits(count[0], count[1], o.replace_with, o.n_replace, o.append_with, o.n_append, m.total(0) < int64_t(snap::kBestCap), edits);
 }
 void apply(Mirror& m, const eg_plan_edit& e) {
   std::vector<uint8_t>& l = m.l[e.list][e.year];
