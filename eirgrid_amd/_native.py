@@ -12,6 +12,7 @@ YEARS, N_ACTIONS, N_DEFICIT, N_COUNTS, N_TYPES = 26, 61, 15, 21, 15
 GRID, CELLS, YEARLY_FIELDS = 51, 2601, 21
 MAX_GENS, MAX_OFFSETS, RUN_CAP, DEF_CAP, ACT_CAP, ONCHIP_GENS = 4096, 4096, 4096, 4096, 4096, 512
 TOPK_MAX = 64      # EG_TOPK_MAX: entries a top-K archive holds at most
+PARETO_MAX = 256   # EG_PARETO_MAX: entries a Pareto archive holds at most
 STATS_LEN = 8 + 2 * YEARS * N_ACTIONS + YEARS * N_DEFICIT
 CANDIDATE_BYTES = 8 + 8 + 32 + 4 * YEARS + 4 * YEARS + RUN_CAP + DEF_CAP
 PACKET_BYTES = 8 * STATS_LEN + CANDIDATE_BYTES
@@ -89,6 +90,7 @@ EXPORTS = [
     "eg_policy_push", "eg_device_rollout", "eg_device_apply", "eg_device_step", "eg_policy_pull",
     "eg_group_create", "eg_group_destroy", "eg_group_rank", "eg_group_push", "eg_group_step", "eg_group_pull", "eg_group_replay_hoist",
     "eg_group_best_result_track", "eg_group_fetch_best_result", "eg_top_k_track", "eg_fetch_top_k", "eg_rank_score",
+    "eg_pareto_track", "eg_pareto_fold_last_batch", "eg_fetch_pareto", "eg_debug_pareto_fold",
     "eg_group_top_k_track", "eg_group_fetch_top_k", "eg_plans_validate", "eg_evaluate_plans", "eg_plans_load", "eg_plans_free",
     "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block", "eg_plans_save", "eg_refine_validate", "eg_refine_plan",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
@@ -252,6 +254,16 @@ def lib():
         L.eg_refine_plan.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts),
                                      C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgRefineStep), _i32p, _i32p, _dp,
                                      C.POINTER(EgEpisodeOut)]
+    # (likewise: scripts/pareto_probe.py may load a build of the parent commit, which has no Pareto archive)
+    if hasattr(L, "eg_pareto_track") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_pareto_track.restype = C.c_int32
+        L.eg_pareto_track.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.eg_pareto_fold_last_batch.restype = C.c_int32
+        L.eg_pareto_fold_last_batch.argtypes = [C.c_void_p]
+        L.eg_fetch_pareto.restype = C.c_int32
+        L.eg_fetch_pareto.argtypes = [C.c_void_p, C.POINTER(EgEpisodeOut), _i32p, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64)]
+        L.eg_debug_pareto_fold.restype = C.c_int32
+        L.eg_debug_pareto_fold.argtypes = [C.c_void_p, _dp, _i32p, C.c_uint32, C.c_uint64]
     L.eg_plans_load.restype = C.POINTER(EgPlanSet)
     L.eg_plans_load.argtypes = [C.c_char_p]
     L.eg_plans_free.argtypes = [C.POINTER(EgPlanSet)]

@@ -258,6 +258,7 @@ int launch_batch(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, con
     EG_LAUNCH("k_topk_merge", launch_topk_merge(c->d_topk, reinterpret_cast<const uint8_t*>(c->d_tk_blocks.ptr), int(topk_chunks(n)), sizeof(TopKBlock), nullptr,
                                      c->topk_k, c->out, first_index, n, 0u, nullptr));
   }
+  if (c->pareto_cap != 0) EG_TRY(pareto_fold(c, n, first_index));      // the Pareto archive, behind the top-K fold
   ring_commit(c, slot, (plan.n_heavy > 0 ? 1 : 0) | (plan.n_lean > 0 ? 2 : 0));
   c->last_n = n; c->last_first = first_index;
   return EG_OK;

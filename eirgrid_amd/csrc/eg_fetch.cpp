@@ -1,5 +1,5 @@
-// eg_fetch.cpp — results back to the host: the records of the last batch, the best run, the best_result fold and the top-K archive
-// of one context (tracking and fetch), what the context holds in HBM.
+// eg_fetch.cpp — results back to the host: the records of the last batch, the best run, the best_result fold, the top-K archive and the
+// Pareto archive of one context (tracking and fetch), what the context holds in HBM.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -19,6 +19,16 @@ int eg::topk_select(eg_ctx* c, uint32_t n, uint64_t first_index, int mode, bool 
   int lr = launch_topk_keys(c->out, n, first_index, mode, use_score_list, d_state, c->d_tk_score, c->d_tk_key, nullptr);
   if (lr == 0) lr = launch_topk_select(c->out, n, first_index, c->d_tk_score, c->d_tk_key, k, c->d_tk_blocks, nullptr);
   EG_LAUNCH("k_topk_keys / k_topk_select", lr);
+  return EG_OK;
+}
+
+int eg::pareto_fold(eg_ctx* c, uint32_t n, uint64_t first_index) {
+  if (n == 0) return EG_OK;
+  if (n > c->pareto_work_n || !c->d_pareto_work) {      // (a larger batch than any before: the old buffer is freed behind the launches that use it)
+    EG_HIP(c->d_pareto_work.reserve(pareto_work_bytes(n)));
+    c->pareto_work_n = n;
+  }
+  EG_LAUNCH("k_pareto_filter .. k_pareto_finalize", launch_pareto_fold(c->d_pareto, pareto_work(c->d_pareto_work, c->pareto_work_n), c->out, n, first_index, nullptr));
   return EG_OK;
 }
 
@@ -204,6 +214,70 @@ int32_t eg_fetch_top_k(eg_ctx* c, eg_episode_out* o, int32_t* n_held, double* sc
   TopKState st{};
   EG_HIP(hipMemcpy(&st, c->d_topk, sizeof(st), hipMemcpyDeviceToHost));
   return fetch_topk_rows("eg_fetch_top_k", st, [c](int, const TopKEntry&) -> const uint8_t* { return c->d_topk; }, o, n_held, scores, global_index);
+}
+
+int32_t eg_pareto_track(eg_ctx* c, int32_t cap, int32_t objectives, int32_t mode) {
+  if (!c) { set_error("eg_pareto_track: bad argument (ctx)"); return EG_ERR_BAD_ARG; }
+  if (cap < 0 || cap > EG_PARETO_MAX) { set_error("eg_pareto_track: cap " + std::to_string(cap) + " is outside 0..EG_PARETO_MAX (256)"); return EG_ERR_BAD_ARG; }
+  if (cap == 0) { c->pareto_cap = 0; return EG_OK; }
+  if (objectives < 1 || objectives > 15) { set_error("eg_pareto_track: objectives " + std::to_string(objectives) + " is outside 1..15 (bit i = metric i)"); return EG_ERR_BAD_ARG; }
+  if (mode != 1 && mode != 2) { set_error("eg_pareto_track: mode " + std::to_string(mode) + " is neither 1 (optimization_mode None) nor 2 (cost_only)"); return EG_ERR_BAD_ARG; }
+  if (c->group_member) { set_error("eg_pareto_track: the context is a rank of an eg_group (the Pareto archive has no group form)"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  static_assert(sizeof(ParetoState) <= kParetoRecords, "pareto state layout");
+  c->pareto_cap = 0;      // (until the new archive stands)
+  EG_HIP(c->d_pareto.reserve(kParetoRecords + size_t(cap) * rec::stride));
+  ParetoState st{};
+  st.cap = cap; st.objectives = objectives; st.mode = mode;
+  EG_HIP(hipMemcpy(c->d_pareto, &st, sizeof(st), hipMemcpyHostToDevice));
+  c->pareto_cap = cap;
+  return EG_OK;
+}
+
+int32_t eg_pareto_fold_last_batch(eg_ctx* c) {
+  if (!c) { set_error("eg_pareto_fold_last_batch: bad argument (ctx)"); return EG_ERR_BAD_ARG; }
+  if (c->pareto_cap == 0) { set_error("eg_pareto_fold_last_batch: eg_pareto_track first (tracking is off)"); return EG_ERR_BAD_ARG; }
+  if (c->last_n == 0) { set_error("eg_pareto_fold_last_batch: there is no last batch"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  return pareto_fold(c, c->last_n, c->last_first);
+}
+
+int32_t eg_fetch_pareto(eg_ctx* c, eg_episode_out* o, int32_t* n_held, int64_t* global_index, double* scores, int64_t* n_dropped) {
+  if (!c || !n_held) { set_error("eg_fetch_pareto: bad argument"); return EG_ERR_BAD_ARG; }
+  if (!c->d_pareto) { set_error("eg_fetch_pareto: eg_pareto_track first"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_sync(c));
+  std::vector<uint8_t> buf(sizeof(ParetoState));
+  EG_HIP(hipMemcpy(buf.data(), c->d_pareto, sizeof(ParetoState), hipMemcpyDeviceToHost));
+  const ParetoState& st = *reinterpret_cast<const ParetoState*>(buf.data());
+  const char* corrupt = "eg_fetch_pareto: the archive's state is corrupt";
+  if (st.cap < 1 || st.cap > EG_PARETO_MAX || st.n_held < 0 || st.n_held > st.cap) { set_error(corrupt); return EG_ERR_INTERNAL; }
+  *n_held = st.n_held;
+  if (n_dropped) *n_dropped = st.n_dropped;
+  for (int i = 0; i < st.n_held; ++i) {
+    const ParetoEntry& e = st.e[i];
+    if (e.slot < 0 || e.slot >= st.cap) { set_error(corrupt); return EG_ERR_INTERNAL; }
+    if (scores) scores[i] = e.score;
+    if (global_index) global_index[i] = e.index;
+    if (!o) continue;
+    eg_episode_out row = out_row(o, size_t(i));
+    EG_TRY(fetch_records(c->d_pareto + kParetoRecords + size_t(e.slot) * rec::stride, 1, &row));
+  }
+  return EG_OK;
+}
+
+int32_t eg_debug_pareto_fold(eg_ctx* c, const double* metrics, const int32_t* status, uint32_t n, uint64_t first_index) {
+  if (!c || !metrics || !status || n == 0) { set_error("eg_debug_pareto_fold: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->pareto_cap == 0) { set_error("eg_debug_pareto_fold: eg_pareto_track first (tracking is off)"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  EG_TRY(ensure_outputs(c, n));
+  EG_HIP(hipMemsetAsync(c->out.base, 0, size_t(n) * rec::stride, nullptr));
+  std::vector<uint64_t> tag(n);
+  for (uint32_t e = 0; e < n; ++e) tag[e] = first_index + e;
+  EG_HIP(hipMemcpy2D(c->out.base + rec::metrics, rec::stride, metrics, 4 * sizeof(double), 4 * sizeof(double), n, hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy2D(c->out.base + rec::status, rec::stride, status, sizeof(int32_t), sizeof(int32_t), n, hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy2D(c->out.base + rec::n_draws, rec::stride, tag.data(), sizeof(uint64_t), sizeof(uint64_t), n, hipMemcpyHostToDevice));
+  c->last_n = n; c->last_first = first_index;
+  return pareto_fold(c, n, first_index);
 }
 
 double eg_rank_score(const double m[4], int32_t mode) { return m ? rm::rank_score(m, mode) : std::nan(""); }

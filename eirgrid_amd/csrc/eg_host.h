@@ -74,6 +74,9 @@ struct eg_ctx {
   // and the record slots; per batch, the rank score and key of every episode and one block per chunk (also a group rank's scratch)
   int topk_mode = 0, topk_k = 0; eg::DevBuf<uint8_t> d_topk;
   eg::DevBuf<double> d_tk_score; eg::DevBuf<unsigned long long> d_tk_key; eg::DevBuf<eg::TopKBlock> d_tk_blocks;
+  // the Pareto archive of outcomes (eg_pareto_track; eg_pareto.h): pareto_cap 0 = not tracked; d_pareto: ParetoState and the cap record
+  // slots, allocated by eg_pareto_track; d_pareto_work: what the kernels of a fold hand each other, sized for pareto_work_n episodes
+  int pareto_cap = 0; eg::DevBuf<uint8_t> d_pareto, d_pareto_work; uint32_t pareto_work_n = 0;
   // Is the best list long (the replay episodes run the heavy-capable variant and are the batch's long pole)?  `list_exact`: the host
   // KNOWS the list the next launch will find on the device (it uploaded, rewound or pulled it and no on-device update has been
   // enqueued since): the replay variant that has nothing to do is then not launched at all.  Otherwise the device may have replaced
@@ -164,6 +167,8 @@ int fetch_records(const uint8_t* d_base, size_t N, eg_episode_out* o);
 int fold_reset(DevBuf<uint8_t>& d_fold);
 int topk_reset(DevBuf<uint8_t>& d_topk, int k, int mode);
 int topk_select(eg_ctx* c, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state, int k);
+// the n results of c->out (global indices first_index..) folded into the Pareto archive, on the null stream
+int pareto_fold(eg_ctx* c, uint32_t n, uint64_t first_index);
 inline uint32_t topk_chunks(uint32_t n) { return (n + kTopKChunk - 1u) / kTopKChunk; }
 // The entries of the archive state `st` into the caller's rows: archive_of(i, entry) is the device archive (TopKState, then the record
 // slots) that holds entry i's record, made current on its device — or NULL with the error text set.  `who` names the entry point.

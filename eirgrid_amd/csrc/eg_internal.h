@@ -430,6 +430,51 @@ struct TopKState { int32_t k, n_held, mode, pad; TopKEntry e[EG_TOPK_MAX]; long 
 constexpr size_t kTopKRecords = (sizeof(TopKState) + 255) & ~size_t(255);
 constexpr size_t kTopKBytes = kTopKRecords + size_t(EG_TOPK_MAX) * rec::stride;
 constexpr uint32_t kTopKChunk = 1024;      // episodes per workgroup of k_topk_select
+// The Pareto archive of a run's outcomes (include/eirgrid_hip.h eg_pareto_track; eg_pareto.h).  The archive is a ParetoState (entries in
+// ascending global index, each naming the record slot that holds its episode) followed by `cap` record slots (rec:: layout).  A slot
+// never moves while its entry is held; a new entry's record goes to the lowest free one.
+struct ParetoEntry { double metrics[4]; double score; long long index; int32_t slot, pad; };
+static_assert(sizeof(ParetoEntry) == 56, "pareto entry");
+struct ParetoState { int32_t cap, n_held, objectives, mode; long long n_dropped, pad; ParetoEntry e[EG_PARETO_MAX]; };
+constexpr size_t kParetoRecords = (sizeof(ParetoState) + 255) & ~size_t(255);
+constexpr uint32_t kParetoChunk = 256;      // episodes per workgroup of k_pareto_filter / k_pareto_compact
+// What the kernels of one fold hand each other, sized for a batch of cap_n episodes — the LIST of cap_n + EG_PARETO_MAX entries (the
+// held entries, then the batch's survivors in index order) as arrays, nothing of it sized by the archive's cap.
+struct ParetoWork {
+  uint32_t cap_n;
+  uint32_t* head;        // [0]: entries of the list (k_pareto_compact)
+  double* m;             // [L][4] metrics as the records hold them
+  double* score;         // [L] rank score
+  long long* index;      // [L] global index
+  int32_t* src;          // [L] a held entry: its slot; a survivor: -1 - its episode of the batch
+  uint32_t* rank;        // [L] alive entries that rank before this one (k_pareto_rank; only when more than cap are alive)
+  uint32_t* blk;         // [ceil(cap_n / kParetoChunk)] survivors per chunk
+  uint8_t* flag;         // [cap_n] the episode survived k_pareto_filter
+  uint8_t* alive;        // [L] not beaten by any entry of the list
+};
+inline size_t pareto_work_bytes(uint32_t cap_n) {
+  const size_t L = size_t(cap_n) + EG_PARETO_MAX, chunks = (size_t(cap_n) + kParetoChunk - 1) / kParetoChunk;
+  return 64 + L * (32 + 8 + 8 + 4 + 4) + ((chunks * 4 + 7) & ~size_t(7)) + ((size_t(cap_n) + 7) & ~size_t(7)) + L;
+}
+inline ParetoWork pareto_work(uint8_t* base, uint32_t cap_n) {
+  const size_t L = size_t(cap_n) + EG_PARETO_MAX, chunks = (size_t(cap_n) + kParetoChunk - 1) / kParetoChunk;
+  ParetoWork w{};
+  w.cap_n = cap_n;
+  uint8_t* p = base;
+  w.head = reinterpret_cast<uint32_t*>(p); p += 64;
+  w.m = reinterpret_cast<double*>(p); p += L * 32;
+  w.score = reinterpret_cast<double*>(p); p += L * 8;
+  w.index = reinterpret_cast<long long*>(p); p += L * 8;
+  w.src = reinterpret_cast<int32_t*>(p); p += L * 4;
+  w.rank = reinterpret_cast<uint32_t*>(p); p += L * 4;
+  w.blk = reinterpret_cast<uint32_t*>(p); p += (chunks * 4 + 7) & ~size_t(7);
+  w.flag = p; p += (size_t(cap_n) + 7) & ~size_t(7);
+  w.alive = p;
+  return w;
+}
+// One fold of the n results in `o` (global indices first_index..) into the archive at d_state: k_pareto_filter, k_pareto_compact,
+// k_pareto_dominate, k_pareto_rank, k_pareto_finalize, in that order on `stream`.  n <= w.cap_n.
+int launch_pareto_fold(uint8_t* d_state, const ParetoWork& w, const DevOut& o, uint32_t n, uint64_t first_index, void* stream);
 // k_plan_edits (eg_plan_edits.h): the n plan blocks of a plan-edit batch into d_pool (snap::kPlanStride bytes each) from the base
 // plan's block d_base and n packed edits (8 bytes each: kind | list << 8 | year << 16 | action << 24, then pos)
 int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream);

@@ -2518,6 +2518,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #ifndef EG_TU_THROUGHPUT      // (everything from here to the launchers lives in eg_rollout.o only)
 #include "eg_replay_coop.h"      // k_replay_coop, k_replay_broadcast: the replay episodes of a batch, computed once
 #include "eg_topk.h"             // k_topk_keys, k_topk_select, k_topk_merge: the top-K archive of distinct scenarios
+#include "eg_pareto.h"           // k_pareto_filter .. k_pareto_finalize: the Pareto archive of a run's outcomes
 #include "eg_plan_edits.h"       // k_plan_edits: the plan blocks of a plan-edit batch from one base block and an edit per variant
 #include "eg_refine.h"           // k_refine_pick: the winner of a refinement round, its block made the next round's base
 
@@ -3357,6 +3358,19 @@ int launch_topk_merge(uint8_t* d_state, const uint8_t* d_blocks, int n_blocks, s
                       uint64_t own_first, uint32_t own_n, uint32_t step, void* stream) {
   hipLaunchKernelGGL(k_topk_merge, dim3(1), dim3(1024), 0, (hipStream_t)stream, reinterpret_cast<TopKState*>(d_state), d_blocks, n_blocks,
                      (unsigned long long)block_stride, d_pack, k, o, (unsigned long long)own_first, own_n, step);
+  return (int)hipGetLastError();
+}
+int launch_pareto_fold(uint8_t* d_state, const ParetoWork& w, const DevOut& o, uint32_t n, uint64_t first_index, void* stream) {
+  if (n == 0 || n > w.cap_n) return n == 0 ? 0 : (int)hipErrorInvalidValue;
+  ParetoState* st = reinterpret_cast<ParetoState*>(d_state);
+  const dim3 chunks((n + kParetoChunk - 1u) / kParetoChunk), block(pareto::kBlock);
+  // (the list's length is the device's: the pairwise grids are sized for the longest one, blocks beyond it return at once)
+  const dim3 pairs((n + (uint32_t)EG_PARETO_MAX + pareto::kBlock - 1u) / pareto::kBlock, pareto::kSplit);
+  hipLaunchKernelGGL(k_pareto_filter, chunks, block, 0, (hipStream_t)stream, o, n, (unsigned long long)first_index, st, w);
+  hipLaunchKernelGGL(k_pareto_compact, chunks, block, 0, (hipStream_t)stream, o, n, (unsigned long long)first_index, st, w);
+  hipLaunchKernelGGL(k_pareto_dominate, pairs, block, 0, (hipStream_t)stream, st, w);
+  hipLaunchKernelGGL(k_pareto_rank, pairs, block, 0, (hipStream_t)stream, st, w);
+  hipLaunchKernelGGL(k_pareto_finalize, dim3(pareto::kCopyBlocks), block, 0, (hipStream_t)stream, st, w, o, n);
   return (int)hipGetLastError();
 }
 static_assert(sizeof(EpisodeMap) == 64 && offsetof(EpisodeMap, solo) == 48, "EpisodeMap: same_index sits in what was padding");

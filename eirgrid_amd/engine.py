@@ -357,6 +357,9 @@ def _refine_opts(mode, max_rounds, replace_with, append_with):
     return opts, (rep, app)
 
 
+PARETO_OBJECTIVES = ("emissions", "opinion", "cost", "reliability")      # bit i of eg_pareto_track's mask = metric i
+
+
 def _fetch_top_k(fn, handle, what):
     """(BatchResult of the n_held entries in rank order, scores [n_held], global indices [n_held]) of a top-K archive."""
     res = BatchResult.alloc(N.TOPK_MAX)
@@ -737,6 +740,42 @@ class Engine:
     def fetch_top_k(self):
         """(BatchResult of the n_held entries in rank order, their rank scores, their global indices)."""
         return _fetch_top_k(N.lib().eg_fetch_top_k, self.h, "eg_fetch_top_k")
+
+    def track_pareto(self, cap: int, objectives=PARETO_OBJECTIVES, cost_only: bool = False) -> None:
+        """Start an empty Pareto archive of at most `cap` non-dominated outcomes over the named objectives (eg_pareto_track); every
+        training batch launched from now on is folded into it on the device.  cap = 0 stops tracking (the archive stays fetchable).
+        cost_only picks the rank score that decides what stays when the front outgrows cap."""
+        mask = 0
+        for name in objectives:
+            if name not in PARETO_OBJECTIVES:
+                raise ValueError(f"track_pareto: unknown objective {name!r} (one of {', '.join(PARETO_OBJECTIVES)})")
+            mask |= 1 << PARETO_OBJECTIVES.index(name)
+        N.check(N.lib().eg_pareto_track(self.h, int(cap), mask, 2 if cost_only else 1), "eg_pareto_track")
+
+    def fetch_pareto(self):
+        """(BatchResult of the n_held entries in ascending global index, their global indices, their rank scores, n_dropped)."""
+        L = N.lib()
+        held = C.c_int32(0); dropped = C.c_int64(0)
+        N.check(L.eg_fetch_pareto(self.h, None, C.byref(held), None, None, None), "eg_fetch_pareto")
+        n = held.value      # (nothing folds between the two calls: rows for the held entries only, not for EG_PARETO_MAX)
+        res = BatchResult.alloc(max(n, 1))
+        out = res.struct()
+        scores = np.zeros(max(n, 1)); index = np.zeros(max(n, 1), np.int64)
+        N.check(L.eg_fetch_pareto(self.h, C.byref(out), C.byref(held), _p(index, C.c_int64), _p(scores, C.c_double), C.byref(dropped)), "eg_fetch_pareto")
+        assert held.value == n
+        rows = BatchResult(*[np.ascontiguousarray(getattr(res, f.name)[:n]) for f in fields(BatchResult)])
+        return rows, index[:n].copy(), scores[:n].copy(), int(dropped.value)
+
+    def fold_pareto_last_batch(self) -> None:
+        """Fold the last batch — whatever kind it was, a plan batch included — into the Pareto archive (eg_pareto_fold_last_batch)."""
+        N.check(N.lib().eg_pareto_fold_last_batch(self.h), "eg_pareto_fold_last_batch")
+
+    def _debug_pareto_fold(self, metrics, status, first_index: int) -> None:
+        """Test hook (eg_debug_pareto_fold): a batch of synthetic records with these metrics [n,4] and status [n], folded."""
+        m = np.ascontiguousarray(metrics, dtype=np.float64).reshape(-1, 4)
+        st = np.ascontiguousarray(status, dtype=np.int32)
+        assert len(st) == len(m)
+        N.check(N.lib().eg_debug_pareto_fold(self.h, _p(m, C.c_double), _p(st, C.c_int32), len(m), C.c_uint64(int(first_index))), "eg_debug_pareto_fold")
 
     def fetch_scores(self, n_episodes: int) -> np.ndarray:
         s = np.zeros(n_episodes)

@@ -270,6 +270,49 @@ int32_t eg_top_k_track(eg_ctx *, int32_t k, int32_t mode);
 int32_t eg_fetch_top_k(eg_ctx *, eg_episode_out *out, int32_t *n_held, double *scores, int64_t *global_index);
 double eg_rank_score(const double metrics[4], int32_t mode);   /* mode 2: cost_only; 0 or 1: optimization_mode None */
 
+/* Pareto archive: the non-dominated outcomes of everything a run has simulated (no counterpart in the reference, which ranks by one
+ * scalar).  eg_pareto_track(ctx, cap, objectives, mode) starts an empty archive of 1 <= cap <= EG_PARETO_MAX entries (cap 0: stop tracking;
+ * the archive stays fetchable); from then on every batch launched on this context — eg_rollout_launch / _launch_update / eg_rollout_batch,
+ * eg_device_rollout / eg_device_step, eg_train_step — is folded into it on the device behind its rollout, where the best_result and
+ * top-K folds run, without host synchronisation.
+ *   objectives   metrics[4] = {final_net_emissions, average_public_opinion, total_cost, power_reliability}: lower emissions and cost are
+ *                better, higher opinion and reliability are better.  `objectives` is a bit mask, bit i = metric i, 1 <= mask <= 15; only
+ *                ACTIVE metrics take part in dominance and identity;
+ *   valid        an episode with status EG_EP_OK and none of its four metrics NaN (whatever the mask); invalid episodes are skipped.
+ *                Infinities compare as IEEE doubles do, and -0.0 equals +0.0;
+ *   dominance    a dominates b when a is at least as good as b in every active metric and strictly better in at least one;
+ *   points       two valid episodes are the same POINT when all their active metrics are equal as values.  A point is held once,
+ *                represented by the episode with the lowest global index among those folded so far, with that episode's whole record
+ *                (the replays of a batch are one entry; no action-record key: the front is a set of outcomes).  An equal point of
+ *                lower index folded later takes the entry and its record over; the same index folded twice keeps the held entry;
+ *   front        F(S) = the points of S that no point of S dominates.  While nothing has been dropped (n_dropped == 0) the archive is
+ *                exactly F(all episodes folded): it depends only on that set — not on how it was split into batches, on their order, or
+ *                on the replay hoist;
+ *   capacity     after a batch the archive becomes F(held u valid(batch)).  If that has more than cap points, the cap points with the
+ *                largest eg_rank_score(metrics, mode) stay (mode 1: optimization_mode None, 2: cost_only, as for top-K; a NaN score
+ *                ranks last), ties to the lower global index, and the sticky counter n_dropped grows by the number removed (points
+ *                removed by dominance are not counted).  ONCE n_dropped > 0 THE ARCHIVE IS THE RESULT OF THIS STREAMING RULE AND DEPENDS
+ *                ON THE BATCH BOUNDARIES: a dropped point no longer dominates anything;
+ *   order        eg_fetch_pareto returns the entries in ascending global index.
+ * Plan batches (eg_evaluate_plans, eg_evaluate_plan_edits, the rounds of eg_refine_plan) are not training and are not folded
+ * automatically: eg_pareto_fold_last_batch(ctx) folds the last batch, whatever kind it was, on request — episode j of it as global index
+ * first_episode_index + j, also in a same_index batch ("which of these 16 384 variants are non-dominated").  EG_ERR_BAD_ARG without
+ * tracking or without a batch.  eg_pareto_track refuses, naming the field: a cap outside 0..EG_PARETO_MAX, objectives outside 1..15, a
+ * mode other than 1 or 2, a rank of a group — a shard's local front has no bounded message size, so there is no group form.  The
+ * archive state and cap record slots (10.6 MB at cap 256) are allocated by eg_pareto_track; like best_result the archive lives as long
+ * as the context and is not part of any checkpoint.
+ * eg_fetch_pareto copies the *n_held <= cap entries: `out` rows (sized for cap episodes; may be NULL), global_index[cap], scores[cap]
+ * (eg_rank_score of each entry), *n_dropped (each may be NULL). */
+#define EG_PARETO_MAX 256
+int32_t eg_pareto_track(eg_ctx *, int32_t cap, int32_t objectives, int32_t mode);
+int32_t eg_pareto_fold_last_batch(eg_ctx *);
+int32_t eg_fetch_pareto(eg_ctx *, eg_episode_out *out /* cap rows, may be NULL */, int32_t *n_held, int64_t *global_index /* [cap] or NULL */,
+                        double *scores /* [cap] or NULL */, int64_t *n_dropped /* or NULL */);
+/* Test hook: makes the context's record buffer a batch of n synthetic records — sized as a launch of n would size it, every byte zero
+ * except status[e], metrics[e] and n_draws[e] = first_index + e as a tag; eg_last_batch_size() = n — and folds it as any batch is folded
+ * (tracking must be on): crafted metric sets that no rollout will produce. */
+int32_t eg_debug_pareto_fold(eg_ctx *, const double *metrics /* [n][4] */, const int32_t *status /* [n] */, uint32_t n, uint64_t first_index);
+
 /* Plan evaluation: what does a given strategy score?  A PLAN is what update_best_strategy installs and a replay episode reads
  * (ai/learning/strategy.rs; sampling.rs:76-145, :240-270): per year a list of canonical action indices 0..60 (best_actions) and the
  * deficit actions, also as canonical indices (best_deficit_actions: an AddGenerator at 100 % or DoNothing), each flat list at most
