@@ -81,6 +81,21 @@ EDIT_NONE, EDIT_DELETE, EDIT_REPLACE, EDIT_INSERT = 0, 1, 2, 3
 REFINE_LOCAL_OPTIMUM, REFINE_MAX_ROUNDS, REFINE_BASE_FAILED = 0, 1, 2
 REFINE_MAX_VARIANTS = 16384      # EG_REFINE_MAX_VARIANTS
 PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
+DEBUG_LIST_LEN, DEBUG_FOLD_BEST_RESULT, DEBUG_FOLD_TOP_K = 8, 1, 2      # EG_DEBUG_*
+
+
+class EgUpdateCandidate(C.Structure):      # the candidate record of an update packet (CANDIDATE_BYTES)
+    _fields_ = [("score", C.c_double), ("index", C.c_int64), ("metrics", C.c_double * 4), ("n_run", C.c_int32 * YEARS), ("n_def", C.c_int32 * YEARS),
+                ("run_log", C.c_uint8 * RUN_CAP), ("def_log", C.c_uint8 * DEF_CAP)]
+
+
+class EgDebugRefineEntry(C.Structure):      # eg_debug_refine_pick's step entry (EG_DEBUG_REFINE_ENTRY_BYTES)
+    _fields_ = [("winner", C.c_int32), ("n_failed", C.c_int32), ("edit", C.c_uint32 * 2), ("score", C.c_double), ("metrics", C.c_double * 4),
+                ("off26", C.c_int32), ("offd26", C.c_int32), ("base_ok", C.c_int32), ("n", C.c_int32), ("base_score", C.c_double),
+                ("base_metrics", C.c_double * 4)]
+
+
+assert C.sizeof(EgUpdateCandidate) == CANDIDATE_BYTES and C.sizeof(EgDebugRefineEntry) == 112
 
 # every symbol include/eirgrid_hip.h declares
 EXPORTS = [
@@ -91,6 +106,7 @@ EXPORTS = [
     "eg_group_create", "eg_group_destroy", "eg_group_rank", "eg_group_push", "eg_group_step", "eg_group_pull", "eg_group_replay_hoist",
     "eg_group_best_result_track", "eg_group_fetch_best_result", "eg_top_k_track", "eg_fetch_top_k", "eg_rank_score",
     "eg_pareto_track", "eg_pareto_fold_last_batch", "eg_fetch_pareto", "eg_debug_pareto_fold",
+    "eg_debug_load_batch", "eg_debug_fold_last_batch", "eg_debug_pick_best", "eg_debug_refine_pick",
     "eg_group_top_k_track", "eg_group_fetch_top_k", "eg_plans_validate", "eg_evaluate_plans", "eg_plans_load", "eg_plans_free",
     "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block", "eg_plans_save", "eg_refine_validate", "eg_refine_plan",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
@@ -264,6 +280,15 @@ def lib():
         L.eg_fetch_pareto.argtypes = [C.c_void_p, C.POINTER(EgEpisodeOut), _i32p, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int64)]
         L.eg_debug_pareto_fold.restype = C.c_int32
         L.eg_debug_pareto_fold.argtypes = [C.c_void_p, _dp, _i32p, C.c_uint32, C.c_uint64]
+    if hasattr(L, "eg_debug_load_batch") or not os.environ.get("EIRGRID_LIB"):      # (likewise: the crafted-batch test hooks)
+        L.eg_debug_load_batch.restype = C.c_int32
+        L.eg_debug_load_batch.argtypes = [C.c_void_p, _dp, _i32p, _i32p, _u8p, _dp, C.c_uint32, C.c_uint64]
+        L.eg_debug_fold_last_batch.restype = C.c_int32
+        L.eg_debug_fold_last_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.eg_debug_pick_best.restype = C.c_int32
+        L.eg_debug_pick_best.argtypes = [C.c_void_p, C.c_void_p]
+        L.eg_debug_refine_pick.restype = C.c_int32
+        L.eg_debug_refine_pick.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, _u8p]
     L.eg_plans_load.restype = C.POINTER(EgPlanSet)
     L.eg_plans_load.argtypes = [C.c_char_p]
     L.eg_plans_free.argtypes = [C.POINTER(EgPlanSet)]

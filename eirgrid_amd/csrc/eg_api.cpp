@@ -1,5 +1,5 @@
 // eg_api.cpp — C ABI glue: the context's life cycle, HBM residency of tables / snapshot / outputs, the batch launches, training steps,
-// the device-resident policy, timing.  (Results: eg_fetch.cpp; plan batches: eg_plans.cpp; placement queries: eg_place.cpp; N ranks in
+// the device-resident policy, timing.  (Results: eg_fetch.cpp; test hooks over crafted batches: eg_debug.cpp; plan batches: eg_plans.cpp; placement queries: eg_place.cpp; N ranks in
 // one process: eg_group.cpp; what they share: eg_host.h.)
 // There is no CPU execution path behind these entry points: without a HIP device eg_create fails.
 #include <algorithm>
@@ -251,13 +251,8 @@ int launch_batch(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, con
     EG_LAUNCH("k_fold_stats", launch_fold_stats(plan.d_stats_rep, d_stats, nullptr));
     c->stats_rep_dirty = false;
   }
-  if (c->fold_mode != 0)      // behind the batch on the null stream: its results are in iteration order in the records
-    EG_LAUNCH("k_fold_best", launch_fold_best(c->out, n, first_index, c->fold_mode == 2, c->d_fold, nullptr));
-  if (c->topk_mode != 0) {      // the top-K archive, behind the batch as well (the epilogue's scores are the rank scores in mode 1)
-    EG_TRY(topk_select(c, n, first_index, c->topk_mode, d_stats != nullptr && c->topk_mode == 1, c->d_topk, c->topk_k));
-    EG_LAUNCH("k_topk_merge", launch_topk_merge(c->d_topk, reinterpret_cast<const uint8_t*>(c->d_tk_blocks.ptr), int(topk_chunks(n)), sizeof(TopKBlock), nullptr,
-                                     c->topk_k, c->out, first_index, n, 0u, nullptr));
-  }
+  if (c->fold_mode != 0) EG_TRY(best_result_fold(c, n, first_index));      // behind the batch on the null stream: its results are in iteration order in the records
+  if (c->topk_mode != 0) EG_TRY(topk_fold(c, n, first_index, d_stats != nullptr && c->topk_mode == 1));      // the top-K archive, behind the batch as well (the epilogue's scores are the rank scores in mode 1)
   if (c->pareto_cap != 0) EG_TRY(pareto_fold(c, n, first_index));      // the Pareto archive, behind the top-K fold
   ring_commit(c, slot, (plan.n_heavy > 0 ? 1 : 0) | (plan.n_lean > 0 ? 2 : 0));
   c->last_n = n; c->last_first = first_index;
@@ -306,14 +301,6 @@ int find_table(const char* who, const Map& tables, const char* name, const T** p
   return EG_OK;
 }
 
-int ensure_packet(eg_ctx* c) {      // eg_train_step / eg_device_step / eg_policy_push
-  bool fresh = false;
-  EG_HIP(c->d_packet.reserve(EG_PACKET_BYTES, &fresh));
-  if (fresh) EG_HIP(hipMemset(c->d_packet, 0, EG_PACKET_BYTES));      // the rollout epilogue ADDS to the statistics
-  EG_HIP(c->h_packet.reserve(EG_PACKET_BYTES));
-  return EG_OK;
-}
-
 int device_rollout(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t replay_period, void* d_packet, bool pick) {
   if (!c || !c->snap_valid || !d_packet) { set_error("eg_device_rollout: push a policy first"); return EG_ERR_BAD_ARG; }
   if (n == 0) { c->last_n = 0; return EG_OK; }
@@ -325,6 +312,14 @@ int device_rollout(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, u
   return EG_OK;
 }
 }  // namespace
+
+int eg::ensure_packet(eg_ctx* c) {      // eg_train_step / eg_device_step / eg_policy_push
+  bool fresh = false;
+  EG_HIP(c->d_packet.reserve(EG_PACKET_BYTES, &fresh));
+  if (fresh) EG_HIP(hipMemset(c->d_packet, 0, EG_PACKET_BYTES));      // the rollout epilogue ADDS to the statistics
+  EG_HIP(c->h_packet.reserve(EG_PACKET_BYTES));
+  return EG_OK;
+}
 
 int eg::device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, size_t packet_stride, void* d_own_packet, uint64_t noise_seed, bool local_pick) {
   if (!c || !c->snap_valid || !d_packets || n_packets < 1 || !d_own_packet) { set_error("eg_device_apply: bad argument"); return EG_ERR_BAD_ARG; }

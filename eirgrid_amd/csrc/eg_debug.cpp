@@ -1,0 +1,119 @@
+// eg_debug.cpp — the crafted-batch test hooks (include/eirgrid_hip.h, debug section): a batch of synthetic records in the context's
+// record buffer, and the reductions that decide what a run keeps run over it — the folds launch_batch runs behind a real batch (through the
+// helpers it calls), k_pick_best, k_refine_pick.  Host code only: no kernel is launched here that a run does not launch.
+#include <cstring>
+
+#include "eg_host.h"
+
+using namespace eg;
+
+namespace {
+int refuse_rank(const eg_ctx* c, const char* who) {
+  if (!c->group_member) return EG_OK;
+  set_error(std::string(who) + ": the context is a rank of an eg_group (the test hooks have no group form)");
+  return EG_ERR_BAD_ARG;
+}
+// one field of the n records from a host array of `width` bytes per record
+int put_field(eg_ctx* c, size_t field, const void* src, size_t width, uint32_t n) {
+  EG_HIP(hipMemcpy2D(c->out.base + field, rec::stride, src, width, width, n, hipMemcpyHostToDevice));
+  return EG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int32_t eg_debug_load_batch(eg_ctx* c, const double* metrics, const int32_t* status, const int32_t* n_act, const uint8_t* act_log, const double* score_list,
+                            uint32_t n, uint64_t first_index) {
+  if (!c || !metrics || !status || n == 0) { set_error("eg_debug_load_batch: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_load_batch"));
+  EG_HIP(hipSetDevice(c->device));
+  EG_TRY(ensure_outputs(c, n));
+  EG_HIP(hipMemsetAsync(c->out.base, 0, size_t(n) * rec::stride, nullptr));
+  EG_HIP(hipMemsetAsync(c->out.score_list, 0, size_t(n) * sizeof(double), nullptr));
+  // the tag and the two lists that show where a copied record or candidate came from: the global index g, its eight bytes, those of ~g
+  std::vector<uint64_t> tag(n), inv(n);
+  std::vector<int32_t> eight(size_t(n) * EG_YEARS, 0);
+  for (uint32_t e = 0; e < n; ++e) { tag[e] = first_index + e; inv[e] = ~tag[e]; eight[size_t(e) * EG_YEARS] = EG_DEBUG_LIST_LEN; }
+  static_assert(EG_DEBUG_LIST_LEN == sizeof(uint64_t), "the lists are the index's bytes (little-endian)");
+  EG_TRY(put_field(c, rec::metrics, metrics, 4 * sizeof(double), n));
+  EG_TRY(put_field(c, rec::status, status, sizeof(int32_t), n));
+  EG_TRY(put_field(c, rec::n_draws, tag.data(), sizeof(uint64_t), n));
+  EG_TRY(put_field(c, rec::n_run, eight.data(), EG_YEARS * sizeof(int32_t), n));
+  EG_TRY(put_field(c, rec::n_def, eight.data(), EG_YEARS * sizeof(int32_t), n));
+  EG_TRY(put_field(c, rec::run_log, tag.data(), sizeof(uint64_t), n));
+  EG_TRY(put_field(c, rec::def_log, inv.data(), sizeof(uint64_t), n));
+  if (n_act) EG_TRY(put_field(c, rec::n_act, n_act, EG_YEARS * sizeof(int32_t), n));
+  if (act_log) EG_TRY(put_field(c, rec::act_log, act_log, EG_ACT_CAP, n));      // the whole row: also what lies behind the log
+  if (score_list) EG_HIP(hipMemcpy(c->out.score_list, score_list, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
+  c->last_n = n; c->last_first = first_index;
+  return EG_OK;
+}
+
+int32_t eg_debug_fold_last_batch(eg_ctx* c, int32_t what, int32_t use_score_list) {
+  if (!c || what < 1 || what > (EG_DEBUG_FOLD_BEST_RESULT | EG_DEBUG_FOLD_TOP_K)) { set_error("eg_debug_fold_last_batch: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_fold_last_batch"));
+  if (c->last_n == 0) { set_error("eg_debug_fold_last_batch: there is no last batch"); return EG_ERR_BAD_ARG; }
+  if ((what & EG_DEBUG_FOLD_BEST_RESULT) && c->fold_mode == 0) { set_error("eg_debug_fold_last_batch: eg_best_result_track first (tracking is off)"); return EG_ERR_BAD_ARG; }
+  if ((what & EG_DEBUG_FOLD_TOP_K) && c->topk_mode == 0) { set_error("eg_debug_fold_last_batch: eg_top_k_track first (tracking is off)"); return EG_ERR_BAD_ARG; }
+  if ((what & EG_DEBUG_FOLD_TOP_K) && use_score_list && c->topk_mode != 1) {
+    set_error("eg_debug_fold_last_batch: use_score_list with top-K mode 2 (the score list holds mode 1's scores)"); return EG_ERR_BAD_ARG;
+  }
+  EG_HIP(hipSetDevice(c->device));
+  if (what & EG_DEBUG_FOLD_BEST_RESULT) EG_TRY(best_result_fold(c, c->last_n, c->last_first));
+  if (what & EG_DEBUG_FOLD_TOP_K) EG_TRY(topk_fold(c, c->last_n, c->last_first, use_score_list != 0));
+  return EG_OK;
+}
+
+int32_t eg_debug_pareto_fold(eg_ctx* c, const double* metrics, const int32_t* status, uint32_t n, uint64_t first_index) {
+  if (!c || !metrics || !status || n == 0) { set_error("eg_debug_pareto_fold: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->pareto_cap == 0) { set_error("eg_debug_pareto_fold: eg_pareto_track first (tracking is off)"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_debug_load_batch(c, metrics, status, nullptr, nullptr, nullptr, n, first_index));
+  return pareto_fold(c, n, first_index);
+}
+
+int32_t eg_debug_pick_best(eg_ctx* c, void* candidate) {
+  if (!c || !candidate) { set_error("eg_debug_pick_best: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_pick_best"));
+  if (c->last_n == 0) { set_error("eg_debug_pick_best: there is no last batch"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  EG_TRY(ensure_packet(c));
+  UpdateCandidate* d_cand = reinterpret_cast<UpdateCandidate*>(c->d_packet.ptr + 8 * EG_STATS_LEN);
+  EG_HIP(hipMemsetAsync(d_cand, 0, sizeof(UpdateCandidate), nullptr));      // (what the kernel leaves alone without a winner reads as zeros)
+  EG_LAUNCH("k_pick_best", launch_pick_best(c->out, c->last_n, c->last_first, d_cand, nullptr));
+  EG_HIP(hipMemcpy(candidate, d_cand, sizeof(UpdateCandidate), hipMemcpyDeviceToHost));
+  return EG_OK;
+}
+
+int32_t eg_debug_refine_pick(eg_ctx* c, int32_t mode, void* entry, uint8_t* base_block) {
+  static_assert(sizeof(RefineEntry) == EG_DEBUG_REFINE_ENTRY_BYTES, "the step entry's layout is what the hook documents");
+  static_assert(EG_PLAN_BLOCK_BYTES == snap::kPlanStride, "plan block");
+  if (!c || !entry || !base_block || (mode != 1 && mode != 2)) { set_error("eg_debug_refine_pick: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_refine_pick"));
+  const uint32_t n = c->last_n;
+  if (n == 0 || n > EG_REFINE_MAX_VARIANTS) { set_error("eg_debug_refine_pick: the last batch holds " + std::to_string(n) + " records (1..EG_REFINE_MAX_VARIANTS)"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  constexpr size_t kWords = snap::kPlanStride / 4, kOff26 = (snap::best_off - snap::best_mask) / 4 + EG_YEARS, kOffD26 = (snap::bestd_off - snap::best_mask) / 4 + EG_YEARS;
+  static_assert(kOff26 == 130 && kOffD26 == 158, "the words of the list totals as the hook documents them");
+  std::vector<uint32_t> blocks(size_t(n) * kWords), head(kWords + size_t(n) * 2);      // head: the base block, then the packed edits
+  for (uint32_t j = 0; j < n; ++j) {
+    uint32_t* b = blocks.data() + size_t(j) * kWords;
+    for (size_t w = 0; w < kWords; ++w) b[w] = j * 0x9E3779B1u + uint32_t(w);
+    b[kOff26] = j % (uint32_t(snap::kBestCap) + 1u); b[kOffD26] = (j / 3u) % (uint32_t(snap::kBestCap) + 1u);
+    head[kWords + 2 * size_t(j)] = j; head[kWords + 2 * size_t(j) + 1] = ~j;
+  }
+  for (size_t w = 0; w < kWords; ++w) head[w] = 0xBA5E0000u + uint32_t(w);
+  head[kOff26] = 7u; head[kOffD26] = 5u;
+  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
+  EG_HIP(c->d_plan_edit_in.reserve(snap::kPlanStride + size_t(n) * 8));
+  EG_HIP(c->d_refine_log.reserve(size_t(kRefineLog) * kRefineEntryStride));
+  EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy(c->d_plan_edit_in, head.data(), head.size() * 4, hipMemcpyHostToDevice));
+  EG_HIP(hipMemsetAsync(c->d_refine_log, 0, kRefineEntryStride, nullptr));
+  c->n_plan_blocks = n;
+  EG_LAUNCH("k_refine_pick", launch_refine_pick(c->out, n, mode, c->d_plan_edit_in + snap::kPlanStride, c->d_plans, c->d_plan_edit_in, c->d_refine_log, nullptr));
+  EG_HIP(hipMemcpy(entry, c->d_refine_log, sizeof(RefineEntry), hipMemcpyDeviceToHost));
+  EG_HIP(hipMemcpy(base_block, c->d_plan_edit_in, snap::kPlanStride, hipMemcpyDeviceToHost));
+  return EG_OK;
+}
+
+}  // extern "C"

@@ -22,6 +22,18 @@ int eg::topk_select(eg_ctx* c, uint32_t n, uint64_t first_index, int mode, bool 
   return EG_OK;
 }
 
+int eg::best_result_fold(eg_ctx* c, uint32_t n, uint64_t first_index) {
+  EG_LAUNCH("k_fold_best", launch_fold_best(c->out, n, first_index, c->fold_mode == 2, c->d_fold, nullptr));
+  return EG_OK;
+}
+
+int eg::topk_fold(eg_ctx* c, uint32_t n, uint64_t first_index, bool use_score_list) {
+  EG_TRY(topk_select(c, n, first_index, c->topk_mode, use_score_list, c->d_topk, c->topk_k));
+  EG_LAUNCH("k_topk_merge", launch_topk_merge(c->d_topk, reinterpret_cast<const uint8_t*>(c->d_tk_blocks.ptr), int(topk_chunks(n)), sizeof(TopKBlock), nullptr,
+                                   c->topk_k, c->out, first_index, n, 0u, nullptr));
+  return EG_OK;
+}
+
 int eg::pareto_fold(eg_ctx* c, uint32_t n, uint64_t first_index) {
   if (n == 0) return EG_OK;
   if (n > c->pareto_work_n || !c->d_pareto_work) {      // (a larger batch than any before: the old buffer is freed behind the launches that use it)
@@ -263,21 +275,6 @@ int32_t eg_fetch_pareto(eg_ctx* c, eg_episode_out* o, int32_t* n_held, int64_t* 
     EG_TRY(fetch_records(c->d_pareto + kParetoRecords + size_t(e.slot) * rec::stride, 1, &row));
   }
   return EG_OK;
-}
-
-int32_t eg_debug_pareto_fold(eg_ctx* c, const double* metrics, const int32_t* status, uint32_t n, uint64_t first_index) {
-  if (!c || !metrics || !status || n == 0) { set_error("eg_debug_pareto_fold: bad argument"); return EG_ERR_BAD_ARG; }
-  if (c->pareto_cap == 0) { set_error("eg_debug_pareto_fold: eg_pareto_track first (tracking is off)"); return EG_ERR_BAD_ARG; }
-  EG_HIP(hipSetDevice(c->device));
-  EG_TRY(ensure_outputs(c, n));
-  EG_HIP(hipMemsetAsync(c->out.base, 0, size_t(n) * rec::stride, nullptr));
-  std::vector<uint64_t> tag(n);
-  for (uint32_t e = 0; e < n; ++e) tag[e] = first_index + e;
-  EG_HIP(hipMemcpy2D(c->out.base + rec::metrics, rec::stride, metrics, 4 * sizeof(double), 4 * sizeof(double), n, hipMemcpyHostToDevice));
-  EG_HIP(hipMemcpy2D(c->out.base + rec::status, rec::stride, status, sizeof(int32_t), sizeof(int32_t), n, hipMemcpyHostToDevice));
-  EG_HIP(hipMemcpy2D(c->out.base + rec::n_draws, rec::stride, tag.data(), sizeof(uint64_t), sizeof(uint64_t), n, hipMemcpyHostToDevice));
-  c->last_n = n; c->last_first = first_index;
-  return pareto_fold(c, n, first_index);
 }
 
 double eg_rank_score(const double m[4], int32_t mode) { return m ? rm::rank_score(m, mode) : std::nan(""); }

@@ -153,6 +153,7 @@ int prepare_heavy(eg_ctx* c, uint32_t n_heavy, bool known_short);
 int ring_take(eg_ctx* c, RolloutPlan& plan, int& slot);
 void ring_commit(eg_ctx* c, int slot, int ev_used);
 int arm_solo(eg_ctx* c, RolloutPlan& plan, uint32_t n);
+int ensure_packet(eg_ctx* c);      // the library-owned update packet (d_packet, zeroed when new) and its pinned copy
 int device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, size_t packet_stride, void* d_own_packet, uint64_t noise_seed, bool local_pick);
 // eg_plans.cpp
 int check_policy(const eg_policy_snapshot* s, const eg_opts* o, const char* who);
@@ -167,7 +168,10 @@ int fetch_records(const uint8_t* d_base, size_t N, eg_episode_out* o);
 int fold_reset(DevBuf<uint8_t>& d_fold);
 int topk_reset(DevBuf<uint8_t>& d_topk, int k, int mode);
 int topk_select(eg_ctx* c, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state, int k);
-// the n results of c->out (global indices first_index..) folded into the Pareto archive, on the null stream
+// the n results of c->out (global indices first_index..) folded behind a batch, on the null stream: into the best_result fold
+// (c->fold_mode != 0), into the top-K archive (c->topk_mode != 0: topk_select, then k_topk_merge), into the Pareto archive
+int best_result_fold(eg_ctx* c, uint32_t n, uint64_t first_index);
+int topk_fold(eg_ctx* c, uint32_t n, uint64_t first_index, bool use_score_list);
 int pareto_fold(eg_ctx* c, uint32_t n, uint64_t first_index);
 inline uint32_t topk_chunks(uint32_t n) { return (n + kTopKChunk - 1u) / kTopKChunk; }
 // The entries of the archive state `st` into the caller's rows: archive_of(i, entry) is the device archive (TopKState, then the record

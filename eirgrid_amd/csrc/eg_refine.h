@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(1024) k_refine_pick(DevOut O, uint32_t n, int 
       }
     }
     fails += __popcll(__ballot(j < n && !cand));
-    if (cand && s > best) { best = s; best_j = (int)j; }      // (a thread's own variants ascend: the first of equal scores stays)
+    if (cand && before(s, (int)j, best, best_j)) { best = s; best_j = (int)j; }      // (the reductions' order: a candidate that scores -inf is recorded as well)
   }
   wave_best(best, best_j);
   if (lane == 0) { s_score[wave] = best; s_index[wave] = best_j; s_fail[wave] = fails; }

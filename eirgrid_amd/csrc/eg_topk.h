@@ -60,7 +60,8 @@ __device__ unsigned long long episode_key(const DevOut& O, uint32_t e, int lane)
 
 }  // namespace topk
 
-// 1. four episodes per workgroup of 256, one wave each.  Score -inf: the episode cannot enter (failed, NaN, or not above the k-th).
+// 1. four episodes per workgroup of 256, one wave each.  Score -inf: the episode cannot enter (failed, NaN, or not above the k-th) — and so
+//    an episode whose rank score IS -inf never enters: only scores above -inf can (include/eirgrid_hip.h, "failures").
 __global__ void __launch_bounds__(256) k_topk_keys(DevOut O, uint32_t n, unsigned long long first_index, int mode, int use_list,
                                                    const TopKState* st, double* c_score, unsigned long long* c_key) {
   const int lane = threadIdx.x & (kWave - 1);

@@ -777,6 +777,42 @@ class Engine:
         assert len(st) == len(m)
         N.check(N.lib().eg_debug_pareto_fold(self.h, _p(m, C.c_double), _p(st, C.c_int32), len(m), C.c_uint64(int(first_index))), "eg_debug_pareto_fold")
 
+    def _debug_load_batch(self, metrics, status, first_index: int, n_act=None, act_log=None, score_list=None) -> None:
+        """Test hook (eg_debug_load_batch): the record buffer becomes a batch of synthetic records with these metrics [n,4] and status [n],
+        tagged with their global index; optionally n_act [n,26], whole act_log rows [n,ACT_CAP] and the score list [n]."""
+        m = np.ascontiguousarray(metrics, dtype=np.float64).reshape(-1, 4)
+        st = np.ascontiguousarray(status, dtype=np.int32)
+        n = len(m)
+        assert st.shape == (n,)
+        na = al = sl = None
+        if n_act is not None:
+            na = np.ascontiguousarray(n_act, dtype=np.int32); assert na.shape == (n, N.YEARS)
+        if act_log is not None:
+            al = np.ascontiguousarray(act_log, dtype=np.uint8); assert al.shape == (n, N.ACT_CAP)
+        if score_list is not None:
+            sl = np.ascontiguousarray(score_list, dtype=np.float64); assert sl.shape == (n,)
+        N.check(N.lib().eg_debug_load_batch(self.h, _p(m, C.c_double), _p(st, C.c_int32), None if na is None else _p(na, C.c_int32),
+                                            None if al is None else _p(al, C.c_uint8), None if sl is None else _p(sl, C.c_double), n,
+                                            C.c_uint64(int(first_index))), "eg_debug_load_batch")
+
+    def _debug_fold_last_batch(self, best_result: bool = False, top_k: bool = False, use_score_list: bool = False) -> None:
+        """Test hook (eg_debug_fold_last_batch): what a training batch runs behind its rollout for the chosen folds, on the last batch."""
+        what = (N.DEBUG_FOLD_BEST_RESULT if best_result else 0) | (N.DEBUG_FOLD_TOP_K if top_k else 0)
+        N.check(N.lib().eg_debug_fold_last_batch(self.h, what, int(use_score_list)), "eg_debug_fold_last_batch")
+
+    def _debug_pick_best(self) -> N.EgUpdateCandidate:
+        """Test hook (eg_debug_pick_best): the update's candidate record of the last batch."""
+        cand = N.EgUpdateCandidate()
+        N.check(N.lib().eg_debug_pick_best(self.h, C.byref(cand)), "eg_debug_pick_best")
+        return cand
+
+    def _debug_refine_pick(self, mode: int = 1):
+        """Test hook (eg_debug_refine_pick): (step entry, base block [PLAN_BLOCK_BYTES] as the kernel left it) over the last batch."""
+        entry = N.EgDebugRefineEntry()
+        base = np.zeros(N.PLAN_BLOCK_BYTES, np.uint8)
+        N.check(N.lib().eg_debug_refine_pick(self.h, int(mode), C.byref(entry), _p(base, C.c_uint8)), "eg_debug_refine_pick")
+        return entry, base
+
     def fetch_scores(self, n_episodes: int) -> np.ndarray:
         s = np.zeros(n_episodes)
         N.check(N.lib().eg_fetch_scores(self.h, _p(s, C.c_double)), "eg_fetch_scores")

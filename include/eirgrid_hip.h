@@ -253,7 +253,8 @@ double eg_evaluate_action_impact(const double current_metrics[4], const double n
  *   rank score   eg_rank_score(metrics, mode): score_metrics of ai/metrics/scoring.rs:5-45 (mode 2: its cost_only branch, :7-15),
  *                evaluated with the shared IEEE-only logarithm of csrc/eg_reduced_math.h, the same bits on the host and the device;
  *   order        score descending, ties to the lower global index;
- *   failures     episodes with status != EG_EP_OK (and a NaN score) are skipped;
+ *   failures     episodes with status != EG_EP_OK (and a NaN score) are skipped; so is a score of -inf (opinion -inf at or below net zero):
+ *                only scores ABOVE -inf can enter, -inf is what the fold's own lists hold for "no candidate";
  *   identity     two episodes are the same scenario when the bit patterns of their 4 metrics AND their 64-bit keys are equal; the key
  *                covers n_act[26] as little-endian int32 followed by act_log[0 .. sum n_act), zero-padded to a multiple of 8 bytes,
  *                read as little-endian 8-byte words w_i:  key = sum_i splitmix64(w_i + i * 0x9E3779B97F4A7C15) mod 2^64, with
@@ -308,9 +309,8 @@ int32_t eg_pareto_track(eg_ctx *, int32_t cap, int32_t objectives, int32_t mode)
 int32_t eg_pareto_fold_last_batch(eg_ctx *);
 int32_t eg_fetch_pareto(eg_ctx *, eg_episode_out *out /* cap rows, may be NULL */, int32_t *n_held, int64_t *global_index /* [cap] or NULL */,
                         double *scores /* [cap] or NULL */, int64_t *n_dropped /* or NULL */);
-/* Test hook: makes the context's record buffer a batch of n synthetic records — sized as a launch of n would size it, every byte zero
- * except status[e], metrics[e] and n_draws[e] = first_index + e as a tag; eg_last_batch_size() = n — and folds it as any batch is folded
- * (tracking must be on): crafted metric sets that no rollout will produce. */
+/* Test hook: eg_debug_load_batch(ctx, metrics, status, NULL, NULL, NULL, n, first_index) (the debug section below), then the batch folded
+ * into the Pareto archive as any batch is folded (tracking must be on): crafted metric sets that no rollout will produce. */
 int32_t eg_debug_pareto_fold(eg_ctx *, const double *metrics /* [n][4] */, const int32_t *status /* [n] */, uint32_t n, uint64_t first_index);
 
 /* Plan evaluation: what does a given strategy score?  A PLAN is what update_best_strategy installs and a replay episode reads
@@ -464,6 +464,39 @@ int32_t eg_group_fetch_top_k(eg_group *, eg_episode_out *out, int32_t *n_held, d
  * kernel that reads a word before writing it sees what the previous tenant left; the parity tests call this with small
  * integers (the values the helper protocol's sequence flags take) before a rollout. */
 int32_t eg_debug_fill_lds(eg_ctx *, uint32_t value);
+/* Test hooks: a crafted batch, and the reductions that decide what a run keeps over it — ties, staircases, NaN and infinities, key
+ * edges, maxima on wave and stride boundaries: what real episodes never produce.  Host code only; every kernel is the one a run launches.
+ * All four refuse a rank of a group.
+ *   eg_debug_load_batch   makes the context's record buffer a batch of n synthetic records — sized as a launch of n would size it;
+ *                         eg_last_batch_size() = n, global indices first_index + e.  Record e is zero except: metrics[e], status[e];
+ *                         n_draws = g = first_index + e as a tag; n_run[0] = n_def[0] = EG_DEBUG_LIST_LEN with run_log[0..8) the bytes of g
+ *                         and def_log[0..8) the bytes of ~g (little-endian), so that a copied list shows its source; n_act[e] and the
+ *                         WHOLE act_log row as given, the bytes behind the log's length included (NULL: zeros); and score_list[e], the
+ *                         back-to-back scores of the statistics epilogue (NULL: zeros).
+ *   eg_debug_fold_last_batch   runs, on the last batch, exactly what a training batch runs behind its rollout for the folds `what`
+ *                         selects (EG_DEBUG_FOLD_BEST_RESULT | EG_DEBUG_FOLD_TOP_K; the fold's tracking must be on).  use_score_list:
+ *                         the top-K fold takes its rank scores from score_list, as behind a batch whose statistics epilogue ran (mode 1).
+ *   eg_debug_pick_best    k_pick_best over the last batch into the context's update packet; `candidate` receives the candidate record
+ *                         (EG_CANDIDATE_BYTES, layout above).  The contract of score_list: the epilogue writes score_metrics (>= 0) for an
+ *                         episode that ended EG_EP_OK and -1.0 for a failed one; the pick is the FIRST maximum among the scores above
+ *                         -1.0 (a NaN never compares above anything), and score -1.0 / index -1 when there is none.
+ *   eg_debug_refine_pick  k_refine_pick over the last batch (n <= EG_REFINE_MAX_VARIANTS records = variants) with n plan blocks,
+ *                         a base block and n packed edits of the hook's own: block j is the 32-bit words j * 0x9E3779B1 + w (w = 0 ..
+ *                         EG_PLAN_BLOCK_BYTES / 4) with the two list totals (words 130 and 158: entry [26] of the prefix offsets)
+ *                         j mod 4097 and (j / 3) mod 4097; the base block is the words 0xBA5E0000 + w with totals 7 and 5; edit j is
+ *                         (j, ~j).  `entry` receives the step entry (EG_DEBUG_REFINE_ENTRY_BYTES: i32 winner, n_failed | u32 edit[2] |
+ *                         f64 score, metrics[4] | i32 off26, offd26, base_ok, n | f64 base_score, base_metrics[4]), `base_block` the base
+ *                         block as the kernel left it. */
+#define EG_DEBUG_LIST_LEN 8
+#define EG_DEBUG_FOLD_BEST_RESULT 1
+#define EG_DEBUG_FOLD_TOP_K 2
+#define EG_DEBUG_REFINE_ENTRY_BYTES 112
+int32_t eg_debug_load_batch(eg_ctx *, const double *metrics /* [n][4] */, const int32_t *status /* [n] */, const int32_t *n_act /* [n][26] or NULL */,
+                            const uint8_t *act_log /* [n][EG_ACT_CAP] or NULL */, const double *score_list /* [n] or NULL */, uint32_t n,
+                            uint64_t first_index);
+int32_t eg_debug_fold_last_batch(eg_ctx *, int32_t what, int32_t use_score_list);
+int32_t eg_debug_pick_best(eg_ctx *, void *candidate /* EG_CANDIDATE_BYTES */);
+int32_t eg_debug_refine_pick(eg_ctx *, int32_t mode /* 1 | 2 */, void *entry /* EG_DEBUG_REFINE_ENTRY_BYTES */, uint8_t *base_block /* EG_PLAN_BLOCK_BYTES */);
 /* Diagnostic hook: ONE idle workgroup of 256 threads on the library's side stream that stays resident for `cycles` shader cycles;
  * variant 0: 1 KB of LDS, few registers; 1: 150 KB of LDS; 2: 200+ registers a lane; 3: both (the hoisted replay's footprint).  What a
  * resident workgroup costs the grid beside it: scripts/side_kernel_probe.py, profiles/r04_ab_notes.log. */
