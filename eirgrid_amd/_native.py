@@ -80,6 +80,7 @@ class EgRefineStep(C.Structure):
 EDIT_NONE, EDIT_DELETE, EDIT_REPLACE, EDIT_INSERT = 0, 1, 2, 3
 REFINE_LOCAL_OPTIMUM, REFINE_MAX_ROUNDS, REFINE_BASE_FAILED = 0, 1, 2
 REFINE_MAX_VARIANTS = 16384      # EG_REFINE_MAX_VARIANTS
+REFINE_MAX_PLANS = 256           # EG_REFINE_MAX_PLANS
 PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
 DEBUG_LIST_LEN, DEBUG_FOLD_BEST_RESULT, DEBUG_FOLD_TOP_K = 8, 1, 2      # EG_DEBUG_*
 
@@ -109,6 +110,7 @@ EXPORTS = [
     "eg_debug_load_batch", "eg_debug_fold_last_batch", "eg_debug_pick_best", "eg_debug_refine_pick",
     "eg_group_top_k_track", "eg_group_fetch_top_k", "eg_plans_validate", "eg_evaluate_plans", "eg_plans_load", "eg_plans_free",
     "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block", "eg_plans_save", "eg_refine_validate", "eg_refine_plan",
+    "eg_refine_plans_validate", "eg_refine_plans", "eg_debug_refine_pick_many",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -270,6 +272,16 @@ def lib():
         L.eg_refine_plan.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts),
                                      C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgRefineStep), _i32p, _i32p, _dp,
                                      C.POINTER(EgEpisodeOut)]
+    # (likewise: scripts/refine_many_probe.py may load a build of the parent commit, which refines one plan a call)
+    if hasattr(L, "eg_refine_plans") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_refine_plans_validate.restype = C.c_int32
+        L.eg_refine_plans_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts)]
+        L.eg_refine_plans.restype = C.c_int32
+        L.eg_refine_plans.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts),
+                                      C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgRefineStep), _i32p, _i32p, _dp,
+                                      C.POINTER(EgEpisodeOut)]
+        L.eg_debug_refine_pick_many.restype = C.c_int32
+        L.eg_debug_refine_pick_many.argtypes = [C.c_void_p, C.c_int32, _u32p, _u32p, C.c_int32, C.c_void_p, _u8p]
     # (likewise: scripts/pareto_probe.py may load a build of the parent commit, which has no Pareto archive)
     if hasattr(L, "eg_pareto_track") or not os.environ.get("EIRGRID_LIB"):
         L.eg_pareto_track.restype = C.c_int32

@@ -462,6 +462,23 @@ eg_plan_set* eg::make_plan_set(const int32_t* count, const uint8_t* act, const i
   ps->names = ps->name_ptrs.data();
   return ps.release();
 }
+eg_plan_set* eg::make_plan_set_n(int32_t n, const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact, const char* const* names) {
+  std::unique_ptr<PlanSet> ps(new PlanSet());
+  ps->cnt.assign(count, count + size_t(n) * Y); ps->dcnt.assign(dcount, dcount + size_t(n) * Y);
+  int64_t len = 0, dlen = 0;
+  for (size_t i = 0; i < size_t(n) * Y; ++i) { len += count[i]; dlen += dcount[i]; }
+  ps->act.assign(act, act + len); ps->dact.assign(dact, dact + dlen);
+  ps->act.reserve(1); ps->dact.reserve(1);      // (data() of an empty list is not NULL)
+  ps->name_store.reserve(size_t(n));            // (the pointers below stay valid)
+  for (int32_t j = 0; j < n; ++j) ps->name_store.push_back(names && names[j] ? names[j] : "");
+  for (int32_t j = 0; j < n; ++j) ps->name_ptrs.push_back(ps->name_store[size_t(j)].c_str());
+  ps->n_plans = n;
+  ps->best_count = ps->cnt.data(); ps->best_deficit_count = ps->dcnt.data();
+  ps->best_actions = ps->act.data(); ps->best_deficit_actions = ps->dact.data();
+  ps->best_actions_len = len; ps->best_deficit_actions_len = dlen;
+  ps->names = ps->name_ptrs.data();
+  return ps.release();
+}
 
 extern "C" {
 

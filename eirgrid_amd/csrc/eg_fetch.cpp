@@ -100,9 +100,8 @@ int check_internal(const int32_t* status, size_t n) {
 }
 }  // namespace
 
-namespace {
 // row r of a caller's episode-major buffers
-eg_episode_out out_row(const eg_episode_out* o, size_t r) {
+eg_episode_out eg::out_row(const eg_episode_out* o, size_t r) {
   eg_episode_out x = *o;
 #define EG_ROW(field, count) if (x.field) x.field += r * size_t(count)
   EG_ROW(metrics, 4); EG_ROW(yearly, EG_YEARS * EG_YEARLY_FIELDS); EG_ROW(status, 1); EG_ROW(n_run, EG_YEARS); EG_ROW(n_def, EG_YEARS);
@@ -112,7 +111,6 @@ eg_episode_out out_row(const eg_episode_out* o, size_t r) {
 #undef EG_ROW
   return x;
 }
-}  // namespace
 
 // a context's or a group rank's best_result fold, on the current device: allocated on first use, best_result = None (multi_simulation.rs:384)
 int eg::fold_reset(DevBuf<uint8_t>& d_fold) {

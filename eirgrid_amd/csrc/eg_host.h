@@ -1,4 +1,4 @@
-// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_plans / eg_refine / eg_place / eg_group .cpp): owned buffers, the
+// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_plans / eg_refine / eg_refine_many / eg_place / eg_group .cpp): owned buffers, the
 // error macros, the context and the helpers that cross units.  Host only: the kernels include eg_internal.h, never this.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -141,6 +141,11 @@ struct eg_ctx {
   size_t n_plan_blocks = 0;      // blocks of the last plan or plan-edit batch in d_plans (eg_debug_fetch_plan_block)
   // plan refinement (eg_refine_plan): the step log k_refine_pick writes, a ring of kRefineLog entries of kRefineEntryStride bytes
   eg::DevBuf<uint8_t> d_refine_log;
+  // eg_refine_plans: the base blocks of the call's plans (uploaded once, kept current by k_refine_pick_many) and what a launch
+  // uploads in one copy: the packed edits, the base slot of every variant, the segment table
+  // EIRGRID_REFINE_LAUNCH_VARIANTS (default and at most 16 384, at least 1; read at every call): the variants a launch of eg_refine_plans may
+  // hold — a plan with more gets a launch to itself; for tests that want many launches per round at small sizes
+  eg::DevBuf<uint8_t> d_refine_bases, d_refine_in;
 };
 
 namespace eg {
@@ -165,6 +170,7 @@ void pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len, ui
 int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index);
 // eg_fetch.cpp
 int fetch_records(const uint8_t* d_base, size_t N, eg_episode_out* o);
+eg_episode_out out_row(const eg_episode_out* o, size_t r);      // row r of a caller's episode-major buffers
 int fold_reset(DevBuf<uint8_t>& d_fold);
 int topk_reset(DevBuf<uint8_t>& d_topk, int k, int mode);
 int topk_select(eg_ctx* c, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state, int k);

@@ -493,8 +493,18 @@ constexpr size_t kRefineEntryStride = 128;
 constexpr int kRefineLog = 256;
 static_assert(sizeof(RefineEntry) <= kRefineEntryStride, "refine entry");
 int launch_refine_pick(const DevOut& o, uint32_t n, int mode, const void* d_edits, const uint8_t* d_pool, uint8_t* d_base, void* d_entry, void* stream);
+// k_plan_edits_many, k_refine_pick_many (eg_refine_many.h): a refinement round of several plans in ONE launch of n variants (eg_refine_plans).
+// d_bases: n_bases base blocks, one per plan of the call; d_slot[j]: the base block variant j is an edit of; d_segs: n_segs entries
+// {u32 first, count, slot, 0} (kRefineSegmentBytes each), segment s being the variants [first, first + count) of the plan whose base block
+// is `slot`; d_entries: a RefineEntry per segment, kRefineEntryStride bytes apart (winner relative to the segment).
+constexpr size_t kRefineSegmentBytes = 16;
+int launch_plan_edits_many(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_slot, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream);
+int launch_refine_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs, uint32_t n_total, int mode, const void* d_edits, const uint8_t* d_pool,
+                            uint8_t* d_bases, uint32_t n_bases, uint8_t* d_entries, void* stream);
 // eg_checkpoint.cpp: one plan as a set eg_plans_free releases (counts [26], the flat lists)
 eg_plan_set* make_plan_set(const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact, const char* name);
+// ... and n plans as one set: counts [n][26], the flat lists plan-major, names [n] (NULL entries: "")
+eg_plan_set* make_plan_set_n(int32_t n, const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact, const char* const* names);
 // k_topk_keys: rank score and key of every episode of the batch that can still enter the archive at d_state (else score -inf);
 // use_score_list: the statistics epilogue ran for this batch (mode 1 only: its scores are the rank scores)
 int launch_topk_keys(const DevOut& o, uint32_t n, uint64_t first_index, int mode, bool use_score_list, const uint8_t* d_state,

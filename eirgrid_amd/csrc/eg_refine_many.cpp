@@ -1,0 +1,246 @@
+// eg_refine_many.cpp — eg_refine_plans (include/eirgrid_hip.h): eg_refine_plan's loop for MANY plans at once.  Per round the still-active
+// plans' variants are packed into launches, a SEGMENT of consecutive variants per plan; k_plan_edits_many writes every variant's block from
+// its plan's base block, the plan batch runs over the whole launch, k_refine_pick_many picks a winner per segment and keeps that plan's
+// base block current (eg_refine_many.h).  The host follows every plan in a mirror, as eg_refine.cpp does for its one plan — that file
+// and its helpers stay as they are, so what the two loops have in common is written out here once more.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "eg_edit_order.h"
+#include "eg_host.h"
+
+using namespace eg;
+
+namespace {
+// a plan as the host follows it: the two lists, year by year
+struct Mirror {
+  std::vector<uint8_t> l[2][EG_YEARS];
+  int64_t total(int w) const { int64_t n = 0; for (int y = 0; y < EG_YEARS; ++y) n += int64_t(l[w][y].size()); return n; }
+  void counts(int32_t (&count)[2][EG_YEARS]) const {
+    for (int w = 0; w < 2; ++w)
+      for (int y = 0; y < EG_YEARS; ++y) count[w][y] = int32_t(l[w][y].size());
+  }
+};
+// variants of a round over lists of these totals (include/eirgrid_hip.h: none, deletes, replaces, appends)
+int64_t n_variants(int64_t len0, int64_t len1, const eg_refine_opts& o) {
+  return 1 + len0 + len1 + int64_t(o.n_replace) * len0 + (len0 < int64_t(snap::kBestCap) ? int64_t(EG_YEARS) * o.n_append : 0);
+}
+void apply(Mirror& m, const eg_plan_edit& e) {
+  std::vector<uint8_t>& l = m.l[e.list][e.year];
+  if (e.kind == EG_EDIT_DELETE) l.erase(l.begin() + e.pos);
+  else if (e.kind == EG_EDIT_REPLACE) l[e.pos] = e.action;
+  else if (e.kind == EG_EDIT_INSERT) l.insert(l.begin() + e.pos, e.action);
+}
+std::string too_many(int32_t plan, int round, int64_t n) {
+  return "plan " + std::to_string(plan) + ": round " + std::to_string(round) + " enumerates " + std::to_string(n) + " variants (at most " +
+         std::to_string(EG_REFINE_MAX_VARIANTS) + ")";
+}
+// EIRGRID_REFINE_LAUNCH_VARIANTS: the variants a launch may hold (a plan with more gets a launch to itself), read at every call
+uint32_t launch_variants() {
+  const char* v = std::getenv("EIRGRID_REFINE_LAUNCH_VARIANTS");
+  if (!v || !*v) return EG_REFINE_MAX_VARIANTS;
+  return uint32_t(std::min<long long>(std::max<long long>(std::atoll(v), 1), EG_REFINE_MAX_VARIANTS));
+}
+// one plan of a launch: its variants are [first, first + n) of the launch's
+struct Seg { int32_t plan; uint32_t first, n; std::vector<eg_plan_edit> edits; };
+}  // namespace
+
+extern "C" int32_t eg_refine_plans_validate(const eg_plan_set* bases, const eg_refine_opts* o) {
+  auto fail = [](const std::string& m) { set_error("eg_refine_plans_validate: " + m); return EG_ERR_BAD_ARG; };
+  EG_TRY(eg_plans_validate(bases));
+  if (bases->n_plans > EG_REFINE_MAX_PLANS) return fail("the set holds " + std::to_string(bases->n_plans) + " plans (at most " + std::to_string(EG_REFINE_MAX_PLANS) + ")");
+  if (!o) return fail("NULL options");
+  if (o->mode != 1 && o->mode != 2) return fail("mode " + std::to_string(o->mode) + " (1: optimization_mode None, 2: cost_only)");
+  if (o->max_rounds < 1) return fail("max_rounds = " + std::to_string(o->max_rounds) + " (at least 1)");
+  const char* name[2] = {"replace_with", "append_with"};
+  const int32_t count[2] = {o->n_replace, o->n_append};
+  const uint8_t* list[2] = {o->replace_with, o->append_with};
+  for (int k = 0; k < 2; ++k) {
+    const std::string n_name = k == 0 ? "n_replace" : "n_append";
+    if (count[k] < 0) return fail(n_name + " = " + std::to_string(count[k]));
+    if (count[k] > 0 && !list[k]) return fail(std::string("NULL ") + name[k] + " with " + n_name + " = " + std::to_string(count[k]));
+    for (int32_t i = 0; i < count[k]; ++i)
+      if (list[k][i] >= EG_N_ACTIONS) return fail(std::string(name[k]) + "[" + std::to_string(i) + "]: action " + std::to_string(int(list[k][i])) + " >= " + std::to_string(EG_N_ACTIONS));
+  }
+  for (int32_t p = 0; p < bases->n_plans; ++p) {
+    int64_t len[2] = {0, 0};
+    for (int y = 0; y < EG_YEARS; ++y) { len[0] += bases->best_count[size_t(p) * EG_YEARS + y]; len[1] += bases->best_deficit_count[size_t(p) * EG_YEARS + y]; }
+    const int64_t n = n_variants(len[0], len[1], *o);
+    if (n > EG_REFINE_MAX_VARIANTS) return fail(too_many(p, 0, n));
+  }
+  return EG_OK;
+}
+
+extern "C" int32_t eg_refine_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro, uint64_t seed,
+                                   uint64_t episode_index, eg_plan_set** refined, eg_refine_step* steps, int32_t* n_steps, int32_t* stop_reason,
+                                   double* start_score, eg_episode_out* out) {
+  if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plans: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->group_member) { set_error("eg_refine_plans: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_refine_plans_validate(bases, ro));
+  EG_TRY(check_policy(s, o, "eg_refine_plans"));
+  EG_HIP(hipSetDevice(c->device));
+  *refined = nullptr;
+  const int32_t P = bases->n_plans;
+  std::vector<Mirror> mirror((size_t(P)));
+  {
+    const int32_t* count[2] = {bases->best_count, bases->best_deficit_count};
+    const uint8_t* flat[2] = {bases->best_actions, bases->best_deficit_actions};
+    for (int w = 0; w < 2; ++w) {
+      int64_t at = 0;
+      for (int32_t p = 0; p < P; ++p)
+        for (int y = 0; y < EG_YEARS; ++y) {
+          const int32_t k = count[w][size_t(p) * EG_YEARS + y];
+          mirror[size_t(p)].l[w][y].assign(flat[w] + at, flat[w] + at + k); at += k;
+        }
+    }
+  }
+  // every buffer once, for the largest launch max_rounds steps can lead to: a plan's best_actions grows by an entry a step at most, and
+  // only by an append (a round beyond EG_REFINE_MAX_VARIANTS is refused when it is reached); a launch holds a plan larger than the
+  // launch size alone, else no more variants than the launch size
+  const uint32_t launch_max = launch_variants();
+  uint32_t n_cap = 0;
+  {
+    int64_t largest = 0, sum = 0;
+    for (int32_t p = 0; p < P; ++p) {
+      const int64_t len0 = mirror[size_t(p)].total(0), len1 = mirror[size_t(p)].total(1);
+      const int64_t grown = ro->n_append > 0 ? std::min<int64_t>(len0 + ro->max_rounds, int64_t(snap::kBestCap)) : len0;
+      const int64_t most = std::min<int64_t>(std::max(n_variants(len0, len1, *ro), 1 + grown + len1 + int64_t(ro->n_replace) * grown + int64_t(EG_YEARS) * ro->n_append),
+                                             EG_REFINE_MAX_VARIANTS);
+      largest = std::max(largest, most); sum += most;
+    }
+    n_cap = uint32_t(std::max(largest, std::min<int64_t>(sum, launch_max)));
+  }
+  const size_t segs_cap = std::min<size_t>(size_t(P), n_cap);
+  EG_TRY(ensure_outputs(c, n_cap));
+  EG_HIP(c->d_plans.reserve(size_t(n_cap) * snap::kPlanStride));
+  EG_HIP(c->d_plan_index.reserve(n_cap));
+  EG_HIP(c->d_refine_in.reserve(size_t(n_cap) * 12 + 16 + segs_cap * kRefineSegmentBytes));
+  EG_HIP(c->d_refine_log.reserve(size_t(kRefineLog) * kRefineEntryStride));
+  static_assert(EG_REFINE_MAX_PLANS <= kRefineLog, "a launch's entries fit the step log");
+  EG_HIP(c->d_refine_bases.reserve(size_t(P) * snap::kPlanStride));
+  {      // the base blocks go up once; from then on k_refine_pick_many keeps them current
+    std::vector<uint8_t> blocks(size_t(P) * snap::kPlanStride, 0);
+    int64_t pos = 0, dpos = 0;
+    for (int32_t p = 0; p < P; ++p) {
+      const int32_t* cnt = bases->best_count + size_t(p) * EG_YEARS;
+      const int32_t* dcnt = bases->best_deficit_count + size_t(p) * EG_YEARS;
+      write_lists(blocks.data() + size_t(p) * snap::kPlanStride, cnt, bases->best_actions + pos, dcnt, bases->best_deficit_actions + dpos);
+      pos += mirror[size_t(p)].total(0); dpos += mirror[size_t(p)].total(1);
+    }
+    EG_HIP(hipMemcpy(c->d_refine_bases, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
+  }
+  DevSnapshot S{};
+  EG_TRY(stage_eval_snapshot(c, s, o, &S));
+  std::vector<char> active(size_t(P), 1);
+  for (int32_t p = 0; p < P; ++p) { n_steps[p] = 0; stop_reason[p] = EG_REFINE_MAX_ROUNDS; if (start_score) start_score[p] = std::nan(""); }
+  std::vector<Seg> segs;
+  std::vector<uint8_t> in;
+  std::vector<uint32_t> local_idx, idx, longs;
+  std::vector<uint8_t> entries;
+  for (int round = 0;; ++round) {
+    // the round's variant counts, plan by plan
+    std::vector<std::pair<int32_t, uint32_t>> todo;      // (plan, variants), ascending
+    for (int32_t p = 0; p < P; ++p) {
+      if (!active[size_t(p)]) continue;
+      const int64_t want = n_variants(mirror[size_t(p)].total(0), mirror[size_t(p)].total(1), *ro);
+      if (want > EG_REFINE_MAX_VARIANTS) { set_error("eg_refine_plans: " + too_many(p, round, want)); return EG_ERR_BAD_ARG; }
+      todo.emplace_back(p, uint32_t(want));
+    }
+    if (todo.empty()) break;
+    for (size_t t0 = 0; t0 < todo.size();) {
+      // a launch: consecutive plans while they fit; a plan never straddles two launches
+      size_t t1 = t0 + 1;
+      uint32_t n = todo[t0].second;
+      while (t1 < todo.size() && n + todo[t1].second <= launch_max) n += todo[t1++].second;
+      const uint32_t n_segs = uint32_t(t1 - t0);
+      if (n > n_cap || n_segs > segs_cap) { set_error("eg_refine_plans: round " + std::to_string(round) + ": a launch of " + std::to_string(n) + " variants outgrew its buffers"); return EG_ERR_INTERNAL; }
+      // what goes up in one copy: the packed edits (8 bytes a variant), every variant's base slot, the segment table; and the routing —
+      // the short variants of the whole launch first, then the long ones (launch_plans)
+      const size_t at_slot = size_t(n) * 8, at_segs = (size_t(n) * 12 + 15) / 16 * 16;
+      in.assign(at_segs + size_t(n_segs) * kRefineSegmentBytes, 0);
+      uint32_t* packed = reinterpret_cast<uint32_t*>(in.data());
+      uint32_t* slot = reinterpret_cast<uint32_t*>(in.data() + at_slot);
+      uint32_t* table = reinterpret_cast<uint32_t*>(in.data() + at_segs);
+      segs.resize(n_segs); idx.clear(); longs.clear();
+      uint32_t first = 0;
+      for (uint32_t k = 0; k < n_segs; ++k) {
+        Seg& sg = segs[k];
+        sg.plan = todo[t0 + k].first; sg.first = first; sg.n = todo[t0 + k].second;
+        const Mirror& m = mirror[size_t(sg.plan)];
+        int32_t count[2][EG_YEARS];
+        m.counts(count);
+        enumerate_edits(count[0], count[1], ro->replace_with, ro->n_replace, ro->append_with, ro->n_append, m.total(0) < int64_t(snap::kBestCap), sg.edits);
+        if (sg.edits.size() != size_t(sg.n)) { set_error("eg_refine_plans: plan " + std::to_string(sg.plan) + ": round " + std::to_string(round) + ": the enumeration and its count disagree"); return EG_ERR_INTERNAL; }
+        local_idx.resize(sg.n);
+        uint32_t n_short = 0;
+        pack_plan_edits(sg.edits.data(), sg.n, m.total(0), packed + 2 * size_t(first), local_idx.data(), &n_short);
+        for (uint32_t j = 0; j < sg.n; ++j) (j < n_short ? idx : longs).push_back(first + local_idx[j]);
+        std::fill(slot + first, slot + first + sg.n, uint32_t(sg.plan));
+        table[4 * k] = first; table[4 * k + 1] = sg.n; table[4 * k + 2] = uint32_t(sg.plan);
+        first += sg.n;
+      }
+      const uint32_t n_short = uint32_t(idx.size());
+      idx.insert(idx.end(), longs.begin(), longs.end());
+      EG_HIP(hipMemcpy(c->d_refine_in, in.data(), in.size(), hipMemcpyHostToDevice));
+      EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+      const uint8_t* d_edits = c->d_refine_in;
+      EG_LAUNCH("k_plan_edits_many", launch_plan_edits_many(c->d_refine_bases, uint32_t(P), reinterpret_cast<const uint32_t*>(c->d_refine_in + at_slot), d_edits, n, c->d_plans, nullptr));
+      c->n_plan_blocks = n;
+      EG_TRY(launch_plans(c, S, seed, episode_index, n, n_short, true));
+      EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + at_segs, n_segs, n, ro->mode, d_edits, c->d_plans, c->d_refine_bases, uint32_t(P),
+                                                              c->d_refine_log, nullptr));
+      entries.resize(size_t(n_segs) * kRefineEntryStride);
+      EG_HIP(hipMemcpy(entries.data(), c->d_refine_log, entries.size(), hipMemcpyDeviceToHost));      // (waits for the launch)
+      for (uint32_t k = 0; k < n_segs; ++k) {
+        const Seg& sg = segs[k];
+        const int32_t p = sg.plan;
+        const std::string who = "eg_refine_plans: plan " + std::to_string(p) + ": round " + std::to_string(round) + ": ";
+        Mirror& m = mirror[size_t(p)];
+        RefineEntry e{};
+        std::memcpy(&e, entries.data() + size_t(k) * kRefineEntryStride, sizeof(e));
+        if (round == 0 && start_score && e.base_ok) start_score[p] = e.base_score;
+        if (!e.base_ok) { stop_reason[p] = EG_REFINE_BASE_FAILED; active[size_t(p)] = 0; continue; }
+        const uint32_t* mine = packed + 2 * size_t(sg.first);
+        if (e.n != int32_t(sg.n) || e.winner < 0 || e.winner >= int32_t(sg.n) || e.edit[0] != mine[2 * size_t(e.winner)] || e.edit[1] != mine[2 * size_t(e.winner) + 1]) {
+          set_error(who + "the device's step entry does not name a variant of the plan's round");
+          return EG_ERR_INTERNAL;
+        }
+        // the plan on the device against the mirror: the totals of the winner's block
+        if (e.winner != 0) apply(m, sg.edits[size_t(e.winner)]);
+        if (e.off26 != int32_t(m.total(0)) || e.offd26 != int32_t(m.total(1))) {
+          set_error(who + "the device's plan holds " + std::to_string(e.off26) + " + " + std::to_string(e.offd26) + " entries, the host's " +
+                    std::to_string(m.total(0)) + " + " + std::to_string(m.total(1)));
+          return EG_ERR_INTERNAL;
+        }
+        if (e.winner == 0) { stop_reason[p] = EG_REFINE_LOCAL_OPTIMUM; active[size_t(p)] = 0; }
+        else {
+          eg_refine_step& st = steps[size_t(p) * size_t(ro->max_rounds) + size_t(n_steps[p])];
+          st.edit = sg.edits[size_t(e.winner)]; st.variant = e.winner; st.n_variants = int32_t(sg.n); st.n_failed = e.n_failed; st.score = e.score;
+          std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
+          if (++n_steps[p] == ro->max_rounds) { stop_reason[p] = EG_REFINE_MAX_ROUNDS; active[size_t(p)] = 0; }
+        }
+        if (!active[size_t(p)] && out) {      // the refined plan's record, before the next launch overwrites the records
+          eg_episode_out row = out_row(out, size_t(p));
+          EG_TRY(fetch_records(c->out.base + (size_t(sg.first) + size_t(e.winner)) * rec::stride, 1, &row));
+          if (row.status && row.status[0] == EG_EP_INTERNAL) { set_error(who + "k_rollout: helper-wave protocol timed out in the refined plan's episode (EG_EP_INTERNAL)"); return EG_ERR_INTERNAL; }
+        }
+      }
+      t0 = t1;
+    }
+  }
+  {
+    std::vector<int32_t> count[2];
+    std::vector<uint8_t> flat[2];
+    for (int w = 0; w < 2; ++w)
+      for (int32_t p = 0; p < P; ++p)
+        for (int y = 0; y < EG_YEARS; ++y) {
+          const std::vector<uint8_t>& l = mirror[size_t(p)].l[w][y];
+          count[w].push_back(int32_t(l.size())); flat[w].insert(flat[w].end(), l.begin(), l.end());
+        }
+    flat[0].reserve(1); flat[1].reserve(1);
+    *refined = make_plan_set_n(P, count[0].data(), flat[0].data(), count[1].data(), flat[1].data(), bases->names);
+  }
+  return EG_OK;
+}

@@ -1,0 +1,160 @@
+// eg_refine_many.h — k_plan_edits_many and k_refine_pick_many: a refinement round of MANY plans in one launch (include/eirgrid_hip.h
+// eg_refine_plans; the host loop is eg_refine_many.cpp).  Included by eg_rollout.hip (eg_rollout.o only) behind eg_refine.h.
+//
+// A launch holds the variants of several plans back to back: SEGMENT s is the variants [first_s, first_s + n_s) of one plan, whose base
+// block is block slot_s of a buffer of base blocks (one per plan of the call, uploaded once).  Both kernels are the one-plan kernels
+// (eg_plan_edits.h k_plan_edits, eg_refine.h k_refine_pick) with that indirection, and share nothing with them but __forceinline__
+// helpers: the one-plan kernels' code is not to change with this file.
+//   k_plan_edits_many   variant j's block from base block slot[j] and edit j: byte for byte what write_lists builds for the edited plan
+//                       in a zeroed block; one wave per variant, 8-byte words, every store of a wave 512 consecutive bytes; no LDS, no
+//                       scratch memory; writes inside block j only.
+//   k_refine_pick_many  one workgroup per segment, on the null stream behind the launch's rollout grids.  Workgroup s reduces ITS
+//                       variants exactly as k_refine_pick reduces [0, n): candidates have status EG_EP_OK and a rank score that is not
+//                       NaN, the largest score wins, ties to the lowest variant, the segment's first variant is its base.  It reads no
+//                       record outside its segment, counts its own non-candidates, writes entry s of the launch's entries (`winner`
+//                       relative to the segment; edit and list totals the winner's) and, when the winner is not the segment's variant 0,
+//                       copies the winner's block over base block slot_s.
+// Every index read from memory or computed from one is clamped.
+// The two kernels live in a namespace of their own, `many`: scripts/kernel_resources.sh prints a kernel by what is left of its mangled
+// name, and the tests that pin the one-plan kernels' resource lines pick those by the word k_plan_edits / k_refine_pick at the start of
+// that name.  Behind a namespace the new names print as many17k_plan_edits_many / many18k_refine_pick_many, which such a pattern does not
+// take for the one-plan kernels (tests/test_refine_many_resources.py looks for the full names).
+#pragma once
+
+namespace refine {
+
+// what the host uploads per segment of a launch
+struct Segment { uint32_t first, count, slot, pad; };
+static_assert(sizeof(Segment) == 16, "segment table entry");
+
+}  // namespace refine
+
+namespace many {
+
+// four variants per workgroup of 256, one wave each
+__global__ void __launch_bounds__(256) k_plan_edits_many(const uint8_t* __restrict__ bases, uint32_t n_bases, const uint32_t* __restrict__ slot,
+                                                         const uint2* __restrict__ edits, uint32_t n, uint8_t* __restrict__ pool) {
+  using namespace pedit;
+  const int lane = threadIdx.x & (kWave - 1);
+  const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (j >= n || n_bases == 0u) return;
+  const uint32_t sl = slot[j];
+  const uint8_t* base = bases + (size_t)(sl < n_bases ? sl : n_bases - 1u) * snap::kPlanStride;
+  const Edit e = unpack(edits[j]);
+  uint8_t* blk = pool + (size_t)j * snap::kPlanStride;
+  const int32_t* off = reinterpret_cast<const int32_t*>(base + kOffOff);
+  const int32_t* doff = reinterpret_cast<const int32_t*>(base + kOffDOff);
+  const uint8_t* act = base + kOffAct;
+  const uint8_t* dact = base + kOffDAct;
+  // the edit point in the flat list, and what the edit does to the length of the list
+  int P = (e.list ? doff : off)[e.year] + e.pos;
+  P = P < 0 ? 0 : (P > (int)snap::kBestCap - 1 ? (int)snap::kBestCap - 1 : P);
+  const int delta = e.kind == kInsert ? 1 : (e.kind == kDelete ? -1 : 0);
+  const int k0 = e.list == 0 ? e.kind : kNone, k1 = e.list == 1 ? e.kind : kNone;
+  write_list(reinterpret_cast<unsigned long long*>(blk + kOffAct), reinterpret_cast<const unsigned long long*>(act), lane, k0, P, e.action);
+  write_list(reinterpret_cast<unsigned long long*>(blk + kOffDAct), reinterpret_cast<const unsigned long long*>(dact), lane, k1, P, e.action);
+  // prefix offsets: lanes 0..27 the first list's, 32..59 the second's (entry 27 is padding)
+  {
+    const int l = lane & 31, which = lane >> 5;
+    if (l < 28) {
+      int v = (which ? doff : off)[l];
+      if (which == e.list && l > e.year && l <= EG_YEARS) v += delta;
+      reinterpret_cast<int32_t*>(blk + (which ? kOffDOff : kOffOff))[l] = v;
+    }
+  }
+  // masks: the edited year's from its two lists as edited, the others copied
+  unsigned long long m = 0ull, dm = 0ull;
+  if (e.kind != kNone) {
+    int a0 = off[e.year], d0 = doff[e.year];
+    const int a1 = off[e.year + 1] + (e.list == 0 ? delta : 0), d1 = doff[e.year + 1] + (e.list == 1 ? delta : 0);
+    a0 = a0 < 0 ? 0 : a0; d0 = d0 < 0 ? 0 : d0;
+    for (int i = a0 + lane; i < a1 && i < (int)snap::kBestCap; i += kWave) {
+      const int a = edited_entry(act, i, k0, P, e.action);
+      if (a < 64) m |= 1ull << a;
+    }
+    for (int i = d0 + lane; i < d1 && i < (int)snap::kBestCap; i += kWave) {
+      const int a = edited_entry(dact, i, k1, P, e.action);
+      if (a < 64) dm |= 1ull << a;
+    }
+    m = wave_or_u64(m | dm); dm = wave_or_u64(dm);
+  }
+  if (lane < EG_YEARS) {
+    const unsigned long long* bm = reinterpret_cast<const unsigned long long*>(base + kOffMask);
+    const unsigned long long* bdm = reinterpret_cast<const unsigned long long*>(base + kOffDMask);
+    const bool mine = e.kind != kNone && lane == e.year;
+    reinterpret_cast<unsigned long long*>(blk + kOffMask)[lane] = mine ? m : bm[lane];
+    reinterpret_cast<unsigned long long*>(blk + kOffDMask)[lane] = mine ? dm : bdm[lane];
+  }
+}
+
+// workgroup s: segment s of the launch's n_total variants
+__global__ void __launch_bounds__(1024) k_refine_pick_many(DevOut O, const refine::Segment* __restrict__ segs, uint32_t n_total, int mode,
+                                                           const uint2* __restrict__ edits, const uint8_t* __restrict__ pool, uint8_t* __restrict__ bases,
+                                                           uint32_t n_bases, uint8_t* __restrict__ entries) {
+  using namespace refine;
+  __shared__ double s_score[kWaves];
+  __shared__ int s_index[kWaves], s_fail[kWaves];
+  __shared__ int s_base_ok;
+  const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+  const Segment sg = segs[blockIdx.x];
+  RefineEntry* entry = reinterpret_cast<RefineEntry*>(entries + (size_t)blockIdx.x * kRefineEntryStride);
+  // the segment inside the launch (uniform in the workgroup)
+  const uint32_t first = sg.first < n_total ? sg.first : n_total;
+  const uint32_t n = sg.count < n_total - first ? sg.count : n_total - first;
+  if (n == 0u || n_bases == 0u) {      // (no host launch describes one: an entry that says so, nothing copied)
+    if (tid == 0) { entry->winner = -1; entry->n_failed = 0; entry->base_ok = 0; entry->n = 0; }
+    return;
+  }
+  uint8_t* base = bases + (size_t)(sg.slot < n_bases ? sg.slot : n_bases - 1u) * snap::kPlanStride;
+  double best = -__builtin_huge_val();
+  int best_j = kNoIndex, fails = 0;      // (variant indices relative to the segment)
+  for (uint32_t j0 = 0; j0 < n; j0 += (uint32_t)kThreads) {      // (uniform: the ballot below wants every lane)
+    const uint32_t j = j0 + (uint32_t)tid;
+    bool cand = false;
+    double s = 0.0;
+    if (j < n) {
+      const double* m = O.metrics(first + j);
+      const double mm[4] = {m[0], m[1], m[2], m[3]};
+      s = rm::rank_score(mm, mode);
+      cand = *O.status(first + j) == EG_EP_OK && s == s;
+      if (j == 0u) {      // what the segment's base scores
+        s_base_ok = cand ? 1 : 0;
+        entry->base_ok = cand ? 1 : 0; entry->base_score = s;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) entry->base_metrics[k] = mm[k];
+      }
+    }
+    fails += __popcll(__ballot(j < n && !cand));
+    if (cand && before(s, (int)j, best, best_j)) { best = s; best_j = (int)j; }
+  }
+  wave_best(best, best_j);
+  if (lane == 0) { s_score[wave] = best; s_index[wave] = best_j; s_fail[wave] = fails; }
+  __syncthreads();
+  best = -__builtin_huge_val(); best_j = kNoIndex; fails = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    const double s = s_score[w];
+    const int j = s_index[w];
+    if (before(s, j, best, best_j)) { best = s; best_j = j; }
+    fails += s_fail[w];
+  }
+  const bool base_ok = s_base_ok != 0;
+  const int winner = base_ok ? (best_j < 0 ? 0 : (best_j >= (int)n ? (int)n - 1 : best_j)) : -1;
+  const uint32_t w = first + (winner < 0 ? 0u : (uint32_t)winner);      // the winner among the launch's variants
+  const uint8_t* blk = pool + (size_t)w * snap::kPlanStride;
+  if (tid == 0) {
+    const uint2 e = edits[w];
+    const double* m = O.metrics(w);
+    entry->winner = winner; entry->n_failed = fails;
+    entry->edit[0] = e.x; entry->edit[1] = e.y;
+    entry->score = base_ok ? best : 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) entry->metrics[k] = m[k];
+    entry->off26 = reinterpret_cast<const int32_t*>(blk + pedit::kOffOff)[EG_YEARS];
+    entry->offd26 = reinterpret_cast<const int32_t*>(blk + pedit::kOffDOff)[EG_YEARS];
+    entry->n = (int32_t)n;
+  }
+  if (winner > 0 && tid < (int)(snap::kPlanStride / 16)) reinterpret_cast<uint4*>(base)[tid] = reinterpret_cast<const uint4*>(blk)[tid];
+}
+
+}  // namespace many

@@ -590,6 +590,40 @@ class Engine:
         reason = REFINE_STOP[stop.value]
         return plan, rows, reason, start.value, (None if reason == "base_failed" else res)
 
+    def refine_plans(self, weights: ActionWeights, bases, seed: int, index: int = 0, mode: int = 1, max_rounds: int = 64, replace_with=None,
+                     append_with=None, enable_energy_sales=True, write_yearly=True):
+        """Greedy refinement of many plans in one call (eg_refine_plans): the rounds of all plans stepped together, a launch holding the
+        variants of as many plans as fit.  Returns a list with one tuple per plan of `bases` (1..REFINE_MAX_PLANS plans), each exactly the
+        tuple refine_plan returns for that plan alone."""
+        ps = bases if isinstance(bases, PlanSet) else PlanSet(bases)
+        n = ps.s.n_plans
+        ro, keep = _refine_opts(mode, max_rounds, replace_with, append_with)
+        rounds = max(int(max_rounds), 1)
+        steps = (N.EgRefineStep * (max(n, 1) * rounds))()
+        n_steps = np.zeros(max(n, 1), np.int32); stop = np.zeros(max(n, 1), np.int32)
+        start = np.full(max(n, 1), np.nan)
+        refined = C.POINTER(N.EgPlanSet)()
+        res = BatchResult.alloc(max(n, 1))
+        snap = weights.snapshot()
+        opts = self._opts(enable_energy_sales, False, write_yearly)
+        out = res.struct()
+        L = N.lib()
+        N.check(L.eg_refine_plans(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(ro), C.c_uint64(seed & (2**64 - 1)), C.c_uint64(index),
+                                  C.byref(refined), steps, _p(n_steps, C.c_int32), _p(stop, C.c_int32), _p(start, C.c_double), C.byref(out)), "eg_refine_plans")
+        try:
+            plans = Plan._from_set(refined.contents)
+        finally:
+            L.eg_plans_free(refined)
+        names = [f.name for f in fields(BatchResult)]
+        result = []
+        for p in range(n):
+            rows = [RefineStep(PlanEdit(PlanEdit.KINDS[s.edit.kind], s.edit.list, s.edit.year, s.edit.pos, s.edit.action), s.variant, s.n_variants, s.n_failed,
+                               s.score, np.array(s.metrics[:])) for s in steps[p * rounds:p * rounds + int(n_steps[p])]]
+            reason = REFINE_STOP[int(stop[p])]
+            rec = None if reason == "base_failed" else BatchResult(*[np.ascontiguousarray(getattr(res, f)[p:p + 1]) for f in names])
+            result.append((plans[p], rows, reason, float(start[p]), rec))
+        return result
+
     # device-resident path used by bench.py
     def upload_snapshot(self, weights: ActionWeights, enable_energy_sales=True, write_yearly=True):
         snap = weights.snapshot()
@@ -812,6 +846,17 @@ class Engine:
         base = np.zeros(N.PLAN_BLOCK_BYTES, np.uint8)
         N.check(N.lib().eg_debug_refine_pick(self.h, int(mode), C.byref(entry), _p(base, C.c_uint8)), "eg_debug_refine_pick")
         return entry, base
+
+    def _debug_refine_pick_many(self, seg_first, seg_count, mode: int = 1):
+        """Test hook (eg_debug_refine_pick_many): (the step entries, one per segment; the base blocks [n_segs, PLAN_BLOCK_BYTES] as the kernel
+        left them) over the last batch cut into the given segments."""
+        first = np.ascontiguousarray(seg_first, np.uint32); count = np.ascontiguousarray(seg_count, np.uint32)
+        assert first.shape == count.shape and first.ndim == 1
+        entries = (N.EgDebugRefineEntry * max(len(first), 1))()
+        base = np.zeros((max(len(first), 1), N.PLAN_BLOCK_BYTES), np.uint8)
+        N.check(N.lib().eg_debug_refine_pick_many(self.h, int(mode), _p(first, C.c_uint32), _p(count, C.c_uint32), len(first), entries, _p(base, C.c_uint8)),
+                "eg_debug_refine_pick_many")
+        return list(entries), base
 
     def fetch_scores(self, n_episodes: int) -> np.ndarray:
         s = np.zeros(n_episodes)

@@ -422,6 +422,45 @@ int32_t eg_refine_plan(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, co
                        eg_plan_set **refined /* eg_plans_free */, eg_refine_step *steps /* max_rounds */,
                        int32_t *n_steps, int32_t *stop_reason, double *start_score, eg_episode_out *out /* 1 episode or NULL */);
 
+/* Many plans refined in one call: eg_refine_plans(ctx, policy, opts, bases, refine_opts, seed, episode_index, ...) takes a set of 1 ..
+ * EG_REFINE_MAX_PLANS base plans (a whole Pareto front, the scenarios of --top-k) and refines every one of them as eg_refine_plan would.
+ * For every plan p the following are EXACTLY what eg_refine_plan returns for a base set holding plan p alone, with the same policy, options,
+ * refine_opts, seed and episode_index:
+ *   *refined          plan p of the returned set (n_plans plans in the bases' order, their names kept; free with eg_plans_free)
+ *   steps             row p of steps[n_plans][max_rounds], entries 0 .. n_steps[p]: every field — `variant`, `n_variants` and `n_failed`
+ *                     count within the plan's own round, score and metrics bit for bit
+ *   n_steps[p], stop_reason[p], start_score[p] (start_score may be NULL)
+ *   out               row p of `out` (n_plans episodes, may be NULL): the refined plan's record — variant 0 of the plan's last round on
+ *                     LOCAL_OPTIMUM, the last winner on MAX_ROUNDS; a row is NOT written when its plan stops with BASE_FAILED
+ * (Of a record, n_chunks excepted: it counts what the search that really ran requested, and a launch of many plans' variants may run
+ * the throughput kernels where a plan's own round would run the small-batch kernel.)
+ * Plans are independent: they stop in different rounds and for different reasons, and a stopped plan takes no further part.  What makes
+ * the call worth having is that the rounds are stepped TOGETHER: per round the still-active plans, in ascending order, are packed into
+ * launches of at most EG_REFINE_MAX_VARIANTS variants, a SEGMENT of consecutive variants per plan (a plan never straddles two launches);
+ * csrc/eg_refine_many.h k_plan_edits_many writes every variant's block from its plan's base block, the plan batch runs over the whole
+ * launch with same_index = 1 — a variant's result does not depend on what else is in its launch —, and k_refine_pick_many picks a winner
+ * per segment and makes its block that plan's next base.  Per launch the host uploads 16 bytes per variant and 16 per segment and reads
+ * one entry of at most 128 bytes per segment back, in ONE copy: the launch's only synchronisation.  The base blocks of all plans go up
+ * once.  The result does not depend on how the library packs plans into launches.  The environment variable
+ * EIRGRID_REFINE_LAUNCH_VARIANTS (read at every call, clamped to 1..16 384) lowers the variants a launch may hold — a plan with more gets
+ * a launch to itself —, for tests that want many launches per round at small sizes.
+ * A later round of some plan that would enumerate more than EG_REFINE_MAX_VARIANTS variants fails the WHOLE call with EG_ERR_BAD_ARG, the
+ * message naming the plan and the round; nothing is returned then.
+ * Everything else is eg_refine_plan's contract: no statistics, update or folds, the resident policy untouched, a rank of a group refused,
+ * the policy checked, staged and uploaded once per call; what stays behind as the last batch for eg_fetch / eg_fetch_record is the LAST
+ * launch's variants.
+ * eg_refine_plans_validate runs the checks alone and names the plan in every message about one ("plan 3: round 0 enumerates ..."): a
+ * valid set (eg_plans_validate) of 1..EG_REFINE_MAX_PLANS plans; the option checks of eg_refine_validate; per plan, the variant count of
+ * round 0. */
+#define EG_REFINE_MAX_PLANS 256          /* = EG_PARETO_MAX: a whole front fits */
+int32_t eg_refine_plans_validate(const eg_plan_set *bases, const eg_refine_opts *);
+int32_t eg_refine_plans(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, const eg_plan_set *bases /* 1..EG_REFINE_MAX_PLANS */,
+                        const eg_refine_opts *, uint64_t seed, uint64_t episode_index,
+                        eg_plan_set **refined      /* n_plans plans in the bases' order, names kept; eg_plans_free */,
+                        eg_refine_step *steps      /* [n_plans][max_rounds], row p = plan p */,
+                        int32_t *n_steps           /* [n_plans] */, int32_t *stop_reason /* [n_plans] */,
+                        double *start_score        /* [n_plans] or NULL */, eg_episode_out *out /* n_plans episodes or NULL */);
+
 /* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
  * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
  * copies, no collective library — and every call enqueues the work of all ranks from the calling thread without synchronising
@@ -466,7 +505,7 @@ int32_t eg_group_fetch_top_k(eg_group *, eg_episode_out *out, int32_t *n_held, d
 int32_t eg_debug_fill_lds(eg_ctx *, uint32_t value);
 /* Test hooks: a crafted batch, and the reductions that decide what a run keeps over it — ties, staircases, NaN and infinities, key
  * edges, maxima on wave and stride boundaries: what real episodes never produce.  Host code only; every kernel is the one a run launches.
- * All four refuse a rank of a group.
+ * All of them refuse a rank of a group.
  *   eg_debug_load_batch   makes the context's record buffer a batch of n synthetic records — sized as a launch of n would size it;
  *                         eg_last_batch_size() = n, global indices first_index + e.  Record e is zero except: metrics[e], status[e];
  *                         n_draws = g = first_index + e as a tag; n_run[0] = n_def[0] = EG_DEBUG_LIST_LEN with run_log[0..8) the bytes of g
@@ -486,7 +525,12 @@ int32_t eg_debug_fill_lds(eg_ctx *, uint32_t value);
  *                         j mod 4097 and (j / 3) mod 4097; the base block is the words 0xBA5E0000 + w with totals 7 and 5; edit j is
  *                         (j, ~j).  `entry` receives the step entry (EG_DEBUG_REFINE_ENTRY_BYTES: i32 winner, n_failed | u32 edit[2] |
  *                         f64 score, metrics[4] | i32 off26, offd26, base_ok, n | f64 base_score, base_metrics[4]), `base_block` the base
- *                         block as the kernel left it. */
+ *                         block as the kernel left it.
+ *   eg_debug_refine_pick_many  k_refine_pick_many over the last batch cut into n_segs segments (1..EG_REFINE_MAX_PLANS; segment s is the
+ *                         records [seg_first[s], + seg_count[s]); the segments must tile [0, n) in order): plan block j, the packed
+ *                         edits (j, ~j) and the list totals as for eg_debug_refine_pick; base block s is the words 0xBA5E0000 + (s << 8)
+ *                         + w with totals 7 and 5.  `entries` receives n_segs step entries of EG_DEBUG_REFINE_ENTRY_BYTES (`winner`
+ *                         relative to the segment), `base_blocks` the n_segs base blocks as the kernel left them. */
 #define EG_DEBUG_LIST_LEN 8
 #define EG_DEBUG_FOLD_BEST_RESULT 1
 #define EG_DEBUG_FOLD_TOP_K 2
@@ -497,6 +541,8 @@ int32_t eg_debug_load_batch(eg_ctx *, const double *metrics /* [n][4] */, const 
 int32_t eg_debug_fold_last_batch(eg_ctx *, int32_t what, int32_t use_score_list);
 int32_t eg_debug_pick_best(eg_ctx *, void *candidate /* EG_CANDIDATE_BYTES */);
 int32_t eg_debug_refine_pick(eg_ctx *, int32_t mode /* 1 | 2 */, void *entry /* EG_DEBUG_REFINE_ENTRY_BYTES */, uint8_t *base_block /* EG_PLAN_BLOCK_BYTES */);
+int32_t eg_debug_refine_pick_many(eg_ctx *, int32_t mode, const uint32_t *seg_first, const uint32_t *seg_count, int32_t n_segs,
+                                  void *entries /* n_segs * EG_DEBUG_REFINE_ENTRY_BYTES */, uint8_t *base_blocks /* n_segs * EG_PLAN_BLOCK_BYTES */);
 /* Diagnostic hook: ONE idle workgroup of 256 threads on the library's side stream that stays resident for `cycles` shader cycles;
  * variant 0: 1 KB of LDS, few registers; 1: 150 KB of LDS; 2: 200+ registers a lane; 3: both (the hoisted replay's footprint).  What a
  * resident workgroup costs the grid beside it: scripts/side_kernel_probe.py, profiles/r04_ab_notes.log. */

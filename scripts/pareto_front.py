@@ -7,7 +7,8 @@ Runs the device-resident training loop (Engine.device_step, every 10th episode a
 the Pareto archive on (include/eirgrid_hip.h eg_pareto_track) and writes
     DIR/pareto/index.csv      global index, the four metrics and the rank score of every entry, in ascending global index, as %.17g
     DIR/pareto/plans.jsonl    every entry's run_log / def_log per year as a plan (eg_plans_save) named by its global index: the lists
-                              update_best_strategy would install, so `eirgrid-hip --evaluate` and `--refine` read them back
+                              update_best_strategy would install, so `eirgrid-hip --evaluate` and scripts/refine_front.py read them back
+                              (`--refine` takes a file with ONE plan)
 --world takes a world as World.to_json_dict writes it, or the word `synthetic`."""
 import argparse
 import json
