@@ -1,6 +1,6 @@
 // eg_debug.cpp — the crafted-batch test hooks (include/eirgrid_hip.h, debug section): a batch of synthetic records in the context's
 // record buffer, and the reductions that decide what a run keeps run over it — the folds launch_batch runs behind a real batch (through the
-// helpers it calls), k_pick_best, k_refine_pick, k_refine_pick_many.  Host code only: no kernel is launched here that a run does not launch.
+// helpers it calls), k_pick_best, k_refine_pick_many.  Host code only: no kernel is launched here that a run does not launch.
 #include <cstring>
 
 #include "eg_host.h"
@@ -16,6 +16,46 @@ int refuse_rank(const eg_ctx* c, const char* who) {
 // one field of the n records from a host array of `width` bytes per record
 int put_field(eg_ctx* c, size_t field, const void* src, size_t width, uint32_t n) {
   EG_HIP(hipMemcpy2D(c->out.base + field, rec::stride, src, width, width, n, hipMemcpyHostToDevice));
+  return EG_OK;
+}
+// k_refine_pick_many over the last batch, cut into n_segs segments that tile it (checked by the callers): tagged plan blocks, edits and
+// base blocks as include/eirgrid_hip.h documents them, segment s on base slot s; the entries and the base blocks as the kernel left them
+int refine_pick(eg_ctx* c, int32_t mode, const uint32_t* seg_first, const uint32_t* seg_count, int32_t n_segs, void* entries, uint8_t* base_blocks) {
+  static_assert(sizeof(RefineEntry) == EG_DEBUG_REFINE_ENTRY_BYTES, "the step entry's layout is what the hooks document");
+  static_assert(EG_PLAN_BLOCK_BYTES == snap::kPlanStride, "plan block");
+  const uint32_t n = c->last_n;
+  EG_HIP(hipSetDevice(c->device));
+  constexpr size_t kWords = snap::kPlanStride / 4, kOff26 = (snap::best_off - snap::best_mask) / 4 + EG_YEARS, kOffD26 = (snap::bestd_off - snap::best_mask) / 4 + EG_YEARS;
+  static_assert(kOff26 == 130 && kOffD26 == 158, "the words of the list totals as the hooks document them");
+  const size_t S = size_t(n_segs);
+  std::vector<uint32_t> blocks(size_t(n) * kWords), base(S * kWords), in(size_t(n) * 2 + S * 4);      // in: the packed edits, then the segment table
+  for (uint32_t j = 0; j < n; ++j) {
+    uint32_t* b = blocks.data() + size_t(j) * kWords;
+    for (size_t w = 0; w < kWords; ++w) b[w] = j * 0x9E3779B1u + uint32_t(w);
+    b[kOff26] = j % (uint32_t(snap::kBestCap) + 1u); b[kOffD26] = (j / 3u) % (uint32_t(snap::kBestCap) + 1u);
+    in[2 * size_t(j)] = j; in[2 * size_t(j) + 1] = ~j;
+  }
+  for (size_t s = 0; s < S; ++s) {
+    uint32_t* b = base.data() + s * kWords;
+    for (size_t w = 0; w < kWords; ++w) b[w] = 0xBA5E0000u + (uint32_t(s) << 8) + uint32_t(w);
+    b[kOff26] = 7u; b[kOffD26] = 5u;
+    uint32_t* t = in.data() + size_t(n) * 2 + s * 4;
+    t[0] = seg_first[s]; t[1] = seg_count[s]; t[2] = uint32_t(s); t[3] = 0u;
+  }
+  static_assert(kRefineSegmentBytes == 16, "segment table entry");
+  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
+  EG_HIP(c->d_refine_bases.reserve(S * snap::kPlanStride));
+  EG_HIP(c->d_refine_in.reserve(in.size() * 4));
+  EG_HIP(c->d_refine_log.reserve(size_t(kRefineLog) * kRefineEntryStride));
+  EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy(c->d_refine_bases, base.data(), base.size() * 4, hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy(c->d_refine_in, in.data(), in.size() * 4, hipMemcpyHostToDevice));
+  EG_HIP(hipMemsetAsync(c->d_refine_log, 0, S * kRefineEntryStride, nullptr));
+  c->n_plan_blocks = n;
+  EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + size_t(n) * 8, uint32_t(n_segs), n, mode, c->d_refine_in, c->d_plans, c->d_refine_bases,
+                                                          uint32_t(n_segs), c->d_refine_log, nullptr));
+  EG_HIP(hipMemcpy2D(entries, sizeof(RefineEntry), c->d_refine_log, kRefineEntryStride, sizeof(RefineEntry), S, hipMemcpyDeviceToHost));
+  EG_HIP(hipMemcpy(base_blocks, c->d_refine_bases, S * snap::kPlanStride, hipMemcpyDeviceToHost));
   return EG_OK;
 }
 }  // namespace
@@ -85,35 +125,11 @@ int32_t eg_debug_pick_best(eg_ctx* c, void* candidate) {
 }
 
 int32_t eg_debug_refine_pick(eg_ctx* c, int32_t mode, void* entry, uint8_t* base_block) {
-  static_assert(sizeof(RefineEntry) == EG_DEBUG_REFINE_ENTRY_BYTES, "the step entry's layout is what the hook documents");
-  static_assert(EG_PLAN_BLOCK_BYTES == snap::kPlanStride, "plan block");
   if (!c || !entry || !base_block || (mode != 1 && mode != 2)) { set_error("eg_debug_refine_pick: bad argument"); return EG_ERR_BAD_ARG; }
   EG_TRY(refuse_rank(c, "eg_debug_refine_pick"));
-  const uint32_t n = c->last_n;
+  const uint32_t first = 0, n = c->last_n;
   if (n == 0 || n > EG_REFINE_MAX_VARIANTS) { set_error("eg_debug_refine_pick: the last batch holds " + std::to_string(n) + " records (1..EG_REFINE_MAX_VARIANTS)"); return EG_ERR_BAD_ARG; }
-  EG_HIP(hipSetDevice(c->device));
-  constexpr size_t kWords = snap::kPlanStride / 4, kOff26 = (snap::best_off - snap::best_mask) / 4 + EG_YEARS, kOffD26 = (snap::bestd_off - snap::best_mask) / 4 + EG_YEARS;
-  static_assert(kOff26 == 130 && kOffD26 == 158, "the words of the list totals as the hook documents them");
-  std::vector<uint32_t> blocks(size_t(n) * kWords), head(kWords + size_t(n) * 2);      // head: the base block, then the packed edits
-  for (uint32_t j = 0; j < n; ++j) {
-    uint32_t* b = blocks.data() + size_t(j) * kWords;
-    for (size_t w = 0; w < kWords; ++w) b[w] = j * 0x9E3779B1u + uint32_t(w);
-    b[kOff26] = j % (uint32_t(snap::kBestCap) + 1u); b[kOffD26] = (j / 3u) % (uint32_t(snap::kBestCap) + 1u);
-    head[kWords + 2 * size_t(j)] = j; head[kWords + 2 * size_t(j) + 1] = ~j;
-  }
-  for (size_t w = 0; w < kWords; ++w) head[w] = 0xBA5E0000u + uint32_t(w);
-  head[kOff26] = 7u; head[kOffD26] = 5u;
-  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
-  EG_HIP(c->d_plan_edit_in.reserve(snap::kPlanStride + size_t(n) * 8));
-  EG_HIP(c->d_refine_log.reserve(size_t(kRefineLog) * kRefineEntryStride));
-  EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice));
-  EG_HIP(hipMemcpy(c->d_plan_edit_in, head.data(), head.size() * 4, hipMemcpyHostToDevice));
-  EG_HIP(hipMemsetAsync(c->d_refine_log, 0, kRefineEntryStride, nullptr));
-  c->n_plan_blocks = n;
-  EG_LAUNCH("k_refine_pick", launch_refine_pick(c->out, n, mode, c->d_plan_edit_in + snap::kPlanStride, c->d_plans, c->d_plan_edit_in, c->d_refine_log, nullptr));
-  EG_HIP(hipMemcpy(entry, c->d_refine_log, sizeof(RefineEntry), hipMemcpyDeviceToHost));
-  EG_HIP(hipMemcpy(base_block, c->d_plan_edit_in, snap::kPlanStride, hipMemcpyDeviceToHost));
-  return EG_OK;
+  return refine_pick(c, mode, &first, &n, 1, entry, base_block);      // one segment, base slot 0: its tags are 0xBA5E0000 + w
 }
 
 int32_t eg_debug_refine_pick_many(eg_ctx* c, int32_t mode, const uint32_t* seg_first, const uint32_t* seg_count, int32_t n_segs, void* entries, uint8_t* base_blocks) {
@@ -130,38 +146,7 @@ int32_t eg_debug_refine_pick_many(eg_ctx* c, int32_t mode, const uint32_t* seg_f
     }
     if (at != n) { set_error("eg_debug_refine_pick_many: the segments cover " + std::to_string(at) + " of the last batch's " + std::to_string(n) + " records"); return EG_ERR_BAD_ARG; }
   }
-  EG_HIP(hipSetDevice(c->device));
-  constexpr size_t kWords = snap::kPlanStride / 4, kOff26 = (snap::best_off - snap::best_mask) / 4 + EG_YEARS, kOffD26 = (snap::bestd_off - snap::best_mask) / 4 + EG_YEARS;
-  const size_t S = size_t(n_segs);
-  std::vector<uint32_t> blocks(size_t(n) * kWords), base(S * kWords), in(size_t(n) * 2 + S * 4);      // in: the packed edits, then the segment table
-  for (uint32_t j = 0; j < n; ++j) {
-    uint32_t* b = blocks.data() + size_t(j) * kWords;
-    for (size_t w = 0; w < kWords; ++w) b[w] = j * 0x9E3779B1u + uint32_t(w);
-    b[kOff26] = j % (uint32_t(snap::kBestCap) + 1u); b[kOffD26] = (j / 3u) % (uint32_t(snap::kBestCap) + 1u);
-    in[2 * size_t(j)] = j; in[2 * size_t(j) + 1] = ~j;
-  }
-  for (size_t s = 0; s < S; ++s) {
-    uint32_t* b = base.data() + s * kWords;
-    for (size_t w = 0; w < kWords; ++w) b[w] = 0xBA5E0000u + (uint32_t(s) << 8) + uint32_t(w);
-    b[kOff26] = 7u; b[kOffD26] = 5u;
-    uint32_t* t = in.data() + size_t(n) * 2 + s * 4;
-    t[0] = seg_first[s]; t[1] = seg_count[s]; t[2] = uint32_t(s); t[3] = 0u;
-  }
-  static_assert(kRefineSegmentBytes == 16, "segment table entry");
-  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
-  EG_HIP(c->d_refine_bases.reserve(S * snap::kPlanStride));
-  EG_HIP(c->d_refine_in.reserve(in.size() * 4));
-  EG_HIP(c->d_refine_log.reserve(size_t(kRefineLog) * kRefineEntryStride));
-  EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice));
-  EG_HIP(hipMemcpy(c->d_refine_bases, base.data(), base.size() * 4, hipMemcpyHostToDevice));
-  EG_HIP(hipMemcpy(c->d_refine_in, in.data(), in.size() * 4, hipMemcpyHostToDevice));
-  EG_HIP(hipMemsetAsync(c->d_refine_log, 0, S * kRefineEntryStride, nullptr));
-  c->n_plan_blocks = n;
-  EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + size_t(n) * 8, uint32_t(n_segs), n, mode, c->d_refine_in, c->d_plans, c->d_refine_bases,
-                                                          uint32_t(n_segs), c->d_refine_log, nullptr));
-  EG_HIP(hipMemcpy2D(entries, sizeof(RefineEntry), c->d_refine_log, kRefineEntryStride, sizeof(RefineEntry), S, hipMemcpyDeviceToHost));
-  EG_HIP(hipMemcpy(base_blocks, c->d_refine_bases, S * snap::kPlanStride, hipMemcpyDeviceToHost));
-  return EG_OK;
+  return refine_pick(c, mode, seg_first, seg_count, n_segs, entries, base_blocks);
 }
 
 }  // extern "C"

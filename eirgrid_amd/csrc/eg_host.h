@@ -1,4 +1,4 @@
-// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_plans / eg_refine / eg_refine_many / eg_place / eg_group .cpp): owned buffers, the
+// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_plans / eg_refine / eg_place / eg_group .cpp): owned buffers, the
 // error macros, the context and the helpers that cross units.  Host only: the kernels include eg_internal.h, never this.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -139,13 +139,12 @@ struct eg_ctx {
   // plan-edit batches (eg_evaluate_plan_edits): the base plan's block followed by the packed edits, 8 bytes each — what k_plan_edits reads
   eg::DevBuf<uint8_t> d_plan_edit_in;
   size_t n_plan_blocks = 0;      // blocks of the last plan or plan-edit batch in d_plans (eg_debug_fetch_plan_block)
-  // plan refinement (eg_refine_plan): the step log k_refine_pick writes, a ring of kRefineLog entries of kRefineEntryStride bytes
-  eg::DevBuf<uint8_t> d_refine_log;
-  // eg_refine_plans: the base blocks of the call's plans (uploaded once, kept current by k_refine_pick_many) and what a launch
-  // uploads in one copy: the packed edits, the base slot of every variant, the segment table
-  // EIRGRID_REFINE_LAUNCH_VARIANTS (default and at most 16 384, at least 1; read at every call): the variants a launch of eg_refine_plans may
-  // hold — a plan with more gets a launch to itself; for tests that want many launches per round at small sizes
-  eg::DevBuf<uint8_t> d_refine_bases, d_refine_in;
+  // plan refinement (eg_refine_plan, eg_refine_plans): the step log k_refine_pick_many writes, an entry per plan of a launch from the
+  // start (kRefineLog entries of kRefineEntryStride bytes); the base blocks of the call's plans (uploaded once, kept current by
+  // k_refine_pick_many) and what a launch uploads in one copy: the packed edits, the base slot of every variant, the segment table
+  // EIRGRID_REFINE_LAUNCH_VARIANTS (default and at most 16 384, at least 1; read at every call): the variants a launch may hold — a plan
+  // with more gets a launch to itself (so eg_refine_plan's one plan always does); for tests that want many launches per round at small sizes
+  eg::DevBuf<uint8_t> d_refine_log, d_refine_bases, d_refine_in;
 };
 
 namespace eg {

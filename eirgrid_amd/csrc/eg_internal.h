@@ -478,9 +478,8 @@ int launch_pareto_fold(uint8_t* d_state, const ParetoWork& w, const DevOut& o, u
 // k_plan_edits (eg_plan_edits.h): the n plan blocks of a plan-edit batch into d_pool (snap::kPlanStride bytes each) from the base
 // plan's block d_base and n packed edits (8 bytes each: kind | list << 8 | year << 16 | action << 24, then pos)
 int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream);
-// k_refine_pick (eg_refine.h): the best candidate of the n variants of a refinement round (eg_refine_plan) — status EG_EP_OK and a rank
-// score that is not NaN; the largest score, ties to the lowest variant — into one entry of the step log, and, when it is not variant 0,
-// its plan block (d_pool + winner * snap::kPlanStride) over the base block d_base.  d_edits: the round's packed edits.
+// What k_refine_pick_many leaves per plan of a refinement round (eg_refine_plan, eg_refine_plans): the best candidate of the plan's n
+// variants — status EG_EP_OK and a rank score that is not NaN; the largest score, ties to the lowest variant.
 struct RefineEntry {
   int32_t winner, n_failed;        // -1: variant 0 is no candidate (nothing copied); variants that are no candidates
   uint32_t edit[2];                // the winner's packed edit
@@ -490,13 +489,13 @@ struct RefineEntry {
   double base_score, base_metrics[4];
 };
 constexpr size_t kRefineEntryStride = 128;
-constexpr int kRefineLog = 256;
+constexpr int kRefineLog = 256;      // entries of the step log: a launch writes one per plan it holds
 static_assert(sizeof(RefineEntry) <= kRefineEntryStride, "refine entry");
-int launch_refine_pick(const DevOut& o, uint32_t n, int mode, const void* d_edits, const uint8_t* d_pool, uint8_t* d_base, void* d_entry, void* stream);
-// k_plan_edits_many, k_refine_pick_many (eg_refine_many.h): a refinement round of several plans in ONE launch of n variants (eg_refine_plans).
+// k_plan_edits_many, k_refine_pick_many (eg_refine_many.h): a refinement round of one or several plans in ONE launch of n variants.
 // d_bases: n_bases base blocks, one per plan of the call; d_slot[j]: the base block variant j is an edit of; d_segs: n_segs entries
 // {u32 first, count, slot, 0} (kRefineSegmentBytes each), segment s being the variants [first, first + count) of the plan whose base block
-// is `slot`; d_entries: a RefineEntry per segment, kRefineEntryStride bytes apart (winner relative to the segment).
+// is `slot`; d_entries: a RefineEntry per segment, kRefineEntryStride bytes apart (winner relative to the segment).  A winner that is not
+// its segment's first variant has its plan block (d_pool + (first + winner) * snap::kPlanStride) copied over base block `slot`.
 constexpr size_t kRefineSegmentBytes = 16;
 int launch_plan_edits_many(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_slot, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream);
 int launch_refine_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs, uint32_t n_total, int mode, const void* d_edits, const uint8_t* d_pool,

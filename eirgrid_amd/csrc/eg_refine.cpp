@@ -1,9 +1,13 @@
-// eg_refine.cpp — eg_refine_plan (include/eirgrid_hip.h): the loop "score every one-entry edit of the plan, apply the best one" with the
-// plan, its variants and the pick of the winner on the device.  The pieces are eg_plans.cpp's (stage_eval_snapshot, pack_plan_edits,
-// launch_plans, write_lists) and k_plan_edits; what is new is k_refine_pick (eg_refine.h) behind each round's rollout grids and the
-// host's mirror of the plan, from which the next round's edits are enumerated.
+// eg_refine.cpp — eg_refine_plan and eg_refine_plans (include/eirgrid_hip.h): the loop "score every one-entry edit of a plan, apply the
+// best one" with the plans, their variants and the pick of each winner on the device.  ONE loop serves both: eg_refine_plan is its case of
+// one plan.  Per round the still-active plans' variants are packed into launches, a SEGMENT of consecutive variants per plan;
+// k_plan_edits_many writes every variant's block from its plan's base block, the plan batch runs over the whole launch (eg_plans.cpp:
+// stage_eval_snapshot, pack_plan_edits, launch_plans, write_lists), k_refine_pick_many picks a winner per segment and keeps that plan's base
+// block current (eg_refine_many.h).  The host follows every plan in a mirror, from which the next round's edits are enumerated.
+// A plan never straddles two launches, so a single plan always gets a launch of exactly its own variants, whatever the launch size.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 #include "eg_edit_order.h"
@@ -12,20 +16,18 @@
 using namespace eg;
 
 namespace {
-// the plan as the host follows it: the two lists, year by year
+// a plan as the host follows it: the two lists, year by year
 struct Mirror {
   std::vector<uint8_t> l[2][EG_YEARS];
   int64_t total(int w) const { int64_t n = 0; for (int y = 0; y < EG_YEARS; ++y) n += int64_t(l[w][y].size()); return n; }
+  void counts(int32_t (&count)[2][EG_YEARS]) const {
+    for (int w = 0; w < 2; ++w)
+      for (int y = 0; y < EG_YEARS; ++y) count[w][y] = int32_t(l[w][y].size());
+  }
 };
 // variants of a round over lists of these totals (include/eirgrid_hip.h: none, deletes, replaces, appends)
 int64_t n_variants(int64_t len0, int64_t len1, const eg_refine_opts& o) {
   return 1 + len0 + len1 + int64_t(o.n_replace) * len0 + (len0 < int64_t(snap::kBestCap) ? int64_t(EG_YEARS) * o.n_append : 0);
-}
-void enumerate(const Mirror& m, const eg_refine_opts& o, std::vector<eg_plan_edit>& edits) {      // the round's edits, in the canonical order
-  int32_t count[2][EG_YEARS];
-  for (int w = 0; w < 2; ++w)
-    for (int y = 0; y < EG_YEARS; ++y) count[w][y] = int32_t(m.l[w][y].size());
-  enumerate_edits(count[0], count[1], o.replace_with, o.n_replace, o.append_with, o.n_append, m.total(0) < int64_t(snap::kBestCap), edits);
 }
 void apply(Mirror& m, const eg_plan_edit& e) {
   std::vector<uint8_t>& l = m.l[e.list][e.year];
@@ -33,15 +35,14 @@ void apply(Mirror& m, const eg_plan_edit& e) {
   else if (e.kind == EG_EDIT_REPLACE) l[e.pos] = e.action;
   else if (e.kind == EG_EDIT_INSERT) l.insert(l.begin() + e.pos, e.action);
 }
+// who speaks in a message: the entry point `fn`, and the plan where the entry point takes many (the one-plan forms name none)
+std::string who(const char* fn, bool name_plan, int32_t plan) { return std::string(fn) + ": " + (name_plan ? "plan " + std::to_string(plan) + ": " : ""); }
 std::string too_many(int round, int64_t n) {
   return "round " + std::to_string(round) + " enumerates " + std::to_string(n) + " variants (at most " + std::to_string(EG_REFINE_MAX_VARIANTS) + ")";
 }
-}  // namespace
-
-extern "C" int32_t eg_refine_validate(const eg_plan_set* base, const eg_refine_opts* o) {
-  auto fail = [](const std::string& m) { set_error("eg_refine_validate: " + m); return EG_ERR_BAD_ARG; };
-  EG_TRY(eg_plans_validate(base));
-  if (base->n_plans != 1) return fail("the base holds " + std::to_string(base->n_plans) + " plans (exactly 1)");
+// what both validators ask of the options, and of every plan's round 0 (the set itself is the caller's to check)
+int32_t validate_opts(const char* fn, bool name_plan, const eg_plan_set* bases, const eg_refine_opts* o) {
+  auto fail = [fn](const std::string& m) { set_error(std::string(fn) + ": " + m); return EG_ERR_BAD_ARG; };
   if (!o) return fail("NULL options");
   if (o->mode != 1 && o->mode != 2) return fail("mode " + std::to_string(o->mode) + " (1: optimization_mode None, 2: cost_only)");
   if (o->max_rounds < 1) return fail("max_rounds = " + std::to_string(o->max_rounds) + " (at least 1)");
@@ -55,9 +56,210 @@ extern "C" int32_t eg_refine_validate(const eg_plan_set* base, const eg_refine_o
     for (int32_t i = 0; i < count[k]; ++i)
       if (list[k][i] >= EG_N_ACTIONS) return fail(std::string(name[k]) + "[" + std::to_string(i) + "]: action " + std::to_string(int(list[k][i])) + " >= " + std::to_string(EG_N_ACTIONS));
   }
-  const int64_t n = n_variants(base->best_actions_len, base->best_deficit_actions_len, *o);
-  if (n > EG_REFINE_MAX_VARIANTS) return fail(too_many(0, n));
+  for (int32_t p = 0; p < bases->n_plans; ++p) {
+    int64_t len[2] = {0, 0};
+    for (int y = 0; y < EG_YEARS; ++y) { len[0] += bases->best_count[size_t(p) * EG_YEARS + y]; len[1] += bases->best_deficit_count[size_t(p) * EG_YEARS + y]; }
+    const int64_t n = n_variants(len[0], len[1], *o);
+    if (n > EG_REFINE_MAX_VARIANTS) { set_error(who(fn, name_plan, p) + too_many(0, n)); return EG_ERR_BAD_ARG; }
+  }
   return EG_OK;
+}
+// EIRGRID_REFINE_LAUNCH_VARIANTS: the variants a launch may hold (a plan with more gets a launch to itself), read at every call
+uint32_t launch_variants() {
+  const char* v = std::getenv("EIRGRID_REFINE_LAUNCH_VARIANTS");
+  if (!v || !*v) return EG_REFINE_MAX_VARIANTS;
+  return uint32_t(std::min<long long>(std::max<long long>(std::atoll(v), 1), EG_REFINE_MAX_VARIANTS));
+}
+// one plan of a launch: its variants are [first, first + n) of the launch's
+struct Seg { int32_t plan; uint32_t first, n; std::vector<eg_plan_edit> edits; };
+
+// the loop, for the validated plans of `bases`: steps [P][max_rounds], n_steps / stop_reason / start_score / out's rows [P]
+int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro,
+               uint64_t seed, uint64_t episode_index, eg_plan_set** refined, eg_refine_step* steps, int32_t* n_steps, int32_t* stop_reason, double* start_score,
+               eg_episode_out* out) {
+  EG_TRY(check_policy(s, o, fn));
+  EG_HIP(hipSetDevice(c->device));
+  *refined = nullptr;
+  const int32_t P = bases->n_plans;
+  std::vector<Mirror> mirror((size_t(P)));
+  {
+    const int32_t* count[2] = {bases->best_count, bases->best_deficit_count};
+    const uint8_t* flat[2] = {bases->best_actions, bases->best_deficit_actions};
+    for (int w = 0; w < 2; ++w) {
+      int64_t at = 0;
+      for (int32_t p = 0; p < P; ++p)
+        for (int y = 0; y < EG_YEARS; ++y) {
+          const int32_t k = count[w][size_t(p) * EG_YEARS + y];
+          mirror[size_t(p)].l[w][y].assign(flat[w] + at, flat[w] + at + k); at += k;
+        }
+    }
+  }
+  // every buffer once, for the largest launch max_rounds steps can lead to: a plan's best_actions grows by an entry a step at most, and
+  // only by an append (a round beyond EG_REFINE_MAX_VARIANTS is refused when it is reached); a launch holds a plan larger than the
+  // launch size alone, else no more variants than the launch size
+  const uint32_t launch_max = launch_variants();
+  uint32_t n_cap = 0;
+  {
+    int64_t largest = 0, sum = 0;
+    for (int32_t p = 0; p < P; ++p) {
+      const int64_t len0 = mirror[size_t(p)].total(0), len1 = mirror[size_t(p)].total(1);
+      const int64_t grown = ro->n_append > 0 ? std::min<int64_t>(len0 + ro->max_rounds, int64_t(snap::kBestCap)) : len0;
+      const int64_t most = std::min<int64_t>(std::max(n_variants(len0, len1, *ro), 1 + grown + len1 + int64_t(ro->n_replace) * grown + int64_t(EG_YEARS) * ro->n_append),
+                                             EG_REFINE_MAX_VARIANTS);
+      largest = std::max(largest, most); sum += most;
+    }
+    n_cap = uint32_t(std::max(largest, std::min<int64_t>(sum, launch_max)));
+  }
+  const size_t segs_cap = std::min<size_t>(size_t(P), n_cap);
+  EG_TRY(ensure_outputs(c, n_cap));
+  EG_HIP(c->d_plans.reserve(size_t(n_cap) * snap::kPlanStride));
+  EG_HIP(c->d_plan_index.reserve(n_cap));
+  EG_HIP(c->d_refine_in.reserve(size_t(n_cap) * 12 + 16 + segs_cap * kRefineSegmentBytes));
+  EG_HIP(c->d_refine_log.reserve(size_t(kRefineLog) * kRefineEntryStride));
+  static_assert(EG_REFINE_MAX_PLANS <= kRefineLog, "a launch's entries fit the step log");
+  EG_HIP(c->d_refine_bases.reserve(size_t(P) * snap::kPlanStride));
+  {      // the base blocks go up once; from then on k_refine_pick_many keeps them current
+    std::vector<uint8_t> blocks(size_t(P) * snap::kPlanStride, 0);
+    int64_t pos = 0, dpos = 0;
+    for (int32_t p = 0; p < P; ++p) {
+      const int32_t* cnt = bases->best_count + size_t(p) * EG_YEARS;
+      const int32_t* dcnt = bases->best_deficit_count + size_t(p) * EG_YEARS;
+      write_lists(blocks.data() + size_t(p) * snap::kPlanStride, cnt, bases->best_actions + pos, dcnt, bases->best_deficit_actions + dpos);
+      pos += mirror[size_t(p)].total(0); dpos += mirror[size_t(p)].total(1);
+    }
+    EG_HIP(hipMemcpy(c->d_refine_bases, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
+  }
+  DevSnapshot S{};
+  EG_TRY(stage_eval_snapshot(c, s, o, &S));
+  std::vector<char> active(size_t(P), 1);
+  for (int32_t p = 0; p < P; ++p) { n_steps[p] = 0; stop_reason[p] = EG_REFINE_MAX_ROUNDS; if (start_score) start_score[p] = std::nan(""); }
+  std::vector<Seg> segs;
+  std::vector<uint8_t> in;
+  std::vector<uint32_t> local_idx, idx, longs;
+  std::vector<uint8_t> entries;
+  for (int round = 0;; ++round) {
+    // the round's variant counts, plan by plan
+    std::vector<std::pair<int32_t, uint32_t>> todo;      // (plan, variants), ascending
+    for (int32_t p = 0; p < P; ++p) {
+      if (!active[size_t(p)]) continue;
+      const int64_t want = n_variants(mirror[size_t(p)].total(0), mirror[size_t(p)].total(1), *ro);
+      if (want > EG_REFINE_MAX_VARIANTS) { set_error(who(fn, name_plan, p) + too_many(round, want)); return EG_ERR_BAD_ARG; }
+      todo.emplace_back(p, uint32_t(want));
+    }
+    if (todo.empty()) break;
+    for (size_t t0 = 0; t0 < todo.size();) {
+      // a launch: consecutive plans while they fit; a plan never straddles two launches
+      size_t t1 = t0 + 1;
+      uint32_t n = todo[t0].second;
+      while (t1 < todo.size() && n + todo[t1].second <= launch_max) n += todo[t1++].second;
+      const uint32_t n_segs = uint32_t(t1 - t0);
+      if (n > n_cap || n_segs > segs_cap) { set_error(std::string(fn) + ": round " + std::to_string(round) + ": a launch of " + std::to_string(n) + " variants outgrew its buffers"); return EG_ERR_INTERNAL; }
+      // what goes up in one copy: the packed edits (8 bytes a variant), every variant's base slot, the segment table; and the routing —
+      // the short variants of the whole launch first, then the long ones (launch_plans)
+      const size_t at_slot = size_t(n) * 8, at_segs = (size_t(n) * 12 + 15) / 16 * 16;
+      in.assign(at_segs + size_t(n_segs) * kRefineSegmentBytes, 0);
+      uint32_t* packed = reinterpret_cast<uint32_t*>(in.data());
+      uint32_t* slot = reinterpret_cast<uint32_t*>(in.data() + at_slot);
+      uint32_t* table = reinterpret_cast<uint32_t*>(in.data() + at_segs);
+      segs.resize(n_segs); idx.clear(); longs.clear();
+      uint32_t first = 0;
+      for (uint32_t k = 0; k < n_segs; ++k) {
+        Seg& sg = segs[k];
+        sg.plan = todo[t0 + k].first; sg.first = first; sg.n = todo[t0 + k].second;
+        const Mirror& m = mirror[size_t(sg.plan)];
+        int32_t count[2][EG_YEARS];
+        m.counts(count);
+        enumerate_edits(count[0], count[1], ro->replace_with, ro->n_replace, ro->append_with, ro->n_append, m.total(0) < int64_t(snap::kBestCap), sg.edits);
+        if (sg.edits.size() != size_t(sg.n)) { set_error(who(fn, name_plan, sg.plan) + "round " + std::to_string(round) + ": the enumeration and its count disagree"); return EG_ERR_INTERNAL; }
+        local_idx.resize(sg.n);
+        uint32_t n_short = 0;
+        pack_plan_edits(sg.edits.data(), sg.n, m.total(0), packed + 2 * size_t(first), local_idx.data(), &n_short);
+        for (uint32_t j = 0; j < sg.n; ++j) (j < n_short ? idx : longs).push_back(first + local_idx[j]);
+        std::fill(slot + first, slot + first + sg.n, uint32_t(sg.plan));
+        table[4 * k] = first; table[4 * k + 1] = sg.n; table[4 * k + 2] = uint32_t(sg.plan);
+        first += sg.n;
+      }
+      const uint32_t n_short = uint32_t(idx.size());
+      idx.insert(idx.end(), longs.begin(), longs.end());
+      EG_HIP(hipMemcpy(c->d_refine_in, in.data(), in.size(), hipMemcpyHostToDevice));
+      EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+      const uint8_t* d_edits = c->d_refine_in;
+      EG_LAUNCH("k_plan_edits_many", launch_plan_edits_many(c->d_refine_bases, uint32_t(P), reinterpret_cast<const uint32_t*>(c->d_refine_in + at_slot), d_edits, n, c->d_plans, nullptr));
+      c->n_plan_blocks = n;
+      EG_TRY(launch_plans(c, S, seed, episode_index, n, n_short, true));
+      EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + at_segs, n_segs, n, ro->mode, d_edits, c->d_plans, c->d_refine_bases, uint32_t(P),
+                                                              c->d_refine_log, nullptr));
+      entries.resize(size_t(n_segs) * kRefineEntryStride);
+      EG_HIP(hipMemcpy(entries.data(), c->d_refine_log, entries.size(), hipMemcpyDeviceToHost));      // (waits for the launch)
+      for (uint32_t k = 0; k < n_segs; ++k) {
+        const Seg& sg = segs[k];
+        const int32_t p = sg.plan;
+        const std::string at = who(fn, name_plan, p) + "round " + std::to_string(round) + ": ";
+        Mirror& m = mirror[size_t(p)];
+        RefineEntry e{};
+        std::memcpy(&e, entries.data() + size_t(k) * kRefineEntryStride, sizeof(e));
+        if (round == 0 && start_score && e.base_ok) start_score[p] = e.base_score;
+        if (!e.base_ok) { stop_reason[p] = EG_REFINE_BASE_FAILED; active[size_t(p)] = 0; continue; }
+        const uint32_t* mine = packed + 2 * size_t(sg.first);
+        if (e.n != int32_t(sg.n) || e.winner < 0 || e.winner >= int32_t(sg.n) || e.edit[0] != mine[2 * size_t(e.winner)] || e.edit[1] != mine[2 * size_t(e.winner) + 1]) {
+          set_error(at + "the device's step entry does not name a variant of the " + (name_plan ? "plan's " : "") + "round");
+          return EG_ERR_INTERNAL;
+        }
+        // the plan on the device against the mirror: the totals of the winner's block
+        if (e.winner != 0) apply(m, sg.edits[size_t(e.winner)]);
+        if (e.off26 != int32_t(m.total(0)) || e.offd26 != int32_t(m.total(1))) {
+          set_error(at + "the device's plan holds " + std::to_string(e.off26) + " + " + std::to_string(e.offd26) + " entries, the host's " +
+                    std::to_string(m.total(0)) + " + " + std::to_string(m.total(1)));
+          return EG_ERR_INTERNAL;
+        }
+        if (e.winner == 0) { stop_reason[p] = EG_REFINE_LOCAL_OPTIMUM; active[size_t(p)] = 0; }
+        else {
+          eg_refine_step& st = steps[size_t(p) * size_t(ro->max_rounds) + size_t(n_steps[p])];
+          st.edit = sg.edits[size_t(e.winner)]; st.variant = e.winner; st.n_variants = int32_t(sg.n); st.n_failed = e.n_failed; st.score = e.score;
+          std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
+          if (++n_steps[p] == ro->max_rounds) { stop_reason[p] = EG_REFINE_MAX_ROUNDS; active[size_t(p)] = 0; }
+        }
+        if (!active[size_t(p)] && out) {      // the refined plan's record, before the next launch overwrites the records
+          eg_episode_out row = out_row(out, size_t(p));
+          EG_TRY(fetch_records(c->out.base + (size_t(sg.first) + size_t(e.winner)) * rec::stride, 1, &row));
+          if (row.status && row.status[0] == EG_EP_INTERNAL) {      // (eg_refine_plan has always reported this one without a prefix)
+            set_error((name_plan ? at : std::string()) + "k_rollout: helper-wave protocol timed out in the refined plan's episode (EG_EP_INTERNAL)");
+            return EG_ERR_INTERNAL;
+          }
+        }
+      }
+      t0 = t1;
+    }
+  }
+  {
+    std::vector<int32_t> count[2];
+    std::vector<uint8_t> flat[2];
+    for (int w = 0; w < 2; ++w)
+      for (int32_t p = 0; p < P; ++p)
+        for (int y = 0; y < EG_YEARS; ++y) {
+          const std::vector<uint8_t>& l = mirror[size_t(p)].l[w][y];
+          count[w].push_back(int32_t(l.size())); flat[w].insert(flat[w].end(), l.begin(), l.end());
+        }
+    flat[0].reserve(1); flat[1].reserve(1);
+    *refined = make_plan_set_n(P, count[0].data(), flat[0].data(), count[1].data(), flat[1].data(), bases->names);
+  }
+  return EG_OK;
+}
+}  // namespace
+
+extern "C" int32_t eg_refine_validate(const eg_plan_set* base, const eg_refine_opts* o) {
+  EG_TRY(eg_plans_validate(base));
+  if (base->n_plans != 1) { set_error("eg_refine_validate: the base holds " + std::to_string(base->n_plans) + " plans (exactly 1)"); return EG_ERR_BAD_ARG; }
+  return validate_opts("eg_refine_validate", false, base, o);
+}
+
+extern "C" int32_t eg_refine_plans_validate(const eg_plan_set* bases, const eg_refine_opts* o) {
+  EG_TRY(eg_plans_validate(bases));
+  if (bases->n_plans > EG_REFINE_MAX_PLANS) {
+    set_error("eg_refine_plans_validate: the set holds " + std::to_string(bases->n_plans) + " plans (at most " + std::to_string(EG_REFINE_MAX_PLANS) + ")");
+    return EG_ERR_BAD_ARG;
+  }
+  return validate_opts("eg_refine_plans_validate", true, bases, o);
 }
 
 extern "C" int32_t eg_refine_plan(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* base, const eg_refine_opts* ro, uint64_t seed,
@@ -66,91 +268,14 @@ extern "C" int32_t eg_refine_plan(eg_ctx* c, const eg_policy_snapshot* s, const 
   if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plan: bad argument"); return EG_ERR_BAD_ARG; }
   if (c->group_member) { set_error("eg_refine_plan: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
   EG_TRY(eg_refine_validate(base, ro));
-  EG_TRY(check_policy(s, o, "eg_refine_plan"));
-  EG_HIP(hipSetDevice(c->device));
-  *refined = nullptr; *n_steps = 0;
-  Mirror m;
-  {
-    const int32_t* count[2] = {base->best_count, base->best_deficit_count};
-    const uint8_t* flat[2] = {base->best_actions, base->best_deficit_actions};
-    for (int w = 0; w < 2; ++w) {
-      int64_t at = 0;
-      for (int y = 0; y < EG_YEARS; ++y) { m.l[w][y].assign(flat[w] + at, flat[w] + at + count[w][y]); at += count[w][y]; }
-    }
-  }
-  // every buffer once, for the largest round max_rounds steps can lead to: best_actions grows by an entry a step at most, and only by
-  // an append; a round beyond EG_REFINE_MAX_VARIANTS is refused when it is reached
-  const int64_t len0 = m.total(0), len1 = m.total(1);
-  const int64_t grown = ro->n_append > 0 ? std::min<int64_t>(len0 + ro->max_rounds, int64_t(snap::kBestCap)) : len0;
-  const uint32_t n_cap = uint32_t(std::min<int64_t>(std::max(n_variants(len0, len1, *ro), 1 + grown + len1 + int64_t(ro->n_replace) * grown + int64_t(EG_YEARS) * ro->n_append),
-                                                    EG_REFINE_MAX_VARIANTS));
-  EG_TRY(ensure_outputs(c, n_cap));
-  EG_HIP(c->d_plans.reserve(size_t(n_cap) * snap::kPlanStride));
-  EG_HIP(c->d_plan_index.reserve(n_cap));
-  EG_HIP(c->d_plan_edit_in.reserve(snap::kPlanStride + size_t(n_cap) * 8));
-  EG_HIP(c->d_refine_log.reserve(size_t(kRefineLog) * kRefineEntryStride));
-  {      // the base block goes up once; from then on k_refine_pick keeps it current
-    std::vector<uint8_t> block(snap::kPlanStride, 0);
-    write_lists(block.data(), base->best_count, base->best_actions, base->best_deficit_count, base->best_deficit_actions);
-    EG_HIP(hipMemcpy(c->d_plan_edit_in, block.data(), block.size(), hipMemcpyHostToDevice));
-  }
-  DevSnapshot S{};
-  EG_TRY(stage_eval_snapshot(c, s, o, &S));
-  uint8_t* d_edits = c->d_plan_edit_in + snap::kPlanStride;
-  std::vector<eg_plan_edit> edits;
-  std::vector<uint32_t> packed, idx;
-  int stop = EG_REFINE_MAX_ROUNDS;
-  int32_t last = 0;      // the refined plan's record among the last round's
-  if (start_score) *start_score = std::nan("");
-  for (int round = 0;; ++round) {
-    const int64_t want = n_variants(m.total(0), m.total(1), *ro);
-    if (want > EG_REFINE_MAX_VARIANTS) { set_error("eg_refine_plan: " + too_many(round, want)); return EG_ERR_BAD_ARG; }
-    enumerate(m, *ro, edits);
-    const uint32_t n = uint32_t(edits.size());
-    packed.resize(size_t(n) * 2); idx.resize(n);
-    uint32_t n_short = 0;
-    pack_plan_edits(edits.data(), n, m.total(0), packed.data(), idx.data(), &n_short);
-    EG_HIP(hipMemcpy(d_edits, packed.data(), size_t(n) * 8, hipMemcpyHostToDevice));
-    EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-    EG_LAUNCH("k_plan_edits", launch_plan_edits(c->d_plan_edit_in, d_edits, n, c->d_plans, nullptr));
-    c->n_plan_blocks = n;
-    EG_TRY(launch_plans(c, S, seed, episode_index, n, n_short, true));
-    uint8_t* d_entry = c->d_refine_log + size_t(round % kRefineLog) * kRefineEntryStride;
-    EG_LAUNCH("k_refine_pick", launch_refine_pick(c->out, n, ro->mode, d_edits, c->d_plans, c->d_plan_edit_in, d_entry, nullptr));
-    RefineEntry e{};
-    EG_HIP(hipMemcpy(&e, d_entry, sizeof(e), hipMemcpyDeviceToHost));      // (waits for the round)
-    if (round == 0 && start_score && e.base_ok) *start_score = e.base_score;
-    if (!e.base_ok) { stop = EG_REFINE_BASE_FAILED; break; }
-    if (e.n != int32_t(n) || e.winner < 0 || e.winner >= int32_t(n) || e.edit[0] != packed[2 * size_t(e.winner)] || e.edit[1] != packed[2 * size_t(e.winner) + 1]) {
-      set_error("eg_refine_plan: round " + std::to_string(round) + ": the device's step entry does not name a variant of the round");
-      return EG_ERR_INTERNAL;
-    }
-    last = e.winner;
-    // the plan on the device against the mirror: the totals of the winner's block
-    if (e.winner != 0) apply(m, edits[size_t(e.winner)]);
-    if (e.off26 != int32_t(m.total(0)) || e.offd26 != int32_t(m.total(1))) {
-      set_error("eg_refine_plan: round " + std::to_string(round) + ": the device's plan holds " + std::to_string(e.off26) + " + " + std::to_string(e.offd26) +
-                " entries, the host's " + std::to_string(m.total(0)) + " + " + std::to_string(m.total(1)));
-      return EG_ERR_INTERNAL;
-    }
-    if (e.winner == 0) { stop = EG_REFINE_LOCAL_OPTIMUM; break; }
-    eg_refine_step& st = steps[*n_steps];
-    st.edit = edits[size_t(e.winner)]; st.variant = e.winner; st.n_variants = int32_t(n); st.n_failed = e.n_failed; st.score = e.score;
-    std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
-    if (++*n_steps == ro->max_rounds) { stop = EG_REFINE_MAX_ROUNDS; break; }
-  }
-  *stop_reason = stop;
-  if (out && stop != EG_REFINE_BASE_FAILED) {
-    EG_TRY(fetch_records(c->out.base + size_t(last) * rec::stride, 1, out));
-    if (out->status && out->status[0] == EG_EP_INTERNAL) { set_error("k_rollout: helper-wave protocol timed out in the refined plan's episode (EG_EP_INTERNAL)"); return EG_ERR_INTERNAL; }
-  }
-  {
-    int32_t count[2][EG_YEARS];
-    std::vector<uint8_t> flat[2];
-    for (int w = 0; w < 2; ++w)
-      for (int y = 0; y < EG_YEARS; ++y) { count[w][y] = int32_t(m.l[w][y].size()); flat[w].insert(flat[w].end(), m.l[w][y].begin(), m.l[w][y].end()); }
-    flat[0].reserve(1); flat[1].reserve(1);
-    *refined = make_plan_set(count[0], flat[0].data(), count[1], flat[1].data(), base->names && base->names[0] ? base->names[0] : "");
-  }
-  return EG_OK;
+  return refine("eg_refine_plan", false, c, s, o, base, ro, seed, episode_index, refined, steps, n_steps, stop_reason, start_score, out);
+}
+
+extern "C" int32_t eg_refine_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro, uint64_t seed,
+                                   uint64_t episode_index, eg_plan_set** refined, eg_refine_step* steps, int32_t* n_steps, int32_t* stop_reason,
+                                   double* start_score, eg_episode_out* out) {
+  if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plans: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->group_member) { set_error("eg_refine_plans: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_refine_plans_validate(bases, ro));
+  return refine("eg_refine_plans", true, c, s, o, bases, ro, seed, episode_index, refined, steps, n_steps, stop_reason, start_score, out);
 }

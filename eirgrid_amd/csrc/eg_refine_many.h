@@ -1,24 +1,30 @@
-// eg_refine_many.h — k_plan_edits_many and k_refine_pick_many: a refinement round of MANY plans in one launch (include/eirgrid_hip.h
-// eg_refine_plans; the host loop is eg_refine_many.cpp).  Included by eg_rollout.hip (eg_rollout.o only) behind eg_refine.h.
+// eg_refine_many.h — k_plan_edits_many and k_refine_pick_many: a refinement round in one launch, of one plan (include/eirgrid_hip.h
+// eg_refine_plan) or of many (eg_refine_plans); the host loop of both is eg_refine.cpp.  Included by eg_rollout.hip (eg_rollout.o only)
+// behind eg_refine.h.
 //
-// A launch holds the variants of several plans back to back: SEGMENT s is the variants [first_s, first_s + n_s) of one plan, whose base
-// block is block slot_s of a buffer of base blocks (one per plan of the call, uploaded once).  Both kernels are the one-plan kernels
-// (eg_plan_edits.h k_plan_edits, eg_refine.h k_refine_pick) with that indirection, and share nothing with them but __forceinline__
-// helpers: the one-plan kernels' code is not to change with this file.
+// A launch holds the variants of its plans back to back: SEGMENT s is the variants [first_s, first_s + n_s) of one plan, whose base
+// block is block slot_s of a buffer of base blocks (one per plan of the call, uploaded once).
 //   k_plan_edits_many   variant j's block from base block slot[j] and edit j: byte for byte what write_lists builds for the edited plan
 //                       in a zeroed block; one wave per variant, 8-byte words, every store of a wave 512 consecutive bytes; no LDS, no
-//                       scratch memory; writes inside block j only.
-//   k_refine_pick_many  one workgroup per segment, on the null stream behind the launch's rollout grids.  Workgroup s reduces ITS
-//                       variants exactly as k_refine_pick reduces [0, n): candidates have status EG_EP_OK and a rank score that is not
-//                       NaN, the largest score wins, ties to the lowest variant, the segment's first variant is its base.  It reads no
-//                       record outside its segment, counts its own non-candidates, writes entry s of the launch's entries (`winner`
-//                       relative to the segment; edit and list totals the winner's) and, when the winner is not the segment's variant 0,
-//                       copies the winner's block over base block slot_s.
+//                       scratch memory; writes inside block j only.  It is eg_plan_edits.h's k_plan_edits with the slot indirection and
+//                       two more clamps, and shares only __forceinline__ helpers with it: that kernel's code is pinned.
+//   k_refine_pick_many  one workgroup per segment, on the null stream behind the launch's rollout grids.  Workgroup s
+//     reads    status and metrics of ITS variants straight from the records (32 + 4 bytes of each 12 KB record), a thread a variant,
+//              striding by the workgroup's width when there are more variants than threads — the trip count is the same for every
+//              thread; no record outside its segment;
+//     reduces  (score, index relative to the segment) per wave and across the sixteen waves (eg_refine.h): the largest score wins, ties
+//              to the lowest variant; a candidate that scores -inf is recorded as well, and a candidate base — the segment's first
+//              variant — is itself in the running, so there is a winner (the clamp is for a record that lies about it);
+//     counts   its variants that are no candidates, a ballot per trip;
+//     writes   entry s of the launch's entries (RefineEntry, eg_internal.h): winner, its packed edit, score, metrics, the count, the
+//              list totals of the winner's block, and what the base scored;
+//     copies   the winner's plan block over base block slot_s when the winner is not the segment's variant 0 — 552 16-byte vector
+//              stores, one per thread — so that the next round's k_plan_edits_many finds the plan's base where the host uploaded it.
 // Every index read from memory or computed from one is clamped.
 // The two kernels live in a namespace of their own, `many`: scripts/kernel_resources.sh prints a kernel by what is left of its mangled
-// name, and the tests that pin the one-plan kernels' resource lines pick those by the word k_plan_edits / k_refine_pick at the start of
-// that name.  Behind a namespace the new names print as many17k_plan_edits_many / many18k_refine_pick_many, which such a pattern does not
-// take for the one-plan kernels (tests/test_refine_many_resources.py looks for the full names).
+// name, and the test that pins k_plan_edits' resource line picks it by the word k_plan_edits at the start of that name.  Behind the
+// namespace the names print as many17k_plan_edits_many / many18k_refine_pick_many, which such a pattern does not take for it
+// (tests/test_refine_many_resources.py looks for the full names).
 #pragma once
 
 namespace refine {

@@ -2520,8 +2520,8 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_topk.h"             // k_topk_keys, k_topk_select, k_topk_merge: the top-K archive of distinct scenarios
 #include "eg_pareto.h"           // k_pareto_filter .. k_pareto_finalize: the Pareto archive of a run's outcomes
 #include "eg_plan_edits.h"       // k_plan_edits: the plan blocks of a plan-edit batch from one base block and an edit per variant
-#include "eg_refine.h"           // k_refine_pick: the winner of a refinement round, its block made the next round's base
-#include "eg_refine_many.h"      // k_plan_edits_many, k_refine_pick_many: the same round for the plans of eg_refine_plans, a segment each
+#include "eg_refine.h"           // refine::before, wave_best: what the pick of a refinement round reduces with
+#include "eg_refine_many.h"      // k_plan_edits_many, k_refine_pick_many: a refinement round, a segment of the launch's variants per plan
 
 // ---- B2: a single placement search, for parity tests of the arg-max --------------------------------------------
 __global__ void __launch_bounds__(kWave) k_place(DevTables T, int type, int yi, const uint16_t* __restrict__ cells,
@@ -3378,12 +3378,6 @@ static_assert(sizeof(EpisodeMap) == 64 && offsetof(EpisodeMap, solo) == 48, "Epi
 int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream) {
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_plan_edits, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_base, reinterpret_cast<const uint2*>(d_edits), n, d_pool);
-  return (int)hipGetLastError();
-}
-int launch_refine_pick(const DevOut& o, uint32_t n, int mode, const void* d_edits, const uint8_t* d_pool, uint8_t* d_base, void* d_entry, void* stream) {
-  if (n == 0) return 0;
-  hipLaunchKernelGGL(k_refine_pick, dim3(1), dim3(refine::kThreads), 0, (hipStream_t)stream, o, n, mode, reinterpret_cast<const uint2*>(d_edits), d_pool, d_base,
-                     reinterpret_cast<RefineEntry*>(d_entry));
   return (int)hipGetLastError();
 }
 int launch_plan_edits_many(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_slot, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream) {

@@ -219,16 +219,21 @@ class Plan:
         return out
 
     @staticmethod
+    def _take_set(ps) -> "list[Plan]":
+        """the plans of a set the library returned (eg_plan_set *), which is freed"""
+        try:
+            return Plan._from_set(ps.contents)
+        finally:
+            N.lib().eg_plans_free(ps)
+
+    @staticmethod
     def load(path: str) -> "list[Plan]":
         """Plans of a file in the checkpoint schema: one checkpoint (one plan) or JSON Lines with optional names (eg_plans_load)."""
         L = N.lib()
         ps = L.eg_plans_load(str(path).encode())
         if not ps:
             raise N.EirgridError(L.eg_last_error().decode())
-        try:
-            return Plan._from_set(ps.contents)
-        finally:
-            L.eg_plans_free(ps)
+        return Plan._take_set(ps)
 
     @staticmethod
     def save(path: str, plans) -> None:
@@ -348,6 +353,12 @@ class RefineStep:
 
 
 REFINE_STOP = ("local_optimum", "max_rounds", "base_failed")
+
+
+def _refine_steps(steps) -> "list[RefineStep]":
+    """eg_refine_step structs as RefineSteps"""
+    return [RefineStep(PlanEdit(PlanEdit.KINDS[s.edit.kind], s.edit.list, s.edit.year, s.edit.pos, s.edit.action), s.variant, s.n_variants, s.n_failed,
+                       s.score, np.array(s.metrics[:])) for s in steps]
 
 
 def _refine_opts(mode, max_rounds, replace_with, append_with):
@@ -581,14 +592,9 @@ class Engine:
         L = N.lib()
         N.check(L.eg_refine_plan(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(ro), C.c_uint64(seed & (2**64 - 1)), C.c_uint64(index),
                                  C.byref(refined), steps, C.byref(n_steps), C.byref(stop), C.byref(start), C.byref(out)), "eg_refine_plan")
-        try:
-            plan = Plan._from_set(refined.contents)[0]
-        finally:
-            L.eg_plans_free(refined)
-        rows = [RefineStep(PlanEdit(PlanEdit.KINDS[s.edit.kind], s.edit.list, s.edit.year, s.edit.pos, s.edit.action), s.variant, s.n_variants, s.n_failed,
-                           s.score, np.array(s.metrics[:])) for s in steps[:n_steps.value]]
+        plan = Plan._take_set(refined)[0]
         reason = REFINE_STOP[stop.value]
-        return plan, rows, reason, start.value, (None if reason == "base_failed" else res)
+        return plan, _refine_steps(steps[:n_steps.value]), reason, start.value, (None if reason == "base_failed" else res)
 
     def refine_plans(self, weights: ActionWeights, bases, seed: int, index: int = 0, mode: int = 1, max_rounds: int = 64, replace_with=None,
                      append_with=None, enable_energy_sales=True, write_yearly=True):
@@ -610,18 +616,13 @@ class Engine:
         L = N.lib()
         N.check(L.eg_refine_plans(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(ro), C.c_uint64(seed & (2**64 - 1)), C.c_uint64(index),
                                   C.byref(refined), steps, _p(n_steps, C.c_int32), _p(stop, C.c_int32), _p(start, C.c_double), C.byref(out)), "eg_refine_plans")
-        try:
-            plans = Plan._from_set(refined.contents)
-        finally:
-            L.eg_plans_free(refined)
+        plans = Plan._take_set(refined)
         names = [f.name for f in fields(BatchResult)]
         result = []
         for p in range(n):
-            rows = [RefineStep(PlanEdit(PlanEdit.KINDS[s.edit.kind], s.edit.list, s.edit.year, s.edit.pos, s.edit.action), s.variant, s.n_variants, s.n_failed,
-                               s.score, np.array(s.metrics[:])) for s in steps[p * rounds:p * rounds + int(n_steps[p])]]
             reason = REFINE_STOP[int(stop[p])]
             rec = None if reason == "base_failed" else BatchResult(*[np.ascontiguousarray(getattr(res, f)[p:p + 1]) for f in names])
-            result.append((plans[p], rows, reason, float(start[p]), rec))
+            result.append((plans[p], _refine_steps(steps[p * rounds:p * rounds + int(n_steps[p])]), reason, float(start[p]), rec))
         return result
 
     # device-resident path used by bench.py

@@ -399,9 +399,9 @@ int32_t eg_debug_fetch_plan_block(eg_ctx *, uint32_t plan, uint8_t *out /* EG_PL
  *   otherwise                   B_{r+1} is the winner's plan and a step is recorded: its edit (against B_r), its variant index, the round's
  *                               variant count, how many variants were no candidates, its score and metrics
  *   after max_rounds steps      stop with EG_REFINE_MAX_ROUNDS
- * The winner is picked on the device (csrc/eg_refine.h k_refine_pick) and its plan block becomes the next round's base there; per round
- * the host uploads 12 bytes per variant and reads one entry of at most 128 bytes back.  The policy is checked, staged and uploaded once
- * per call.  Everything else is the contract of eg_evaluate_plan_edits: no statistics, update or folds, the resident policy untouched, a
+ * The winner is picked on the device (csrc/eg_refine_many.h k_refine_pick_many) and its plan block becomes the next round's base there:
+ * the call is eg_refine_plans' loop (below) over its one plan, which always has a launch to itself.  Per round the host uploads 16 bytes
+ * per variant and 16 more and reads one entry of at most 128 bytes back.  The policy is checked, staged and uploaded once per call.  Everything else is the contract of eg_evaluate_plan_edits: no statistics, update or folds, the resident policy untouched, a
  * rank of a group refused; the last round's variants stay behind as the last batch for eg_fetch / eg_fetch_record.
  * *refined: the final plan (free with eg_plans_free); steps[max_rounds], *n_steps, *stop_reason; *start_score: s_0 of round 0 (NaN when
  * the base failed); `out` (one episode, may be NULL): the refined plan's record — variant 0 of the last round on LOCAL_OPTIMUM, the last
@@ -519,7 +519,8 @@ int32_t eg_debug_fill_lds(eg_ctx *, uint32_t value);
  *                         (EG_CANDIDATE_BYTES, layout above).  The contract of score_list: the epilogue writes score_metrics (>= 0) for an
  *                         episode that ended EG_EP_OK and -1.0 for a failed one; the pick is the FIRST maximum among the scores above
  *                         -1.0 (a NaN never compares above anything), and score -1.0 / index -1 when there is none.
- *   eg_debug_refine_pick  k_refine_pick over the last batch (n <= EG_REFINE_MAX_VARIANTS records = variants) with n plan blocks,
+ *   eg_debug_refine_pick  k_refine_pick_many over the last batch as ONE segment (n <= EG_REFINE_MAX_VARIANTS records = variants:
+ *                         eg_debug_refine_pick_many with the segment [0, n), as eg_refine_plan launches the kernel) with n plan blocks,
  *                         a base block and n packed edits of the hook's own: block j is the 32-bit words j * 0x9E3779B1 + w (w = 0 ..
  *                         EG_PLAN_BLOCK_BYTES / 4) with the two list totals (words 130 and 158: entry [26] of the prefix offsets)
  *                         j mod 4097 and (j / 3) mod 4097; the base block is the words 0xBA5E0000 + w with totals 7 and 5; edit j is

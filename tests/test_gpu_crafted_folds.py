@@ -1,5 +1,5 @@
 """GPU: the four device reductions that decide what a run keeps, exports and trains on — the best_result fold (k_fold_best / fold_windows),
-the top-K archive (csrc/eg_topk.h), the update's best pick (k_pick_best) and the refinement's pick (csrc/eg_refine.h k_refine_pick) — on
+the top-K archive (csrc/eg_topk.h), the update's best pick (k_pick_best) and the refinement's pick (csrc/eg_refine_many.h k_refine_pick_many) — on
 crafted batches through the test hooks eg_debug_load_batch / _fold_last_batch / _pick_best / _refine_pick: ties, staircases in which every
 result takes over, NaN and infinities, action logs on the key's padding edges, maxima on row, wave and stride boundaries, global
 indices across 2^32.  Every comparison is exact — indices, score bits, metrics bytes, the n_draws tag and the tagged lists of every kept

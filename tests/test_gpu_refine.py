@@ -1,7 +1,7 @@
-"""GPU: greedy plan refinement (include/eirgrid_hip.h eg_refine_plan; csrc/eg_refine.cpp, csrc/eg_refine.h k_refine_pick).  The device
-picks each round's winner and makes its plan block the next round's base; the trajectory must be the one the definition gives — restated
-once as a loop over Engine.evaluate_plan_edits + rank_score (scores and metrics bit for bit) and once over the tabled oracle
-(tests/test_refine.py refine_restated)."""
+"""GPU: greedy plan refinement (include/eirgrid_hip.h eg_refine_plan; csrc/eg_refine.cpp, csrc/eg_refine_many.h k_refine_pick_many).  The
+device picks each round's winner and makes its plan block the next round's base; the trajectory must be the one the definition gives — restated
+once as a loop over Engine.evaluate_plan_edits + rank_score (scores and metrics bit for bit) and once over the tabled
+oracle (tests/test_refine.py refine_restated)."""
 import csv
 import json
 import os
@@ -67,13 +67,33 @@ def test_the_device_applied_base_is_the_refined_plans_block(world, engine):
     pol, base, ev, want = oracle_run(world, "short, mode 2")
     plan, steps, stop, start, rec = engine.refine_plan(pol, base, SEED, 0, case["mode"], case["max_rounds"], replace_with=case["replace_with"])
     assert stop == "local_optimum" and len(steps) == 1
-    dev = engine.debug_fetch_plan_block(0)      # variant 0 of the last round: a copy of the base k_refine_pick installed
+    dev = engine.debug_fetch_plan_block(0)      # variant 0 of the last round: a copy of the base k_refine_pick_many installed
     last = engine.fetch(237)                    # the last round's variants stay behind as the last batch (239 less the deleted entry's delete and replace)
     assert last.metrics[0].tobytes() == rec.metrics[0].tobytes()
     engine.evaluate_plans(pol, [plan], SEED, 0)
     host = engine.debug_fetch_plan_block(0)
     assert dev.tobytes() == host.tobytes(), np.flatnonzero(dev != host)[:8]
     assert dev.tobytes() != _block_of(engine, pol, base).tobytes()
+
+
+def test_one_plan_gets_a_launch_to_itself_whatever_the_launch_size(engine, monkeypatch):
+    """eg_refine_plan is eg_refine_plans' loop over one plan.  A plan never straddles two launches, so the smallest launch size must not
+    split its 239 variants: the same plan, steps, stop reason and start score, and the same record in every field, n_chunks included."""
+    case = CASES["short, mode 2"]
+    pol = case["policy"]()
+    base = Plan.from_policy(pol)
+    runs = []
+    for cap in ("1", None):
+        if cap is None:
+            monkeypatch.delenv("EIRGRID_REFINE_LAUNCH_VARIANTS", raising=False)
+        else:
+            monkeypatch.setenv("EIRGRID_REFINE_LAUNCH_VARIANTS", cap)
+        runs.append(engine.refine_plan(pol, base, SEED, 0, case["mode"], case["max_rounds"], replace_with=case["replace_with"]))
+    (plan, steps, stop, start, rec), unset = runs
+    assert stop == "local_optimum" and len(steps) == 1 and steps[0].n_variants == 239
+    _assert_same_trajectory(runs[0], (unset[0], [(s.edit, s.variant, s.n_variants, s.n_failed, s.score, s.metrics) for s in unset[1]], unset[2], unset[3]),
+                            "a launch size of 1 against the default")
+    _same_records(rec, unset[4], "the refined plan's record")
 
 
 def _block_of(eng, pol, plan):

@@ -1,7 +1,7 @@
-"""GPU: many plans refined in one call (include/eirgrid_hip.h eg_refine_plans; csrc/eg_refine_many.cpp, csrc/eg_refine_many.h).  The
+"""GPU: many plans refined in one call (include/eirgrid_hip.h eg_refine_plans; csrc/eg_refine.cpp, csrc/eg_refine_many.h).  The
 specification exists already: per plan the result is eg_refine_plan's for that plan alone, bit for bit — so every test compares with
-Engine.refine_plan on the same engine (code this feature does not touch) and with the definition restated over the tabled oracle
-(tests/test_refine.py refine_restated), never with the new call itself.  The two kernels are held on their own as well: the blocks
+Engine.refine_plan on the same engine (the same loop over that plan alone: a launch of another shape, of its variants only) and with the
+definition restated over the tabled oracle (tests/test_refine.py refine_restated), never with the call itself.  The two kernels are held on their own as well: the blocks
 k_plan_edits_many writes against the host's, and k_refine_pick_many on crafted batches cut into segments.
 
 (The bases' trajectories do not depend on the policy's weights — no variant of them draws a fallback — so one call under one policy is
