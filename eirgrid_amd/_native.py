@@ -77,6 +77,21 @@ class EgRefineStep(C.Structure):
                 ("metrics", C.c_double * 4)]
 
 
+class EgPlanMove(C.Structure):
+    _fields_ = [("list", C.c_uint8), ("to_year", C.c_uint8), ("year", C.c_uint16), ("pos", C.c_uint32), ("to_pos", C.c_uint32)]
+
+
+class EgRefineMoveOpts(C.Structure):
+    _fields_ = [("max_shift", C.c_int32)]
+
+
+class EgRefineMoveStep(C.Structure):
+    _fields_ = [("is_move", C.c_int32), ("edit", EgPlanEdit), ("move", EgPlanMove), ("variant", C.c_int32), ("n_variants", C.c_int32),
+                ("n_failed", C.c_int32), ("score", C.c_double), ("metrics", C.c_double * 4)]
+
+
+assert C.sizeof(EgPlanMove) == 12
+
 EDIT_NONE, EDIT_DELETE, EDIT_REPLACE, EDIT_INSERT = 0, 1, 2, 3
 REFINE_LOCAL_OPTIMUM, REFINE_MAX_ROUNDS, REFINE_BASE_FAILED = 0, 1, 2
 REFINE_MAX_VARIANTS = 16384      # EG_REFINE_MAX_VARIANTS
@@ -111,6 +126,7 @@ EXPORTS = [
     "eg_group_top_k_track", "eg_group_fetch_top_k", "eg_plans_validate", "eg_evaluate_plans", "eg_plans_load", "eg_plans_free",
     "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block", "eg_plans_save", "eg_refine_validate", "eg_refine_plan",
     "eg_refine_plans_validate", "eg_refine_plans", "eg_debug_refine_pick_many",
+    "eg_plan_moves_validate", "eg_evaluate_plan_moves", "eg_refine_plans_moves_validate", "eg_refine_plans_moves",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -282,6 +298,19 @@ def lib():
                                       C.POINTER(EgEpisodeOut)]
         L.eg_debug_refine_pick_many.restype = C.c_int32
         L.eg_debug_refine_pick_many.argtypes = [C.c_void_p, C.c_int32, _u32p, _u32p, C.c_int32, C.c_void_p, _u8p]
+    # (likewise: a probe may load a build of the parent commit, which has no plan moves)
+    if hasattr(L, "eg_evaluate_plan_moves") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_plan_moves_validate.restype = C.c_int32
+        L.eg_plan_moves_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgPlanMove), C.c_int32]
+        L.eg_evaluate_plan_moves.restype = C.c_int32
+        L.eg_evaluate_plan_moves.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgPlanMove),
+                                             C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(EgEpisodeOut)]
+        L.eg_refine_plans_moves_validate.restype = C.c_int32
+        L.eg_refine_plans_moves_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts), C.POINTER(EgRefineMoveOpts)]
+        L.eg_refine_plans_moves.restype = C.c_int32
+        L.eg_refine_plans_moves.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts),
+                                            C.POINTER(EgRefineMoveOpts), C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgRefineMoveStep),
+                                            _i32p, _i32p, _dp, C.POINTER(EgEpisodeOut)]
     # (likewise: scripts/pareto_probe.py may load a build of the parent commit, which has no Pareto archive)
     if hasattr(L, "eg_pareto_track") or not os.environ.get("EIRGRID_LIB"):
         L.eg_pareto_track.restype = C.c_int32

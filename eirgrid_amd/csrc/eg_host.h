@@ -166,6 +166,8 @@ DevSnapshot snapshot_of(uint8_t* d_base, const eg_opts* o);
 void write_lists(uint8_t* dst, const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact);
 int stage_eval_snapshot(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, DevSnapshot* S);
 void pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len, uint32_t* packed, uint32_t* idx, uint32_t* n_short);
+// ... and a move's 8 bytes (eg_plan_moves.h unpack_move)
+void pack_plan_move(const eg_plan_move& m, uint32_t* packed);
 int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index);
 // eg_fetch.cpp
 int fetch_records(const uint8_t* d_base, size_t N, eg_episode_out* o);

@@ -500,6 +500,11 @@ constexpr size_t kRefineSegmentBytes = 16;
 int launch_plan_edits_many(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_slot, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream);
 int launch_refine_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs, uint32_t n_total, int mode, const void* d_edits, const uint8_t* d_pool,
                             uint8_t* d_bases, uint32_t n_bases, uint8_t* d_entries, void* stream);
+// k_plan_moves (eg_plan_moves.h): the plan blocks of the variants among the n that are MOVES (8 bytes each: kPlanMoveTag | list << 8 |
+// year << 16 | to_year << 24, then pos | to_pos << 16) into d_pool from base block d_slot[j] of d_bases (d_slot NULL: base block 0); a
+// variant whose first byte is not the tag is left alone.  The tag is no edit kind: k_plan_edits_many reads such a variant as "none".
+constexpr uint32_t kPlanMoveTag = 4;
+int launch_plan_moves(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_slot, const void* d_moves, uint32_t n, uint8_t* d_pool, void* stream);
 // eg_checkpoint.cpp: one plan as a set eg_plans_free releases (counts [26], the flat lists)
 eg_plan_set* make_plan_set(const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact, const char* name);
 // ... and n plans as one set: counts [n][26], the flat lists plan-major, names [n] (NULL entries: "")

@@ -1,5 +1,5 @@
 // eg_plans.cpp — a policy in snapshot layout (shared with eg_upload_snapshot) and plan batches: eg_evaluate_plans, eg_evaluate_plan_edits,
-// launch_plans (eg_refine.cpp loops over the same pieces).
+// eg_evaluate_plan_moves, launch_plans (eg_refine.cpp loops over the same pieces).
 #include <algorithm>
 #include <cstring>
 
@@ -134,15 +134,18 @@ void eg::pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len
   *n_short = ns;
 }
 namespace {
-// The rest of a plan batch whose routing is in c->d_plan_index: the policy into its device snapshot, then the launches.  `edits`: a
-// plan-edit batch, whose blocks k_plan_edits writes on the launches' stream from c->d_plan_edit_in (the base block, then the packed edits).
+// The rest of a plan batch whose routing is in c->d_plan_index: the policy into its device snapshot, then the launches.  `blocks`: a
+// plan-edit or plan-move batch, whose blocks k_plan_edits / k_plan_moves writes on the launches' stream from c->d_plan_edit_in (the base
+// block, then the packed edits or moves).
 // (The snapshot is staged last before the launches: a launch's start event takes the time the stream's previous command ended — with
 //  the snapshot staged first, eg_timing_read counted the host building the plan blocks.)
+enum class Blocks { kHost, kEdits, kMoves };      // who writes the plan blocks: the host has, k_plan_edits, k_plan_moves
 int stage_and_launch_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short,
-                           bool edits, bool same_index) {
+                           Blocks blocks, bool same_index) {
   DevSnapshot S{};
   EG_TRY(stage_eval_snapshot(c, s, o, &S));
-  if (edits) EG_LAUNCH("k_plan_edits", launch_plan_edits(c->d_plan_edit_in, c->d_plan_edit_in + snap::kPlanStride, n, c->d_plans, nullptr));
+  if (blocks == Blocks::kEdits) EG_LAUNCH("k_plan_edits", launch_plan_edits(c->d_plan_edit_in, c->d_plan_edit_in + snap::kPlanStride, n, c->d_plans, nullptr));
+  if (blocks == Blocks::kMoves) EG_LAUNCH("k_plan_moves", launch_plan_moves(c->d_plan_edit_in, 1u, nullptr, c->d_plan_edit_in + snap::kPlanStride, n, c->d_plans, nullptr));
   c->n_plan_blocks = n;
   return launch_plans(c, S, seed, first_index, n, n_short, same_index);
 }
@@ -179,7 +182,7 @@ extern "C" int32_t eg_evaluate_plans(eg_ctx* c, const eg_policy_snapshot* s, con
   EG_HIP(c->d_plan_index.reserve(n));
   EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
   EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, false, false));
+  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, Blocks::kHost, false));
   return out ? eg_fetch(c, out) : EG_OK;
 }
 
@@ -235,7 +238,67 @@ extern "C" int32_t eg_evaluate_plan_edits(eg_ctx* c, const eg_policy_snapshot* s
   EG_HIP(c->d_plan_edit_in.reserve(in.size()));
   EG_HIP(hipMemcpy(c->d_plan_edit_in, in.data(), in.size(), hipMemcpyHostToDevice));
   EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, true, same_index != 0));
+  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, Blocks::kEdits, same_index != 0));
+  return out ? eg_fetch(c, out) : EG_OK;
+}
+
+// ---------------------------------------------------------------- plan moves (include/eirgrid_hip.h eg_evaluate_plan_moves)
+// what goes up per move, 8 bytes (eg_plan_moves.h unpack_move); the first byte is no edit kind
+static_assert(sizeof(eg_plan_move) == 12 && sizeof(eg_refine_move_step) == 80, "the move structs are part of the C ABI");
+void eg::pack_plan_move(const eg_plan_move& m, uint32_t* packed) {
+  packed[0] = kPlanMoveTag | uint32_t(m.list) << 8 | uint32_t(m.year) << 16 | uint32_t(m.to_year) << 24;
+  packed[1] = m.pos | m.to_pos << 16;
+}
+
+extern "C" int32_t eg_plan_moves_validate(const eg_plan_set* base, const eg_plan_move* moves, int32_t n_moves) {
+  auto fail = [](const std::string& m) { set_error("eg_plan_moves_validate: " + m); return EG_ERR_BAD_ARG; };
+  EG_TRY(eg_plans_validate(base));
+  if (base->n_plans != 1) return fail("the base holds " + std::to_string(base->n_plans) + " plans (exactly 1)");
+  if (n_moves < 1) return fail("n_moves = " + std::to_string(n_moves) + " (at least 1)");
+  if (!moves) return fail("NULL moves");
+  const char* field[2] = {"best_actions", "best_deficit_actions"};
+  const int32_t* count[2] = {base->best_count, base->best_deficit_count};
+  for (int32_t j = 0; j < n_moves; ++j) {
+    const eg_plan_move& m = moves[j];
+    const std::string who = "move " + std::to_string(j) + ": ";
+    if (m.list > 1) return fail(who + "list " + std::to_string(int(m.list)) + " (0 best_actions, 1 best_deficit_actions)");
+    if (m.year >= EG_YEARS) return fail(who + "year " + std::to_string(int(m.year)) + " (a year index 0.." + std::to_string(EG_YEARS - 1) + ")");
+    if (m.to_year >= EG_YEARS) return fail(who + "to_year " + std::to_string(int(m.to_year)) + " (a year index 0.." + std::to_string(EG_YEARS - 1) + ")");
+    const int64_t len = count[m.list][m.year];
+    if (int64_t(m.pos) >= len)
+      return fail(who + "pos " + std::to_string(m.pos) + " outside " + field[m.list] + " year " + std::to_string(2025 + int(m.year)) + " (" + std::to_string(len) + " entries): 0..len-1");
+    const int64_t to_len = count[m.list][m.to_year] - (m.to_year == m.year ? 1 : 0);
+    if (int64_t(m.to_pos) > to_len)
+      return fail(who + "to_pos " + std::to_string(m.to_pos) + " outside " + field[m.list] + " year " + std::to_string(2025 + int(m.to_year)) + " (" + std::to_string(to_len) +
+                  " entries after the removal)");
+  }
+  return EG_OK;
+}
+
+extern "C" int32_t eg_evaluate_plan_moves(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* base, const eg_plan_move* moves,
+                                          int32_t n_moves, uint64_t seed, uint64_t first_index, int32_t same_index, eg_episode_out* out) {
+  if (!c || !s || !s->weights || !s->deficit_weights) { set_error("eg_evaluate_plan_moves: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->group_member) { set_error("eg_evaluate_plan_moves: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_plan_moves_validate(base, moves, n_moves));
+  EG_TRY(check_policy(s, o, "eg_evaluate_plan_moves"));
+  EG_HIP(hipSetDevice(c->device));
+  const uint32_t n = uint32_t(n_moves);
+  EG_TRY(ensure_outputs(c, n));
+  // what goes up: the base plan's block and the packed moves; a move keeps the lists' lengths, so every variant takes the base's route
+  std::vector<uint8_t> in(snap::kPlanStride + size_t(n) * 8, 0);
+  write_lists(in.data(), base->best_count, base->best_actions, base->best_deficit_count, base->best_deficit_actions);
+  int64_t base_len = 0;
+  for (int y = 0; y < EG_YEARS; ++y) base_len += base->best_count[y];
+  uint32_t* packed = reinterpret_cast<uint32_t*>(in.data() + snap::kPlanStride);
+  std::vector<uint32_t> idx(n);
+  for (uint32_t j = 0; j < n; ++j) { pack_plan_move(moves[j], packed + 2 * size_t(j)); idx[j] = j; }
+  const uint32_t n_short = base_len > kShortReplayMax ? 0u : n;
+  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
+  EG_HIP(c->d_plan_index.reserve(n));
+  EG_HIP(c->d_plan_edit_in.reserve(in.size()));
+  EG_HIP(hipMemcpy(c->d_plan_edit_in, in.data(), in.size(), hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, Blocks::kMoves, same_index != 0));
   return out ? eg_fetch(c, out) : EG_OK;
 }
 

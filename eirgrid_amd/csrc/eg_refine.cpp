@@ -5,6 +5,8 @@
 // stage_eval_snapshot, pack_plan_edits, launch_plans, write_lists), k_refine_pick_many picks a winner per segment and keeps that plan's base
 // block current (eg_refine_many.h).  The host follows every plan in a mirror, from which the next round's edits are enumerated.
 // A plan never straddles two launches, so a single plan always gets a launch of exactly its own variants, whatever the launch size.
+// eg_refine_plans_moves runs the same loop with move variants behind every plan's edits: k_plan_moves (eg_plan_moves.h) overwrites their
+// blocks behind k_plan_edits_many, which has written a copy of the base for them.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -29,11 +31,22 @@ struct Mirror {
 int64_t n_variants(int64_t len0, int64_t len1, const eg_refine_opts& o) {
   return 1 + len0 + len1 + int64_t(o.n_replace) * len0 + (len0 < int64_t(snap::kBestCap) ? int64_t(EG_YEARS) * o.n_append : 0);
 }
+// ... and with the move variants behind them (eg_refine_plans_moves; mo == NULL: none); count0: the years' best_actions lengths
+int64_t n_variants(const int32_t* count0, int64_t len0, int64_t len1, const eg_refine_opts& o, const eg_refine_move_opts* mo) {
+  return n_variants(len0, len1, o) + (mo ? count_moves(count0, mo->max_shift) : 0);
+}
 void apply(Mirror& m, const eg_plan_edit& e) {
   std::vector<uint8_t>& l = m.l[e.list][e.year];
   if (e.kind == EG_EDIT_DELETE) l.erase(l.begin() + e.pos);
   else if (e.kind == EG_EDIT_REPLACE) l[e.pos] = e.action;
   else if (e.kind == EG_EDIT_INSERT) l.insert(l.begin() + e.pos, e.action);
+}
+void apply(Mirror& m, const eg_plan_move& v) {
+  std::vector<uint8_t>& from = m.l[v.list][v.year];
+  const uint8_t a = from[v.pos];
+  from.erase(from.begin() + v.pos);
+  std::vector<uint8_t>& to = m.l[v.list][v.to_year];
+  to.insert(to.begin() + v.to_pos, a);
 }
 // who speaks in a message: the entry point `fn`, and the plan where the entry point takes many (the one-plan forms name none)
 std::string who(const char* fn, bool name_plan, int32_t plan) { return std::string(fn) + ": " + (name_plan ? "plan " + std::to_string(plan) + ": " : ""); }
@@ -41,7 +54,7 @@ std::string too_many(int round, int64_t n) {
   return "round " + std::to_string(round) + " enumerates " + std::to_string(n) + " variants (at most " + std::to_string(EG_REFINE_MAX_VARIANTS) + ")";
 }
 // what both validators ask of the options, and of every plan's round 0 (the set itself is the caller's to check)
-int32_t validate_opts(const char* fn, bool name_plan, const eg_plan_set* bases, const eg_refine_opts* o) {
+int32_t validate_opts(const char* fn, bool name_plan, const eg_plan_set* bases, const eg_refine_opts* o, const eg_refine_move_opts* mo = nullptr) {
   auto fail = [fn](const std::string& m) { set_error(std::string(fn) + ": " + m); return EG_ERR_BAD_ARG; };
   if (!o) return fail("NULL options");
   if (o->mode != 1 && o->mode != 2) return fail("mode " + std::to_string(o->mode) + " (1: optimization_mode None, 2: cost_only)");
@@ -59,7 +72,7 @@ int32_t validate_opts(const char* fn, bool name_plan, const eg_plan_set* bases, 
   for (int32_t p = 0; p < bases->n_plans; ++p) {
     int64_t len[2] = {0, 0};
     for (int y = 0; y < EG_YEARS; ++y) { len[0] += bases->best_count[size_t(p) * EG_YEARS + y]; len[1] += bases->best_deficit_count[size_t(p) * EG_YEARS + y]; }
-    const int64_t n = n_variants(len[0], len[1], *o);
+    const int64_t n = n_variants(bases->best_count + size_t(p) * EG_YEARS, len[0], len[1], *o, mo);
     if (n > EG_REFINE_MAX_VARIANTS) { set_error(who(fn, name_plan, p) + too_many(0, n)); return EG_ERR_BAD_ARG; }
   }
   return EG_OK;
@@ -71,12 +84,14 @@ uint32_t launch_variants() {
   return uint32_t(std::min<long long>(std::max<long long>(std::atoll(v), 1), EG_REFINE_MAX_VARIANTS));
 }
 // one plan of a launch: its variants are [first, first + n) of the launch's
-struct Seg { int32_t plan; uint32_t first, n; std::vector<eg_plan_edit> edits; };
+// (with moves: its edits, then its moves)
+struct Seg { int32_t plan; uint32_t first, n; std::vector<eg_plan_edit> edits; std::vector<eg_plan_move> moves; };
 
-// the loop, for the validated plans of `bases`: steps [P][max_rounds], n_steps / stop_reason / start_score / out's rows [P]
+// the loop, for the validated plans of `bases`: steps [P][max_rounds], n_steps / stop_reason / start_score / out's rows [P].
+// mo: the move variants behind every plan's edits (eg_refine_plans_moves), whose steps go to msteps instead of steps; NULL: none
 int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro,
                uint64_t seed, uint64_t episode_index, eg_plan_set** refined, eg_refine_step* steps, int32_t* n_steps, int32_t* stop_reason, double* start_score,
-               eg_episode_out* out) {
+               eg_episode_out* out, const eg_refine_move_opts* mo = nullptr, eg_refine_move_step* msteps = nullptr) {
   EG_TRY(check_policy(s, o, fn));
   EG_HIP(hipSetDevice(c->device));
   *refined = nullptr;
@@ -104,7 +119,9 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
     for (int32_t p = 0; p < P; ++p) {
       const int64_t len0 = mirror[size_t(p)].total(0), len1 = mirror[size_t(p)].total(1);
       const int64_t grown = ro->n_append > 0 ? std::min<int64_t>(len0 + ro->max_rounds, int64_t(snap::kBestCap)) : len0;
-      const int64_t most = std::min<int64_t>(std::max(n_variants(len0, len1, *ro), 1 + grown + len1 + int64_t(ro->n_replace) * grown + int64_t(EG_YEARS) * ro->n_append),
+      // (moves: at most 2 * max_shift per entry, wherever the steps take the entries)
+      const int64_t moves_most = mo ? grown * 2 * mo->max_shift : 0;
+      const int64_t most = std::min<int64_t>(std::max(n_variants(len0, len1, *ro), 1 + grown + len1 + int64_t(ro->n_replace) * grown + int64_t(EG_YEARS) * ro->n_append) + moves_most,
                                              EG_REFINE_MAX_VARIANTS);
       largest = std::max(largest, most); sum += most;
     }
@@ -142,7 +159,9 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
     std::vector<std::pair<int32_t, uint32_t>> todo;      // (plan, variants), ascending
     for (int32_t p = 0; p < P; ++p) {
       if (!active[size_t(p)]) continue;
-      const int64_t want = n_variants(mirror[size_t(p)].total(0), mirror[size_t(p)].total(1), *ro);
+      int32_t count[2][EG_YEARS];
+      mirror[size_t(p)].counts(count);
+      const int64_t want = n_variants(count[0], mirror[size_t(p)].total(0), mirror[size_t(p)].total(1), *ro, mo);
       if (want > EG_REFINE_MAX_VARIANTS) { set_error(who(fn, name_plan, p) + too_many(round, want)); return EG_ERR_BAD_ARG; }
       todo.emplace_back(p, uint32_t(want));
     }
@@ -163,6 +182,7 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
       uint32_t* table = reinterpret_cast<uint32_t*>(in.data() + at_segs);
       segs.resize(n_segs); idx.clear(); longs.clear();
       uint32_t first = 0;
+      bool any_moves = false;
       for (uint32_t k = 0; k < n_segs; ++k) {
         Seg& sg = segs[k];
         sg.plan = todo[t0 + k].first; sg.first = first; sg.n = todo[t0 + k].second;
@@ -170,11 +190,19 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
         int32_t count[2][EG_YEARS];
         m.counts(count);
         enumerate_edits(count[0], count[1], ro->replace_with, ro->n_replace, ro->append_with, ro->n_append, m.total(0) < int64_t(snap::kBestCap), sg.edits);
-        if (sg.edits.size() != size_t(sg.n)) { set_error(who(fn, name_plan, sg.plan) + "round " + std::to_string(round) + ": the enumeration and its count disagree"); return EG_ERR_INTERNAL; }
-        local_idx.resize(sg.n);
+        sg.moves.clear();
+        if (mo) enumerate_moves(count[0], mo->max_shift, sg.moves);
+        any_moves = any_moves || !sg.moves.empty();
+        const uint32_t n_edits = uint32_t(sg.edits.size());
+        if (sg.edits.size() + sg.moves.size() != size_t(sg.n)) { set_error(who(fn, name_plan, sg.plan) + "round " + std::to_string(round) + ": the enumeration and its count disagree"); return EG_ERR_INTERNAL; }
+        local_idx.resize(n_edits);
         uint32_t n_short = 0;
-        pack_plan_edits(sg.edits.data(), sg.n, m.total(0), packed + 2 * size_t(first), local_idx.data(), &n_short);
-        for (uint32_t j = 0; j < sg.n; ++j) (j < n_short ? idx : longs).push_back(first + local_idx[j]);
+        pack_plan_edits(sg.edits.data(), n_edits, m.total(0), packed + 2 * size_t(first), local_idx.data(), &n_short);
+        for (uint32_t j = 0; j < n_edits; ++j) (j < n_short ? idx : longs).push_back(first + local_idx[j]);
+        for (uint32_t j = n_edits; j < sg.n; ++j) {      // a move keeps the lengths: the base's route
+          pack_plan_move(sg.moves[j - n_edits], packed + 2 * (size_t(first) + j));
+          (m.total(0) > kShortReplayMax ? longs : idx).push_back(first + j);
+        }
         std::fill(slot + first, slot + first + sg.n, uint32_t(sg.plan));
         table[4 * k] = first; table[4 * k + 1] = sg.n; table[4 * k + 2] = uint32_t(sg.plan);
         first += sg.n;
@@ -185,6 +213,8 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
       EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
       const uint8_t* d_edits = c->d_refine_in;
       EG_LAUNCH("k_plan_edits_many", launch_plan_edits_many(c->d_refine_bases, uint32_t(P), reinterpret_cast<const uint32_t*>(c->d_refine_in + at_slot), d_edits, n, c->d_plans, nullptr));
+      // (the move variants' blocks: over the base copies k_plan_edits_many has just written for them, on the same stream)
+      if (any_moves) EG_LAUNCH("k_plan_moves", launch_plan_moves(c->d_refine_bases, uint32_t(P), reinterpret_cast<const uint32_t*>(c->d_refine_in + at_slot), d_edits, n, c->d_plans, nullptr));
       c->n_plan_blocks = n;
       EG_TRY(launch_plans(c, S, seed, episode_index, n, n_short, true));
       EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + at_segs, n_segs, n, ro->mode, d_edits, c->d_plans, c->d_refine_bases, uint32_t(P),
@@ -206,14 +236,24 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
           return EG_ERR_INTERNAL;
         }
         // the plan on the device against the mirror: the totals of the winner's block
-        if (e.winner != 0) apply(m, sg.edits[size_t(e.winner)]);
+        const bool is_move = size_t(e.winner) >= sg.edits.size();
+        if (is_move) apply(m, sg.moves[size_t(e.winner) - sg.edits.size()]);
+        else if (e.winner != 0) apply(m, sg.edits[size_t(e.winner)]);
         if (e.off26 != int32_t(m.total(0)) || e.offd26 != int32_t(m.total(1))) {
           set_error(at + "the device's plan holds " + std::to_string(e.off26) + " + " + std::to_string(e.offd26) + " entries, the host's " +
                     std::to_string(m.total(0)) + " + " + std::to_string(m.total(1)));
           return EG_ERR_INTERNAL;
         }
         if (e.winner == 0) { stop_reason[p] = EG_REFINE_LOCAL_OPTIMUM; active[size_t(p)] = 0; }
-        else {
+        else if (msteps) {
+          eg_refine_move_step& st = msteps[size_t(p) * size_t(ro->max_rounds) + size_t(n_steps[p])];
+          std::memset(&st, 0, sizeof(st));
+          st.is_move = is_move ? 1 : 0;
+          if (is_move) st.move = sg.moves[size_t(e.winner) - sg.edits.size()]; else st.edit = sg.edits[size_t(e.winner)];
+          st.variant = e.winner; st.n_variants = int32_t(sg.n); st.n_failed = e.n_failed; st.score = e.score;
+          std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
+          if (++n_steps[p] == ro->max_rounds) { stop_reason[p] = EG_REFINE_MAX_ROUNDS; active[size_t(p)] = 0; }
+        } else {
           eg_refine_step& st = steps[size_t(p) * size_t(ro->max_rounds) + size_t(n_steps[p])];
           st.edit = sg.edits[size_t(e.winner)]; st.variant = e.winner; st.n_variants = int32_t(sg.n); st.n_failed = e.n_failed; st.score = e.score;
           std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
@@ -278,4 +318,28 @@ extern "C" int32_t eg_refine_plans(eg_ctx* c, const eg_policy_snapshot* s, const
   if (c->group_member) { set_error("eg_refine_plans: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
   EG_TRY(eg_refine_plans_validate(bases, ro));
   return refine("eg_refine_plans", true, c, s, o, bases, ro, seed, episode_index, refined, steps, n_steps, stop_reason, start_score, out);
+}
+
+extern "C" int32_t eg_refine_plans_moves_validate(const eg_plan_set* bases, const eg_refine_opts* o, const eg_refine_move_opts* mo) {
+  const char* fn = "eg_refine_plans_moves_validate";
+  EG_TRY(eg_plans_validate(bases));
+  if (bases->n_plans > EG_REFINE_MAX_PLANS) {
+    set_error(std::string(fn) + ": the set holds " + std::to_string(bases->n_plans) + " plans (at most " + std::to_string(EG_REFINE_MAX_PLANS) + ")");
+    return EG_ERR_BAD_ARG;
+  }
+  if (!mo) { set_error(std::string(fn) + ": NULL move options"); return EG_ERR_BAD_ARG; }
+  if (mo->max_shift < 0 || mo->max_shift > EG_YEARS - 1) {
+    set_error(std::string(fn) + ": max_shift = " + std::to_string(mo->max_shift) + " (0.." + std::to_string(EG_YEARS - 1) + " years; 0: no moves)");
+    return EG_ERR_BAD_ARG;
+  }
+  return validate_opts(fn, true, bases, o, mo);
+}
+
+extern "C" int32_t eg_refine_plans_moves(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro,
+                                         const eg_refine_move_opts* mo, uint64_t seed, uint64_t episode_index, eg_plan_set** refined, eg_refine_move_step* steps,
+                                         int32_t* n_steps, int32_t* stop_reason, double* start_score, eg_episode_out* out) {
+  if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plans_moves: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->group_member) { set_error("eg_refine_plans_moves: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_refine_plans_moves_validate(bases, ro, mo));
+  return refine("eg_refine_plans_moves", true, c, s, o, bases, ro, seed, episode_index, refined, nullptr, n_steps, stop_reason, start_score, out, mo, steps);
 }

@@ -2522,6 +2522,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_plan_edits.h"       // k_plan_edits: the plan blocks of a plan-edit batch from one base block and an edit per variant
 #include "eg_refine.h"           // refine::before, wave_best: what the pick of a refinement round reduces with
 #include "eg_refine_many.h"      // k_plan_edits_many, k_refine_pick_many: a refinement round, a segment of the launch's variants per plan
+#include "eg_plan_moves.h"       // k_plan_moves: the plan blocks of the variants that move an entry to another year
 
 // ---- B2: a single placement search, for parity tests of the arg-max --------------------------------------------
 __global__ void __launch_bounds__(kWave) k_place(DevTables T, int type, int yi, const uint16_t* __restrict__ cells,
@@ -3383,6 +3384,11 @@ int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, ui
 int launch_plan_edits_many(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_slot, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream) {
   if (n == 0 || n_bases == 0) return 0;
   hipLaunchKernelGGL(many::k_plan_edits_many, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_bases, n_bases, d_slot, reinterpret_cast<const uint2*>(d_edits), n, d_pool);
+  return (int)hipGetLastError();
+}
+int launch_plan_moves(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_slot, const void* d_moves, uint32_t n, uint8_t* d_pool, void* stream) {
+  if (n == 0 || n_bases == 0) return 0;
+  hipLaunchKernelGGL(k_plan_moves, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_bases, n_bases, d_slot, reinterpret_cast<const uint2*>(d_moves), n, d_pool);
   return (int)hipGetLastError();
 }
 int launch_refine_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs, uint32_t n_total, int mode, const void* d_edits, const uint8_t* d_pool,

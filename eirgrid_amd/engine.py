@@ -296,6 +296,58 @@ class PlanEdit:
         return Plan(lists[0], lists[1], plan.name)
 
 
+@dataclass(frozen=True)
+class PlanMove:
+    """One move of a plan (eg_plan_move): entry `pos` of year `year` of a list (0 = best_actions, 1 = best_deficit_actions) is taken out
+    and put back in front of entry `to_pos` of year `to_year`'s list as that list stands after the removal (to_pos = its length: behind
+    the last entry).  to_year == year reorders within the year; with to_pos == pos as well the move is the plan itself."""
+    list: int = 0
+    year: int = 0
+    pos: int = 0
+    to_year: int = 0
+    to_pos: int = 0
+
+    def struct(self) -> N.EgPlanMove:
+        return N.EgPlanMove(self.list, self.to_year, self.year, self.pos, self.to_pos)
+
+    def apply(self, plan: "Plan") -> "Plan":
+        """The moved plan (a copy), as the device builds it."""
+        lists = ([list(l) for l in plan.best_actions], [list(l) for l in plan.best_deficit_actions])
+        a = lists[self.list][self.year].pop(self.pos)
+        lists[self.list][self.to_year].insert(self.to_pos, a)
+        return Plan(lists[0], lists[1], plan.name)
+
+
+def _move_array(moves):
+    moves = list(moves)
+    arr = (N.EgPlanMove * max(len(moves), 1))()
+    for j, m in enumerate(moves):
+        arr[j] = m.struct() if isinstance(m, PlanMove) else m
+    return arr, len(moves)
+
+
+def refine_moves(base: "Plan", max_shift: int) -> "list[PlanMove]":
+    """The move variants of one round of Engine.refine_plans(..., max_shift): every best_actions entry in (year, position) order, and
+    per entry each shift d = -1, +1, -2, +2, ..., -max_shift, +max_shift that stays inside the 26 years: the entry moved behind the
+    last entry of year year + d."""
+    return [PlanMove(0, y, i, y + d, len(base.best_actions[y + d])) for y, l in enumerate(base.best_actions) for i in range(len(l))
+            for s in range(1, int(max_shift) + 1) for d in (-s, s) if 0 <= y + d < N.YEARS]
+
+
+@dataclass
+class Timing:
+    """Engine.plan_timing: per move (row 0: the base plan, as the move of an entry onto itself, or None for a plan without entries) the
+    record's status, the four metrics, the rank score (NaN for a variant that failed) and their differences from row 0 (NaN where the
+    base or the variant failed): the rows Sensitivity has for edits."""
+    moves: list
+    result: "BatchResult"
+    status: np.ndarray        # [n]
+    metrics: np.ndarray       # [n,4]
+    score: np.ndarray         # [n]
+    d_metrics: np.ndarray     # [n,4]
+    d_score: np.ndarray       # [n]
+
+
 def _edit_array(edits):
     edits = list(edits)
     arr = (N.EgPlanEdit * max(len(edits), 1))()
@@ -344,7 +396,7 @@ def refine_edits(base: "Plan", replace_with=None, append_with=None) -> "list[Pla
 class RefineStep:
     """One applied edit of Engine.refine_plan (eg_refine_step): the edit against the plan of its round, its place among the round's
     n_variants variants, how many of them were no candidates, and the score and metrics it reached."""
-    edit: "PlanEdit"
+    edit: "PlanEdit"      # (a PlanMove where the step is a move: Engine.refine_plans with max_shift > 0)
     variant: int
     n_variants: int
     n_failed: int
@@ -358,6 +410,13 @@ REFINE_STOP = ("local_optimum", "max_rounds", "base_failed")
 def _refine_steps(steps) -> "list[RefineStep]":
     """eg_refine_step structs as RefineSteps"""
     return [RefineStep(PlanEdit(PlanEdit.KINDS[s.edit.kind], s.edit.list, s.edit.year, s.edit.pos, s.edit.action), s.variant, s.n_variants, s.n_failed,
+                       s.score, np.array(s.metrics[:])) for s in steps]
+
+
+def _refine_move_steps(steps) -> "list[RefineStep]":
+    """eg_refine_move_step structs as RefineSteps, the move where the step is one"""
+    return [RefineStep(PlanMove(s.move.list, s.move.year, s.move.pos, s.move.to_year, s.move.to_pos) if s.is_move else
+                       PlanEdit(PlanEdit.KINDS[s.edit.kind], s.edit.list, s.edit.year, s.edit.pos, s.edit.action), s.variant, s.n_variants, s.n_failed,
                        s.score, np.array(s.metrics[:])) for s in steps]
 
 
@@ -553,6 +612,40 @@ class Engine:
                                                C.c_uint64(first_index), int(bool(same_index)), C.byref(out)), "eg_evaluate_plan_edits")
         return res
 
+    def evaluate_plan_moves(self, weights: ActionWeights, base: "Plan", moves, seed: int, first_index: int = 0, same_index: bool = True,
+                            enable_energy_sales=True, write_yearly=True) -> BatchResult:
+        """Score moves of one plan (eg_evaluate_plan_moves): variant j is `base` with moves[j] (PlanMove) applied, evaluated as
+        evaluate_plans would evaluate it — at global index first_index for every variant (same_index), or at first_index + j.  The
+        variants' plan blocks are built on the device."""
+        ps = PlanSet([base])
+        arr, n = _move_array(moves)
+        res = BatchResult.alloc(max(n, 1))
+        snap = weights.snapshot()
+        opts = self._opts(enable_energy_sales, False, write_yearly)
+        out = res.struct()
+        N.check(N.lib().eg_evaluate_plan_moves(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), arr, n, C.c_uint64(seed & (2**64 - 1)),
+                                               C.c_uint64(first_index), int(bool(same_index)), C.byref(out)), "eg_evaluate_plan_moves")
+        return res
+
+    def plan_timing(self, weights: ActionWeights, base: "Plan", seed: int, mode: int = 1, max_shift: int = 1) -> Timing:
+        """Which entries of `base` would be better placed in another year: the base (row 0) and the moves of refine_moves(base,
+        max_shift) in one batch, all at global index 0 of `seed`; per move the metrics, eg_rank_score in `mode` (1: optimization_mode
+        None, 2: cost_only) and their differences from the base's."""
+        moves = refine_moves(base, max_shift)
+        first = next(((y, 0) for y, l in enumerate(base.best_actions) if l), None)
+        if first is None:      # nothing to move: the base alone, through the plan batch
+            res = self.evaluate_plans(weights, [base], seed, 0)
+            rows = [None]
+        else:
+            rows = [PlanMove(0, first[0], 0, first[0], 0)] + moves      # (an entry moved onto itself: the base)
+            res = self.evaluate_plan_moves(weights, base, rows, seed, 0, True)
+        L = N.lib()
+        score = np.array([L.eg_rank_score(_p(np.ascontiguousarray(res.metrics[j]), C.c_double), int(mode)) if res.status[j] == N.EG_EP_OK else np.nan
+                          for j in range(len(rows))])
+        both = (res.status == N.EG_EP_OK) & (res.status[0] == N.EG_EP_OK)
+        d_metrics = np.where(both[:, None], res.metrics - res.metrics[0], np.nan)
+        return Timing(rows, res, res.status.copy(), res.metrics.copy(), score, d_metrics, np.where(both, score - score[0], np.nan))
+
     def debug_fetch_plan_block(self, plan: int) -> np.ndarray:
         """Test hook (eg_debug_fetch_plan_block): the bytes of plan block `plan` of the last plan or plan-edit batch."""
         out = np.zeros(N.PLAN_BLOCK_BYTES, np.uint8)
@@ -597,15 +690,18 @@ class Engine:
         return plan, _refine_steps(steps[:n_steps.value]), reason, start.value, (None if reason == "base_failed" else res)
 
     def refine_plans(self, weights: ActionWeights, bases, seed: int, index: int = 0, mode: int = 1, max_rounds: int = 64, replace_with=None,
-                     append_with=None, enable_energy_sales=True, write_yearly=True):
+                     append_with=None, enable_energy_sales=True, write_yearly=True, max_shift: int = 0):
         """Greedy refinement of many plans in one call (eg_refine_plans): the rounds of all plans stepped together, a launch holding the
         variants of as many plans as fit.  Returns a list with one tuple per plan of `bases` (1..REFINE_MAX_PLANS plans), each exactly the
-        tuple refine_plan returns for that plan alone."""
+        tuple refine_plan returns for that plan alone.
+        max_shift > 0 (eg_refine_plans_moves): behind a round's edits come the moves of refine_moves(plan, max_shift), a best_actions
+        entry shifted by up to max_shift years; a step that is a move carries a PlanMove as its `edit`."""
         ps = bases if isinstance(bases, PlanSet) else PlanSet(bases)
         n = ps.s.n_plans
         ro, keep = _refine_opts(mode, max_rounds, replace_with, append_with)
         rounds = max(int(max_rounds), 1)
-        steps = (N.EgRefineStep * (max(n, 1) * rounds))()
+        moves = int(max_shift) != 0
+        steps = ((N.EgRefineMoveStep if moves else N.EgRefineStep) * (max(n, 1) * rounds))()
         n_steps = np.zeros(max(n, 1), np.int32); stop = np.zeros(max(n, 1), np.int32)
         start = np.full(max(n, 1), np.nan)
         refined = C.POINTER(N.EgPlanSet)()
@@ -614,15 +710,21 @@ class Engine:
         opts = self._opts(enable_energy_sales, False, write_yearly)
         out = res.struct()
         L = N.lib()
-        N.check(L.eg_refine_plans(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(ro), C.c_uint64(seed & (2**64 - 1)), C.c_uint64(index),
-                                  C.byref(refined), steps, _p(n_steps, C.c_int32), _p(stop, C.c_int32), _p(start, C.c_double), C.byref(out)), "eg_refine_plans")
+        if moves:
+            mo = N.EgRefineMoveOpts(int(max_shift))
+            N.check(L.eg_refine_plans_moves(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(ro), C.byref(mo), C.c_uint64(seed & (2**64 - 1)),
+                                            C.c_uint64(index), C.byref(refined), steps, _p(n_steps, C.c_int32), _p(stop, C.c_int32), _p(start, C.c_double),
+                                            C.byref(out)), "eg_refine_plans_moves")
+        else:
+            N.check(L.eg_refine_plans(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(ro), C.c_uint64(seed & (2**64 - 1)), C.c_uint64(index),
+                                      C.byref(refined), steps, _p(n_steps, C.c_int32), _p(stop, C.c_int32), _p(start, C.c_double), C.byref(out)), "eg_refine_plans")
         plans = Plan._take_set(refined)
         names = [f.name for f in fields(BatchResult)]
         result = []
         for p in range(n):
             reason = REFINE_STOP[int(stop[p])]
             rec = None if reason == "base_failed" else BatchResult(*[np.ascontiguousarray(getattr(res, f)[p:p + 1]) for f in names])
-            result.append((plans[p], _refine_steps(steps[p * rounds:p * rounds + int(n_steps[p])]), reason, float(start[p]), rec))
+            result.append((plans[p], (_refine_move_steps if moves else _refine_steps)(steps[p * rounds:p * rounds + int(n_steps[p])]), reason, float(start[p]), rec))
         return result
 
     # device-resident path used by bench.py

@@ -461,6 +461,56 @@ int32_t eg_refine_plans(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, c
                         int32_t *n_steps           /* [n_plans] */, int32_t *stop_reason /* [n_plans] */,
                         double *start_score        /* [n_plans] or NULL */, eg_episode_out *out /* n_plans episodes or NULL */);
 
+/* Plan moves: should this plant be built in another year?  A MOVE takes one entry of one year's list out and puts it back into another
+ * year's list (or elsewhere in the same one); both lists keep their lengths.  As two edits it is a delete and then an insert, which the
+ * greedy refinement cannot cross when the first half alone is worse than the base; as a move it is one variant.
+ * eg_evaluate_plan_moves evaluates n_moves VARIANTS of one base plan (a plan set of exactly one plan), variant j being the base with
+ * move j applied to one of its two lists:
+ *   list     0 = best_actions, 1 = best_deficit_actions
+ *   year     the year index 0..25 the entry is taken from, and `pos` its position there, 0..len-1
+ *   to_year  the year index 0..25 it goes to (to_year == year: a reorder within the year)
+ *   to_pos   it is put back in front of entry to_pos of year to_year's list AS THAT LIST STANDS AFTER THE REMOVAL: 0..len', len' being
+ *            the length of year to_year, minus one when to_year == year; to_pos == len' puts it behind the last entry
+ * to_year == year with to_pos == pos is the base plan itself, the "none" of moves, so variant 0 of a batch can be the base.
+ * Everything else is the contract of eg_evaluate_plan_edits, word for word: variant j is evaluated exactly as eg_evaluate_plans
+ * evaluates the moved plan as plan j — the same replay semantics, seeded draws when a list runs out, no statistics, update or folds, the
+ * resident policy untouched, the batch left behind for eg_fetch / eg_fetch_record / eg_debug_fetch_plan_block, ranks of a group refused —
+ * at global episode first_episode_index + j (same_index = 0), or with same_index = 1 every variant at first_episode_index.  The host
+ * uploads the base plan's block once and 8 bytes per variant; the variants' plan blocks are written on the device
+ * (csrc/eg_plan_moves.h k_plan_moves).  The list lengths do not change, so every variant takes the base's short or long replay route.
+ * eg_plan_moves_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the move and the field ("move 2: to_pos 4 outside
+ * best_actions year 2031 (3 entries after the removal)") for a list above 1, a year or to_year >= 26, a pos outside the year's list, a
+ * to_pos outside 0..len', n_moves < 1, NULL moves, or a base that is not exactly one valid plan. */
+typedef struct { uint8_t list, to_year; uint16_t year; uint32_t pos, to_pos; } eg_plan_move;   /* 12 bytes */
+int32_t eg_plan_moves_validate(const eg_plan_set *base /* 1 plan */, const eg_plan_move *moves, int32_t n_moves);
+int32_t eg_evaluate_plan_moves(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts *, const eg_plan_set *base /* n_plans == 1 */,
+                               const eg_plan_move *moves, int32_t n_moves, uint64_t seed, uint64_t first_episode_index, int32_t same_index,
+                               eg_episode_out *out /* may be NULL */);
+
+/* Refinement with moves: eg_refine_plans_moves is eg_refine_plans with one more family of variants at the END of a round's enumeration.
+ * After the variants of eg_refine_plans (the base, the deletes, the replaces, the appends) come the MOVE variants: for every
+ * best_actions entry in (year, position) order, and for each shift d in the order -1, +1, -2, +2, ..., -max_shift, +max_shift with
+ * 0 <= year + d <= 25, that entry moved behind the last entry of year year + d (eg_plan_move: list 0, to_year = year + d, to_pos = the
+ * length of that year's list).  Entries of best_deficit_actions are not moved.  Variant 0 stays the base and ties go to the lowest
+ * variant, so on a tie a plain edit wins over a move.
+ * A step says with is_move which of `edit` / `move` it holds (against the plan of its round); the other one is zeroed.
+ * EG_REFINE_MAX_VARIANTS holds over edits and moves together, with eg_refine_plans' messages: round 0 is refused by the validator, a
+ * later round fails the whole call.  The move variants ride in the launches of eg_refine_plans, behind their plan's edits in its
+ * segment: a move is packed into 8 bytes whose first byte is no edit kind, k_plan_edits_many writes a copy of the base for it,
+ * csrc/eg_plan_moves.h k_plan_moves overwrites that block behind it on the same stream, and k_refine_pick_many picks as before.
+ * With max_shift == 0 every returned field equals eg_refine_plans' and is_move is 0 throughout.  Everything else is eg_refine_plans'
+ * contract.
+ * eg_refine_plans_moves_validate runs the checks alone: those of eg_refine_plans_validate, move options that are not NULL, max_shift
+ * 0..25, and per plan the variant count of round 0, moves included. */
+typedef struct { int32_t max_shift; } eg_refine_move_opts;   /* 0..25 years; 0: no moves */
+typedef struct { int32_t is_move; eg_plan_edit edit; eg_plan_move move; int32_t variant, n_variants, n_failed;
+                 double score; double metrics[4]; } eg_refine_move_step;
+int32_t eg_refine_plans_moves_validate(const eg_plan_set *bases, const eg_refine_opts *, const eg_refine_move_opts *);
+int32_t eg_refine_plans_moves(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, const eg_plan_set *bases /* 1..EG_REFINE_MAX_PLANS */,
+                              const eg_refine_opts *, const eg_refine_move_opts *, uint64_t seed, uint64_t episode_index,
+                              eg_plan_set **refined, eg_refine_move_step *steps /* [n_plans][max_rounds] */, int32_t *n_steps,
+                              int32_t *stop_reason, double *start_score, eg_episode_out *out);
+
 /* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
  * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
  * copies, no collective library — and every call enqueues the work of all ranks from the calling thread without synchronising
