@@ -90,12 +90,18 @@ class EgRefineMoveStep(C.Structure):
                 ("n_failed", C.c_int32), ("score", C.c_double), ("metrics", C.c_double * 4)]
 
 
-assert C.sizeof(EgPlanMove) == 12
+class EgPlanCross(C.Structure):
+    _fields_ = [("a", C.c_uint16), ("b", C.c_uint16), ("from_year", C.c_uint8), ("to_year", C.c_uint8)]
+
+
+assert C.sizeof(EgPlanMove) == 12 and C.sizeof(EgPlanCross) == 6
 
 EDIT_NONE, EDIT_DELETE, EDIT_REPLACE, EDIT_INSERT = 0, 1, 2, 3
 REFINE_LOCAL_OPTIMUM, REFINE_MAX_ROUNDS, REFINE_BASE_FAILED = 0, 1, 2
 REFINE_MAX_VARIANTS = 16384      # EG_REFINE_MAX_VARIANTS
 REFINE_MAX_PLANS = 256           # EG_REFINE_MAX_PLANS
+CROSS_MAX_PARENTS = 256          # EG_CROSS_MAX_PARENTS
+CROSS_MAX_VARIANTS = 16384       # EG_CROSS_MAX_VARIANTS
 PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
 DEBUG_LIST_LEN, DEBUG_FOLD_BEST_RESULT, DEBUG_FOLD_TOP_K = 8, 1, 2      # EG_DEBUG_*
 
@@ -127,6 +133,7 @@ EXPORTS = [
     "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block", "eg_plans_save", "eg_refine_validate", "eg_refine_plan",
     "eg_refine_plans_validate", "eg_refine_plans", "eg_debug_refine_pick_many",
     "eg_plan_moves_validate", "eg_evaluate_plan_moves", "eg_refine_plans_moves_validate", "eg_refine_plans_moves",
+    "eg_plan_crosses_validate", "eg_evaluate_plan_crosses",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -311,6 +318,13 @@ def lib():
         L.eg_refine_plans_moves.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts),
                                             C.POINTER(EgRefineMoveOpts), C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgRefineMoveStep),
                                             _i32p, _i32p, _dp, C.POINTER(EgEpisodeOut)]
+    # (likewise: a probe may load a build of the parent commit, which has no plan crosses)
+    if hasattr(L, "eg_evaluate_plan_crosses") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_plan_crosses_validate.restype = C.c_int32
+        L.eg_plan_crosses_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgPlanCross), C.c_int32]
+        L.eg_evaluate_plan_crosses.restype = C.c_int32
+        L.eg_evaluate_plan_crosses.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgPlanCross),
+                                               C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(EgEpisodeOut)]
     # (likewise: scripts/pareto_probe.py may load a build of the parent commit, which has no Pareto archive)
     if hasattr(L, "eg_pareto_track") or not os.environ.get("EIRGRID_LIB"):
         L.eg_pareto_track.restype = C.c_int32

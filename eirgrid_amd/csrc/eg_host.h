@@ -137,6 +137,7 @@ struct eg_ctx {
   eg::DevBuf<uint8_t> d_eval_snap, d_plans;
   eg::DevBuf<uint32_t> d_plan_index;
   // plan-edit batches (eg_evaluate_plan_edits): the base plan's block followed by the packed edits, 8 bytes each — what k_plan_edits reads
+  // (a plan-cross batch, eg_evaluate_plan_crosses: every parent's block, then the packed crosses — what k_plan_crosses reads)
   eg::DevBuf<uint8_t> d_plan_edit_in;
   size_t n_plan_blocks = 0;      // blocks of the last plan or plan-edit batch in d_plans (eg_debug_fetch_plan_block)
   // plan refinement (eg_refine_plan, eg_refine_plans): the step log k_refine_pick_many writes, an entry per plan of a launch from the

@@ -505,6 +505,10 @@ int launch_refine_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs
 // variant whose first byte is not the tag is left alone.  The tag is no edit kind: k_plan_edits_many reads such a variant as "none".
 constexpr uint32_t kPlanMoveTag = 4;
 int launch_plan_moves(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_slot, const void* d_moves, uint32_t n, uint8_t* d_pool, void* stream);
+// k_plan_crosses (eg_plan_crosses.h): the n plan blocks of a plan-cross batch into d_pool from the n_parents parent blocks at d_parents and
+// n packed crosses (8 bytes each: a | b << 8 | from_year << 16 | to_year << 24, then zero): parent a with the years [from_year, to_year)
+// of both lists taken from parent b
+int launch_plan_crosses(const uint8_t* d_parents, uint32_t n_parents, const void* d_crosses, uint32_t n, uint8_t* d_pool, void* stream);
 // eg_checkpoint.cpp: one plan as a set eg_plans_free releases (counts [26], the flat lists)
 eg_plan_set* make_plan_set(const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact, const char* name);
 // ... and n plans as one set: counts [n][26], the flat lists plan-major, names [n] (NULL entries: "")

@@ -1,0 +1,107 @@
+// eg_plan_crosses.h — k_plan_crosses: the plan blocks of a plan-cross batch (include/eirgrid_hip.h eg_evaluate_plan_crosses), written on
+// the device from the parents' blocks and an 8-byte cross per variant, on the stream the plan launches use.  Included by eg_rollout.hip
+// (eg_rollout.o only) behind eg_plan_moves.h.
+//
+// Variant j is parent a with BOTH lists of the years from <= y < to replaced by parent b's lists of those years, and block j must be
+// byte for byte what eg_plans.cpp write_lists builds for that child in a zeroed block.  With oA, oB the parents' prefix offsets of one list:
+//   lists    A[0, oA[from]), then B[oB[from], oB[to]), then A[oA[to], oA[26]), then zeros up to the capacity: three byte-unaligned
+//            segments.  A lane writes 8-byte words; an output word can hold bytes of all three (a middle segment shorter than 8 bytes),
+//            so a lane forms up to three candidate words — A's word in place, B's bytes at the middle segment's shift, A's bytes at the
+//            tail's shift, the latter two funnel-shifted from two aligned words each — and selects among them bytewise.  A candidate
+//            is loaded only by the lanes whose word holds a byte of its segment; reads outside [0, kBestCap) count as zero.  Every store
+//            instruction of the wave writes 512 consecutive bytes.  The two lists have offsets of their own, so their shifts differ.
+//   offsets  y <= from: oA[y]; from < y <= to: oA[from] + oB[y] - oB[from]; to < y <= 26: oA[y] plus the difference of the two windows'
+//            lengths; entry 27 stays the padding zero.
+//   masks    a year's two lists come from one parent, so its two masks are that parent's, copied: nothing is recomputed.
+// from == to or a == b: parent a's block, copied.  No LDS, no scratch memory, nothing but vector loads and stores; the host has validated
+// every cross (eg_plan_crosses_validate), the kernel clamps what it indexes with all the same and only ever writes inside block j.
+#pragma once
+
+namespace pcross {
+
+using namespace pedit;      // the block layout (kOff*, kWords)
+using pmove::bytes_before;
+
+// what the host packs per variant (eg_plans.cpp pack_plan_cross): a | b << 8 | from_year << 16 | to_year << 24, then zero
+struct Cross { uint32_t a, b; int from, to; };
+__device__ __forceinline__ Cross unpack_cross(uint2 w, uint32_t n_parents) {
+  Cross x;
+  x.a = w.x & 0xFFu; x.b = (w.x >> 8) & 0xFFu; x.to = (int)(w.x >> 24); x.from = (int)((w.x >> 16) & 0xFFu);
+  if (x.a >= n_parents) x.a = n_parents - 1u;
+  if (x.b >= n_parents) x.b = n_parents - 1u;
+  if (x.to > EG_YEARS) x.to = EG_YEARS;
+  if (x.from > x.to) x.from = x.to;
+  return x;
+}
+__device__ __forceinline__ int clamp_len(int v) { return v < 0 ? 0 : (v > (int)snap::kBestCap ? (int)snap::kBestCap : v); }
+
+// the 8 bytes of the flat list `src` from byte q on (q of either sign; bytes outside the list are zero); need == false: not loaded
+__device__ __forceinline__ unsigned long long bytes_at(const unsigned long long* src, int q, bool need) {
+  const int k = q >> 3, r = (q & 7) * 8;      // (an arithmetic shift: the word below a negative q)
+  const unsigned long long lo = (need && k >= 0 && k < kWords) ? src[k] : 0ull;
+  const unsigned long long hi = (need && r != 0 && k + 1 >= 0 && k + 1 < kWords) ? src[k + 1] : 0ull;
+  return r == 0 ? lo : (lo >> r) | (hi << (64 - r));
+}
+
+// one flat list of the child: head [0, p0) of A in place, middle [p0, p1) from B's byte p0 + sB on, tail [p1, end) from A's byte
+// p1 + sA on, zeros behind; 8 bytes a lane and step
+__device__ __forceinline__ void write_crossed_list(unsigned long long* dst, const unsigned long long* A, const unsigned long long* B, int lane,
+                                                   int p0, int p1, int end, int sB, int sA) {
+#pragma unroll
+  for (int r = 0; r < kWords / kWave; ++r) {
+    const int w = r * kWave + lane;
+    const unsigned long long head = bytes_before(p0, w), upto_mid = bytes_before(p1, w), upto_end = bytes_before(end, w);
+    const unsigned long long mid = upto_mid & ~head, tail = upto_end & ~upto_mid;
+    const unsigned long long h = head != 0ull ? A[w] : 0ull;
+    const unsigned long long m = bytes_at(B, 8 * w + sB, mid != 0ull);
+    const unsigned long long t = bytes_at(A, 8 * w + sA, tail != 0ull);
+    dst[w] = (h & head) | (m & mid) | (t & tail);
+  }
+}
+
+}  // namespace pcross
+
+// four variants per workgroup of 256, one wave each
+__global__ void __launch_bounds__(256) k_plan_crosses(const uint8_t* __restrict__ parents, uint32_t n_parents, const uint2* __restrict__ crosses, uint32_t n,
+                                                      uint8_t* __restrict__ pool) {
+  using namespace pcross;
+  const int lane = threadIdx.x & (kWave - 1);
+  const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (j >= n || n_parents == 0u) return;
+  const Cross x = unpack_cross(crosses[j], n_parents);
+  const uint8_t* pa = parents + (size_t)x.a * snap::kPlanStride;
+  const uint8_t* pb = parents + (size_t)x.b * snap::kPlanStride;
+  uint8_t* blk = pool + (size_t)j * snap::kPlanStride;
+  // (a rolled loop, one list's code run twice: with both bodies in one block hipcc 7.2's register allocator crashes under the
+  //  iterative-ilp scheduler this file is built with)
+#pragma unroll 1
+  for (int which = 0; which < 2; ++which) {
+    const int32_t* oA = reinterpret_cast<const int32_t*>(pa + (which ? kOffDOff : kOffOff));
+    const int32_t* oB = reinterpret_cast<const int32_t*>(pb + (which ? kOffDOff : kOffOff));
+    // the child's three segments: [0, p0) A's head, [p0, p1) B's window, [p1, end) A's tail
+    const int p0 = clamp_len(oA[x.from]), a_to = clamp_len(oA[x.to]), b_from = clamp_len(oB[x.from]);
+    const int p1 = clamp_len(p0 + clamp_len(oB[x.to]) - b_from);
+    const int end = clamp_len(p1 + clamp_len(oA[EG_YEARS]) - a_to);
+    write_crossed_list(reinterpret_cast<unsigned long long*>(blk + (which ? kOffDAct : kOffAct)),
+                       reinterpret_cast<const unsigned long long*>(pa + (which ? kOffDAct : kOffAct)),
+                       reinterpret_cast<const unsigned long long*>(pb + (which ? kOffDAct : kOffAct)), lane, p0, p1, end, b_from - p0, a_to - p1);
+  }
+  // prefix offsets: lanes 0..27 the first list's, 32..59 the second's (entry 27 is padding: parent a's zero)
+  {
+    const int l = lane & 31, which = lane >> 5;
+    if (l < 28) {
+      const int32_t* oA = reinterpret_cast<const int32_t*>(pa + (which ? kOffDOff : kOffOff));
+      const int32_t* oB = reinterpret_cast<const int32_t*>(pb + (which ? kOffDOff : kOffOff));
+      uint32_t v = (uint32_t)oA[l];      // (unsigned: whatever the blocks hold, the sums wrap)
+      if (l > x.from && l <= x.to) v = (uint32_t)oA[x.from] + (uint32_t)oB[l] - (uint32_t)oB[x.from];
+      else if (l > x.to && l <= EG_YEARS) v += ((uint32_t)oB[x.to] - (uint32_t)oB[x.from]) - ((uint32_t)oA[x.to] - (uint32_t)oA[x.from]);
+      reinterpret_cast<int32_t*>(blk + (which ? kOffDOff : kOffOff))[l] = (int32_t)v;
+    }
+  }
+  // masks: year y's two are those of the parent its lists come from
+  if (lane < EG_YEARS) {
+    const uint8_t* p = (lane >= x.from && lane < x.to) ? pb : pa;
+    reinterpret_cast<unsigned long long*>(blk + kOffMask)[lane] = reinterpret_cast<const unsigned long long*>(p + kOffMask)[lane];
+    reinterpret_cast<unsigned long long*>(blk + kOffDMask)[lane] = reinterpret_cast<const unsigned long long*>(p + kOffDMask)[lane];
+  }
+}

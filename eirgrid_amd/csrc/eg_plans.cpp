@@ -1,5 +1,5 @@
 // eg_plans.cpp — a policy in snapshot layout (shared with eg_upload_snapshot) and plan batches: eg_evaluate_plans, eg_evaluate_plan_edits,
-// eg_evaluate_plan_moves, launch_plans (eg_refine.cpp loops over the same pieces).
+// eg_evaluate_plan_moves, eg_evaluate_plan_crosses, launch_plans (eg_refine.cpp loops over the same pieces).
 #include <algorithm>
 #include <cstring>
 
@@ -135,17 +135,19 @@ void eg::pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len
 }
 namespace {
 // The rest of a plan batch whose routing is in c->d_plan_index: the policy into its device snapshot, then the launches.  `blocks`: a
-// plan-edit or plan-move batch, whose blocks k_plan_edits / k_plan_moves writes on the launches' stream from c->d_plan_edit_in (the base
-// block, then the packed edits or moves).
+// plan-edit, plan-move or plan-cross batch, whose blocks k_plan_edits / k_plan_moves / k_plan_crosses writes on the launches' stream from
+// c->d_plan_edit_in (the base block — a cross batch: the n_parents parent blocks —, then the packed edits, moves or crosses).
 // (The snapshot is staged last before the launches: a launch's start event takes the time the stream's previous command ended — with
 //  the snapshot staged first, eg_timing_read counted the host building the plan blocks.)
-enum class Blocks { kHost, kEdits, kMoves };      // who writes the plan blocks: the host has, k_plan_edits, k_plan_moves
+enum class Blocks { kHost, kEdits, kMoves, kCrosses };      // who writes the plan blocks: the host has, k_plan_edits, k_plan_moves, k_plan_crosses
 int stage_and_launch_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short,
-                           Blocks blocks, bool same_index) {
+                           Blocks blocks, bool same_index, uint32_t n_parents = 1u) {
   DevSnapshot S{};
   EG_TRY(stage_eval_snapshot(c, s, o, &S));
   if (blocks == Blocks::kEdits) EG_LAUNCH("k_plan_edits", launch_plan_edits(c->d_plan_edit_in, c->d_plan_edit_in + snap::kPlanStride, n, c->d_plans, nullptr));
   if (blocks == Blocks::kMoves) EG_LAUNCH("k_plan_moves", launch_plan_moves(c->d_plan_edit_in, 1u, nullptr, c->d_plan_edit_in + snap::kPlanStride, n, c->d_plans, nullptr));
+  if (blocks == Blocks::kCrosses)
+    EG_LAUNCH("k_plan_crosses", launch_plan_crosses(c->d_plan_edit_in, n_parents, c->d_plan_edit_in + size_t(n_parents) * snap::kPlanStride, n, c->d_plans, nullptr));
   c->n_plan_blocks = n;
   return launch_plans(c, S, seed, first_index, n, n_short, same_index);
 }
@@ -299,6 +301,94 @@ extern "C" int32_t eg_evaluate_plan_moves(eg_ctx* c, const eg_policy_snapshot* s
   EG_HIP(hipMemcpy(c->d_plan_edit_in, in.data(), in.size(), hipMemcpyHostToDevice));
   EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
   EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, Blocks::kMoves, same_index != 0));
+  return out ? eg_fetch(c, out) : EG_OK;
+}
+
+// ---------------------------------------------------------------- plan crosses (include/eirgrid_hip.h eg_evaluate_plan_crosses)
+static_assert(sizeof(eg_plan_cross) == 6, "eg_plan_cross is part of the C ABI");
+static_assert(EG_CROSS_MAX_PARENTS <= 256, "a parent index is packed into one byte (eg_plan_crosses.h unpack_cross)");
+namespace {
+// the two lists' prefix offsets of every plan of a valid set: off[w][p * 27 + y], w = 0 best_actions, 1 best_deficit_actions
+void parent_offsets(const eg_plan_set* p, std::vector<int32_t> off[2]) {
+  const int32_t* count[2] = {p->best_count, p->best_deficit_count};
+  for (int w = 0; w < 2; ++w) {
+    off[w].assign(size_t(p->n_plans) * 27, 0);
+    for (int32_t j = 0; j < p->n_plans; ++j)
+      for (int y = 0; y < EG_YEARS; ++y) off[w][size_t(j) * 27 + y + 1] = off[w][size_t(j) * 27 + y] + count[w][size_t(j) * EG_YEARS + y];
+  }
+}
+// the length of list w of the child of cross x: a's, with a's window taken out and b's put in
+int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x) {
+  const int32_t* oa = off.data() + size_t(x.a) * 27;
+  const int32_t* ob = off.data() + size_t(x.b) * 27;
+  return int64_t(oa[EG_YEARS]) - (oa[x.to_year] - oa[x.from_year]) + (ob[x.to_year] - ob[x.from_year]);
+}
+}  // namespace
+
+extern "C" int32_t eg_plan_crosses_validate(const eg_plan_set* parents, const eg_plan_cross* crosses, int32_t n_crosses) {
+  auto fail = [](const std::string& m) { set_error("eg_plan_crosses_validate: " + m); return EG_ERR_BAD_ARG; };
+  EG_TRY(eg_plans_validate(parents));
+  if (parents->n_plans > EG_CROSS_MAX_PARENTS)
+    return fail("the set holds " + std::to_string(parents->n_plans) + " plans (at most " + std::to_string(EG_CROSS_MAX_PARENTS) + ")");
+  if (n_crosses < 1 || n_crosses > EG_CROSS_MAX_VARIANTS) return fail("n_crosses = " + std::to_string(n_crosses) + " (1.." + std::to_string(EG_CROSS_MAX_VARIANTS) + ")");
+  if (!crosses) return fail("NULL crosses");
+  const char* field[2] = {"best_actions", "best_deficit_actions"};
+  std::vector<int32_t> off[2];
+  parent_offsets(parents, off);
+  for (int32_t j = 0; j < n_crosses; ++j) {
+    const eg_plan_cross& x = crosses[j];
+    const std::string who = "cross " + std::to_string(j) + ": ";
+    if (int32_t(x.a) >= parents->n_plans) return fail(who + "a " + std::to_string(int(x.a)) + " >= n_plans " + std::to_string(parents->n_plans));
+    if (int32_t(x.b) >= parents->n_plans) return fail(who + "b " + std::to_string(int(x.b)) + " >= n_plans " + std::to_string(parents->n_plans));
+    if (x.to_year > EG_YEARS) return fail(who + "to_year " + std::to_string(int(x.to_year)) + " (at most " + std::to_string(EG_YEARS) + ")");
+    if (x.from_year > x.to_year) return fail(who + "from_year " + std::to_string(int(x.from_year)) + " > to_year " + std::to_string(int(x.to_year)));
+    for (int w = 0; w < 2; ++w) {
+      const int64_t len = child_len(off[w], x);
+      if (len > int64_t(snap::kBestCap))
+        return fail(who + field[w] + " would hold " + std::to_string(len) + " entries (at most " + std::to_string(snap::kBestCap) + ")");
+    }
+  }
+  return EG_OK;
+}
+
+extern "C" int32_t eg_evaluate_plan_crosses(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* parents, const eg_plan_cross* crosses,
+                                            int32_t n_crosses, uint64_t seed, uint64_t first_index, int32_t same_index, eg_episode_out* out) {
+  if (!c || !s || !s->weights || !s->deficit_weights) { set_error("eg_evaluate_plan_crosses: bad argument"); return EG_ERR_BAD_ARG; }
+  if (c->group_member) { set_error("eg_evaluate_plan_crosses: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_plan_crosses_validate(parents, crosses, n_crosses));
+  EG_TRY(check_policy(s, o, "eg_evaluate_plan_crosses"));
+  EG_HIP(hipSetDevice(c->device));
+  const uint32_t n = uint32_t(n_crosses), P = uint32_t(parents->n_plans);
+  EG_TRY(ensure_outputs(c, n));
+  // what goes up: every parent's block, once, and the packed crosses (eg_plan_crosses.h unpack_cross); the routing from the counts — two
+  // short parents can make a long child and the reverse
+  std::vector<uint8_t> in(size_t(P) * snap::kPlanStride + size_t(n) * 8, 0);
+  {
+    int64_t pos = 0, dpos = 0;
+    for (uint32_t p = 0; p < P; ++p) {
+      const int32_t* cnt = parents->best_count + size_t(p) * EG_YEARS;
+      const int32_t* dcnt = parents->best_deficit_count + size_t(p) * EG_YEARS;
+      write_lists(in.data() + size_t(p) * snap::kPlanStride, cnt, parents->best_actions + pos, dcnt, parents->best_deficit_actions + dpos);
+      for (int y = 0; y < EG_YEARS; ++y) { pos += cnt[y]; dpos += dcnt[y]; }
+    }
+  }
+  std::vector<int32_t> off[2];
+  parent_offsets(parents, off);
+  uint32_t* packed = reinterpret_cast<uint32_t*>(in.data() + size_t(P) * snap::kPlanStride);
+  std::vector<uint32_t> idx(n), longs;
+  uint32_t n_short = 0;
+  for (uint32_t j = 0; j < n; ++j) {
+    const eg_plan_cross& x = crosses[j];
+    packed[2 * size_t(j)] = uint32_t(x.a) | uint32_t(x.b) << 8 | uint32_t(x.from_year) << 16 | uint32_t(x.to_year) << 24;
+    if (child_len(off[0], x) > kShortReplayMax) longs.push_back(j); else idx[n_short++] = j;
+  }
+  std::copy(longs.begin(), longs.end(), idx.begin() + n_short);
+  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
+  EG_HIP(c->d_plan_index.reserve(n));
+  EG_HIP(c->d_plan_edit_in.reserve(in.size()));
+  EG_HIP(hipMemcpy(c->d_plan_edit_in, in.data(), in.size(), hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
+  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, Blocks::kCrosses, same_index != 0, P));
   return out ? eg_fetch(c, out) : EG_OK;
 }
 

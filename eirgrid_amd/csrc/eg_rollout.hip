@@ -2523,6 +2523,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_refine.h"           // refine::before, wave_best: what the pick of a refinement round reduces with
 #include "eg_refine_many.h"      // k_plan_edits_many, k_refine_pick_many: a refinement round, a segment of the launch's variants per plan
 #include "eg_plan_moves.h"       // k_plan_moves: the plan blocks of the variants that move an entry to another year
+#include "eg_plan_crosses.h"     // k_plan_crosses: the plan blocks of the variants that splice one parent's years into another
 
 // ---- B2: a single placement search, for parity tests of the arg-max --------------------------------------------
 __global__ void __launch_bounds__(kWave) k_place(DevTables T, int type, int yi, const uint16_t* __restrict__ cells,
@@ -3389,6 +3390,11 @@ int launch_plan_edits_many(const uint8_t* d_bases, uint32_t n_bases, const uint3
 int launch_plan_moves(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_slot, const void* d_moves, uint32_t n, uint8_t* d_pool, void* stream) {
   if (n == 0 || n_bases == 0) return 0;
   hipLaunchKernelGGL(k_plan_moves, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_bases, n_bases, d_slot, reinterpret_cast<const uint2*>(d_moves), n, d_pool);
+  return (int)hipGetLastError();
+}
+int launch_plan_crosses(const uint8_t* d_parents, uint32_t n_parents, const void* d_crosses, uint32_t n, uint8_t* d_pool, void* stream) {
+  if (n == 0 || n_parents == 0) return 0;
+  hipLaunchKernelGGL(k_plan_crosses, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_parents, n_parents, reinterpret_cast<const uint2*>(d_crosses), n, d_pool);
   return (int)hipGetLastError();
 }
 int launch_refine_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs, uint32_t n_total, int mode, const void* d_edits, const uint8_t* d_pool,

@@ -334,6 +334,88 @@ def refine_moves(base: "Plan", max_shift: int) -> "list[PlanMove]":
             for s in range(1, int(max_shift) + 1) for d in (-s, s) if 0 <= y + d < N.YEARS]
 
 
+@dataclass(frozen=True)
+class PlanCross:
+    """One cross of two plans of a parent set (eg_plan_cross): parent `a` with BOTH lists of the years from_year <= y < to_year replaced
+    by parent `b`'s lists of those years (0 <= from_year <= to_year <= 26).  from_year == to_year or a == b is parent a itself;
+    to_year == 26 is the one-point crossover (head of a, tail of b); to_year == from_year + 1 transplants one year."""
+    a: int = 0
+    b: int = 0
+    from_year: int = 0
+    to_year: int = 0
+
+    def struct(self) -> N.EgPlanCross:
+        return N.EgPlanCross(self.a, self.b, self.from_year, self.to_year)
+
+    def apply(self, parents) -> "Plan":
+        """The child (a new plan, named after parent a), as the device builds it."""
+        pa, pb = parents[self.a], parents[self.b]
+        take = lambda la, lb: [list(lb[y] if self.from_year <= y < self.to_year else la[y]) for y in range(N.YEARS)]
+        return Plan(take(pa.best_actions, pb.best_actions), take(pa.best_deficit_actions, pb.best_deficit_actions), pa.name)
+
+
+def _cross_array(crosses):
+    crosses = list(crosses)
+    arr = (N.EgPlanCross * max(len(crosses), 1))()
+    for j, x in enumerate(crosses):
+        arr[j] = x.struct() if isinstance(x, PlanCross) else x
+    return arr, len(crosses)
+
+
+def cross_pairs(n_plans: int, cuts=range(1, 26)) -> "list[PlanCross]":
+    """The variants of Engine.cross_front over n_plans parents: every parent itself, PlanCross(p, p, 0, 0), in order; then for a, b != a
+    and c of `cuts`, in lexicographic order, the one-point crossover PlanCross(a, b, c, 26): a's years before c, b's from c on."""
+    cuts = [int(c) for c in cuts]
+    return [PlanCross(p, p, 0, 0) for p in range(n_plans)] + \
+           [PlanCross(a, b, c, N.YEARS) for a in range(n_plans) for b in range(n_plans) if b != a for c in cuts]
+
+
+def _objective_mask(objectives, who: str) -> int:
+    mask = 0
+    for name in objectives:
+        if name not in PARETO_OBJECTIVES:
+            raise ValueError(f"{who}: unknown objective {name!r} (one of {', '.join(PARETO_OBJECTIVES)})")
+        mask |= 1 << PARETO_OBJECTIVES.index(name)
+    return mask
+
+
+def pareto_filter(front_index, front_metrics, index, metrics, status, mask: int):
+    """One step of a streaming non-dominated filter on the host, with eg_pareto_track's definitions over the objectives of `mask` (bit
+    i = metric i): an entry is valid with status EG_EP_OK and none of its four metrics NaN; a dominates b when it is at least as good
+    in every active metric (lower emissions and cost, higher opinion and reliability) and strictly better in one; entries whose
+    active metrics are all equal are one point, held once by the entry that came first.  (front_index [f], front_metrics [f,4]): a
+    front in ascending index; the entries (index [n] ascending and above the front's, metrics [n,4], status [n]) are taken in in
+    order.  Returns the new (front_index, front_metrics), ascending."""
+    active = [i for i in range(4) if mask >> i & 1]
+    sign = np.array([1.0, -1.0, 1.0, -1.0])[active]      # (as costs: lower is better)
+    fi = [int(i) for i in front_index]
+    fm = np.asarray(front_metrics, np.float64).reshape(-1, 4)
+    fg = fm[:, active] * sign
+    metrics = np.asarray(metrics, np.float64).reshape(-1, 4)
+    valid = (np.asarray(status) == N.EG_EP_OK) & ~np.isnan(metrics).any(axis=1)
+    for j in np.flatnonzero(valid):
+        g = metrics[j, active] * sign
+        if len(fi) and (fg <= g).all(axis=1).any():      # dominated by a held point, or the same point
+            continue
+        keep = ~(g <= fg).all(axis=1)                    # (none of them equals g: what g is at least as good as, it dominates)
+        fi = [i for i, k in zip(fi, keep) if k] + [int(index[j])]
+        fm = np.concatenate([fm[keep], metrics[j:j + 1]]); fg = np.concatenate([fg[keep], g[None]])
+    return np.array(fi, np.int64), fm
+
+
+@dataclass
+class CrossFront:
+    """Engine.cross_front: the non-dominated variants among the parents and their one-cut children, a row each in ascending variant
+    number — the variant's number in cross_pairs' order, its PlanCross, its four metrics, its rank score and whether it is a parent."""
+    variant: np.ndarray       # [k]
+    crosses: list             # [k] PlanCross
+    metrics: np.ndarray       # [k,4]
+    score: np.ndarray         # [k]
+    is_parent: np.ndarray     # [k] bool
+    n_variants: int           # variants evaluated
+    n_valid: int              # ... of which valid
+
+
 @dataclass
 class Timing:
     """Engine.plan_timing: per move (row 0: the base plan, as the move of an entry onto itself, or None for a plan without entries) the
@@ -627,6 +709,53 @@ class Engine:
                                                C.c_uint64(first_index), int(bool(same_index)), C.byref(out)), "eg_evaluate_plan_moves")
         return res
 
+    def evaluate_plan_crosses(self, weights: ActionWeights, parents, crosses, seed: int, first_index: int = 0, same_index: bool = True,
+                              enable_energy_sales=True, write_yearly=True) -> BatchResult:
+        """Score crosses of a set of parent plans (eg_evaluate_plan_crosses): variant j is crosses[j] (PlanCross) applied to `parents`,
+        evaluated as evaluate_plans would evaluate it — at global index first_index for every variant (same_index), or at
+        first_index + j.  The variants' plan blocks are built on the device."""
+        ps = parents if isinstance(parents, PlanSet) else PlanSet(parents)
+        arr, n = _cross_array(crosses)
+        res = BatchResult.alloc(max(n, 1))
+        snap = weights.snapshot()
+        opts = self._opts(enable_energy_sales, False, write_yearly)
+        out = res.struct()
+        N.check(N.lib().eg_evaluate_plan_crosses(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), arr, n, C.c_uint64(seed & (2**64 - 1)),
+                                                 C.c_uint64(first_index), int(bool(same_index)), C.byref(out)), "eg_evaluate_plan_crosses")
+        return res
+
+    def cross_front(self, weights: ActionWeights, parents, seed: int, index: int = 0, objectives=PARETO_OBJECTIVES, cost_only: bool = False,
+                    cuts=range(1, 26), max_variants: int = N.CROSS_MAX_VARIANTS) -> CrossFront:
+        """The non-dominated plans among `parents` and their one-cut children: the variants of cross_pairs(len(parents), cuts), evaluated
+        in chunks of at most max_variants (<= 16 384) in order, every one at global index `index` of `seed` (the same fallback draws),
+        and filtered on the host with eg_pareto_track's definitions over `objectives` (pareto_filter), chunk by chunk against the
+        front so far; an equal point is held once, at the lowest variant number.  Per variant only the metrics and the status come
+        back (36 bytes).  The context's own Pareto archive is not touched.  cost_only picks the rank score of the rows."""
+        mask = _objective_mask(objectives, "cross_front")
+        if mask == 0:
+            raise ValueError("cross_front: no objectives")
+        if not 1 <= int(max_variants) <= N.CROSS_MAX_VARIANTS:
+            raise ValueError(f"cross_front: max_variants = {max_variants} (1..{N.CROSS_MAX_VARIANTS})")
+        parents = list(parents)
+        ps = PlanSet(parents)
+        crosses = cross_pairs(len(parents), cuts)
+        snap = weights.snapshot()
+        opts = self._opts(True, False, False)      # (no yearly rows: nothing reads them)
+        L = N.lib()
+        fi, fm = np.zeros(0, np.int64), np.zeros((0, 4))
+        n_valid = 0
+        for first in range(0, len(crosses), int(max_variants)):
+            arr, n = _cross_array(crosses[first:first + int(max_variants)])
+            N.check(L.eg_evaluate_plan_crosses(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), arr, n, C.c_uint64(seed & (2**64 - 1)),
+                                               C.c_uint64(index), 1, None), "eg_evaluate_plan_crosses")
+            metrics = np.zeros((n, 4)); status = np.zeros(n, np.int32)
+            out = N.EgEpisodeOut(metrics=_p(metrics, C.c_double), status=_p(status, C.c_int32))
+            N.check(L.eg_fetch(self.h, C.byref(out)), "eg_fetch")
+            n_valid += int(((status == N.EG_EP_OK) & ~np.isnan(metrics).any(axis=1)).sum())
+            fi, fm = pareto_filter(fi, fm, np.arange(first, first + n), metrics, status, mask)
+        score = np.array([rank_score(m, cost_only) for m in fm])
+        return CrossFront(fi, [crosses[i] for i in fi], fm, score, fi < len(parents), len(crosses), n_valid)
+
     def plan_timing(self, weights: ActionWeights, base: "Plan", seed: int, mode: int = 1, max_shift: int = 1) -> Timing:
         """Which entries of `base` would be better placed in another year: the base (row 0) and the moves of refine_moves(base,
         max_shift) in one batch, all at global index 0 of `seed`; per move the metrics, eg_rank_score in `mode` (1: optimization_mode
@@ -882,11 +1011,7 @@ class Engine:
         """Start an empty Pareto archive of at most `cap` non-dominated outcomes over the named objectives (eg_pareto_track); every
         training batch launched from now on is folded into it on the device.  cap = 0 stops tracking (the archive stays fetchable).
         cost_only picks the rank score that decides what stays when the front outgrows cap."""
-        mask = 0
-        for name in objectives:
-            if name not in PARETO_OBJECTIVES:
-                raise ValueError(f"track_pareto: unknown objective {name!r} (one of {', '.join(PARETO_OBJECTIVES)})")
-            mask |= 1 << PARETO_OBJECTIVES.index(name)
+        mask = _objective_mask(objectives, "track_pareto")
         N.check(N.lib().eg_pareto_track(self.h, int(cap), mask, 2 if cost_only else 1), "eg_pareto_track")
 
     def fetch_pareto(self):

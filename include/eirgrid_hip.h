@@ -511,6 +511,33 @@ int32_t eg_refine_plans_moves(eg_ctx *, const eg_policy_snapshot *, const eg_opt
                               eg_plan_set **refined, eg_refine_move_step *steps /* [n_plans][max_rounds] */, int32_t *n_steps,
                               int32_t *stop_reason, double *start_score, eg_episode_out *out);
 
+/* Plan crosses: what does A's first decade followed by B's last fifteen years score?  A CROSS splices the years of one plan into another:
+ * the first variant with two parents.  eg_evaluate_plan_crosses evaluates n_crosses VARIANTS over a set of 1..EG_CROSS_MAX_PARENTS parent
+ * plans, variant j being parent `a` with BOTH lists (best_actions and best_deficit_actions) of the years from_year <= y < to_year
+ * replaced by parent `b`'s lists of those years:
+ *   a, b                 indices into the parent set, 0..n_plans-1
+ *   from_year, to_year   year indices with 0 <= from_year <= to_year <= 26; the window is [from_year, to_year)
+ * from_year == to_year or a == b is parent `a` itself, the "none" of crosses, so the parents can ride in the batch; to_year == 26 is the
+ * one-point crossover (head of a, tail of b); to_year == from_year + 1 transplants one year.
+ * Everything else is the contract of eg_evaluate_plan_edits, word for word: variant j is evaluated exactly as eg_evaluate_plans
+ * evaluates the host-built child as plan j — the same replay semantics, seeded draws when a list runs out, no statistics, update or folds,
+ * the resident policy untouched, the batch left behind for eg_fetch / eg_fetch_record / eg_debug_fetch_plan_block, ranks of a group
+ * refused — at global episode first_episode_index + j (same_index = 0), or with same_index = 1 every variant at first_episode_index.  The
+ * host uploads every parent's block once and 8 bytes per variant; the variants' plan blocks are written on the device
+ * (csrc/eg_plan_crosses.h k_plan_crosses).  A child's best_actions length differs from its parents', so the short or long replay route
+ * is chosen per variant from the counts, as eg_evaluate_plans chooses it.
+ * eg_plan_crosses_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the cross and the field ("cross 7: best_actions
+ * would hold 4212 entries (at most 4096)") for a parent set that is not a valid set of 1..EG_CROSS_MAX_PARENTS plans, n_crosses outside
+ * 1..EG_CROSS_MAX_VARIANTS, NULL crosses, a or b >= n_plans, to_year > 26, from_year > to_year, or a child whose best_actions or
+ * best_deficit_actions would exceed 4 096 entries.  Nothing is launched after a refusal. */
+#define EG_CROSS_MAX_PARENTS 256      /* = EG_PARETO_MAX */
+#define EG_CROSS_MAX_VARIANTS 16384   /* = EG_REFINE_MAX_VARIANTS */
+typedef struct { uint16_t a, b; uint8_t from_year, to_year; } eg_plan_cross;   /* 6 bytes */
+int32_t eg_plan_crosses_validate(const eg_plan_set *parents, const eg_plan_cross *crosses, int32_t n_crosses);
+int32_t eg_evaluate_plan_crosses(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts *, const eg_plan_set *parents,
+                                 const eg_plan_cross *crosses, int32_t n_crosses, uint64_t seed, uint64_t first_episode_index,
+                                 int32_t same_index, eg_episode_out *out /* may be NULL */);
+
 /* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
  * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
  * copies, no collective library — and every call enqueues the work of all ranks from the calling thread without synchronising
