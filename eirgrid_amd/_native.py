@@ -94,7 +94,22 @@ class EgPlanCross(C.Structure):
     _fields_ = [("a", C.c_uint16), ("b", C.c_uint16), ("from_year", C.c_uint8), ("to_year", C.c_uint8)]
 
 
+class EgBreedOpts(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("objectives", C.c_int32), ("cap", C.c_int32), ("max_generations", C.c_int32), ("n_cuts", C.c_int32),
+                ("cuts", _u8p), ("launch_variants", C.c_int32)]
+
+
+class EgBreedGeneration(C.Structure):
+    _fields_ = [("n_parents", C.c_int32), ("n_skipped", C.c_int32), ("n_kept", C.c_int32), ("n_children_kept", C.c_int32),
+                ("n_variants", C.c_int64), ("n_valid", C.c_int64), ("n_dropped", C.c_int64)]
+
+
+class EgBreedMember(C.Structure):
+    _fields_ = [("cross", EgPlanCross), ("variant", C.c_int32), ("score", C.c_double), ("metrics", C.c_double * 4)]
+
+
 assert C.sizeof(EgPlanMove) == 12 and C.sizeof(EgPlanCross) == 6
+assert C.sizeof(EgBreedOpts) == 40 and C.sizeof(EgBreedGeneration) == 40 and C.sizeof(EgBreedMember) == 56
 
 EDIT_NONE, EDIT_DELETE, EDIT_REPLACE, EDIT_INSERT = 0, 1, 2, 3
 REFINE_LOCAL_OPTIMUM, REFINE_MAX_ROUNDS, REFINE_BASE_FAILED = 0, 1, 2
@@ -102,6 +117,7 @@ REFINE_MAX_VARIANTS = 16384      # EG_REFINE_MAX_VARIANTS
 REFINE_MAX_PLANS = 256           # EG_REFINE_MAX_PLANS
 CROSS_MAX_PARENTS = 256          # EG_CROSS_MAX_PARENTS
 CROSS_MAX_VARIANTS = 16384       # EG_CROSS_MAX_VARIANTS
+BREED_CONVERGED, BREED_MAX_GENERATIONS, BREED_EMPTY = 0, 1, 2      # EG_BREED_*
 PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
 DEBUG_LIST_LEN, DEBUG_FOLD_BEST_RESULT, DEBUG_FOLD_TOP_K = 8, 1, 2      # EG_DEBUG_*
 
@@ -134,6 +150,7 @@ EXPORTS = [
     "eg_refine_plans_validate", "eg_refine_plans", "eg_debug_refine_pick_many",
     "eg_plan_moves_validate", "eg_evaluate_plan_moves", "eg_refine_plans_moves_validate", "eg_refine_plans_moves",
     "eg_plan_crosses_validate", "eg_evaluate_plan_crosses",
+    "eg_breed_validate", "eg_breed_plans",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -325,6 +342,14 @@ def lib():
         L.eg_evaluate_plan_crosses.restype = C.c_int32
         L.eg_evaluate_plan_crosses.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgPlanCross),
                                                C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(EgEpisodeOut)]
+    # (likewise: scripts/breed_probe.py may load a build of the parent commit, which crosses one generation a call)
+    if hasattr(L, "eg_breed_plans") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_breed_validate.restype = C.c_int32
+        L.eg_breed_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgBreedOpts)]
+        L.eg_breed_plans.restype = C.c_int32
+        L.eg_breed_plans.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgBreedOpts),
+                                     C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgBreedGeneration), C.POINTER(EgBreedMember),
+                                     _i32p, _i32p, C.POINTER(EgEpisodeOut)]
     # (likewise: scripts/pareto_probe.py may load a build of the parent commit, which has no Pareto archive)
     if hasattr(L, "eg_pareto_track") or not os.environ.get("EIRGRID_LIB"):
         L.eg_pareto_track.restype = C.c_int32

@@ -146,6 +146,9 @@ struct eg_ctx {
   // EIRGRID_REFINE_LAUNCH_VARIANTS (default and at most 16 384, at least 1; read at every call): the variants a launch may hold — a plan
   // with more gets a launch to itself (so eg_refine_plan's one plan always does); for tests that want many launches per round at small sizes
   eg::DevBuf<uint8_t> d_refine_log, d_refine_bases, d_refine_in;
+  // generations of crosses (eg_breed_plans): the private archive with its block slots, parent arrays and readback (eg_internal.h breed_at),
+  // allocated at the first call, and Pareto work of its own sized for a launch of EG_CROSS_MAX_VARIANTS
+  eg::DevBuf<uint8_t> d_breed, d_breed_work;
 };
 
 namespace eg {
@@ -170,6 +173,12 @@ void pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len, ui
 // ... and a move's 8 bytes (eg_plan_moves.h unpack_move)
 void pack_plan_move(const eg_plan_move& m, uint32_t* packed);
 int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index);
+// ... and what a cross batch and the generations of eg_breed_plans (eg_breed.cpp) share: the prefix offsets of every plan of a set
+// (off[w][p * 27 + y]), a child's list length from them, a cross's 8 bytes (eg_plan_crosses.h unpack_cross), a set's plan blocks
+void parent_offsets(const eg_plan_set* p, std::vector<int32_t> off[2]);
+int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x);
+void pack_plan_cross(const eg_plan_cross& x, uint32_t* packed);
+void write_plan_blocks(const eg_plan_set* p, uint8_t* dst);
 // eg_fetch.cpp
 int fetch_records(const uint8_t* d_base, size_t N, eg_episode_out* o);
 eg_episode_out out_row(const eg_episode_out* o, size_t r);      // row r of a caller's episode-major buffers

@@ -509,6 +509,30 @@ int launch_plan_moves(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* 
 // n packed crosses (8 bytes each: a | b << 8 | from_year << 16 | to_year << 24, then zero): parent a with the years [from_year, to_year)
 // of both lists taken from parent b
 int launch_plan_crosses(const uint8_t* d_parents, uint32_t n_parents, const void* d_crosses, uint32_t n, uint8_t* d_pool, void* stream);
+// Generations of crosses (include/eirgrid_hip.h eg_breed_plans; eg_breed.h, eg_breed.cpp).  The private archive of a call, one buffer
+// kept with the context: a ParetoState and EG_PARETO_MAX record slots exactly as eg_pareto_track lays them out (so launch_pareto_fold
+// folds into it), a plan BLOCK slot per record slot, two parent arrays of EG_PARETO_MAX blocks (this generation's, the next one's), the
+// readback buffer of a generation — a BreedHeader, then a row per survivor: its ParetoEntry padded to 64 bytes and the 2 x 28 prefix
+// offsets of its block — and the counters the two kernels keep.
+struct BreedHeader { int32_t n_held, pad; long long n_dropped, n_valid, pad2; };
+struct BreedCounters { unsigned long long n_valid; unsigned done, pad; };
+constexpr size_t kBreedHeaderBytes = 32, kBreedRowBytes = 64 + 2 * 4 * 28;
+static_assert(sizeof(BreedHeader) == kBreedHeaderBytes && kBreedRowBytes % 16 == 0 && sizeof(BreedCounters) == 16, "breed readback layout");
+namespace breed_at {
+constexpr size_t records = kParetoRecords;
+constexpr size_t blocks = records + size_t(EG_PARETO_MAX) * rec::stride;
+constexpr size_t parents = blocks + size_t(EG_PARETO_MAX) * snap::kPlanStride;      // two arrays, one behind the other
+constexpr size_t kParentArray = size_t(EG_PARETO_MAX) * snap::kPlanStride;
+constexpr size_t readback = parents + 2 * kParentArray;
+constexpr size_t kReadbackBytes = kBreedHeaderBytes + size_t(EG_PARETO_MAX) * kBreedRowBytes;
+constexpr size_t counters = readback + kReadbackBytes;
+constexpr size_t total = counters + sizeof(BreedCounters);
+static_assert(records % 16 == 0 && rec::stride % 16 == 0 && readback % 16 == 0 && counters % 16 == 0, "16-byte lanes");
+}  // namespace breed_at
+// k_breed_gather: behind the fold of a chunk of n variants (variant numbers first..) into the archive at d_breed, from the chunk's plan
+// blocks d_pool; k_breed_turnover: behind a generation's last gather, the survivors' blocks into parent array `next` (0 | 1)
+int launch_breed_gather(uint8_t* d_breed, const DevOut& o, uint32_t n, uint64_t first, const uint8_t* d_pool, void* stream);
+int launch_breed_turnover(uint8_t* d_breed, int next, void* stream);
 // eg_checkpoint.cpp: one plan as a set eg_plans_free releases (counts [26], the flat lists)
 eg_plan_set* make_plan_set(const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact, const char* name);
 // ... and n plans as one set: counts [n][26], the flat lists plan-major, names [n] (NULL entries: "")

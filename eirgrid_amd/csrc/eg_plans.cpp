@@ -307,9 +307,8 @@ extern "C" int32_t eg_evaluate_plan_moves(eg_ctx* c, const eg_policy_snapshot* s
 // ---------------------------------------------------------------- plan crosses (include/eirgrid_hip.h eg_evaluate_plan_crosses)
 static_assert(sizeof(eg_plan_cross) == 6, "eg_plan_cross is part of the C ABI");
 static_assert(EG_CROSS_MAX_PARENTS <= 256, "a parent index is packed into one byte (eg_plan_crosses.h unpack_cross)");
-namespace {
 // the two lists' prefix offsets of every plan of a valid set: off[w][p * 27 + y], w = 0 best_actions, 1 best_deficit_actions
-void parent_offsets(const eg_plan_set* p, std::vector<int32_t> off[2]) {
+void eg::parent_offsets(const eg_plan_set* p, std::vector<int32_t> off[2]) {
   const int32_t* count[2] = {p->best_count, p->best_deficit_count};
   for (int w = 0; w < 2; ++w) {
     off[w].assign(size_t(p->n_plans) * 27, 0);
@@ -318,12 +317,26 @@ void parent_offsets(const eg_plan_set* p, std::vector<int32_t> off[2]) {
   }
 }
 // the length of list w of the child of cross x: a's, with a's window taken out and b's put in
-int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x) {
+int64_t eg::child_len(const std::vector<int32_t>& off, const eg_plan_cross& x) {
   const int32_t* oa = off.data() + size_t(x.a) * 27;
   const int32_t* ob = off.data() + size_t(x.b) * 27;
   return int64_t(oa[EG_YEARS]) - (oa[x.to_year] - oa[x.from_year]) + (ob[x.to_year] - ob[x.from_year]);
 }
-}  // namespace
+// what goes up per cross, 8 bytes (eg_plan_crosses.h unpack_cross)
+void eg::pack_plan_cross(const eg_plan_cross& x, uint32_t* packed) {
+  packed[0] = uint32_t(x.a) | uint32_t(x.b) << 8 | uint32_t(x.from_year) << 16 | uint32_t(x.to_year) << 24;
+  packed[1] = 0u;
+}
+// every plan of a valid set as a plan block at dst (zeroed by the caller), snap::kPlanStride bytes apart
+void eg::write_plan_blocks(const eg_plan_set* p, uint8_t* dst) {
+  int64_t pos = 0, dpos = 0;
+  for (int32_t j = 0; j < p->n_plans; ++j) {
+    const int32_t* cnt = p->best_count + size_t(j) * EG_YEARS;
+    const int32_t* dcnt = p->best_deficit_count + size_t(j) * EG_YEARS;
+    write_lists(dst + size_t(j) * snap::kPlanStride, cnt, p->best_actions + pos, dcnt, p->best_deficit_actions + dpos);
+    for (int y = 0; y < EG_YEARS; ++y) { pos += cnt[y]; dpos += dcnt[y]; }
+  }
+}
 
 extern "C" int32_t eg_plan_crosses_validate(const eg_plan_set* parents, const eg_plan_cross* crosses, int32_t n_crosses) {
   auto fail = [](const std::string& m) { set_error("eg_plan_crosses_validate: " + m); return EG_ERR_BAD_ARG; };
@@ -363,15 +376,7 @@ extern "C" int32_t eg_evaluate_plan_crosses(eg_ctx* c, const eg_policy_snapshot*
   // what goes up: every parent's block, once, and the packed crosses (eg_plan_crosses.h unpack_cross); the routing from the counts — two
   // short parents can make a long child and the reverse
   std::vector<uint8_t> in(size_t(P) * snap::kPlanStride + size_t(n) * 8, 0);
-  {
-    int64_t pos = 0, dpos = 0;
-    for (uint32_t p = 0; p < P; ++p) {
-      const int32_t* cnt = parents->best_count + size_t(p) * EG_YEARS;
-      const int32_t* dcnt = parents->best_deficit_count + size_t(p) * EG_YEARS;
-      write_lists(in.data() + size_t(p) * snap::kPlanStride, cnt, parents->best_actions + pos, dcnt, parents->best_deficit_actions + dpos);
-      for (int y = 0; y < EG_YEARS; ++y) { pos += cnt[y]; dpos += dcnt[y]; }
-    }
-  }
+  write_plan_blocks(parents, in.data());
   std::vector<int32_t> off[2];
   parent_offsets(parents, off);
   uint32_t* packed = reinterpret_cast<uint32_t*>(in.data() + size_t(P) * snap::kPlanStride);
@@ -379,7 +384,7 @@ extern "C" int32_t eg_evaluate_plan_crosses(eg_ctx* c, const eg_policy_snapshot*
   uint32_t n_short = 0;
   for (uint32_t j = 0; j < n; ++j) {
     const eg_plan_cross& x = crosses[j];
-    packed[2 * size_t(j)] = uint32_t(x.a) | uint32_t(x.b) << 8 | uint32_t(x.from_year) << 16 | uint32_t(x.to_year) << 24;
+    pack_plan_cross(x, packed + 2 * size_t(j));
     if (child_len(off[0], x) > kShortReplayMax) longs.push_back(j); else idx[n_short++] = j;
   }
   std::copy(longs.begin(), longs.end(), idx.begin() + n_short);

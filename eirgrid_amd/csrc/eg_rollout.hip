@@ -2524,6 +2524,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_refine_many.h"      // k_plan_edits_many, k_refine_pick_many: a refinement round, a segment of the launch's variants per plan
 #include "eg_plan_moves.h"       // k_plan_moves: the plan blocks of the variants that move an entry to another year
 #include "eg_plan_crosses.h"     // k_plan_crosses: the plan blocks of the variants that splice one parent's years into another
+#include "eg_breed.h"            // k_breed_gather, k_breed_turnover: a generation's survivors become the next one's parents on the device
 
 // ---- B2: a single placement search, for parity tests of the arg-max --------------------------------------------
 __global__ void __launch_bounds__(kWave) k_place(DevTables T, int type, int yi, const uint16_t* __restrict__ cells,
@@ -3395,6 +3396,18 @@ int launch_plan_moves(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* 
 int launch_plan_crosses(const uint8_t* d_parents, uint32_t n_parents, const void* d_crosses, uint32_t n, uint8_t* d_pool, void* stream) {
   if (n == 0 || n_parents == 0) return 0;
   hipLaunchKernelGGL(k_plan_crosses, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_parents, n_parents, reinterpret_cast<const uint2*>(d_crosses), n, d_pool);
+  return (int)hipGetLastError();
+}
+int launch_breed_gather(uint8_t* d_breed, const DevOut& o, uint32_t n, uint64_t first, const uint8_t* d_pool, void* stream) {
+  if (n == 0 || n > (uint32_t)EG_PARETO_MAX * kWave) return n == 0 ? 0 : (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_breed_gather, dim3(EG_PARETO_MAX), dim3(kWave), 0, (hipStream_t)stream, reinterpret_cast<const ParetoState*>(d_breed), o, n,
+                     (unsigned long long)first, d_pool, d_breed + breed_at::blocks, reinterpret_cast<BreedCounters*>(d_breed + breed_at::counters));
+  return (int)hipGetLastError();
+}
+int launch_breed_turnover(uint8_t* d_breed, int next, void* stream) {
+  hipLaunchKernelGGL(k_breed_turnover, dim3(EG_PARETO_MAX), dim3(kWave), 0, (hipStream_t)stream, reinterpret_cast<ParetoState*>(d_breed), d_breed + breed_at::blocks,
+                     d_breed + breed_at::parents + (next ? breed_at::kParentArray : 0), d_breed + breed_at::readback,
+                     reinterpret_cast<BreedCounters*>(d_breed + breed_at::counters));
   return (int)hipGetLastError();
 }
 int launch_refine_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs, uint32_t n_total, int mode, const void* d_edits, const uint8_t* d_pool,

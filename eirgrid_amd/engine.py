@@ -416,6 +416,72 @@ class CrossFront:
     n_valid: int              # ... of which valid
 
 
+BREED_STOP = ("converged", "max_generations", "empty")      # EG_BREED_*
+
+
+def _cross_name(parents, x) -> str:
+    """a variant's name as scripts/cross_front.py writes it: a parent keeps its own, a child is `A>B@year`, the year being the first
+    one taken from B (a plan without a name goes by its position in the population)"""
+    if x.a == x.b or x.from_year == x.to_year:
+        return parents[x.a].name
+    name = lambda p: parents[p].name or str(p)
+    return f"{name(x.a)}>{name(x.b)}@{2025 + x.from_year}"
+
+
+@dataclass(frozen=True)
+class BreedGeneration:
+    """One generation of Engine.breed_front (eg_breed_generation): the population it started from, the crosses left out because a
+    child would outgrow a list, what was evaluated and valid, what the archive kept (and how many of those are children) and dropped
+    for want of room."""
+    n_parents: int
+    n_skipped: int
+    n_kept: int
+    n_children_kept: int
+    n_variants: int
+    n_valid: int
+    n_dropped: int
+
+
+@dataclass(frozen=True)
+class BreedMember:
+    """A survivor of a generation (eg_breed_member): its PlanCross against that generation's population, its variant number, rank
+    score and four metrics."""
+    cross: PlanCross
+    variant: int
+    score: float
+    metrics: tuple
+
+
+@dataclass
+class BreedFront:
+    """Engine.breed_front: the final population (plans, a row of metrics and a rank score each, in ascending variant number of the last
+    generation), a BreedGeneration per generation that ran, every generation's survivors ([generation][member] BreedMember — the whole
+    genealogy), why it stopped (one of BREED_STOP) and the final members' records (a BatchResult; None after "empty")."""
+    plans: list
+    metrics: np.ndarray       # [k,4]
+    score: np.ndarray         # [k]
+    generations: list
+    members: list
+    stop_reason: str
+    records: "BatchResult" = None
+
+    def lineage(self, parents) -> "list[list[Plan]]":
+        """Every population from P_0 = `parents` on, rebuilt on the host from the genealogy: P_{g+1} is members[g]'s crosses applied to
+        P_g (PlanCross.apply), named as scripts/cross_front.py names them.  A generation that kept nothing leaves the population as it
+        was.  lineage(parents)[-1] is what `plans` holds."""
+        pops = [[Plan(p.best_actions, p.best_deficit_actions, p.name) for p in parents]]
+        for kept in self.members:
+            if not kept:
+                break
+            pop = pops[-1]
+            nxt = []
+            for m in kept:
+                child = m.cross.apply(pop)
+                nxt.append(Plan(child.best_actions, child.best_deficit_actions, _cross_name(pop, m.cross)))
+            pops.append(nxt)
+        return pops
+
+
 @dataclass
 class Timing:
     """Engine.plan_timing: per move (row 0: the base plan, as the move of an entry onto itself, or None for a plan without entries) the
@@ -755,6 +821,56 @@ class Engine:
             fi, fm = pareto_filter(fi, fm, np.arange(first, first + n), metrics, status, mask)
         score = np.array([rank_score(m, cost_only) for m in fm])
         return CrossFront(fi, [crosses[i] for i in fi], fm, score, fi < len(parents), len(crosses), n_valid)
+
+    def breed_front(self, weights: ActionWeights, parents, seed: int, index: int = 0, objectives=PARETO_OBJECTIVES, cost_only: bool = False,
+                    cuts=range(1, 26), generations: int = 8, cap: int = N.PARETO_MAX, max_variants: int = N.CROSS_MAX_VARIANTS) -> BreedFront:
+        """Generations of cross_front on the device (eg_breed_plans): from the population `parents`, every generation evaluates the
+        variants of cross_pairs(len(population), cuts) — less the crosses whose child would outgrow a list — in chunks of at most
+        max_variants, every one at global index `index` of `seed`, folds each chunk into a private Pareto archive of `cap` entries
+        over `objectives` (eg_pareto_track's rules; cost_only picks the rank score the capacity rule and the rows use), and makes the
+        survivors' plan blocks the next population without leaving the device.  Stops when a generation keeps exactly its parents, after
+        `generations` generations, or when nothing was valid.  The context's own Pareto archive is not touched."""
+        mask = _objective_mask(objectives, "breed_front")
+        if mask == 0:
+            raise ValueError("breed_front: no objectives")
+        parents = list(parents)
+        ps = PlanSet(parents)
+        cut = np.array([int(c) for c in cuts], np.int64)
+        if len(cut) == 0 or (cut < 0).any() or (cut > 255).any():      # (what a byte cannot carry; eg_breed_validate checks the rest)
+            raise ValueError(f"breed_front: cuts = {cut.tolist()} (year indices 1..{N.YEARS - 1}, at least one)")
+        cut = cut.astype(np.uint8)
+        gens, cap = int(generations), int(cap)
+        bo = N.EgBreedOpts(2 if cost_only else 1, mask, cap, gens, len(cut), _p(cut, C.c_uint8), int(max_variants))
+        L = N.lib()
+        N.check(L.eg_breed_validate(C.byref(ps.s), C.byref(bo)), "eg_breed_validate")
+        rows = (N.EgBreedGeneration * gens)()
+        members = (N.EgBreedMember * (gens * cap))()
+        n_gen, stop = C.c_int32(0), C.c_int32(0)
+        population = C.POINTER(N.EgPlanSet)()
+        res = BatchResult.alloc(cap)
+        snap = weights.snapshot()
+        opts = self._opts(True, False, True)
+        out = res.struct()
+        N.check(L.eg_breed_plans(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(bo), C.c_uint64(seed & (2**64 - 1)), C.c_uint64(index),
+                                 C.byref(population), rows, members, C.byref(n_gen), C.byref(stop), C.byref(out)), "eg_breed_plans")
+        plans = Plan._take_set(population)
+        reason = BREED_STOP[stop.value]
+        g_rows = [BreedGeneration(*(int(getattr(rows[g], f)) for f, _ in N.EgBreedGeneration._fields_)) for g in range(n_gen.value)]
+        kept = [[BreedMember(PlanCross(m.cross.a, m.cross.b, m.cross.from_year, m.cross.to_year), int(m.variant), float(m.score), tuple(m.metrics))
+                 for m in members[g * cap:g * cap + g_rows[g].n_kept]] for g in range(n_gen.value)]
+        front = BreedFront(plans, np.zeros((0, 4)), np.zeros(0), g_rows, kept, reason, None)
+        if reason != "empty":
+            last = kept[-1]
+            front.metrics = np.array([m.metrics for m in last], np.float64).reshape(-1, 4)
+            front.score = np.array([m.score for m in last], np.float64)
+            names = [f.name for f in fields(BatchResult)]
+            front.records = BatchResult(*[np.ascontiguousarray(getattr(res, f)[:len(last)]) for f in names])
+            for plan, named in zip(plans, front.lineage(parents)[-1]):
+                plan.name = named.name
+        else:
+            for plan, p in zip(plans, parents):
+                plan.name = p.name
+        return front
 
     def plan_timing(self, weights: ActionWeights, base: "Plan", seed: int, mode: int = 1, max_shift: int = 1) -> Timing:
         """Which entries of `base` would be better placed in another year: the base (row 0) and the moves of refine_moves(base,

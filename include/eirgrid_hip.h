@@ -538,6 +538,55 @@ int32_t eg_evaluate_plan_crosses(eg_ctx *, const eg_policy_snapshot *policy, con
                                  const eg_plan_cross *crosses, int32_t n_crosses, uint64_t seed, uint64_t first_episode_index,
                                  int32_t same_index, eg_episode_out *out /* may be NULL */);
 
+/* Breeding a front: generations of plan crosses with Pareto selection, the survivors' plan blocks becoming the next generation's parents
+ * on the device.  eg_breed_plans(ctx, policy, opts, parents, breed_opts, seed, episode_index, ...) starts from the population P_0 = the
+ * given 1..EG_CROSS_MAX_PARENTS plans, in order.  Generation g = 0, 1, ... :
+ *   variants     with n = |P_g|: every parent first, as the cross {p, p, 0, 0} for p = 0..n-1; then {a, b, c, 26} for a, b != a and c of
+ *                `cuts`, in lexicographic order (a, then b, then the position of c in `cuts`).  A cross whose child would hold more than
+ *                4 096 entries in either list is removed and counted in n_skipped; the call is not refused.  A variant's NUMBER is its
+ *                position in the list that remains;
+ *   evaluation   chunk k holds the variants [k L, (k + 1) L), L = launch_variants (1..EG_CROSS_MAX_VARIANTS; 0 means
+ *                EG_CROSS_MAX_VARIANTS).  Each chunk runs exactly as eg_evaluate_plan_crosses(..., first_episode_index = episode_index,
+ *                same_index = 1) runs it over P_g, the per-variant short or long replay route included;
+ *   selection    a private archive starts empty at every generation (it is NOT the context's eg_pareto_track archive, which stays
+ *                untouched).  After every chunk it is folded with eg_pareto_track's definitions, word for word — valid, oriented
+ *                dominance over `objectives`, the same point held once at the lowest index, the capacity rule with `mode` and the
+ *                sticky n_dropped — the index of a variant being its number.  The archive after the last chunk, in ascending variant
+ *                number, is P_{g+1}.  Parents have the lowest numbers, so a child that only equals a parent's point never displaces
+ *                it; every parent is a variant, so the front never gets worse.  With n_dropped > 0 the result depends on the chunk
+ *                boundaries, which L defines and which are therefore part of the contract; the call is deterministic either way;
+ *   stop         EG_BREED_CONVERGED: P_{g+1} consists of exactly the n parents (n survivors, every number < n) — checked first;
+ *                EG_BREED_MAX_GENERATIONS: max_generations generations have run;
+ *                EG_BREED_EMPTY: no variant of the generation was valid; the population of that generation is returned.  (Only
+ *                generation 0 can end so: a survivor was valid and is evaluated again as the same episode.)
+ * Returned: *population = P_final (free with eg_plans_free; names ""), decoded from the population's blocks as they stand on the device
+ * after the last generation — not rebuilt from the genealogy; generations[max_generations], a row per generation that ran;
+ * members[max_generations][cap], the survivors of every generation in ascending variant number (`cross` is against P_g: the whole
+ * genealogy); *n_generations; *stop_reason; out (cap episodes, may be NULL): the records of P_final's members, row r member r, taken
+ * from the archive's record slots (not written after EG_BREED_EMPTY).
+ * Per chunk the host uploads 8 bytes per variant and the routing; per generation it reads one buffer back (a row per survivor: number,
+ * metrics, score and the block's two prefix-offset tables, from which the next generation is enumerated and routed).  No per-variant
+ * data comes down and no plan block goes up after generation 0 (csrc/eg_breed.h k_breed_gather, k_breed_turnover).
+ * Everything else is the contract of eg_evaluate_plan_crosses: no statistics, update or training folds, the resident policy untouched,
+ * a rank of a group refused, the policy checked and staged once per call, the last launch's variants left behind as the last batch.
+ * eg_breed_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the field for a parent set that is not a valid set of
+ * 1..EG_CROSS_MAX_PARENTS plans, NULL options, a mode other than 1 or 2, objectives outside 1..15, cap outside 1..EG_PARETO_MAX,
+ * max_generations < 1, launch_variants outside 0..EG_CROSS_MAX_VARIANTS, n_cuts outside 0..25, NULL cuts with n_cuts > 0, a cut outside
+ * 1..25.  Nothing is launched after a refusal. */
+#define EG_BREED_CONVERGED 0
+#define EG_BREED_MAX_GENERATIONS 1
+#define EG_BREED_EMPTY 2
+typedef struct { int32_t mode /* 1 | 2 */, objectives /* 1..15 */, cap /* 1..EG_PARETO_MAX */, max_generations /* >= 1 */;
+                 int32_t n_cuts; const uint8_t *cuts /* year indices 1..25; NULL with n_cuts 0: all 25 */;
+                 int32_t launch_variants; } eg_breed_opts;
+typedef struct { int32_t n_parents, n_skipped, n_kept, n_children_kept; int64_t n_variants, n_valid, n_dropped; } eg_breed_generation;   /* 40 bytes */
+typedef struct { eg_plan_cross cross /* against P_g */; int32_t variant; double score, metrics[4]; } eg_breed_member;   /* 56 bytes */
+int32_t eg_breed_validate(const eg_plan_set *parents, const eg_breed_opts *);
+int32_t eg_breed_plans(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts *, const eg_plan_set *parents, const eg_breed_opts *,
+                       uint64_t seed, uint64_t episode_index, eg_plan_set **population, eg_breed_generation *generations /* [max_generations] */,
+                       eg_breed_member *members /* [max_generations][cap] */, int32_t *n_generations, int32_t *stop_reason,
+                       eg_episode_out *out /* cap rows, may be NULL */);
+
 /* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
  * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
  * copies, no collective library — and every call enqueues the work of all ranks from the calling thread without synchronising
