@@ -108,7 +108,24 @@ class EgBreedMember(C.Structure):
     _fields_ = [("cross", EgPlanCross), ("variant", C.c_int32), ("score", C.c_double), ("metrics", C.c_double * 4)]
 
 
+class EgExploreOpts(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("objectives", C.c_int32), ("cap", C.c_int32), ("max_generations", C.c_int32), ("n_replace", C.c_int32),
+                ("replace_with", _u8p), ("n_append", C.c_int32), ("append_with", _u8p), ("max_shift", C.c_int32), ("launch_variants", C.c_int32),
+                ("max_variants", C.c_int64)]
+
+
+class EgExploreGeneration(C.Structure):
+    _fields_ = [("n_frontier", C.c_int32), ("n_held", C.c_int32), ("n_new", C.c_int32), ("pad", C.c_int32),
+                ("n_variants", C.c_int64), ("n_valid", C.c_int64), ("n_dropped", C.c_int64)]
+
+
+class EgExploreMember(C.Structure):
+    _fields_ = [("parent", C.c_int64), ("is_move", C.c_int32), ("edit", EgPlanEdit), ("move", EgPlanMove), ("number", C.c_int64),
+                ("score", C.c_double), ("metrics", C.c_double * 4)]
+
+
 assert C.sizeof(EgPlanMove) == 12 and C.sizeof(EgPlanCross) == 6
+assert C.sizeof(EgExploreOpts) == 64 and C.sizeof(EgExploreGeneration) == 40 and C.sizeof(EgExploreMember) == 88
 assert C.sizeof(EgBreedOpts) == 40 and C.sizeof(EgBreedGeneration) == 40 and C.sizeof(EgBreedMember) == 56
 
 EDIT_NONE, EDIT_DELETE, EDIT_REPLACE, EDIT_INSERT = 0, 1, 2, 3
@@ -118,6 +135,7 @@ REFINE_MAX_PLANS = 256           # EG_REFINE_MAX_PLANS
 CROSS_MAX_PARENTS = 256          # EG_CROSS_MAX_PARENTS
 CROSS_MAX_VARIANTS = 16384       # EG_CROSS_MAX_VARIANTS
 BREED_CONVERGED, BREED_MAX_GENERATIONS, BREED_EMPTY = 0, 1, 2      # EG_BREED_*
+EXPLORE_EXPLORED, EXPLORE_MAX_GENERATIONS, EXPLORE_EMPTY, EXPLORE_BUDGET = 0, 1, 2, 3      # EG_EXPLORE_*
 PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
 DEBUG_LIST_LEN, DEBUG_FOLD_BEST_RESULT, DEBUG_FOLD_TOP_K = 8, 1, 2      # EG_DEBUG_*
 
@@ -150,7 +168,7 @@ EXPORTS = [
     "eg_refine_plans_validate", "eg_refine_plans", "eg_debug_refine_pick_many",
     "eg_plan_moves_validate", "eg_evaluate_plan_moves", "eg_refine_plans_moves_validate", "eg_refine_plans_moves",
     "eg_plan_crosses_validate", "eg_evaluate_plan_crosses",
-    "eg_breed_validate", "eg_breed_plans",
+    "eg_breed_validate", "eg_breed_plans", "eg_explore_validate", "eg_explore_neighbourhood", "eg_explore_plans",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -350,7 +368,16 @@ def lib():
         L.eg_breed_plans.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgBreedOpts),
                                      C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgBreedGeneration), C.POINTER(EgBreedMember),
                                      _i32p, _i32p, C.POINTER(EgEpisodeOut)]
-    # (likewise: scripts/pareto_probe.py may load a build of the parent commit, which has no Pareto archive)
+    # (likewise: a probe may load a build of the parent commit, which does not explore)
+    if hasattr(L, "eg_explore_plans") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_explore_validate.restype = C.c_int32
+        L.eg_explore_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgExploreOpts)]
+        L.eg_explore_neighbourhood.restype = C.c_int32
+        L.eg_explore_neighbourhood.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgExploreOpts), C.POINTER(C.c_int64)]
+        L.eg_explore_plans.restype = C.c_int32
+        L.eg_explore_plans.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgExploreOpts),
+                                       C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgExploreGeneration),
+                                       C.POINTER(EgExploreMember), C.POINTER(C.c_int64), _i32p, _i32p, C.POINTER(EgEpisodeOut)]
     if hasattr(L, "eg_pareto_track") or not os.environ.get("EIRGRID_LIB"):
         L.eg_pareto_track.restype = C.c_int32
         L.eg_pareto_track.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]

@@ -38,27 +38,7 @@ const char* const kFn = "eg_breed_plans";
 int decode_population(const uint8_t* d_blocks, int32_t n, eg_plan_set** population) {
   std::vector<uint8_t> blocks(size_t(n) * snap::kPlanStride);
   EG_HIP(hipMemcpy(blocks.data(), d_blocks, blocks.size(), hipMemcpyDeviceToHost));
-  std::vector<int32_t> count[2];
-  std::vector<uint8_t> flat[2];
-  const size_t at_off[2] = {snap::best_off - snap::best_mask, snap::bestd_off - snap::best_mask};
-  const size_t at_act[2] = {snap::best_actions - snap::best_mask, snap::bestd_actions - snap::best_mask};
-  for (int w = 0; w < 2; ++w)
-    for (int32_t p = 0; p < n; ++p) {
-      const uint8_t* b = blocks.data() + size_t(p) * snap::kPlanStride;
-      int32_t off[28];
-      std::memcpy(off, b + at_off[w], sizeof(off));
-      for (int y = 0; y < EG_YEARS; ++y) {
-        if (off[0] != 0 || off[y + 1] < off[y] || off[y + 1] > int32_t(snap::kBestCap)) {
-          set_error(std::string(kFn) + ": plan " + std::to_string(p) + " of the population has corrupt offsets on the device");
-          return EG_ERR_INTERNAL;
-        }
-        count[w].push_back(off[y + 1] - off[y]);
-      }
-      flat[w].insert(flat[w].end(), b + at_act[w], b + at_act[w] + off[EG_YEARS]);
-    }
-  flat[0].reserve(1); flat[1].reserve(1);
-  *population = make_plan_set_n(n, count[0].data(), flat[0].data(), count[1].data(), flat[1].data(), nullptr);
-  return EG_OK;
+  return decode_plan_blocks(blocks.data(), n, kFn, population);
 }
 }  // namespace
 

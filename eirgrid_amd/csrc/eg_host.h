@@ -147,7 +147,8 @@ struct eg_ctx {
   // with more gets a launch to itself (so eg_refine_plan's one plan always does); for tests that want many launches per round at small sizes
   eg::DevBuf<uint8_t> d_refine_log, d_refine_bases, d_refine_in;
   // generations of crosses (eg_breed_plans): the private archive with its block slots, parent arrays and readback (eg_internal.h breed_at),
-  // allocated at the first call, and Pareto work of its own sized for a launch of EG_CROSS_MAX_VARIANTS
+  // allocated at the first call, and Pareto work of its own sized for a launch of EG_CROSS_MAX_VARIANTS.  eg_explore_plans uses both the
+  // same way (the parent arrays as its frontier arrays); either call starts the archive empty
   eg::DevBuf<uint8_t> d_breed, d_breed_work;
 };
 
@@ -179,6 +180,8 @@ void parent_offsets(const eg_plan_set* p, std::vector<int32_t> off[2]);
 int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x);
 void pack_plan_cross(const eg_plan_cross& x, uint32_t* packed);
 void write_plan_blocks(const eg_plan_set* p, uint8_t* dst);
+// ... and the reverse: n plan blocks read back from the device (host memory) decoded into a plan set (names ""); `who` names the entry point
+int decode_plan_blocks(const uint8_t* blocks, int32_t n, const char* who, eg_plan_set** set);
 // eg_fetch.cpp
 int fetch_records(const uint8_t* d_base, size_t N, eg_episode_out* o);
 eg_episode_out out_row(const eg_episode_out* o, size_t r);      // row r of a caller's episode-major buffers

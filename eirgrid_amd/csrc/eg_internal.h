@@ -533,6 +533,13 @@ static_assert(records % 16 == 0 && rec::stride % 16 == 0 && readback % 16 == 0 &
 // blocks d_pool; k_breed_turnover: behind a generation's last gather, the survivors' blocks into parent array `next` (0 | 1)
 int launch_breed_gather(uint8_t* d_breed, const DevOut& o, uint32_t n, uint64_t first, const uint8_t* d_pool, void* stream);
 int launch_breed_turnover(uint8_t* d_breed, int next, void* stream);
+// A Pareto local search over plan edits (include/eirgrid_hip.h eg_explore_plans; eg_explore.h, eg_explore.cpp) uses the same buffer: the
+// archive lives across the generations of a call, the two parent arrays are its two FRONTIER arrays, and the readback holds an
+// ExploreHeader and a row (BreedLayout's) for every entry that is new — index >= m_first — only, at its position among the new ones.
+// k_explore_turnover: behind a generation's last gather, the new entries' blocks into frontier array `next` (0 | 1)
+struct ExploreHeader { int32_t n_held, n_new; long long n_dropped, n_valid, pad; };
+static_assert(sizeof(ExploreHeader) == kBreedHeaderBytes, "explore readback layout");
+int launch_explore_turnover(uint8_t* d_breed, int next, long long m_first, void* stream);
 // eg_checkpoint.cpp: one plan as a set eg_plans_free releases (counts [26], the flat lists)
 eg_plan_set* make_plan_set(const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact, const char* name);
 // ... and n plans as one set: counts [n][26], the flat lists plan-major, names [n] (NULL entries: "")

@@ -2525,6 +2525,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_plan_moves.h"       // k_plan_moves: the plan blocks of the variants that move an entry to another year
 #include "eg_plan_crosses.h"     // k_plan_crosses: the plan blocks of the variants that splice one parent's years into another
 #include "eg_breed.h"            // k_breed_gather, k_breed_turnover: a generation's survivors become the next one's parents on the device
+#include "eg_explore.h"          // k_explore_turnover: the members that entered an exploration's archive become the next frontier
 
 // ---- B2: a single placement search, for parity tests of the arg-max --------------------------------------------
 __global__ void __launch_bounds__(kWave) k_place(DevTables T, int type, int yi, const uint16_t* __restrict__ cells,
@@ -3408,6 +3409,12 @@ int launch_breed_turnover(uint8_t* d_breed, int next, void* stream) {
   hipLaunchKernelGGL(k_breed_turnover, dim3(EG_PARETO_MAX), dim3(kWave), 0, (hipStream_t)stream, reinterpret_cast<ParetoState*>(d_breed), d_breed + breed_at::blocks,
                      d_breed + breed_at::parents + (next ? breed_at::kParentArray : 0), d_breed + breed_at::readback,
                      reinterpret_cast<BreedCounters*>(d_breed + breed_at::counters));
+  return (int)hipGetLastError();
+}
+int launch_explore_turnover(uint8_t* d_breed, int next, long long m_first, void* stream) {
+  hipLaunchKernelGGL(k_explore_turnover, dim3(EG_PARETO_MAX), dim3(kWave), 0, (hipStream_t)stream, reinterpret_cast<const ParetoState*>(d_breed),
+                     d_breed + breed_at::blocks, d_breed + breed_at::parents + (next ? breed_at::kParentArray : 0), d_breed + breed_at::readback,
+                     reinterpret_cast<BreedCounters*>(d_breed + breed_at::counters), m_first);
   return (int)hipGetLastError();
 }
 int launch_refine_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs, uint32_t n_total, int mode, const void* d_edits, const uint8_t* d_pool,

@@ -482,6 +482,82 @@ class BreedFront:
         return pops
 
 
+EXPLORE_STOP = ("explored", "max_generations", "empty", "budget")      # EG_EXPLORE_*
+
+
+@dataclass(frozen=True)
+class ExploreGeneration:
+    """One generation of Engine.explore_front (eg_explore_generation): the frontier whose neighbourhoods it evaluated, what the archive
+    held after it and how many of those entered in it (the next frontier), the generation's variants and how many were valid, and
+    what the archive has dropped for want of room so far."""
+    n_frontier: int
+    n_held: int
+    n_new: int
+    n_variants: int
+    n_valid: int
+    n_dropped: int
+
+
+@dataclass(frozen=True)
+class ExploreMember:
+    """A member of a frontier (eg_explore_member): the number of the plan it was made from (-1: a start plan), the PlanEdit or PlanMove
+    against that plan (a start plan: PlanEdit()), its own number, rank score and four metrics."""
+    parent: int
+    edit: object
+    number: int
+    score: float
+    metrics: tuple
+
+
+def _explore_name(parent_name: str, parent: int, edit) -> str:
+    """a neighbour's name: its base's (a plan without a name goes by its number), then what was done to it, e.g. `A-2031.2`, `A~2031.2=17`,
+    `A+2040=9`, `A:2031.2>2033` (best_deficit_actions: `d` in front of the year)"""
+    base = parent_name or str(parent)
+    if isinstance(edit, PlanMove):
+        return f"{base}:{2025 + edit.year}.{edit.pos}>{2025 + edit.to_year}"
+    at = f"{'d' if edit.list else ''}{2025 + edit.year}"
+    if edit.kind == "delete":
+        return f"{base}-{at}.{edit.pos}"
+    if edit.kind == "replace":
+        return f"{base}~{at}.{edit.pos}={edit.action}"
+    if edit.kind == "insert":
+        return f"{base}+{at}={edit.action}"
+    return parent_name
+
+
+@dataclass
+class ExploreFront:
+    """Engine.explore_front: the final population — the whole archive: plans, their numbers, a row of metrics and a rank score each, in
+    ascending number —, an ExploreGeneration per generation that ran, the members ([0]: the start plans held after generation 0;
+    [g + 1]: the frontier F_{g+1}, the members that entered in generation g — the whole genealogy), why it stopped (one of
+    EXPLORE_STOP) and the final members' records (a BatchResult; None after "empty")."""
+    plans: list
+    numbers: np.ndarray       # [k]
+    metrics: np.ndarray       # [k,4]
+    score: np.ndarray         # [k]
+    generations: list
+    members: list
+    stop_reason: str
+    records: "BatchResult" = None
+
+    def lineage(self, starts) -> "list[dict]":
+        """Every frontier's plans, rebuilt on the host from the genealogy: element g of the list is {number: Plan} of everything known
+        after row g of `members` — the start plans (numbers 0..n-1), then every member with its edit or move applied to its parent's
+        plan (PlanEdit.apply, PlanMove.apply) and named after it.  Frontier g is the entries of element g whose numbers stand in
+        members[g]; lineage(starts)[-1] filtered to `numbers` is what `plans` holds."""
+        known = {p: Plan(s.best_actions, s.best_deficit_actions, s.name) for p, s in enumerate(starts)}
+        out = []
+        for row in self.members:
+            for m in row:
+                if m.parent < 0:
+                    continue
+                base = known[m.parent]
+                child = m.edit.apply(base)
+                known[m.number] = Plan(child.best_actions, child.best_deficit_actions, _explore_name(base.name, m.parent, m.edit))
+            out.append(dict(known))
+        return out
+
+
 @dataclass
 class Timing:
     """Engine.plan_timing: per move (row 0: the base plan, as the move of an entry onto itself, or None for a plan without entries) the
@@ -869,6 +945,73 @@ class Engine:
                 plan.name = named.name
         else:
             for plan, p in zip(plans, parents):
+                plan.name = p.name
+        return front
+
+    def explore_front(self, weights: ActionWeights, starts, seed: int, index: int = 0, objectives=PARETO_OBJECTIVES, cost_only: bool = False,
+                      generations: int = 8, cap: int = N.PARETO_MAX, replace_with=None, append_with=None, max_shift: int = 0,
+                      max_variants: int = 0, launch: int = 0) -> ExploreFront:
+        """A Pareto local search over one-entry edits and moves on the device (eg_explore_plans): generation 0 evaluates the plans of
+        `starts` and their neighbourhoods — refine_edits(plan, replace_with, append_with)[1:] + refine_moves(plan, max_shift) —, every
+        later generation the neighbourhoods of the members that entered the archive in the one before, every variant at global index
+        `index` of `seed` in chunks of `launch` (0: 16 384), each chunk folded into ONE private Pareto archive of `cap` entries over
+        `objectives` that lives through the call (eg_pareto_track's rules; cost_only picks the rank score the capacity rule and the
+        rows use).  Stops when no member is left unexplored, when nothing was valid, when the next generation would take the call
+        beyond max_variants (0: no budget) or after `generations` generations.  The context's own Pareto archive is not touched."""
+        mask = _objective_mask(objectives, "explore_front")
+        if mask == 0:
+            raise ValueError("explore_front: no objectives")
+        starts = list(starts)
+        ps = PlanSet(starts)
+        rep = np.array([int(a) for a in (replace_with or [])], np.int64); app = np.array([int(a) for a in (append_with or [])], np.int64)
+        for name, l in (("replace_with", rep), ("append_with", app)):
+            if ((l < 0) | (l > 255)).any():      # (what a byte cannot carry; eg_explore_validate checks the rest)
+                raise ValueError(f"explore_front: {name} = {l.tolist()} (actions 0..{N.N_ACTIONS - 1})")
+        rep, app = rep.astype(np.uint8), app.astype(np.uint8)
+        gens, cap = int(generations), int(cap)
+        xo = N.EgExploreOpts(2 if cost_only else 1, mask, cap, gens, len(rep), _p(rep, C.c_uint8) if len(rep) else None, len(app),
+                             _p(app, C.c_uint8) if len(app) else None, int(max_shift), int(launch), int(max_variants))
+        L = N.lib()
+        N.check(L.eg_explore_validate(C.byref(ps.s), C.byref(xo)), "eg_explore_validate")
+        rows = (N.EgExploreGeneration * gens)()
+        members = (N.EgExploreMember * ((gens + 1) * cap))()
+        numbers = (C.c_int64 * cap)()
+        n_gen, stop = C.c_int32(0), C.c_int32(0)
+        population = C.POINTER(N.EgPlanSet)()
+        res = BatchResult.alloc(cap)
+        snap = weights.snapshot()
+        opts = self._opts(True, False, True)
+        out = res.struct()
+        N.check(L.eg_explore_plans(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(xo), C.c_uint64(seed & (2**64 - 1)), C.c_uint64(index),
+                                   C.byref(population), rows, members, numbers, C.byref(n_gen), C.byref(stop), C.byref(out)), "eg_explore_plans")
+        plans = Plan._take_set(population)
+        reason = EXPLORE_STOP[stop.value]
+        fields_g = ("n_frontier", "n_held", "n_new", "n_variants", "n_valid", "n_dropped")
+        g_rows = [ExploreGeneration(*(int(getattr(rows[g], f)) for f in fields_g)) for g in range(n_gen.value)]
+
+        def member(m):
+            edit = PlanMove(m.move.list, m.move.year, m.move.pos, m.move.to_year, m.move.to_pos) if m.is_move else \
+                PlanEdit(PlanEdit.KINDS[m.edit.kind], m.edit.list, m.edit.year, m.edit.pos, m.edit.action)
+            return ExploreMember(int(m.parent), edit, int(m.number), float(m.score), tuple(m.metrics))
+        kept = []
+        if reason != "empty":
+            # row 0: the start plans held after generation 0 — what generation 0 held less what entered as a neighbour
+            kept.append([member(m) for m in members[:g_rows[0].n_held - g_rows[0].n_new]])
+            kept += [[member(m) for m in members[(g + 1) * cap:(g + 1) * cap + g_rows[g].n_new]] for g in range(n_gen.value)]
+        front = ExploreFront(plans, np.zeros(0, np.int64), np.zeros((0, 4)), np.zeros(0), g_rows, kept, reason, None)
+        if reason != "empty":
+            front.numbers = np.array(numbers[:len(plans)], np.int64)
+            by_number = {m.number: m for row in kept for m in row}
+            last = [by_number[int(k)] for k in front.numbers]
+            front.metrics = np.array([m.metrics for m in last], np.float64).reshape(-1, 4)
+            front.score = np.array([m.score for m in last], np.float64)
+            names = [f.name for f in fields(BatchResult)]
+            front.records = BatchResult(*[np.ascontiguousarray(getattr(res, f)[:len(last)]) for f in names])
+            line = front.lineage(starts)[-1]
+            for plan, k in zip(plans, front.numbers):
+                plan.name = line[int(k)].name
+        else:
+            for plan, p in zip(plans, starts):
                 plan.name = p.name
         return front
 

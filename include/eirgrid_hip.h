@@ -587,6 +587,82 @@ int32_t eg_breed_plans(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts
                        eg_breed_member *members /* [max_generations][cap] */, int32_t *n_generations, int32_t *stop_reason,
                        eg_episode_out *out /* cap rows, may be NULL */);
 
+/* Exploring a front: a Pareto local search over one-entry edits and moves, the archive and its unexplored members kept on the device.
+ * eg_refine_plans walks every plan of a front toward the same scalar optimum; eg_breed_plans recombines what a population holds.
+ * eg_explore_plans(ctx, policy, opts, starts, explore_opts, seed, episode_index, ...) changes single entries and selects by dominance.
+ *   neighbourhood  of a plan: the variants of one round of eg_refine_plans_moves for that plan (replace_with, append_with and max_shift
+ *                of the options) WITHOUT its variant 0, in that order: the deletes of best_actions, the deletes of
+ *                best_deficit_actions, the replaces, the appends (none while best_actions holds 4 096 entries), the moves;
+ *   numbers      every variant of the call gets a NUMBER (int64); numbers count on from generation to generation;
+ *   generation 0 the n start plans first, as "none" edits, numbers 0..n-1; then the neighbourhood of each start plan in order.  The
+ *                frontier F_0 is the start plans;
+ *   generation g > 0   the neighbourhoods of the members of F_g in ascending number, and nothing else.  M_g is the number of generation
+ *                g's first neighbour (M_0 = n);
+ *   evaluation   the generation's variants are cut into chunks of L = launch_variants (1..EG_CROSS_MAX_VARIANTS; 0 means
+ *                EG_CROSS_MAX_VARIANTS); a cut falls anywhere, there are no segments: a variant carries the position of its base in the
+ *                frontier array as its slot.  Each chunk runs as a launch of eg_refine_plans_moves runs — k_plan_edits_many writes the
+ *                blocks, k_plan_moves behind it when the chunk holds a move, the plan batch with same_index = 1 at episode_index — the
+ *                short or long replay route chosen per variant from the base's best_actions length plus the edit's delta;
+ *   selection    ONE private archive per call (NOT the context's eg_pareto_track archive, which stays untouched): it starts empty at
+ *                the call and is KEPT across generations.  After every chunk it is folded with eg_pareto_track's definitions, word for
+ *                word — valid, oriented dominance over `objectives`, the same point held once at the lowest index, the capacity rule
+ *                with `mode` and the sticky n_dropped — the index of a variant being its number.  Numbers only grow, so a neighbour that
+ *                merely equals a held point never displaces it, and the front never gets worse.  With n_dropped > 0 the result depends
+ *                on the chunk boundaries, which L defines and which are therefore part of the contract; the call is deterministic
+ *                either way;
+ *   frontier     F_{g+1} is the archive's entries with number >= M_g after the generation's last chunk: the members nobody has
+ *                explored yet.  A member whose neighbourhood has been evaluated is never enumerated again.  A base that a neighbour
+ *                dominates in the middle of a generation still has the rest of its neighbourhood evaluated: the frontier array is not
+ *                touched during a generation;
+ *   stop         checked in this order after a generation:
+ *                EG_EXPLORE_EMPTY: no variant so far was valid (the archive is empty; generation 0 only).  The start plans are returned;
+ *                EG_EXPLORE_EXPLORED: F_{g+1} is empty.  With n_dropped == 0 every member is then a Pareto local optimum of the
+ *                neighbourhood;
+ *                EG_EXPLORE_BUDGET: max_variants > 0, and the next generation's variant count plus those already run would exceed it;
+ *                that generation is not started (generation 0 always runs);
+ *                EG_EXPLORE_MAX_GENERATIONS: max_generations generations have run.
+ * Returned: *population = the archive's plans in ascending number (free with eg_plans_free; names ""), decoded from the archive's block
+ * slots as they stand on the device — not rebuilt from the genealogy; generations[max_generations], a row per generation that ran:
+ * n_frontier = |F_g|, n_held and n_dropped = the archive's after the generation (n_dropped is the call's running total), n_new =
+ * |F_{g+1}|, n_variants and n_valid = the generation's own; members[max_generations + 1][cap]: row 0 holds the start plans the archive
+ * held after generation 0 (parent -1, a "none" edit, number = position in `starts`), row g + 1 holds F_{g+1} in ascending number —
+ * `parent` is the number of the plan the edit or move is against, which stands in the row before (or is a start plan): the whole
+ * genealogy; final_numbers[cap]: the numbers of *population's members, n_held of the last generation; *n_generations; *stop_reason;
+ * out (cap episodes, may be NULL): the records of *population's members, row r member r, taken from the archive's record slots (not
+ * written after EG_EXPLORE_EMPTY).
+ * Per chunk the host uploads 8 bytes per variant, 4 for its slot, and the routing; per generation it reads one buffer back: a header
+ * and a row for every NEW member only (number, metrics, score and the block's two prefix-offset tables, from which the next generation
+ * is enumerated and routed — chunk by chunk: the host never holds a generation's variants, which can be tens of millions).  After
+ * generation 0 the start plans the archive holds have rows too — they entered in it, and that is how row 0 of `members` is known.
+ * After the last generation the archive's entries (56 bytes each) are read once.  No per-variant data comes down and no plan block goes up after
+ * generation 0 (csrc/eg_breed.h k_breed_gather, csrc/eg_explore.h k_explore_turnover).
+ * Everything else is the contract of eg_breed_plans: no statistics, update or training folds, the resident policy and the context's own
+ * archives untouched, a rank of a group refused, the policy checked and staged once per call, the last launch's variants left behind
+ * as the last batch.
+ * eg_explore_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the field for a start set that is not a valid set of
+ * 1..EG_CROSS_MAX_PARENTS plans, NULL options, a mode other than 1 or 2, objectives outside 1..15, cap outside 1..EG_PARETO_MAX,
+ * max_generations < 1, n_replace or n_append < 0, a NULL list with a count, an action above 60, max_shift outside 0..25,
+ * launch_variants outside 0..EG_CROSS_MAX_VARIANTS, max_variants < 0.  Nothing is launched after a refusal.
+ * eg_explore_neighbourhood (host only, the same checks first): sizes[p] = the neighbourhood size of start plan p. */
+#define EG_EXPLORE_EXPLORED 0
+#define EG_EXPLORE_MAX_GENERATIONS 1
+#define EG_EXPLORE_EMPTY 2
+#define EG_EXPLORE_BUDGET 3
+typedef struct { int32_t mode /* 1 | 2 */, objectives /* 1..15 */, cap /* 1..EG_PARETO_MAX */, max_generations /* >= 1 */;
+                 int32_t n_replace; const uint8_t *replace_with; int32_t n_append; const uint8_t *append_with;
+                 int32_t max_shift /* 0..25; 0: no moves */, launch_variants;
+                 int64_t max_variants /* 0: no budget */; } eg_explore_opts;   /* 64 bytes */
+typedef struct { int32_t n_frontier, n_held, n_new, pad; int64_t n_variants, n_valid, n_dropped; } eg_explore_generation;   /* 40 bytes */
+typedef struct { int64_t parent /* a number; -1: a start plan */; int32_t is_move; eg_plan_edit edit; eg_plan_move move;
+                 int64_t number; double score, metrics[4]; } eg_explore_member;   /* 88 bytes */
+int32_t eg_explore_validate(const eg_plan_set *starts, const eg_explore_opts *);
+int32_t eg_explore_neighbourhood(const eg_plan_set *starts, const eg_explore_opts *, int64_t *sizes /* [n_plans] */);
+int32_t eg_explore_plans(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts *, const eg_plan_set *starts, const eg_explore_opts *,
+                         uint64_t seed, uint64_t episode_index, eg_plan_set **population,
+                         eg_explore_generation *generations /* [max_generations] */,
+                         eg_explore_member *members /* [max_generations + 1][cap] */, int64_t *final_numbers /* [cap] */,
+                         int32_t *n_generations, int32_t *stop_reason, eg_episode_out *out /* cap rows, may be NULL */);
+
 /* ---- eg_group: one process drives N ranks, one context per rank (no counterpart in the reference: the N-rank form of the
  * reduced-update loop above).  A group owns its contexts.  The exchange between ranks is inside the library — device-to-device
  * copies, no collective library — and every call enqueues the work of all ranks from the calling thread without synchronising

@@ -1,0 +1,31 @@
+"""What the compiler makes of k_explore_turnover (csrc/eg_explore.h; no GPU needed: scripts/kernel_resources.sh, device code only).  The
+kernel counts an entry's position among the archive's new entries with ballots and copies its plan block, a wave per archive entry: it
+may not touch scratch memory or LDS, may not spill, and stays small.  It lives in eg_rollout.o only."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
+
+
+@pytest.fixture(scope="module")
+def lines():
+    return subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout.splitlines()
+
+
+def test_the_kernel_uses_no_scratch_no_lds_and_few_registers(lines):
+    kernel = "k_explore_turnover"
+    rows = [line for line in lines if kernel in line]
+    assert len(rows) == 1, rows      # (eg_rollout.o only: the throughput object does not carry it)
+    second = next(i for i, line in enumerate(lines) if line.startswith("# eg_rollout.hip") and i > 0)
+    assert lines.index(rows[0]) < second, f"{kernel} belongs to eg_rollout.o"
+    m = re.search(r"VGPRs: (\d+) .*?ScratchSize \[bytes/lane\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+).*?LDS Size \[bytes/block\]: (\d+)", rows[0])
+    assert m, rows[0]
+    vgprs, scratch, sgpr_spill, vgpr_spill, lds = (int(m.group(k)) for k in range(1, 6))
+    assert scratch == 0 and vgpr_spill == 0 and sgpr_spill == 0, rows[0]
+    assert lds == 0, lds
+    assert vgprs <= 72, vgprs      # (seven waves a SIMD: 512 registers in granules of 8)
