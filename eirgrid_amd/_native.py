@@ -138,6 +138,14 @@ BREED_CONVERGED, BREED_MAX_GENERATIONS, BREED_EMPTY = 0, 1, 2      # EG_BREED_*
 EXPLORE_EXPLORED, EXPLORE_MAX_GENERATIONS, EXPLORE_EMPTY, EXPLORE_BUDGET = 0, 1, 2, 3      # EG_EXPLORE_*
 PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
 DEBUG_LIST_LEN, DEBUG_FOLD_BEST_RESULT, DEBUG_FOLD_TOP_K = 8, 1, 2      # EG_DEBUG_*
+# the crafted-generation hooks (eg_debug_breed_*): the canary byte, the multiplier of a block's tag, the two turnovers, and the layouts
+DEBUG_BREED_CANARY, DEBUG_BREED_TAG_MUL = 0xC5, 0x9E3779B97F4A7C15                # EG_DEBUG_BREED_CANARY, EG_DEBUG_BREED_TAG_MUL
+DEBUG_TURNOVER_BREED, DEBUG_TURNOVER_EXPLORE = 1, 2                               # EG_DEBUG_TURNOVER_*
+DEBUG_PARETO_ENTRY_BYTES = 56                                                     # EG_DEBUG_PARETO_ENTRY_BYTES
+DEBUG_PARETO_STATE_BYTES = 32 + PARETO_MAX * DEBUG_PARETO_ENTRY_BYTES             # EG_DEBUG_PARETO_STATE_BYTES
+DEBUG_BREED_HEADER_BYTES, DEBUG_BREED_ROW_BYTES = 32, 288                         # EG_DEBUG_BREED_HEADER_BYTES, EG_DEBUG_BREED_ROW_BYTES
+DEBUG_BREED_READBACK_BYTES = DEBUG_BREED_HEADER_BYTES + PARETO_MAX * DEBUG_BREED_ROW_BYTES      # EG_DEBUG_BREED_READBACK_BYTES
+DEBUG_BREED_BLOCK_OFFSETS = 416                                                   # EG_DEBUG_BREED_BLOCK_OFFSETS
 
 
 class EgUpdateCandidate(C.Structure):      # the candidate record of an update packet (CANDIDATE_BYTES)
@@ -166,6 +174,7 @@ EXPORTS = [
     "eg_group_top_k_track", "eg_group_fetch_top_k", "eg_plans_validate", "eg_evaluate_plans", "eg_plans_load", "eg_plans_free",
     "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block", "eg_plans_save", "eg_refine_validate", "eg_refine_plan",
     "eg_refine_plans_validate", "eg_refine_plans", "eg_debug_refine_pick_many",
+    "eg_debug_breed_begin", "eg_debug_breed_chunk", "eg_debug_breed_turnover", "eg_debug_breed_fetch",
     "eg_plan_moves_validate", "eg_evaluate_plan_moves", "eg_refine_plans_moves_validate", "eg_refine_plans_moves",
     "eg_plan_crosses_validate", "eg_evaluate_plan_crosses",
     "eg_breed_validate", "eg_breed_plans", "eg_explore_validate", "eg_explore_neighbourhood", "eg_explore_plans",
@@ -396,6 +405,15 @@ def lib():
         L.eg_debug_pick_best.argtypes = [C.c_void_p, C.c_void_p]
         L.eg_debug_refine_pick.restype = C.c_int32
         L.eg_debug_refine_pick.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, _u8p]
+    if hasattr(L, "eg_debug_breed_begin") or not os.environ.get("EIRGRID_LIB"):      # (likewise: the crafted-generation test hooks)
+        L.eg_debug_breed_begin.restype = C.c_int32
+        L.eg_debug_breed_begin.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.eg_debug_breed_chunk.restype = C.c_int32
+        L.eg_debug_breed_chunk.argtypes = [C.c_void_p, _dp, _i32p, C.c_uint32, C.c_uint64]
+        L.eg_debug_breed_turnover.restype = C.c_int32
+        L.eg_debug_breed_turnover.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]
+        L.eg_debug_breed_fetch.restype = C.c_int32
+        L.eg_debug_breed_fetch.argtypes = [C.c_void_p, C.c_void_p, _u8p, _u8p, _u8p, _u8p, C.c_void_p, _u64p]
     L.eg_plans_load.restype = C.POINTER(EgPlanSet)
     L.eg_plans_load.argtypes = [C.c_char_p]
     L.eg_plans_free.argtypes = [C.POINTER(EgPlanSet)]

@@ -1,6 +1,7 @@
 // eg_debug.cpp — the crafted-batch test hooks (include/eirgrid_hip.h, debug section): a batch of synthetic records in the context's
 // record buffer, and the reductions that decide what a run keeps run over it — the folds launch_batch runs behind a real batch (through the
-// helpers it calls), k_pick_best, k_refine_pick_many.  Host code only: no kernel is launched here that a run does not launch.
+// helpers it calls), k_pick_best, k_refine_pick_many — and a crafted generation of eg_breed_plans / eg_explore_plans: tagged plan blocks
+// folded into the private archive, gathered and turned over.  Host code only: no kernel is launched here that a run does not launch.
 #include <cstring>
 
 #include "eg_host.h"
@@ -147,6 +148,88 @@ int32_t eg_debug_refine_pick_many(eg_ctx* c, int32_t mode, const uint32_t* seg_f
     if (at != n) { set_error("eg_debug_refine_pick_many: the segments cover " + std::to_string(at) + " of the last batch's " + std::to_string(n) + " records"); return EG_ERR_BAD_ARG; }
   }
   return refine_pick(c, mode, seg_first, seg_count, n_segs, entries, base_blocks);
+}
+
+// ---- a crafted generation of eg_breed_plans / eg_explore_plans: the private archive, k_breed_gather and the two turnover kernels ------
+static_assert(sizeof(ParetoEntry) == EG_DEBUG_PARETO_ENTRY_BYTES && sizeof(ParetoState) == EG_DEBUG_PARETO_STATE_BYTES && offsetof(ParetoState, e) == 32,
+              "the archive's state is what the hooks document");
+static_assert(kBreedHeaderBytes == EG_DEBUG_BREED_HEADER_BYTES && kBreedRowBytes == EG_DEBUG_BREED_ROW_BYTES &&
+              breed_at::kReadbackBytes == EG_DEBUG_BREED_READBACK_BYTES && snap::best_off - snap::best_mask == EG_DEBUG_BREED_BLOCK_OFFSETS &&
+              sizeof(BreedCounters) == 16, "the readback buffer is what the hooks document");
+
+int32_t eg_debug_breed_begin(eg_ctx* c, int32_t cap, int32_t objectives, int32_t mode) {
+  if (!c) { set_error("eg_debug_breed_begin: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_breed_begin"));
+  if (cap < 1 || cap > EG_PARETO_MAX) { set_error("eg_debug_breed_begin: cap " + std::to_string(cap) + " is outside 1..EG_PARETO_MAX (" + std::to_string(EG_PARETO_MAX) + ")"); return EG_ERR_BAD_ARG; }
+  if (objectives < 1 || objectives > 15) { set_error("eg_debug_breed_begin: objectives " + std::to_string(objectives) + " is outside 1..15 (bit i = metric i)"); return EG_ERR_BAD_ARG; }
+  if (mode != 1 && mode != 2) { set_error("eg_debug_breed_begin: mode " + std::to_string(mode) + " is neither 1 (optimization_mode None) nor 2 (cost_only)"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  c->debug_breed = false;
+  EG_HIP(c->d_breed.reserve(breed_at::total));
+  EG_HIP(c->d_breed_work.reserve(pareto_work_bytes(EG_CROSS_MAX_VARIANTS)));
+  ParetoState st{};
+  st.cap = cap; st.objectives = objectives; st.mode = mode;
+  const BreedCounters zero{};
+  static_assert(breed_at::records < breed_at::blocks && breed_at::blocks < breed_at::parents && breed_at::parents < breed_at::readback &&
+                breed_at::readback + breed_at::kReadbackBytes == breed_at::counters, "the canary fills what lies between the state and the counters");
+  EG_HIP(hipMemcpy(c->d_breed, &st, sizeof(st), hipMemcpyHostToDevice));
+  EG_HIP(hipMemset(c->d_breed + breed_at::records, EG_DEBUG_BREED_CANARY, breed_at::counters - breed_at::records));
+  EG_HIP(hipMemcpy(c->d_breed + breed_at::counters, &zero, sizeof(zero), hipMemcpyHostToDevice));
+  c->debug_breed = true;
+  return EG_OK;
+}
+
+int32_t eg_debug_breed_chunk(eg_ctx* c, const double* metrics, const int32_t* status, uint32_t n, uint64_t first_index) {
+  if (!c || !metrics || !status) { set_error("eg_debug_breed_chunk: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_breed_chunk"));
+  if (!c->debug_breed) { set_error("eg_debug_breed_chunk: eg_debug_breed_begin first"); return EG_ERR_BAD_ARG; }
+  if (n == 0 || n > EG_CROSS_MAX_VARIANTS) { set_error("eg_debug_breed_chunk: n = " + std::to_string(n) + " (1..EG_CROSS_MAX_VARIANTS)"); return EG_ERR_BAD_ARG; }
+  if (first_index > uint64_t(INT64_MAX) - n) { set_error("eg_debug_breed_chunk: first_index + n passes 2^63 (an entry's index is an int64)"); return EG_ERR_BAD_ARG; }
+  EG_TRY(eg_debug_load_batch(c, metrics, status, nullptr, nullptr, nullptr, n, first_index));
+  constexpr size_t kWords = snap::kPlanStride / 4;
+  std::vector<uint32_t> blocks(size_t(n) * kWords);
+  for (uint32_t j = 0; j < n; ++j) {
+    const uint32_t h = uint32_t(((first_index + j) * EG_DEBUG_BREED_TAG_MUL) >> 32);
+    uint32_t* b = blocks.data() + size_t(j) * kWords;
+    for (size_t w = 0; w < kWords; ++w) b[w] = h + uint32_t(w);
+  }
+  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
+  // (a synchronous copy on the null stream: it waits for the previous chunk's gather, which read what it overwrites)
+  EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice));
+  c->n_plan_blocks = n;
+  const ParetoWork work = pareto_work(c->d_breed_work, EG_CROSS_MAX_VARIANTS);
+  EG_LAUNCH("k_pareto_filter .. k_pareto_finalize", launch_pareto_fold(c->d_breed, work, c->out, n, first_index, nullptr));
+  EG_LAUNCH("k_breed_gather", launch_breed_gather(c->d_breed, c->out, n, first_index, c->d_plans, nullptr));
+  return EG_OK;
+}
+
+int32_t eg_debug_breed_turnover(eg_ctx* c, int32_t kind, int32_t next, int64_t m_first) {
+  if (!c) { set_error("eg_debug_breed_turnover: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_breed_turnover"));
+  if (!c->debug_breed) { set_error("eg_debug_breed_turnover: eg_debug_breed_begin first"); return EG_ERR_BAD_ARG; }
+  if (kind != EG_DEBUG_TURNOVER_BREED && kind != EG_DEBUG_TURNOVER_EXPLORE) { set_error("eg_debug_breed_turnover: kind " + std::to_string(kind) + " is neither EG_DEBUG_TURNOVER_BREED nor EG_DEBUG_TURNOVER_EXPLORE"); return EG_ERR_BAD_ARG; }
+  if (next != 0 && next != 1) { set_error("eg_debug_breed_turnover: next = " + std::to_string(next) + " (array 0 | 1)"); return EG_ERR_BAD_ARG; }
+  if (kind == EG_DEBUG_TURNOVER_EXPLORE && m_first < 0) { set_error("eg_debug_breed_turnover: m_first = " + std::to_string(m_first) + " (a variant number)"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  if (kind == EG_DEBUG_TURNOVER_BREED) EG_LAUNCH("k_breed_turnover", launch_breed_turnover(c->d_breed, next, nullptr));
+  else EG_LAUNCH("k_explore_turnover", launch_explore_turnover(c->d_breed, next, (long long)m_first, nullptr));
+  return EG_OK;
+}
+
+int32_t eg_debug_breed_fetch(eg_ctx* c, void* state, uint8_t* blocks, uint8_t* array0, uint8_t* array1, uint8_t* readback, void* counters, uint64_t* tags) {
+  if (!c) { set_error("eg_debug_breed_fetch: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_breed_fetch"));
+  if (!c->debug_breed) { set_error("eg_debug_breed_fetch: eg_debug_breed_begin first"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  // (synchronous copies on the null stream: they wait for whatever the hooks have launched)
+  if (state) EG_HIP(hipMemcpy(state, c->d_breed, sizeof(ParetoState), hipMemcpyDeviceToHost));
+  if (blocks) EG_HIP(hipMemcpy(blocks, c->d_breed + breed_at::blocks, breed_at::kParentArray, hipMemcpyDeviceToHost));
+  if (array0) EG_HIP(hipMemcpy(array0, c->d_breed + breed_at::parents, breed_at::kParentArray, hipMemcpyDeviceToHost));
+  if (array1) EG_HIP(hipMemcpy(array1, c->d_breed + breed_at::parents + breed_at::kParentArray, breed_at::kParentArray, hipMemcpyDeviceToHost));
+  if (readback) EG_HIP(hipMemcpy(readback, c->d_breed + breed_at::readback, breed_at::kReadbackBytes, hipMemcpyDeviceToHost));
+  if (counters) EG_HIP(hipMemcpy(counters, c->d_breed + breed_at::counters, sizeof(BreedCounters), hipMemcpyDeviceToHost));
+  if (tags) EG_HIP(hipMemcpy2D(tags, sizeof(uint64_t), c->d_breed + breed_at::records + rec::n_draws, rec::stride, sizeof(uint64_t), EG_PARETO_MAX, hipMemcpyDeviceToHost));
+  return EG_OK;
 }
 
 }  // extern "C"

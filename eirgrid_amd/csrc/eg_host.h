@@ -150,6 +150,7 @@ struct eg_ctx {
   // allocated at the first call, and Pareto work of its own sized for a launch of EG_CROSS_MAX_VARIANTS.  eg_explore_plans uses both the
   // same way (the parent arrays as its frontier arrays); either call starts the archive empty
   eg::DevBuf<uint8_t> d_breed, d_breed_work;
+  bool debug_breed = false;      // eg_debug_breed_begin has started the private archive (the crafted-generation test hooks)
 };
 
 namespace eg {

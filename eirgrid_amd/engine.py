@@ -1345,6 +1345,34 @@ class Engine:
                 "eg_debug_refine_pick_many")
         return list(entries), base
 
+    def _debug_breed_begin(self, cap: int, mask: int, mode: int = 1) -> None:
+        """Test hook (eg_debug_breed_begin): the private archive of eg_breed_plans / eg_explore_plans started empty, canary everywhere."""
+        N.check(N.lib().eg_debug_breed_begin(self.h, int(cap), int(mask), int(mode)), "eg_debug_breed_begin")
+
+    def _debug_breed_chunk(self, metrics, status, first_index: int) -> None:
+        """Test hook (eg_debug_breed_chunk): a chunk of synthetic records with these metrics [n,4] and status [n] and tagged plan blocks,
+        folded into the private archive and gathered."""
+        m = np.ascontiguousarray(metrics, dtype=np.float64).reshape(-1, 4)
+        st = np.ascontiguousarray(status, dtype=np.int32)
+        assert st.shape == (len(m),)
+        N.check(N.lib().eg_debug_breed_chunk(self.h, _p(m, C.c_double), _p(st, C.c_int32), len(m), C.c_uint64(int(first_index))), "eg_debug_breed_chunk")
+
+    def _debug_breed_turnover(self, kind: int, next_array: int, m_first: int = 0) -> None:
+        """Test hook (eg_debug_breed_turnover): k_breed_turnover (N.DEBUG_TURNOVER_BREED) or k_explore_turnover (N.DEBUG_TURNOVER_EXPLORE)."""
+        N.check(N.lib().eg_debug_breed_turnover(self.h, int(kind), int(next_array), C.c_int64(int(m_first))), "eg_debug_breed_turnover")
+
+    def _debug_breed_fetch(self) -> dict:
+        """Test hook (eg_debug_breed_fetch): {state, blocks [256, PLAN_BLOCK_BYTES], arrays (the two parent / frontier arrays, likewise),
+        readback, counters: uint8 arrays; tags: uint64 [256], n_draws of the record slots}."""
+        state = np.zeros(N.DEBUG_PARETO_STATE_BYTES, np.uint8)
+        blocks, a0, a1 = (np.zeros((N.PARETO_MAX, N.PLAN_BLOCK_BYTES), np.uint8) for _ in range(3))
+        readback = np.zeros(N.DEBUG_BREED_READBACK_BYTES, np.uint8)
+        counters = np.zeros(16, np.uint8)
+        tags = np.zeros(N.PARETO_MAX, np.uint64)
+        N.check(N.lib().eg_debug_breed_fetch(self.h, state.ctypes.data_as(C.c_void_p), _p(blocks, C.c_uint8), _p(a0, C.c_uint8), _p(a1, C.c_uint8), _p(readback, C.c_uint8),
+                                             counters.ctypes.data_as(C.c_void_p), _p(tags, C.c_uint64)), "eg_debug_breed_fetch")
+        return {"state": state, "blocks": blocks, "arrays": (a0, a1), "readback": readback, "counters": counters, "tags": tags}
+
     def fetch_scores(self, n_episodes: int) -> np.ndarray:
         s = np.zeros(n_episodes)
         N.check(N.lib().eg_fetch_scores(self.h, _p(s, C.c_double)), "eg_fetch_scores")

@@ -746,6 +746,45 @@ int32_t eg_debug_pick_best(eg_ctx *, void *candidate /* EG_CANDIDATE_BYTES */);
 int32_t eg_debug_refine_pick(eg_ctx *, int32_t mode /* 1 | 2 */, void *entry /* EG_DEBUG_REFINE_ENTRY_BYTES */, uint8_t *base_block /* EG_PLAN_BLOCK_BYTES */);
 int32_t eg_debug_refine_pick_many(eg_ctx *, int32_t mode, const uint32_t *seg_first, const uint32_t *seg_count, int32_t n_segs,
                                   void *entries /* n_segs * EG_DEBUG_REFINE_ENTRY_BYTES */, uint8_t *base_blocks /* n_segs * EG_PLAN_BLOCK_BYTES */);
+/* Test hooks: a crafted generation of eg_breed_plans / eg_explore_plans without a rollout — synthetic records and tagged plan blocks
+ * folded into the calls' private archive and turned over by the kernels the two calls launch (k_pareto_filter .. k_pareto_finalize,
+ * k_breed_gather, k_breed_turnover, k_explore_turnover), through the launch helpers they use, in their order, on the null stream.  The
+ * context's own archive (eg_pareto_track, eg_fetch_pareto) is not touched.  All of them refuse a rank of a group; chunk, turnover and
+ * fetch refuse a context on which eg_debug_breed_begin has not succeeded; a refusal launches nothing.
+ *   eg_debug_breed_begin     reserves the private archive as eg_breed_plans does and starts it: an empty state with cap (1..EG_PARETO_MAX),
+ *                            objectives (1..15) and mode (1 | 2), zero counters, and every byte of the record slots, the block slots, the
+ *                            two parent / frontier arrays and the readback buffer EG_DEBUG_BREED_CANARY.
+ *   eg_debug_breed_chunk     one chunk of a generation, n variants (1..EG_CROSS_MAX_VARIANTS) numbered first_index ..: eg_debug_load_batch(ctx,
+ *                            metrics, status, NULL, NULL, NULL, n, first_index) — the tag n_draws of record j is its number g = first_index
+ *                            + j —, n plan blocks into the plan pool, the fold, k_breed_gather.  32-bit word w of block j (w = 0 ..
+ *                            EG_PLAN_BLOCK_BYTES / 4) is ((g * EG_DEBUG_BREED_TAG_MUL mod 2^64) >> 32) + w mod 2^32: consecutive inside a
+ *                            block, and the block's first word a Fibonacci hash of the whole 64-bit number.
+ *   eg_debug_breed_turnover  kind EG_DEBUG_TURNOVER_BREED: k_breed_turnover into parent array `next` (0 | 1; m_first is not read);
+ *                            kind EG_DEBUG_TURNOVER_EXPLORE: k_explore_turnover into frontier array `next` with m_first (>= 0).
+ *   eg_debug_breed_fetch     copies down whatever is not NULL: `state` (EG_DEBUG_PARETO_STATE_BYTES: i32 cap, n_held, objectives, mode | i64
+ *                            n_dropped, pad | EG_PARETO_MAX entries of EG_DEBUG_PARETO_ENTRY_BYTES: f64 metrics[4], score | i64 index | i32
+ *                            slot, pad), the EG_PARETO_MAX block slots, the two parent / frontier arrays (EG_PARETO_MAX blocks each), the
+ *                            readback buffer (EG_DEBUG_BREED_READBACK_BYTES: a header of EG_DEBUG_BREED_HEADER_BYTES — i32 n_held, i32 0
+ *                            (explore: n_new) | i64 n_dropped, n_valid, 0 — then EG_PARETO_MAX rows of EG_DEBUG_BREED_ROW_BYTES: the entry,
+ *                            zeros up to byte 64, then the EG_DEBUG_BREED_ROW_BYTES - 64 bytes of the block from byte
+ *                            EG_DEBUG_BREED_BLOCK_OFFSETS on, its two prefix-offset tables), the counters (u64 n_valid | u32 done, pad) and
+ *                            the tag n_draws of each of the EG_PARETO_MAX record slots. */
+#define EG_DEBUG_BREED_CANARY 0xC5
+#define EG_DEBUG_BREED_TAG_MUL 0x9E3779B97F4A7C15ull
+#define EG_DEBUG_TURNOVER_BREED 1
+#define EG_DEBUG_TURNOVER_EXPLORE 2
+#define EG_DEBUG_PARETO_ENTRY_BYTES 56
+#define EG_DEBUG_PARETO_STATE_BYTES (32 + EG_PARETO_MAX * EG_DEBUG_PARETO_ENTRY_BYTES)
+#define EG_DEBUG_BREED_HEADER_BYTES 32
+#define EG_DEBUG_BREED_ROW_BYTES 288
+#define EG_DEBUG_BREED_READBACK_BYTES (EG_DEBUG_BREED_HEADER_BYTES + EG_PARETO_MAX * EG_DEBUG_BREED_ROW_BYTES)
+#define EG_DEBUG_BREED_BLOCK_OFFSETS 416
+int32_t eg_debug_breed_begin(eg_ctx *, int32_t cap, int32_t objectives, int32_t mode);
+int32_t eg_debug_breed_chunk(eg_ctx *, const double *metrics /* [n][4] */, const int32_t *status /* [n] */, uint32_t n, uint64_t first_index);
+int32_t eg_debug_breed_turnover(eg_ctx *, int32_t kind, int32_t next, int64_t m_first);
+int32_t eg_debug_breed_fetch(eg_ctx *, void *state /* EG_DEBUG_PARETO_STATE_BYTES */, uint8_t *blocks /* EG_PARETO_MAX * EG_PLAN_BLOCK_BYTES */,
+                             uint8_t *array0 /* EG_PARETO_MAX * EG_PLAN_BLOCK_BYTES */, uint8_t *array1 /* likewise */,
+                             uint8_t *readback /* EG_DEBUG_BREED_READBACK_BYTES */, void *counters /* 16 bytes */, uint64_t *tags /* [EG_PARETO_MAX] */);
 /* Diagnostic hook: ONE idle workgroup of 256 threads on the library's side stream that stays resident for `cycles` shader cycles;
  * variant 0: 1 KB of LDS, few registers; 1: 150 KB of LDS; 2: 200+ registers a lane; 3: both (the hoisted replay's footprint).  What a
  * resident workgroup costs the grid beside it: scripts/side_kernel_probe.py, profiles/r04_ab_notes.log. */
