@@ -45,6 +45,10 @@ struct Options {
   int coop_force = 0;                  // EIRGRID_COOP_FORCE (test hook)
   bool solo_on = true;                 // EIRGRID_REPLAY_SOLO=0: no per-episode replay kernel
   uint32_t solo_tiles = 1u;            // EIRGRID_SOLO_TILES=0: k_replay_solo searches by rank, as the classic variant does (A/B on one library)
+  // EIRGRID_SOLO_LAZY: the longest replay script (generators) that runs with the lazy field (k_replay_lazy in k_replay_solo's place); 0: none
+  // (k_replay_solo: the field current after every placement, as the classic variant keeps it), all: every script.  Default: measured on the benchmark's states — 9 % faster at
+  // 228 generators, 4 % slower at 468, 16 % slower at 916 (profiles/r10_ab_notes.log): six blocks of 64 generators.
+  uint32_t solo_lazy = 384u;
 };
 Options read_options() {
   Options o;
@@ -60,6 +64,7 @@ Options read_options() {
   if (const char* cf = std::getenv("EIRGRID_COOP_FORCE")) o.coop_force = std::atoi(cf);
   if (const char* so = std::getenv("EIRGRID_REPLAY_SOLO")) o.solo_on = so[0] != '0';
   if (const char* st = std::getenv("EIRGRID_SOLO_TILES")) o.solo_tiles = st[0] != '0' ? 1u : 0u;
+  if (const char* sl = std::getenv("EIRGRID_SOLO_LAZY")) o.solo_lazy = std::string(sl) == "all" ? 0xFFFFFFFFu : (uint32_t)std::strtoul(sl, nullptr, 10);
   return o;
 }
 
@@ -362,7 +367,7 @@ eg_ctx* eg_create(int32_t device_ordinal, const eg_world* world) {
   int rc = build_device_blob(c->tables.H, blob, info);
   if (rc == EG_OK) {
     c->dev.n_variants = info.n_variants; c->dev.size_factor = c->tables.H.size_factor; c->dev.n_existing = world->n_existing;
-    c->dev.solo_tiles = opt.solo_tiles;
+    c->dev.solo_tiles = opt.solo_tiles; c->dev.solo_lazy = opt.solo_lazy;
     if (!info.box_list_fits) c->heavy_slots_wanted = 0;
     c->hoist_supported = info.hoist_supported; c->hoist_on = info.hoist_supported && opt.replay_hoist;
     c->coop_force = opt.coop_force; c->solo_on = opt.solo_on;

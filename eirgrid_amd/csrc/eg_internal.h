@@ -152,6 +152,9 @@ struct DevTables {
   // [kMaxVariants][64] f64 (eg_rollout.hip place_tiles; never read by the classic variant)
   double* heavy_tiles;
   uint32_t solo_tiles;      // 1: k_replay_solo searches by tile bounds (place_tiles), 0: by rank (place_heavy; EIRGRID_SOLO_TILES=0)
+  // (with solo_tiles) != 0: k_replay_lazy runs in k_replay_solo's place; the longest script, in generators, whose field it brings up to date
+  // tile by tile, by the searches that read it; longer ones update it after every placement (EIRGRID_SOLO_LAZY = 0 | a length | all)
+  uint32_t solo_lazy;
 #define EG_TAB(name, type) EG_HD const type* name() const { return reinterpret_cast<const type*>(base + tab::name); }
   EG_TAB(usage, double) EG_TAB(population, double)
   EG_TAB(pre_co2, double) EG_TAB(pre_tg, double) EG_TAB(pre_ig, double) EG_TAB(pre_sg, double) EG_TAB(pre_optot, double)

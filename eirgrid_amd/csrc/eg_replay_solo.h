@@ -10,7 +10,11 @@
 //   2. its placements, one after the other, with k_rollout's own searches (place_search / place_heavy / place_exact_long, the penalty
 //      field of the pool, the lists' window in LDS and their tail in the record — the same code, so the same cells and the same
 //      accounting of requested chunks) — except that a search of the field goes by tile bounds (place_tiles: the same cell, the same
-//      chunks, fewer instructions; EIRGRID_SOLO_TILES=0: by rank, as k_rollout searches),
+//      chunks, fewer instructions; EIRGRID_SOLO_TILES=0: by rank, as k_rollout searches), and that the field is then kept lazily: a
+//      placement leaves it alone, a search brings the tiles it reads up to date (eg_rollout.hip tiles_refresh: the same values, the
+//      accounting of the eager update kept) — by k_replay_lazy, the kernel at the end of this file, which contexts with
+//      DevTables::solo_lazy != 0 launch in k_replay_solo's place (EIRGRID_SOLO_LAZY=0: k_replay_solo, its field updated after every
+//      placement, as k_rollout's is),
 //   3. its yearly rows (rs::books_quad, four years at a time), the running totals, the header and the statistics epilogue.
 // An episode whose script cannot be finished without a seeded draw or a capacity, or that finds no location, publishes nothing:
 // k_rollout<0, kReplayLong>, launched behind this kernel, runs every episode whose word in `done` does not carry the batch's sequence
@@ -76,9 +80,11 @@ __device__ __forceinline__ void field_add(unsigned long long field_addr, const E
 
 }  // namespace solo
 
-__global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables T, DevSnapshot S_in, DevOut O, unsigned long long first_index, uint32_t n_episodes,
-                                                                       const uint8_t* __restrict__ replay_mask, uint32_t replay_period, long long* stats,
-                                                                       EpisodeMap emap) {
+// `kLazy`: the episode may keep its field lazily (k_replay_lazy); without it this is k_replay_solo as it has been, instruction for instruction
+template <bool kLazy>
+__device__ __forceinline__ void replay_solo_episode(const DevTables& T, const DevSnapshot& S_in, const DevOut& O, unsigned long long first_index, uint32_t n_episodes,
+                                                    const uint8_t* __restrict__ replay_mask, uint32_t replay_period, long long* stats,
+                                                    const EpisodeMap& emap) {
   const int lane = threadIdx.x;
   if (blockIdx.x >= emap.count) return;
   if (S_in.plan_pool == nullptr && !(S_in.state()->has_lists && S_in.resident_list_len() > kShortReplayMax)) return;      // (uniform for the whole grid: the short variant's; a plan batch launches it over its long plans only)
@@ -120,6 +126,9 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
   PrefixCache prefix_cache0 = {0.0, -1, 0};
   uint32_t search_seq = 0;
   int tile_variants = 0;      // variants whose tile bounds (place_tiles) this episode has set up
+  // the field current only where a search reads it (eg_rollout.hip tiles_refresh) — for scripts up to DevTables::solo_lazy generators: a
+  // tile's catch-up walks the list, so its cost grows with the list, the eager update's does not (profiles/r10_ab_notes.log)
+  const bool lazy = kLazy && T.solo_tiles != 0u && (uint32_t)n_gens <= T.solo_lazy;
   int pk_block = 0;
   solo::Entries E;
 #pragma unroll
@@ -142,22 +151,32 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
         const unsigned long long class_addr = (unsigned long long)T.heavy + (unsigned long long)ep.heavy * slot_bytes + (unsigned long long)(hrc * kFieldStride) * 8ull;
         const unsigned long long tiles_addr = (unsigned long long)T.heavy_tiles + (unsigned long long)((ep.heavy * kMaxVariants + hv) * 64) * 8ull;
         if (!((ep.heavy_classes >> hrc) & 1)) {      // the first search of this radius class: its field joins
-          heavy_build_class<false>(class_addr, tail.gen_cell, lane, hrc, throughput_table(info), (info >> 8) & 15, ep.ngen);
+          if (lazy) { if (lane < kTiles) ((GlobalU16)(class_addr + 8ull * kTileCounters))[lane] = (unsigned short)0; }      // (no tile holds a generator yet; in flight until place_tiles waits)
+          else heavy_build_class<false>(class_addr, tail.gen_cell, lane, hrc, throughput_table(info), (info >> 8) & 15, ep.ngen);
           ep.heavy_classes |= 1 << hrc;
-          ep.heavy_quads = __builtin_amdgcn_readfirstlane(T.hv_quads()[ep.heavy_classes]);
-          wave_sync();
+          ep.heavy_quads = __builtin_amdgcn_readfirstlane(T.hv_quads()[ep.heavy_classes]);      // (lazy: the accounting's only — n_chunks is the classic variant's)
+          if (!lazy) {
+            wave_sync();
 #pragma unroll
-          for (int k = 0; k < kBoxLds / kWave; ++k) sh2.box[k * kWave + lane] = T.hv_lists()[ep.heavy_classes * 1024 + k * kWave + lane];
-          wave_sync();
-          solo::load_entries(E, lane);      // the lane's entries, ready for every field update until the next class joins
+            for (int k = 0; k < kBoxLds / kWave; ++k) sh2.box[k * kWave + lane] = T.hv_lists()[ep.heavy_classes * 1024 + k * kWave + lane];
+            wave_sync();
+            solo::load_entries(E, lane);      // the lane's entries, ready for every field update until the next class joins
+          }
         }
         int hr = kTilesUndecided;
         if (T.solo_tiles && !((tile_variants >> hv) & 1)) {      // the variant's first search of the episode: its tile bounds start at the largest u
           ((GlobalF64)tiles_addr)[lane] = T.umax()[hv * 64 + lane];      // (in flight until place_tiles waits for its stores)
           tile_variants |= 1 << hv;
         }
-        if (T.solo_tiles) hr = place_tiles((unsigned long long)T.base, yi * kMaxVariants + hv, class_addr, tiles_addr, tail.gen_cell, T.size_factor, lane, hrc, throughput_table(info), ep.ngen);
+        if (lazy) hr = place_tiles<true>((unsigned long long)T.base, yi * kMaxVariants + hv, class_addr, tiles_addr, tail.gen_cell, T.size_factor, lane, hrc | (((info >> 8) & 15) << 8), throughput_table(info), ep.ngen);
+        else if (T.solo_tiles) hr = place_tiles<false>((unsigned long long)T.base, yi * kMaxVariants + hv, class_addr, tiles_addr, tail.gen_cell, T.size_factor, lane, hrc, throughput_table(info), ep.ngen);
         if (hr == kTilesUndecided) {      // (EIRGRID_SOLO_TILES=0, or ties that place_heavy resolves on its slow path)
+          if (lazy) {      // the rank scan reads the field anywhere: all of the class's tiles current first
+            tiles_catch_up_all(class_addr, tail.gen_cell, lane, hrc, throughput_table(info), (info >> 8) & 15, ep.ngen);
+#if defined(EG_SOLO_STAMPS) && defined(EG_STAMPS)
+            if (lane == 0) sm.hdbg[0][3] += 1ull << 40;      // (undecided searches: above the count of generators folded)
+#endif
+          }
           const size_t yv = (size_t)(yi * kMaxVariants + hv) * kPsStride, yc = (size_t)(yi * kMaxVariants + hv) * kPcStride;
           hr = place_heavy<false>((unsigned long long)(T.ps() + yv), (unsigned long long)(T.pbase() + yc), (unsigned long long)(T.pcell() + yc), class_addr,
                                   tail.gen_cell, T.size_factor, lane, hrc, throughput_table(info), ep.ngen);
@@ -179,10 +198,12 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
       const unsigned long long field_addr = (unsigned long long)T.heavy + (unsigned long long)ep.heavy * ((unsigned long long)(kRadiusClasses * kFieldStride) * 8ull);
       ep.chunks += 2 * ep.heavy_quads;
       const unsigned long long hv_list = (unsigned long long)(T.hv_lists() + ep.heavy_classes * 1024);
-      if (ep.heavy_quads == 1) solo::field_add<4>(field_addr, E, cell);
-      else solo::field_add<8>(field_addr, E, cell);
-      if (ep.heavy_quads == 3) heavy_add_body<false, 4>(field_addr, hv_list, lane, cell, 8);
-      else if (ep.heavy_quads >= 4) heavy_add_body<false, 8>(field_addr, hv_list, lane, cell, 8);
+      if (!lazy) {      // (lazy: the next search that reads a tile folds this generator into it)
+        if (ep.heavy_quads == 1) solo::field_add<4>(field_addr, E, cell);
+        else solo::field_add<8>(field_addr, E, cell);
+        if (ep.heavy_quads == 3) heavy_add_body<false, 4>(field_addr, hv_list, lane, cell, 8);
+        else if (ep.heavy_quads >= 4) heavy_add_body<false, 8>(field_addr, hv_list, lane, cell, 8);
+      }
     }
     if (cell < 0) {      // EG_EP_NO_LOCATION (or a lost search): the classic path reports it, with the field slot this episode holds
                          // (tagged with the launch's sequence number; the pool has one slot per replay episode of the launch)
@@ -245,8 +266,22 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables
 #ifdef EG_STAMPS      // (with -DEG_STAMPS as well: place_heavy's own counters — scan / candidates / exact evaluation cycles; chunks, candidates, searches)
     for (int i = 0; i < 3; ++i) { dbg[8 + i] = sm.hdbg[0][i]; dbg[11 + i] = sm.hdbg[1][i]; }
     dbg[14] = sm.hdbg[1][3];      // (place_tiles: tiles evaluated)
+    dbg[15] = sm.hdbg[0][3];      // (lazy field: generators folded by tiles_refresh | searches left to place_heavy << 40; eager: heavy_add_body's cycles)
 #endif
   }
 #endif
   if (lane == 0) emap.solo[blockIdx.x] = emap.solo_seq;      // (k_rollout<0, kReplayLong> is stream-ordered behind this kernel)
+}
+
+__global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_solo(DevTables T, DevSnapshot S_in, DevOut O, unsigned long long first_index, uint32_t n_episodes,
+                                                                       const uint8_t* __restrict__ replay_mask, uint32_t replay_period, long long* stats,
+                                                                       EpisodeMap emap) {
+  replay_solo_episode<false>(T, S_in, O, first_index, n_episodes, replay_mask, replay_period, stats, emap);
+}
+// ... and the same kernel for contexts that keep the field lazily (DevTables::solo_lazy != 0 with solo_tiles): a kernel of its own, so that
+// k_replay_solo — what EIRGRID_SOLO_LAZY=0 and EIRGRID_SOLO_TILES=0 run — stays the code it was
+__global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_lazy(DevTables T, DevSnapshot S_in, DevOut O, unsigned long long first_index, uint32_t n_episodes,
+                                                                       const uint8_t* __restrict__ replay_mask, uint32_t replay_period, long long* stats,
+                                                                       EpisodeMap emap) {
+  replay_solo_episode<true>(T, S_in, O, first_index, n_episodes, replay_mask, replay_period, stats, emap);
 }

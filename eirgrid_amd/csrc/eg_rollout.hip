@@ -1428,8 +1428,90 @@ __device__ __noinline__ int place_heavy(unsigned long long list_addr, unsigned l
 // `tab_addr`: the tables (DevTables::base), `yv`: year * kMaxVariants + variant, `tiles_addr`: the variant's 49 tile bounds g
 constexpr int kTilesUndecided = -4;
 static_assert(kTileW * kTileW == kWave, "a cell of a tile per lane");
+constexpr int kNoTile = 63;      // a tile index with no cell on the grid: the second tile of a round that has only one
+static_assert(kNoTile >= kTiles && (kNoTile / kTileCols) * kTileW >= kGrid, "kNoTile is off the grid");
+
+// ---- the lazy field (k_replay_lazy: eg_replay_solo.h, DevTables::solo_lazy) ------------------------------------------------------------------
+// The eager field is kept current for every cell of every joined class after every placement (heavy_add_body), and built whole when
+// a class joins (heavy_build_class) — but a search by tiles reads it in the few tiles it evaluates and nowhere else.  Lazily, a
+// placement leaves the field alone, and a tile's 64 values are brought up to date when a search is about to read them: per field
+// slot, class and tile a counter `applied` — how many generators of the episode's list the tile's stored values hold (0: none, the
+// values are 1.0 whatever is stored: a class joins by zeroing its 49 counters) — in the spare doubles behind the class's cells
+// (index kCells is the dump entry of the eager update; the counters, 16 bits each, start at kCells + 1).
+// Catching up multiplies the factors of generators applied .. ngen - 1 in, in list order.  The eager value of a cell is
+// ((1 * f_1) * f_2) ... over the whole list in list order as well (a generator out of reach contributes exactly 1.0: the table
+// holds 1.0 at the cap, and x * 1.0 == x), so what a search reads is the eager field bit for bit — the same multiplications, later.
+// A tile nobody evaluates keeps stale, larger values; nothing reads them (place_heavy, which reads by rank, is preceded by
+// tiles_catch_up_all), and the tile's bound g is an upper bound of u * field whenever it was taken (the field only shrinks).
+constexpr int kTileCounters = kCells + 1;      // (in doubles, class-relative)
+static_assert((kFieldStride - kTileCounters) * 8 >= kTiles * 2 && EG_MAX_GENS <= 0xFFFF, "a 16-bit counter per tile fits behind a class's cells");
+// `fa`, `fb`: the lane's stored field values of tiles ta, tb (tb may be kNoTile) — on return current, and stored with the tiles'
+// counters; `applied`: the class's counters, a tile per lane.  The generators pass by in blocks of 64, one per lane; a lane-parallel
+// test keeps those within `reach` of either tile's box, and their factors are multiplied in one generator at a time (list order).
+// No control flow per generator and tile: one the tile already holds, or that only reaches the other tile, multiplies by the table's
+// 1.0 (measured: uniform branches around the two halves, an exact distance test and stores only for tiles that changed cost a search
+// 9 % more cycles than they saved).  A lane whose cell is off the grid folds along and stores nothing.
+// returns the generators folded
+__device__ __forceinline__ int tiles_refresh(unsigned long long a_s, int applied, int ta, int tb, int lane, int rc, int tbl, int reach, int ngen_s,
+                                             unsigned long long tail_cells, double& fa, double& fb) {
+  const int cap = factor_cap<false>(tbl);
+  const int ra = (ta / kTileCols) * kTileW, ca = (ta % kTileCols) * kTileW, rb = (tb / kTileCols) * kTileW, cb = (tb % kTileCols) * kTileW;
+  const int ia = ra + (lane >> 3), ja = ca + (lane & 7), ib = rb + (lane >> 3), jb = cb + (lane & 7);
+  const int aa = __builtin_amdgcn_readlane(applied, ta), ab = tb < kTiles ? __builtin_amdgcn_readlane(applied, tb) : ngen_s;
+  fa = aa == 0 ? 1.0 : fa; fb = ab == 0 ? 1.0 : fb;
+  int folded = 0;
+  const unsigned span = (unsigned)(kTileW - 1 + 2 * reach);
+  for (int gb = (aa < ab ? aa : ab) & ~(kWave - 1); gb < ngen_s; gb += kWave) {
+    const int gc = list_cell(tail_cells, gb, lane, ngen_s, 0), g = gb + lane;
+    const int gi = gc / kGrid, gj = gc - gi * kGrid;
+    const bool na = g >= aa && g < ngen_s && (unsigned)(gi - ra + reach) <= span && (unsigned)(gj - ca + reach) <= span;
+    const bool nb = g >= ab && g < ngen_s && (unsigned)(gi - rb + reach) <= span && (unsigned)(gj - cb + reach) <= span;
+    const int gij = gi | (gj << 8);
+    unsigned long long near = __ballot(na || nb);
+    while (near != 0ull) {
+      const int j = __ffsll((long long)near) - 1;
+      const int w = __builtin_amdgcn_readlane(gij, j), si = w & 255, sj = w >> 8;
+      int qa = (ia - si) * (ia - si) + (ja - sj) * (ja - sj), qb = (ib - si) * (ib - si) + (jb - sj) * (jb - sj);
+      qa = qa < cap && gb + j >= aa ? qa : cap;      // (a generator the tile already holds: 1.0, like one out of reach)
+      qb = qb < cap && gb + j >= ab ? qb : cap;
+      fa = fa * factor_by_q<false>(rc, tbl, qa);
+      fb = fb * factor_by_q<false>(rc, tbl, qb);
+      near &= near - 1ull;
+      ++folded;
+    }
+  }
+  if (ia < kGrid && ja < kGrid) *(GlobalF64)(a_s + (unsigned long long)((unsigned)(ia * kGrid + ja) * 8u)) = fa;
+  if (ib < kGrid && jb < kGrid) *(GlobalF64)(a_s + (unsigned long long)((unsigned)(ib * kGrid + jb) * 8u)) = fb;
+  if (lane == 0) {
+    const GlobalU16 cnt = (GlobalU16)(a_s + 8ull * kTileCounters);
+    cnt[ta] = (unsigned short)ngen_s;
+    if (tb < kTiles) cnt[tb] = (unsigned short)ngen_s;
+  }
+  return folded;
+}
+// every tile of a class current: what a search by rank (place_heavy, after kTilesUndecided) reads.  Slow, and rare.
+__device__ __noinline__ void tiles_catch_up_all(unsigned long long class_addr, unsigned long long tail_cells, int lane, int rc, int tbl, int reach, int ngen) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (place_tiles has just stored tiles and counters)
+  const int ngen_s = __builtin_amdgcn_readfirstlane(ngen);
+  const unsigned long long a_s = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(class_addr >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)class_addr);
+  const int applied = lane < kTiles ? tail_u16(a_s + 8ull * kTileCounters, lane) : 0;
+  if (__ballot(lane < kTiles && applied != ngen_s) == 0ull) return;
+#pragma nounroll
+  for (int ta = 0; ta < kTiles; ta += 2) {
+    const int tb = ta + 1 < kTiles ? ta + 1 : kNoTile;
+    const int ia = (ta / kTileCols) * kTileW + (lane >> 3), ja = (ta % kTileCols) * kTileW + (lane & 7);
+    const int ib = (tb / kTileCols) * kTileW + (lane >> 3), jb = (tb % kTileCols) * kTileW + (lane & 7);
+    const int ca = ia < kGrid && ja < kGrid ? ia * kGrid + ja : 0, cb = ib < kGrid && jb < kGrid ? ib * kGrid + jb : 0;
+    double fa = field_load((GlobalF64)a_s + ca), fb = field_load((GlobalF64)a_s + cb);
+    tiles_refresh(a_s, applied, ta, tb, lane, rc, tbl, reach, ngen_s, tail_cells, fa, fb);
+  }
+}
+
+// `kLazy`: the field is brought up to date tile by tile, here (above); `rc_in` then carries the class's radius in cells too (rc | reach << 8)
+template <bool kLazy>
 __device__ __noinline__ int place_tiles(unsigned long long tab_addr, int yv, unsigned long long class_addr, unsigned long long tiles_addr,
-                                        unsigned long long tail_cells, double size_factor, int lane, int rc, int tbl, int ngen) {
+                                        unsigned long long tail_cells, double size_factor, int lane, int rc_in, int tbl, int ngen) {
+  const int rc = kLazy ? rc_in & 255 : rc_in, reach = kLazy ? rc_in >> 8 : 0;
 #ifdef EG_STAMPS
   const unsigned long long ts0 = __builtin_readcyclecounter();
 #endif
@@ -1437,8 +1519,6 @@ __device__ __noinline__ int place_tiles(unsigned long long tab_addr, int yv, uns
   const int ngen_s = __builtin_amdgcn_readfirstlane(ngen);
   constexpr int kChunks = (kCells + kWave - 1) / kWave, kGroup = 4, kGroups = (kChunks + kGroup - 1) / kGroup;
   constexpr double kKeep = 1.0 - 0x1p-30, kKeepTile = 1.0 - 0x1p-29;
-  constexpr int kNoTile = 63;      // a tile index with no cell on the grid: the second tile of a round that has only one
-  static_assert(kNoTile >= kTiles && (kNoTile / kTileCols) * kTileW >= kGrid, "kNoTile is off the grid");
   auto uniform_u64 = [](unsigned long long a) { return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a); };
   const unsigned long long tab_s = uniform_u64(tab_addr), a_s = uniform_u64(class_addr), t_s = uniform_u64(tiles_addr);
   const unsigned long long yv_s = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(yv);
@@ -1454,6 +1534,8 @@ __device__ __noinline__ int place_tiles(unsigned long long tab_addr, int yv, uns
   const double gb = lane >= 1 && lane < kGroups ? *(GlobalF64c)(pb_s + (unsigned long long)((unsigned)(lane * kGroup * kWave) * 8u)) : 0.0;
   // 1. the bounds, and the two best tiles
   const double bound = lane < kTiles ? *(GlobalF64c)(rm_s + (unsigned long long)((unsigned)lane * 8u)) * field_load(gmax + lane) : 0.0;
+  int applied = 0;      // (kLazy) the class's tile counters, in the bounds' round trip; a search evaluates a tile once, so they hold for all of it
+  if constexpr (kLazy) applied = lane < kTiles ? tail_u16(a_s + 8ull * kTileCounters, lane) : 0;
   unsigned long long left = __ballot(bound > 0.0);      // tiles not evaluated yet that may hold a positive score
   if (left == 0ull) return kSearchFallback;             // (place_heavy's M: below 1e-250)
   const unsigned hb = (unsigned)__double2hiint(bound);
@@ -1485,8 +1567,17 @@ __device__ __noinline__ int place_tiles(unsigned long long tab_addr, int yv, uns
     const int ib = (tb / kTileCols) * kTileW + (lane >> 3), jb = (tb % kTileCols) * kTileW + (lane & 7);
     const bool ina = ia < kGrid && ja < kGrid, inb = ib < kGrid && jb < kGrid;
     const int ca = ina ? ia * kGrid + ja : 0, cb = inb ? ib * kGrid + jb : 0;      // (a lane off the grid reads cell 0 and scores 0)
-    const double fa = field_at(ca), fb = field_at(cb), pa = cb_at(ca), pb = cb_at(cb), ua = uc_at(ca), ub = uc_at(cb);
+    double fa = field_at(ca), fb = field_at(cb);
+    const double pa = cb_at(ca), pb = cb_at(cb), ua = uc_at(ca), ub = uc_at(cb);
     const int ra = rk_at(ca), rb = rk_at(cb);
+    if constexpr (kLazy) {      // the two tiles' field values current before the keys are formed
+      const int folded = tiles_refresh(a_s, applied, ta, tb, lane, rc, tbl, reach, ngen_s, tail_cells, fa, fb);
+#ifdef EG_STAMPS
+      if (lane == 0) sm.hdbg[0][3] += (unsigned long long)folded;      // (free in lazy mode: heavy_add_body's cycles otherwise)
+#else
+      (void)folded;
+#endif
+    }
     fold(ina ? pa * fa : 0.0, ra, ca);
     fold(inb ? pb * fb : 0.0, rb, cb);
     // the tiles' present maxima of u * field, rounded up within their high word: their g from now on
@@ -3121,7 +3212,10 @@ int launch_rollout_throughput(int kind, const DevTables& t, const DevSnapshot& s
   if (kind == kReplayLong) {
     // every long replay episode on its own wave, script / placements / rows one after the other (eg_replay_solo.h); the classic variant
     // behind it runs what that kernel left undone (a script that needs a seeded draw or hits a capacity) and carries the stop event
-    if (solo_seq != 0ull)
+    if (solo_seq != 0ull && t.solo_tiles != 0u && t.solo_lazy != 0u)
+      hipLaunchKernelGGL(k_replay_lazy, dim3(map.count), dim3(kWave), 0, (hipStream_t)stream, t, s, o, (unsigned long long)first_index, n, d_replay_mask, replay_period,
+                         d_stats, map);
+    else if (solo_seq != 0ull)
       hipLaunchKernelGGL(k_replay_solo, dim3(map.count), dim3(kWave), 0, (hipStream_t)stream, t, s, o, (unsigned long long)first_index, n, d_replay_mask, replay_period,
                          d_stats, map);
     EG_LAUNCH_TP(kReplayLong);

@@ -24,7 +24,7 @@ VARIANTS = ("heavy", "short", "lean", "coop", "books", "bcast", "solo")
 
 def variant_of(name):      # k_rollout<helpers, kind>: kind 2 = long-replay (heavy-capable) variant, 1 = short-replay, 0 = lean
     for key, v in (("k_replay_coop", "coop"), ("k_replay_books", "books"), ("k_replay_broadcast", "bcast"),      # the replay hoist's kernels
-                   ("k_replay_solo", "solo")):      # the per-episode replay kernel (k_rollout<.., 2> behind it then has nothing to do)
+                   ("k_replay_solo", "solo"), ("k_replay_lazy", "solo")):      # the per-episode replay kernel, eager / lazy field (k_rollout<.., 2> behind it then has nothing to do)
         if key in name: return v
     if "k_rollout" not in name: return None
     return "heavy" if ", 2>" in name else ("short" if ", 1>" in name else "lean")

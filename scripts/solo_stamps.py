@@ -38,3 +38,7 @@ if full[:, 13].mean() > 0:      # built with -DEG_STAMPS as well: place_heavy's 
           f"chunks scanned per search {full[:, 11].mean() / n:.1f}, candidates {full[:, 12].mean() / n:.2f}")
     if full[:, 14].mean() > 0:      # place_tiles (EIRGRID_SOLO_TILES=1, the default): tiles evaluated
         print(f"  place_tiles: tiles evaluated per search {full[:, 14].mean() / n:.2f} (the searches that place_heavy decided count as none)")
+        if os.environ.get("EIRGRID_SOLO_LAZY", "1")[0] != "0" and os.environ.get("EIRGRID_SOLO_TILES", "1")[0] != "0":      # the lazy field's counters (eager: heavy_add_body's cycles)
+            lazy = res.act_log[:n_rep, -256:].copy().view(np.uint64)[:, 15]
+            print(f"  lazy field: pending generators folded per search {(lazy & ((1 << 40) - 1)).mean() / n:.2f}, "
+                  f"searches left to place_heavy (every tile caught up first) per episode {(lazy >> 40).mean():.3f}")

@@ -21,7 +21,7 @@ for spec in specs:
     for path in glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(path)):
             nm = r["Kernel_Name"]
-            hoist = [v for key, v in (("k_replay_coop", "coop"), ("k_replay_books", "books"), ("k_replay_broadcast", "bcast"), ("k_replay_solo", "solo")) if key in nm]
+            hoist = [v for key, v in (("k_replay_coop", "coop"), ("k_replay_books", "books"), ("k_replay_broadcast", "bcast"), ("k_replay_solo", "solo"), ("k_replay_lazy", "solo")) if key in nm]
             if "k_rollout" not in nm and not hoist: continue
             v = hoist[0] if hoist else ("heavy" if ", 2>" in nm else ("short" if ", 1>" in nm else "lean"))      # k_rollout<helpers, kind>; the replay hoist's kernels
             e = per[v].setdefault(int(r["Dispatch_Id"]), {"grid": int(r["Grid_Size"])})

@@ -1,0 +1,27 @@
+"""What the compiler makes of k_replay_lazy, the per-episode replay kernel with the lazy field (no GPU needed:
+scripts/kernel_resources.sh, device code only).
+
+It runs in k_replay_solo's place, beside the lean grid at four waves per SIMD, and is held to what tests/test_solo_kernel_resources.py
+holds k_replay_solo to: no scratch memory, at most 128 vector registers, no more LDS than the long-replay variant of k_rollout."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
+def test_replay_lazy_keeps_four_waves_per_simd_and_no_scratch():
+    out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout
+    lazy = [re.search(r"VGPRs: (\d+) .*?ScratchSize \[bytes/lane\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", line)
+            for line in out.splitlines() if re.search(r"\bk_replay_lazy\b", line)]
+    long_replay = [re.search(r"LDS Size \[bytes/block\]: (\d+)", line) for line in out.splitlines() if line.startswith("k_rolloutILi0ELi2E")]
+    assert lazy and all(lazy) and long_replay and all(long_replay), out
+    for m in lazy:
+        vgprs, scratch, lds = (int(m.group(k)) for k in (1, 2, 3))
+        assert vgprs <= 128, vgprs
+        assert scratch == 0, scratch
+        assert lds <= int(long_replay[0].group(1)), (lds, long_replay[0].group(1))
