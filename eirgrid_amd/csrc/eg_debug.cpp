@@ -1,7 +1,8 @@
 // eg_debug.cpp — the crafted-batch test hooks (include/eirgrid_hip.h, debug section): a batch of synthetic records in the context's
 // record buffer, and the reductions that decide what a run keeps run over it — the folds launch_batch runs behind a real batch (through the
 // helpers it calls), k_pick_best, k_refine_pick_many — and a crafted generation of eg_breed_plans / eg_explore_plans: tagged plan blocks
-// folded into the private archive, gathered and turned over.  Host code only: no kernel is launched here that a run does not launch.
+// folded into the private archive, gathered and turned over — through the archive functions the entry points run (eg_plan_host.cpp).
+// Host code only: no kernel is launched here that a run does not launch.
 #include <cstring>
 
 #include "eg_host.h"
@@ -160,21 +161,16 @@ static_assert(kBreedHeaderBytes == EG_DEBUG_BREED_HEADER_BYTES && kBreedRowBytes
 int32_t eg_debug_breed_begin(eg_ctx* c, int32_t cap, int32_t objectives, int32_t mode) {
   if (!c) { set_error("eg_debug_breed_begin: bad argument"); return EG_ERR_BAD_ARG; }
   EG_TRY(refuse_rank(c, "eg_debug_breed_begin"));
-  if (cap < 1 || cap > EG_PARETO_MAX) { set_error("eg_debug_breed_begin: cap " + std::to_string(cap) + " is outside 1..EG_PARETO_MAX (" + std::to_string(EG_PARETO_MAX) + ")"); return EG_ERR_BAD_ARG; }
-  if (objectives < 1 || objectives > 15) { set_error("eg_debug_breed_begin: objectives " + std::to_string(objectives) + " is outside 1..15 (bit i = metric i)"); return EG_ERR_BAD_ARG; }
-  if (mode != 1 && mode != 2) { set_error("eg_debug_breed_begin: mode " + std::to_string(mode) + " is neither 1 (optimization_mode None) nor 2 (cost_only)"); return EG_ERR_BAD_ARG; }
+  auto fail = [](const std::string& m) { set_error("eg_debug_breed_begin: " + m); return EG_ERR_BAD_ARG; };
+  EG_TRY(check_cap(fail, cap)); EG_TRY(check_objectives(fail, objectives)); EG_TRY(check_mode(fail, mode));
   EG_HIP(hipSetDevice(c->device));
   c->debug_breed = false;
-  EG_HIP(c->d_breed.reserve(breed_at::total));
-  EG_HIP(c->d_breed_work.reserve(pareto_work_bytes(EG_CROSS_MAX_VARIANTS)));
-  ParetoState st{};
-  st.cap = cap; st.objectives = objectives; st.mode = mode;
-  const BreedCounters zero{};
   static_assert(breed_at::records < breed_at::blocks && breed_at::blocks < breed_at::parents && breed_at::parents < breed_at::readback &&
                 breed_at::readback + breed_at::kReadbackBytes == breed_at::counters, "the canary fills what lies between the state and the counters");
-  EG_HIP(hipMemcpy(c->d_breed, &st, sizeof(st), hipMemcpyHostToDevice));
-  EG_HIP(hipMemset(c->d_breed + breed_at::records, EG_DEBUG_BREED_CANARY, breed_at::counters - breed_at::records));
-  EG_HIP(hipMemcpy(c->d_breed + breed_at::counters, &zero, sizeof(zero), hipMemcpyHostToDevice));
+  EG_TRY(archive_begin(c, cap, objectives, mode, [c] {
+    EG_HIP(hipMemset(c->d_breed + breed_at::records, EG_DEBUG_BREED_CANARY, breed_at::counters - breed_at::records));
+    return EG_OK;
+  }));
   c->debug_breed = true;
   return EG_OK;
 }
@@ -197,10 +193,7 @@ int32_t eg_debug_breed_chunk(eg_ctx* c, const double* metrics, const int32_t* st
   // (a synchronous copy on the null stream: it waits for the previous chunk's gather, which read what it overwrites)
   EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size() * 4, hipMemcpyHostToDevice));
   c->n_plan_blocks = n;
-  const ParetoWork work = pareto_work(c->d_breed_work, EG_CROSS_MAX_VARIANTS);
-  EG_LAUNCH("k_pareto_filter .. k_pareto_finalize", launch_pareto_fold(c->d_breed, work, c->out, n, first_index, nullptr));
-  EG_LAUNCH("k_breed_gather", launch_breed_gather(c->d_breed, c->out, n, first_index, c->d_plans, nullptr));
-  return EG_OK;
+  return archive_fold(c, n, first_index);
 }
 
 int32_t eg_debug_breed_turnover(eg_ctx* c, int32_t kind, int32_t next, int64_t m_first) {

@@ -3,7 +3,8 @@
 // buffer (eg_internal.h breed_at); the host keeps, per member of the current frontier, its number and the per-year counts of its two
 // lists, enumerates a generation CHUNK BY CHUNK from them (one member's neighbourhood at a time: a generation's variants are never
 // held), uploads 12 bytes a variant and the routing, and reads one buffer back per generation with a row per new member
-// (eg_breed.h k_breed_gather, eg_explore.h k_explore_turnover).
+// (eg_breed.h k_breed_gather, eg_explore.h k_explore_turnover).  The packing, the launch of a chunk, the archive and the shared option
+// checks are eg_plan_host.cpp's.
 #include <algorithm>
 #include <cstring>
 
@@ -57,27 +58,11 @@ int delta(const eg_plan_edit& e, int w) { return e.list == w ? (e.kind == EG_EDI
 extern "C" int32_t eg_explore_validate(const eg_plan_set* starts, const eg_explore_opts* xo) {
   auto fail = [](const std::string& m) { set_error("eg_explore_validate: " + m); return EG_ERR_BAD_ARG; };
   EG_TRY(eg_plans_validate(starts));
-  if (starts->n_plans > EG_CROSS_MAX_PARENTS)
-    return fail("the set holds " + std::to_string(starts->n_plans) + " plans (at most " + std::to_string(EG_CROSS_MAX_PARENTS) + ")");
-  if (!xo) return fail("NULL options");
-  if (xo->mode != 1 && xo->mode != 2) return fail("mode " + std::to_string(xo->mode) + " is neither 1 (optimization_mode None) nor 2 (cost_only)");
-  if (xo->objectives < 1 || xo->objectives > 15) return fail("objectives " + std::to_string(xo->objectives) + " is outside 1..15 (bit i = metric i)");
-  if (xo->cap < 1 || xo->cap > EG_PARETO_MAX) return fail("cap " + std::to_string(xo->cap) + " is outside 1..EG_PARETO_MAX (" + std::to_string(EG_PARETO_MAX) + ")");
-  if (xo->max_generations < 1) return fail("max_generations = " + std::to_string(xo->max_generations) + " (at least 1)");
-  const char* name[2] = {"replace_with", "append_with"};
-  const int32_t count[2] = {xo->n_replace, xo->n_append};
-  const uint8_t* list[2] = {xo->replace_with, xo->append_with};
-  for (int k = 0; k < 2; ++k) {
-    const std::string n_name = k == 0 ? "n_replace" : "n_append";
-    if (count[k] < 0) return fail(n_name + " = " + std::to_string(count[k]));
-    if (count[k] > 0 && !list[k]) return fail(std::string("NULL ") + name[k] + " with " + n_name + " = " + std::to_string(count[k]));
-    for (int32_t i = 0; i < count[k]; ++i)
-      if (list[k][i] >= EG_N_ACTIONS) return fail(std::string(name[k]) + "[" + std::to_string(i) + "]: action " + std::to_string(int(list[k][i])) + " >= " + std::to_string(EG_N_ACTIONS));
-  }
+  EG_TRY(validate_front_opts(fail, starts, xo));
+  EG_TRY(validate_action_lists(fail, xo->n_replace, xo->replace_with, xo->n_append, xo->append_with));
   if (xo->max_shift < 0 || xo->max_shift > EG_YEARS - 1)
     return fail("max_shift = " + std::to_string(xo->max_shift) + " (0.." + std::to_string(EG_YEARS - 1) + " years; 0: no moves)");
-  if (xo->launch_variants < 0 || xo->launch_variants > EG_CROSS_MAX_VARIANTS)
-    return fail("launch_variants = " + std::to_string(xo->launch_variants) + " (1.." + std::to_string(EG_CROSS_MAX_VARIANTS) + "; 0: " + std::to_string(EG_CROSS_MAX_VARIANTS) + ")");
+  EG_TRY(check_launch_variants(fail, xo->launch_variants));
   if (xo->max_variants < 0) return fail("max_variants = " + std::to_string(xo->max_variants) + " (0: no budget)");
   return EG_OK;
 }
@@ -95,28 +80,13 @@ extern "C" int32_t eg_explore_plans(eg_ctx* c, const eg_policy_snapshot* s, cons
   if (!c || !s || !s->weights || !s->deficit_weights || !population || !generations || !members || !final_numbers || !n_generations || !stop_reason) {
     set_error(std::string(kFn) + ": bad argument"); return EG_ERR_BAD_ARG;
   }
-  if (c->group_member) { set_error(std::string(kFn) + ": the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
-  EG_TRY(eg_explore_validate(starts, xo));
-  EG_TRY(check_policy(s, o, kFn));
-  EG_HIP(hipSetDevice(c->device));
+  EG_TRY(plan_entry(c, s, o, kFn, [&] { return eg_explore_validate(starts, xo); }));
   const int64_t L = xo->launch_variants == 0 ? int64_t(EG_CROSS_MAX_VARIANTS) : int64_t(xo->launch_variants);
   const int32_t n = starts->n_plans;
-  // the private archive: allocated at the first call (eg_breed_plans' buffer), started empty at every call and kept through it
-  EG_HIP(c->d_breed.reserve(breed_at::total));
-  EG_HIP(c->d_breed_work.reserve(pareto_work_bytes(EG_CROSS_MAX_VARIANTS)));
-  const ParetoWork work = pareto_work(c->d_breed_work, EG_CROSS_MAX_VARIANTS);
-  uint8_t* const d_frontier[2] = {c->d_breed + breed_at::parents, c->d_breed + breed_at::parents + breed_at::kParentArray};
-  {
-    ParetoState st{};
-    st.cap = xo->cap; st.objectives = xo->objectives; st.mode = xo->mode;
-    EG_HIP(hipMemcpy(c->d_breed, &st, sizeof(st), hipMemcpyHostToDevice));
-    const BreedCounters zero{};
-    EG_HIP(hipMemcpy(c->d_breed + breed_at::counters, &zero, sizeof(zero), hipMemcpyHostToDevice));
-    // generation 0: the start plans' blocks go up; no block goes up after this
-    std::vector<uint8_t> blocks(size_t(n) * snap::kPlanStride, 0);
-    write_plan_blocks(starts, blocks.data());
-    EG_HIP(hipMemcpy(d_frontier[0], blocks.data(), blocks.size(), hipMemcpyHostToDevice));
-  }
+  // the private archive (eg_breed_plans' buffer), started empty and kept through the call; generation 0: the start plans' blocks go up
+  // into frontier array 0; no block goes up after this
+  EG_TRY(archive_begin(c, xo->cap, xo->objectives, xo->mode));
+  EG_TRY(archive_upload(c, starts, 0));
   DevSnapshot S{};
   EG_TRY(stage_eval_snapshot(c, s, o, &S));
   std::vector<Base> F, next;      // the frontier: member i's block is block base_at + i of frontier array `cur`
@@ -126,8 +96,8 @@ extern "C" int32_t eg_explore_plans(eg_ctx* c, const eg_policy_snapshot* s, cons
   uint32_t base_at = 0;
   int64_t number = 0;      // of the next variant
   Hood hood;
-  std::vector<uint8_t> in, rb(breed_at::kReadbackBytes);
-  std::vector<uint32_t> local_idx, idx, longs;
+  std::vector<uint8_t> in, rb;
+  Routing R;
   std::vector<int64_t> first_of;      // the number of every member's first neighbour
   *n_generations = 0; *stop_reason = EG_EXPLORE_MAX_GENERATIONS; *population = nullptr;
   int32_t n_held = 0;
@@ -161,12 +131,12 @@ extern "C" int32_t eg_explore_plans(eg_ctx* c, const eg_policy_snapshot* s, cons
       in.assign(size_t(m) * 12, 0);
       uint32_t* packed = reinterpret_cast<uint32_t*>(in.data());
       uint32_t* slot = reinterpret_cast<uint32_t*>(in.data() + size_t(m) * 8);
-      idx.clear(); longs.clear();
+      R.clear();
       bool any_moves = false;
       uint32_t j = 0;
       for (; nones > none_at && j < m; ++j, ++none_at) {      // (packed zeros: "none")
         slot[j] = uint32_t(none_at);
-        (F[size_t(none_at)].len[0] > kShortReplayMax ? longs : idx).push_back(j);
+        R.add(j, F[size_t(none_at)].len[0]);
       }
       while (j < m) {
         while (ci < F.size() && ck == F[ci].size) { ++ci; ck = 0; }      // (V counts what is left: there is a member with variants to give)
@@ -175,39 +145,19 @@ extern "C" int32_t eg_explore_plans(eg_ctx* c, const eg_policy_snapshot* s, cons
         hood.load(int64_t(ci), b, *xo);
         if (hood.n_edits() + int64_t(hood.moves.size()) != b.size) { set_error(at + "the enumeration and its count disagree"); return EG_ERR_INTERNAL; }
         const uint32_t take = uint32_t(std::min<int64_t>(int64_t(m - j), b.size - ck));
-        const uint32_t n_e = uint32_t(std::max<int64_t>(0, std::min<int64_t>(hood.n_edits() - ck, take)));
-        if (n_e > 0) {
-          local_idx.resize(n_e);
-          uint32_t n_short = 0;
-          pack_plan_edits(hood.edits.data() + 1 + ck, n_e, b.len[0], packed + 2 * size_t(j), local_idx.data(), &n_short);
-          for (uint32_t k = 0; k < n_e; ++k) (k < n_short ? idx : longs).push_back(j + local_idx[k]);
-        }
-        for (uint32_t k = n_e; k < take; ++k) {      // a move keeps the lengths: the base's route
-          pack_plan_move(hood.moves[size_t(ck + k - hood.n_edits())], packed + 2 * (size_t(j) + k));
-          (b.len[0] > kShortReplayMax ? longs : idx).push_back(j + k);
+        // (the part [ck, ck + take) of the neighbourhood: what is left of its edits, then moves)
+        const int64_t e0 = std::min(ck, hood.n_edits()), n_e = std::min<int64_t>(hood.n_edits() - e0, take);
+        if (pack_neighbourhood(base_at + uint32_t(ci), b.len[0], hood.edits.data() + 1 + e0, uint32_t(n_e), hood.moves.data() + (ck - e0), take - uint32_t(n_e), j, packed, slot, R))
           any_moves = true;
-        }
-        std::fill(slot + j, slot + j + take, base_at + uint32_t(ci));
         j += take; ck += take;
       }
-      const uint32_t n_short = uint32_t(idx.size());
-      idx.insert(idx.end(), longs.begin(), longs.end());
-      // (synchronous copies on the null stream: they wait for the previous chunk, whose kernels read what they overwrite)
-      EG_HIP(hipMemcpy(c->d_refine_in, in.data(), in.size(), hipMemcpyHostToDevice));
-      EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * m, hipMemcpyHostToDevice));
-      const uint32_t* d_slot = reinterpret_cast<const uint32_t*>(c->d_refine_in + size_t(m) * 8);
-      EG_LAUNCH("k_plan_edits_many", launch_plan_edits_many(d_frontier[cur], n_bases, d_slot, c->d_refine_in, m, c->d_plans, nullptr));
-      // (the move variants' blocks: over the base copies k_plan_edits_many has just written for them, on the same stream)
-      if (any_moves) EG_LAUNCH("k_plan_moves", launch_plan_moves(d_frontier[cur], n_bases, d_slot, c->d_refine_in, m, c->d_plans, nullptr));
-      c->n_plan_blocks = m;
-      EG_TRY(launch_plans(c, S, seed, episode_index, m, n_short, true));
-      EG_LAUNCH("k_pareto_filter .. k_pareto_finalize", launch_pareto_fold(c->d_breed, work, c->out, m, uint64_t(number), nullptr));
-      EG_LAUNCH("k_breed_gather", launch_breed_gather(c->d_breed, c->out, m, uint64_t(number), c->d_plans, nullptr));
+      EG_TRY(launch_variants(c, S, archive_array(c, cur), n_bases, in, size_t(m) * 8, m, R, any_moves, seed, episode_index));
+      EG_TRY(archive_fold(c, m, uint64_t(number)));
       done += m; number += m;
     }
     // (generation 0: the start plans the archive holds entered in it too — their rows are row 0 of `members` — so everything held is new)
     EG_LAUNCH("k_explore_turnover", launch_explore_turnover(c->d_breed, 1 - cur, g == 0 ? 0 : m_first, nullptr));
-    EG_HIP(hipMemcpy(rb.data(), c->d_breed + breed_at::readback, rb.size(), hipMemcpyDeviceToHost));      // (waits for the generation)
+    EG_TRY(archive_read_generation(c, rb));
     ExploreHeader h{};
     std::memcpy(&h, rb.data(), sizeof(h));
     if (h.n_held < 0 || h.n_held > xo->cap || h.n_new < 0 || h.n_new > h.n_held || h.n_valid < 0 || h.n_valid > V || h.n_dropped < 0 ||
@@ -218,31 +168,20 @@ extern "C" int32_t eg_explore_plans(eg_ctx* c, const eg_policy_snapshot* s, cons
     *n_generations = g + 1;
     if (h.n_held == 0) {      // no valid variant: the start plans stand in frontier array 0
       *stop_reason = EG_EXPLORE_EMPTY;
-      std::vector<uint8_t> blocks(size_t(n) * snap::kPlanStride);
-      EG_HIP(hipMemcpy(blocks.data(), d_frontier[0], blocks.size(), hipMemcpyDeviceToHost));
-      return decode_plan_blocks(blocks.data(), n, kFn, population);
+      return decode_device_blocks(archive_array(c, 0), n, nullptr, kFn, population);
     }
     next.clear();
     uint32_t n_starts_held = 0;
     long long before = -1;
     hood.owner = -1;
     for (int32_t r = 0; r < h.n_new; ++r) {
-      const uint8_t* row = rb.data() + kBreedHeaderBytes + size_t(r) * kBreedRowBytes;
       ParetoEntry e{};
-      std::memcpy(&e, row, sizeof(e));
       Base b;
       int32_t tab[2][28];
-      std::memcpy(tab, row + 64, sizeof(tab));
-      bool ok = e.index > before && e.index >= (g == 0 ? 0 : m_first) && e.index < gen_first + V && e.slot >= 0 && e.slot < xo->cap;
-      for (int w = 0; w < 2 && ok; ++w) {
-        ok = tab[w][0] == 0;
-        for (int y = 0; y < EG_YEARS && ok; ++y) {
-          ok = tab[w][y + 1] >= tab[w][y] && tab[w][y + 1] <= int32_t(snap::kBestCap);
-          b.count[w][y] = tab[w][y + 1] - tab[w][y];
-        }
-      }
+      bool ok = archive_row(rb, r, xo->cap, &e, tab) && e.index > before && e.index >= (g == 0 ? 0 : m_first) && e.index < gen_first + V;
       eg_explore_member M{};
       if (ok) {
+        for (int w = 0; w < 2; ++w) for (int y = 0; y < EG_YEARS; ++y) b.count[w][y] = tab[w][y + 1] - tab[w][y];
         b.number = e.index; b.finish(*xo);
         M.number = e.index; M.score = e.score;
         std::memcpy(M.metrics, e.metrics, sizeof(M.metrics));
@@ -285,18 +224,14 @@ extern "C" int32_t eg_explore_plans(eg_ctx* c, const eg_policy_snapshot* s, cons
   // the archive as it stands: its entries in ascending number, each naming its record slot, beside which its block is kept
   std::vector<ParetoEntry> held((size_t(n_held)));
   EG_HIP(hipMemcpy(held.data(), c->d_breed + offsetof(ParetoState, e), held.size() * sizeof(ParetoEntry), hipMemcpyDeviceToHost));
-  std::vector<uint8_t> blocks(size_t(n_held) * snap::kPlanStride);
+  std::vector<int32_t> slots((size_t(n_held)));
   for (int32_t r = 0; r < n_held; ++r) {
     const ParetoEntry& e = held[size_t(r)];
     if (e.index < (r ? held[size_t(r) - 1].index + 1 : 0) || e.index >= number || e.slot < 0 || e.slot >= xo->cap) {
       set_error(std::string(kFn) + ": entry " + std::to_string(r) + " of the archive on the device is corrupt"); return EG_ERR_INTERNAL;
     }
-    final_numbers[r] = e.index;
-    EG_HIP(hipMemcpy(blocks.data() + size_t(r) * snap::kPlanStride, c->d_breed + breed_at::blocks + size_t(e.slot) * snap::kPlanStride, snap::kPlanStride, hipMemcpyDeviceToHost));
-    if (out) {
-      eg_episode_out row = out_row(out, size_t(r));
-      EG_TRY(fetch_records(c->d_breed + breed_at::records + size_t(e.slot) * rec::stride, 1, &row));
-    }
+    final_numbers[r] = e.index; slots[size_t(r)] = e.slot;
+    EG_TRY(archive_fetch_record(c, e.slot, out, size_t(r)));
   }
-  return decode_plan_blocks(blocks.data(), n_held, kFn, population);
+  return decode_device_blocks(c->d_breed + breed_at::blocks, n_held, slots.data(), kFn, population);
 }

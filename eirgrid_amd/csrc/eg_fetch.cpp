@@ -230,8 +230,8 @@ int32_t eg_pareto_track(eg_ctx* c, int32_t cap, int32_t objectives, int32_t mode
   if (!c) { set_error("eg_pareto_track: bad argument (ctx)"); return EG_ERR_BAD_ARG; }
   if (cap < 0 || cap > EG_PARETO_MAX) { set_error("eg_pareto_track: cap " + std::to_string(cap) + " is outside 0..EG_PARETO_MAX (256)"); return EG_ERR_BAD_ARG; }
   if (cap == 0) { c->pareto_cap = 0; return EG_OK; }
-  if (objectives < 1 || objectives > 15) { set_error("eg_pareto_track: objectives " + std::to_string(objectives) + " is outside 1..15 (bit i = metric i)"); return EG_ERR_BAD_ARG; }
-  if (mode != 1 && mode != 2) { set_error("eg_pareto_track: mode " + std::to_string(mode) + " is neither 1 (optimization_mode None) nor 2 (cost_only)"); return EG_ERR_BAD_ARG; }
+  auto fail = [](const std::string& m) { set_error("eg_pareto_track: " + m); return EG_ERR_BAD_ARG; };
+  EG_TRY(check_objectives(fail, objectives)); EG_TRY(check_mode(fail, mode));      // (eg_plan_host.cpp: the searches' archives word them alike)
   if (c->group_member) { set_error("eg_pareto_track: the context is a rank of an eg_group (the Pareto archive has no group form)"); return EG_ERR_BAD_ARG; }
   EG_HIP(hipSetDevice(c->device));
   static_assert(sizeof(ParetoState) <= kParetoRecords, "pareto state layout");

@@ -1,5 +1,5 @@
-// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_plans / eg_refine / eg_place / eg_group .cpp): owned buffers, the
-// error macros, the context and the helpers that cross units.  Host only: the kernels include eg_internal.h, never this.
+// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_debug / eg_plans / eg_plan_host / eg_refine / eg_breed / eg_explore /
+// eg_place / eg_group .cpp): owned buffers, the error macros, the context and the helpers that cross units, listed by the unit that holds them.  Host only: the kernels include eg_internal.h, never this.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -165,24 +165,71 @@ void ring_commit(eg_ctx* c, int slot, int ev_used);
 int arm_solo(eg_ctx* c, RolloutPlan& plan, uint32_t n);
 int ensure_packet(eg_ctx* c);      // the library-owned update packet (d_packet, zeroed when new) and its pinned copy
 int device_apply(eg_ctx* c, const void* d_packets, int32_t n_packets, size_t packet_stride, void* d_own_packet, uint64_t noise_seed, bool local_pick);
-// eg_plans.cpp
+// eg_plans.cpp: a policy in snapshot layout, a plan batch's launches, what is packed per variant, plan sets to blocks and back
 int check_policy(const eg_policy_snapshot* s, const eg_opts* o, const char* who);
 void stage_policy(eg_ctx* c, const eg_policy_snapshot* s, bool have_lists, uint8_t* h);
 DevSnapshot snapshot_of(uint8_t* d_base, const eg_opts* o);
 void write_lists(uint8_t* dst, const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact);
 int stage_eval_snapshot(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, DevSnapshot* S);
-void pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len, uint32_t* packed, uint32_t* idx, uint32_t* n_short);
-// ... and a move's 8 bytes (eg_plan_moves.h unpack_move)
-void pack_plan_move(const eg_plan_move& m, uint32_t* packed);
 int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index);
-// ... and what a cross batch and the generations of eg_breed_plans (eg_breed.cpp) share: the prefix offsets of every plan of a set
-// (off[w][p * 27 + y]), a child's list length from them, a cross's 8 bytes (eg_plan_crosses.h unpack_cross), a set's plan blocks
+// ... a move's 8 bytes (eg_plan_moves.h unpack_move) and a cross's (eg_plan_crosses.h unpack_cross)
+void pack_plan_move(const eg_plan_move& m, uint32_t* packed);
+void pack_plan_cross(const eg_plan_cross& x, uint32_t* packed);
+// ... the prefix offsets of every plan of a set (off[w][p * 27 + y]) and a child's list length from them
 void parent_offsets(const eg_plan_set* p, std::vector<int32_t> off[2]);
 int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x);
-void pack_plan_cross(const eg_plan_cross& x, uint32_t* packed);
+// ... a set's plan blocks, and the reverse: n plan blocks read back from the device (host memory) decoded into a plan set (names "")
 void write_plan_blocks(const eg_plan_set* p, uint8_t* dst);
-// ... and the reverse: n plan blocks read back from the device (host memory) decoded into a plan set (names ""); `who` names the entry point
 int decode_plan_blocks(const uint8_t* blocks, int32_t n, const char* who, eg_plan_set** set);
+
+// eg_plan_host.cpp: the pieces a plan search is written from.  `fn` / `who` name the entry point in the messages.
+// Behind an entry point's own NULL test: a rank of a group is refused, then `validate` runs, then check_policy, then hipSetDevice
+int plan_entry(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const char* fn, const std::function<int32_t()>& validate);
+// The routing of a launch (launch_plans): the variants whose best_actions list is short (<= kShortReplayMax entries) first, then the long
+// ones, each in the order they were added.  finish(): the short ones' count; idx is then the index array.
+struct Routing {
+  std::vector<uint32_t> idx, longs;
+  void clear() { idx.clear(); longs.clear(); }
+  void add(uint32_t j, int64_t len0) { (len0 > kShortReplayMax ? longs : idx).push_back(j); }
+  uint32_t finish() { const uint32_t n_short = uint32_t(idx.size()); idx.insert(idx.end(), longs.begin(), longs.end()); longs.clear(); return n_short; }
+};
+void pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len, uint32_t* packed, uint32_t* idx, uint32_t* n_short);
+// Variants [first, first + n_edits + n_moves) of a launch: edits, then moves, of the plan in base block `base_slot` whose best_actions
+// holds len0 entries — their 8 bytes into `packed`, their route into R, their base into `slot`.  Returns whether a move was packed.
+bool pack_neighbourhood(uint32_t base_slot, int64_t len0, const eg_plan_edit* edits, uint32_t n_edits, const eg_plan_move* moves, uint32_t n_moves, uint32_t first,
+                        uint32_t* packed, uint32_t* slot, Routing& R);
+// A launch of n variants: `in` (the packed variants, at at_slot every variant's base slot) into c->d_refine_in and R's finished index up,
+// k_plan_edits_many and (any_moves) k_plan_moves over the n_bases blocks at d_bases, then the plan batch with same_index
+int launch_variants(eg_ctx* c, const DevSnapshot& S, const uint8_t* d_bases, uint32_t n_bases, const std::vector<uint8_t>& in, size_t at_slot, uint32_t n,
+                    Routing& R, bool any_moves, uint64_t seed, uint64_t index);
+// The private archive of a breed / explore call (c->d_breed, eg_internal.h breed_at; c->d_breed_work).  begin: allocated at the first call,
+// started empty at every call (`between`, the test hooks': runs between the state's upload and the counters'); array: parent / frontier
+// array 0 | 1; upload: a set's blocks into it; fold: the n results of c->out with the blocks of c->d_plans, launch_pareto_fold then
+// k_breed_gather; read_generation: the readback buffer (waits for the generation); row: row r of it, false unless its tables start at 0,
+// ascend and stay within snap::kBestCap and its slot lies in [0, cap) — the index is the caller's to check; fetch_record: the record in
+// `slot` into row r of `out` (NULL: nothing); decode: n blocks at d_blocks (slots != NULL: block r is in slots[r]) as a plan set
+int archive_begin(eg_ctx* c, int32_t cap, int32_t objectives, int32_t mode, const std::function<int()>& between = nullptr);
+inline uint8_t* archive_array(eg_ctx* c, int which) { return c->d_breed + breed_at::parents + size_t(which) * breed_at::kParentArray; }
+int archive_upload(eg_ctx* c, const eg_plan_set* set, int array);
+int archive_fold(eg_ctx* c, uint32_t n, uint64_t first_index);
+int archive_read_generation(eg_ctx* c, std::vector<uint8_t>& rb);
+bool archive_row(const std::vector<uint8_t>& rb, int32_t r, int32_t cap, ParetoEntry* entry, int32_t (&tab)[2][28]);
+int archive_fetch_record(eg_ctx* c, int32_t slot, const eg_episode_out* out, size_t r);
+int decode_device_blocks(const uint8_t* d_blocks, int32_t n, const int32_t* slots, const char* who, eg_plan_set** set);
+// The option checks the validators share; `fail` sets "<validator>: <message>" and returns EG_ERR_BAD_ARG
+using Fail = std::function<int32_t(const std::string&)>;
+int32_t check_mode(const Fail& fail, int32_t mode);
+int32_t check_objectives(const Fail& fail, int32_t objectives);
+int32_t check_cap(const Fail& fail, int32_t cap);
+int32_t check_launch_variants(const Fail& fail, int32_t launch_variants);
+int32_t validate_action_lists(const Fail& fail, int32_t n_replace, const uint8_t* replace_with, int32_t n_append, const uint8_t* append_with);
+// what eg_breed_validate and eg_explore_validate open with (their options begin alike): the set's size, the options, mode .. max_generations
+template <typename Opts> int32_t validate_front_opts(const Fail& fail, const eg_plan_set* set, const Opts* o) {
+  if (set->n_plans > EG_CROSS_MAX_PARENTS) return fail("the set holds " + std::to_string(set->n_plans) + " plans (at most " + std::to_string(EG_CROSS_MAX_PARENTS) + ")");
+  if (!o) return fail("NULL options");
+  EG_TRY(check_mode(fail, o->mode)); EG_TRY(check_objectives(fail, o->objectives)); EG_TRY(check_cap(fail, o->cap));
+  return o->max_generations < 1 ? fail("max_generations = " + std::to_string(o->max_generations) + " (at least 1)") : EG_OK;
+}
 // eg_fetch.cpp
 int fetch_records(const uint8_t* d_base, size_t N, eg_episode_out* o);
 eg_episode_out out_row(const eg_episode_out* o, size_t r);      // row r of a caller's episode-major buffers

@@ -1,5 +1,6 @@
 // eg_plans.cpp — a policy in snapshot layout (shared with eg_upload_snapshot) and plan batches: eg_evaluate_plans, eg_evaluate_plan_edits,
-// eg_evaluate_plan_moves, eg_evaluate_plan_crosses, launch_plans (eg_refine.cpp loops over the same pieces).
+// eg_evaluate_plan_moves, eg_evaluate_plan_crosses over one tail (evaluate_batch), launch_plans, and plan sets to blocks and back (the
+// searches are written from these and eg_plan_host.cpp's pieces).
 #include <algorithm>
 #include <cstring>
 
@@ -117,75 +118,57 @@ int eg::stage_eval_snapshot(eg_ctx* c, const eg_policy_snapshot* s, const eg_opt
   S->plan_pool = c->d_plans;
   return EG_OK;
 }
-// What a plan-edit batch uploads behind the base block, 8 bytes per variant (eg_plan_edits.h unpack), and its routing — a variant's
-// best_actions list is the base's (base_len entries), one entry longer or shorter: the short variants' indices first, then the long ones'
-void eg::pack_plan_edits(const eg_plan_edit* edits, uint32_t n, int64_t base_len, uint32_t* packed, uint32_t* idx, uint32_t* n_short) {
-  std::vector<uint32_t> longs;
-  uint32_t ns = 0;
-  for (uint32_t j = 0; j < n; ++j) {
-    const eg_plan_edit& e = edits[j];
-    const bool none = e.kind == EG_EDIT_NONE;
-    packed[2 * j] = none ? 0u : uint32_t(e.kind) | uint32_t(e.list) << 8 | uint32_t(e.year) << 16 | uint32_t(e.kind == EG_EDIT_DELETE ? 0 : e.action) << 24;
-    packed[2 * j + 1] = none ? 0u : e.pos;
-    const int64_t len = base_len + (!none && e.list == 0 ? (e.kind == EG_EDIT_INSERT ? 1 : e.kind == EG_EDIT_DELETE ? -1 : 0) : 0);
-    if (len > kShortReplayMax) longs.push_back(j); else idx[ns++] = j;
-  }
-  std::copy(longs.begin(), longs.end(), idx + ns);
-  *n_short = ns;
-}
 namespace {
-// The rest of a plan batch whose routing is in c->d_plan_index: the policy into its device snapshot, then the launches.  `blocks`: a
-// plan-edit, plan-move or plan-cross batch, whose blocks k_plan_edits / k_plan_moves / k_plan_crosses writes on the launches' stream from
-// c->d_plan_edit_in (the base block — a cross batch: the n_parents parent blocks —, then the packed edits, moves or crosses).
+// The rest of a plan batch of the n variants `idx` routes, the n_short short ones first.  `in` goes up: the plan blocks themselves into c->d_plans (Blocks::kHost), else into
+// c->d_plan_edit_in the base block (a cross batch: the n_parents parent blocks), then the packed edits, moves or crosses, from which
+// k_plan_edits / k_plan_moves / k_plan_crosses writes the blocks on the launches' stream.  Then the index, the policy into its device
+// snapshot, the launches and the fetch.
 // (The snapshot is staged last before the launches: a launch's start event takes the time the stream's previous command ended — with
 //  the snapshot staged first, eg_timing_read counted the host building the plan blocks.)
 enum class Blocks { kHost, kEdits, kMoves, kCrosses };      // who writes the plan blocks: the host has, k_plan_edits, k_plan_moves, k_plan_crosses
-int stage_and_launch_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short,
-                           Blocks blocks, bool same_index, uint32_t n_parents = 1u) {
+int evaluate_batch(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, Blocks blocks, const std::vector<uint8_t>& in, const std::vector<uint32_t>& idx,
+                   uint32_t n_short, uint64_t seed, uint64_t first_index, bool same_index, eg_episode_out* out, uint32_t n_parents = 1u) {
+  const uint32_t n = uint32_t(idx.size());
+  EG_TRY(ensure_outputs(c, n));
+  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
+  EG_HIP(c->d_plan_index.reserve(n));
+  if (blocks != Blocks::kHost) EG_HIP(c->d_plan_edit_in.reserve(in.size()));
+  EG_HIP(hipMemcpy(blocks == Blocks::kHost ? c->d_plans.ptr : c->d_plan_edit_in.ptr, in.data(), in.size(), hipMemcpyHostToDevice));
+  EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
   DevSnapshot S{};
   EG_TRY(stage_eval_snapshot(c, s, o, &S));
-  if (blocks == Blocks::kEdits) EG_LAUNCH("k_plan_edits", launch_plan_edits(c->d_plan_edit_in, c->d_plan_edit_in + snap::kPlanStride, n, c->d_plans, nullptr));
-  if (blocks == Blocks::kMoves) EG_LAUNCH("k_plan_moves", launch_plan_moves(c->d_plan_edit_in, 1u, nullptr, c->d_plan_edit_in + snap::kPlanStride, n, c->d_plans, nullptr));
-  if (blocks == Blocks::kCrosses)
-    EG_LAUNCH("k_plan_crosses", launch_plan_crosses(c->d_plan_edit_in, n_parents, c->d_plan_edit_in + size_t(n_parents) * snap::kPlanStride, n, c->d_plans, nullptr));
+  const uint8_t* d_in = c->d_plan_edit_in;
+  if (blocks == Blocks::kEdits) EG_LAUNCH("k_plan_edits", launch_plan_edits(d_in, d_in + snap::kPlanStride, n, c->d_plans, nullptr));
+  if (blocks == Blocks::kMoves) EG_LAUNCH("k_plan_moves", launch_plan_moves(d_in, 1u, nullptr, d_in + snap::kPlanStride, n, c->d_plans, nullptr));
+  if (blocks == Blocks::kCrosses) EG_LAUNCH("k_plan_crosses", launch_plan_crosses(d_in, n_parents, d_in + size_t(n_parents) * snap::kPlanStride, n, c->d_plans, nullptr));
   c->n_plan_blocks = n;
-  return launch_plans(c, S, seed, first_index, n, n_short, same_index);
+  EG_TRY(launch_plans(c, S, seed, first_index, n, n_short, same_index));
+  return out ? eg_fetch(c, out) : EG_OK;
+}
+// what goes up for an edit or move batch of n variants: the base plan's block, then room for 8 bytes a variant; *base_len: of its best_actions
+std::vector<uint8_t> base_and_room(const eg_plan_set* base, uint32_t n, int64_t* base_len) {
+  std::vector<uint8_t> in(snap::kPlanStride + size_t(n) * 8, 0);
+  write_plan_blocks(base, in.data());
+  *base_len = 0;
+  for (int y = 0; y < EG_YEARS; ++y) *base_len += base->best_count[y];
+  return in;
 }
 }  // namespace
 
 extern "C" int32_t eg_evaluate_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* p, uint64_t seed, uint64_t first_index,
                           eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights) { set_error("eg_evaluate_plans: bad argument"); return EG_ERR_BAD_ARG; }
-  if (c->group_member) { set_error("eg_evaluate_plans: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
-  EG_TRY(eg_plans_validate(p));
-  EG_TRY(check_policy(s, o, "eg_evaluate_plans"));
-  EG_HIP(hipSetDevice(c->device));
+  EG_TRY(plan_entry(c, s, o, "eg_evaluate_plans", [&] { return eg_plans_validate(p); }));
   const uint32_t n = uint32_t(p->n_plans);
-  EG_TRY(ensure_outputs(c, n));
-  // the plan blocks (the list section's layout, one per plan) and the routing: the short plans' indices first, then the long ones'
+  // the plan blocks (the list section's layout, one per plan) and the routing, from the plans' best_actions totals
   std::vector<uint8_t> blocks(size_t(n) * snap::kPlanStride, 0);
-  std::vector<uint32_t> idx(n);
-  uint32_t n_short = 0;
-  {
-    std::vector<uint32_t> longs;
-    int64_t pos = 0, dpos = 0;
-    for (uint32_t j = 0; j < n; ++j) {
-      const int32_t* cnt = p->best_count + size_t(j) * EG_YEARS;
-      const int32_t* dcnt = p->best_deficit_count + size_t(j) * EG_YEARS;
-      int64_t len = 0, dlen = 0;
-      for (int y = 0; y < EG_YEARS; ++y) { len += cnt[y]; dlen += dcnt[y]; }
-      write_lists(blocks.data() + size_t(j) * snap::kPlanStride, cnt, p->best_actions + pos, dcnt, p->best_deficit_actions + dpos);
-      pos += len; dpos += dlen;
-      if (len > kShortReplayMax) longs.push_back(j); else idx[n_short++] = j;
-    }
-    std::copy(longs.begin(), longs.end(), idx.begin() + n_short);
-  }
-  EG_HIP(c->d_plans.reserve(blocks.size()));
-  EG_HIP(c->d_plan_index.reserve(n));
-  EG_HIP(hipMemcpy(c->d_plans, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
-  EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, Blocks::kHost, false));
-  return out ? eg_fetch(c, out) : EG_OK;
+  write_plan_blocks(p, blocks.data());
+  std::vector<int32_t> off[2];
+  parent_offsets(p, off);
+  Routing R;
+  for (uint32_t j = 0; j < n; ++j) R.add(j, off[0][size_t(j) * 27 + EG_YEARS]);
+  const uint32_t n_short = R.finish();
+  return evaluate_batch(c, s, o, Blocks::kHost, blocks, R.idx, n_short, seed, first_index, false, out);
 }
 
 // ---------------------------------------------------------------- plan edits (include/eirgrid_hip.h eg_evaluate_plan_edits)
@@ -221,27 +204,14 @@ extern "C" int32_t eg_plan_edits_validate(const eg_plan_set* base, const eg_plan
 extern "C" int32_t eg_evaluate_plan_edits(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* base, const eg_plan_edit* edits,
                                           int32_t n_edits, uint64_t seed, uint64_t first_index, int32_t same_index, eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights) { set_error("eg_evaluate_plan_edits: bad argument"); return EG_ERR_BAD_ARG; }
-  if (c->group_member) { set_error("eg_evaluate_plan_edits: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
-  EG_TRY(eg_plan_edits_validate(base, edits, n_edits));
-  EG_TRY(check_policy(s, o, "eg_evaluate_plan_edits"));
-  EG_HIP(hipSetDevice(c->device));
+  EG_TRY(plan_entry(c, s, o, "eg_evaluate_plan_edits", [&] { return eg_plan_edits_validate(base, edits, n_edits); }));
   const uint32_t n = uint32_t(n_edits);
-  EG_TRY(ensure_outputs(c, n));
-  // what goes up: the base plan's block, the packed edits and the routing (pack_plan_edits)
-  std::vector<uint8_t> in(snap::kPlanStride + size_t(n) * 8, 0);
-  write_lists(in.data(), base->best_count, base->best_actions, base->best_deficit_count, base->best_deficit_actions);
   int64_t base_len = 0;
-  for (int y = 0; y < EG_YEARS; ++y) base_len += base->best_count[y];
+  std::vector<uint8_t> in = base_and_room(base, n, &base_len);
   std::vector<uint32_t> idx(n);
   uint32_t n_short = 0;
   pack_plan_edits(edits, n, base_len, reinterpret_cast<uint32_t*>(in.data() + snap::kPlanStride), idx.data(), &n_short);
-  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
-  EG_HIP(c->d_plan_index.reserve(n));
-  EG_HIP(c->d_plan_edit_in.reserve(in.size()));
-  EG_HIP(hipMemcpy(c->d_plan_edit_in, in.data(), in.size(), hipMemcpyHostToDevice));
-  EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, Blocks::kEdits, same_index != 0));
-  return out ? eg_fetch(c, out) : EG_OK;
+  return evaluate_batch(c, s, o, Blocks::kEdits, in, idx, n_short, seed, first_index, same_index != 0, out);
 }
 
 // ---------------------------------------------------------------- plan moves (include/eirgrid_hip.h eg_evaluate_plan_moves)
@@ -280,28 +250,15 @@ extern "C" int32_t eg_plan_moves_validate(const eg_plan_set* base, const eg_plan
 extern "C" int32_t eg_evaluate_plan_moves(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* base, const eg_plan_move* moves,
                                           int32_t n_moves, uint64_t seed, uint64_t first_index, int32_t same_index, eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights) { set_error("eg_evaluate_plan_moves: bad argument"); return EG_ERR_BAD_ARG; }
-  if (c->group_member) { set_error("eg_evaluate_plan_moves: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
-  EG_TRY(eg_plan_moves_validate(base, moves, n_moves));
-  EG_TRY(check_policy(s, o, "eg_evaluate_plan_moves"));
-  EG_HIP(hipSetDevice(c->device));
+  EG_TRY(plan_entry(c, s, o, "eg_evaluate_plan_moves", [&] { return eg_plan_moves_validate(base, moves, n_moves); }));
   const uint32_t n = uint32_t(n_moves);
-  EG_TRY(ensure_outputs(c, n));
-  // what goes up: the base plan's block and the packed moves; a move keeps the lists' lengths, so every variant takes the base's route
-  std::vector<uint8_t> in(snap::kPlanStride + size_t(n) * 8, 0);
-  write_lists(in.data(), base->best_count, base->best_actions, base->best_deficit_count, base->best_deficit_actions);
   int64_t base_len = 0;
-  for (int y = 0; y < EG_YEARS; ++y) base_len += base->best_count[y];
+  std::vector<uint8_t> in = base_and_room(base, n, &base_len);
   uint32_t* packed = reinterpret_cast<uint32_t*>(in.data() + snap::kPlanStride);
-  std::vector<uint32_t> idx(n);
-  for (uint32_t j = 0; j < n; ++j) { pack_plan_move(moves[j], packed + 2 * size_t(j)); idx[j] = j; }
-  const uint32_t n_short = base_len > kShortReplayMax ? 0u : n;
-  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
-  EG_HIP(c->d_plan_index.reserve(n));
-  EG_HIP(c->d_plan_edit_in.reserve(in.size()));
-  EG_HIP(hipMemcpy(c->d_plan_edit_in, in.data(), in.size(), hipMemcpyHostToDevice));
-  EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, Blocks::kMoves, same_index != 0));
-  return out ? eg_fetch(c, out) : EG_OK;
+  Routing R;      // (a move keeps the lists' lengths, so every variant takes the base's route)
+  for (uint32_t j = 0; j < n; ++j) { pack_plan_move(moves[j], packed + 2 * size_t(j)); R.add(j, base_len); }
+  const uint32_t n_short = R.finish();
+  return evaluate_batch(c, s, o, Blocks::kMoves, in, R.idx, n_short, seed, first_index, same_index != 0, out);
 }
 
 // ---------------------------------------------------------------- plan crosses (include/eirgrid_hip.h eg_evaluate_plan_crosses)
@@ -392,12 +349,8 @@ extern "C" int32_t eg_plan_crosses_validate(const eg_plan_set* parents, const eg
 extern "C" int32_t eg_evaluate_plan_crosses(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* parents, const eg_plan_cross* crosses,
                                             int32_t n_crosses, uint64_t seed, uint64_t first_index, int32_t same_index, eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights) { set_error("eg_evaluate_plan_crosses: bad argument"); return EG_ERR_BAD_ARG; }
-  if (c->group_member) { set_error("eg_evaluate_plan_crosses: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
-  EG_TRY(eg_plan_crosses_validate(parents, crosses, n_crosses));
-  EG_TRY(check_policy(s, o, "eg_evaluate_plan_crosses"));
-  EG_HIP(hipSetDevice(c->device));
+  EG_TRY(plan_entry(c, s, o, "eg_evaluate_plan_crosses", [&] { return eg_plan_crosses_validate(parents, crosses, n_crosses); }));
   const uint32_t n = uint32_t(n_crosses), P = uint32_t(parents->n_plans);
-  EG_TRY(ensure_outputs(c, n));
   // what goes up: every parent's block, once, and the packed crosses (eg_plan_crosses.h unpack_cross); the routing from the counts — two
   // short parents can make a long child and the reverse
   std::vector<uint8_t> in(size_t(P) * snap::kPlanStride + size_t(n) * 8, 0);
@@ -405,21 +358,10 @@ extern "C" int32_t eg_evaluate_plan_crosses(eg_ctx* c, const eg_policy_snapshot*
   std::vector<int32_t> off[2];
   parent_offsets(parents, off);
   uint32_t* packed = reinterpret_cast<uint32_t*>(in.data() + size_t(P) * snap::kPlanStride);
-  std::vector<uint32_t> idx(n), longs;
-  uint32_t n_short = 0;
-  for (uint32_t j = 0; j < n; ++j) {
-    const eg_plan_cross& x = crosses[j];
-    pack_plan_cross(x, packed + 2 * size_t(j));
-    if (child_len(off[0], x) > kShortReplayMax) longs.push_back(j); else idx[n_short++] = j;
-  }
-  std::copy(longs.begin(), longs.end(), idx.begin() + n_short);
-  EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
-  EG_HIP(c->d_plan_index.reserve(n));
-  EG_HIP(c->d_plan_edit_in.reserve(in.size()));
-  EG_HIP(hipMemcpy(c->d_plan_edit_in, in.data(), in.size(), hipMemcpyHostToDevice));
-  EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-  EG_TRY(stage_and_launch_plans(c, s, o, seed, first_index, n, n_short, Blocks::kCrosses, same_index != 0, P));
-  return out ? eg_fetch(c, out) : EG_OK;
+  Routing R;
+  for (uint32_t j = 0; j < n; ++j) { pack_plan_cross(crosses[j], packed + 2 * size_t(j)); R.add(j, child_len(off[0], crosses[j])); }
+  const uint32_t n_short = R.finish();
+  return evaluate_batch(c, s, o, Blocks::kCrosses, in, R.idx, n_short, seed, first_index, same_index != 0, out, P);
 }
 
 extern "C" int32_t eg_debug_fetch_plan_block(eg_ctx* c, uint32_t plan, uint8_t* out) {

@@ -2,8 +2,9 @@
 // best one" with the plans, their variants and the pick of each winner on the device.  ONE loop serves both: eg_refine_plan is its case of
 // one plan.  Per round the still-active plans' variants are packed into launches, a SEGMENT of consecutive variants per plan;
 // k_plan_edits_many writes every variant's block from its plan's base block, the plan batch runs over the whole launch (eg_plans.cpp:
-// stage_eval_snapshot, pack_plan_edits, launch_plans, write_lists), k_refine_pick_many picks a winner per segment and keeps that plan's base
-// block current (eg_refine_many.h).  The host follows every plan in a mirror, from which the next round's edits are enumerated.
+// stage_eval_snapshot, launch_plans, write_plan_blocks), k_refine_pick_many picks a winner per segment and keeps that plan's base
+// block current (eg_refine_many.h; the packing and the launch are eg_plan_host.cpp's pack_neighbourhood and launch_variants).  The host
+// follows every plan in a mirror, from which the next round's edits are enumerated.
 // A plan never straddles two launches, so a single plan always gets a launch of exactly its own variants, whatever the launch size.
 // eg_refine_plans_moves runs the same loop with move variants behind every plan's edits: k_plan_moves (eg_plan_moves.h) overwrites their
 // blocks behind k_plan_edits_many, which has written a copy of the base for them.
@@ -27,6 +28,28 @@ struct Mirror {
       for (int y = 0; y < EG_YEARS; ++y) count[w][y] = int32_t(l[w][y].size());
   }
 };
+// the plans of a valid set as mirrors, and the reverse (the set's names carried over)
+std::vector<Mirror> mirrors_of(const eg_plan_set* p) {
+  std::vector<Mirror> mirror((size_t(p->n_plans)));
+  const int32_t* count[2] = {p->best_count, p->best_deficit_count};
+  const uint8_t* flat[2] = {p->best_actions, p->best_deficit_actions};
+  for (int w = 0; w < 2; ++w) {
+    size_t at = 0;      // (k: the year-lists of the set, plan-major)
+    for (size_t k = 0; k < mirror.size() * EG_YEARS; at += size_t(count[w][k]), ++k)
+      mirror[k / EG_YEARS].l[w][k % EG_YEARS].assign(flat[w] + at, flat[w] + at + count[w][k]);
+  }
+  return mirror;
+}
+eg_plan_set* set_of(const std::vector<Mirror>& mirror, const char* const* names) {
+  std::vector<int32_t> count[2];
+  std::vector<uint8_t> flat[2];
+  for (int w = 0; w < 2; ++w) {
+    for (const Mirror& m : mirror)
+      for (const std::vector<uint8_t>& l : m.l[w]) { count[w].push_back(int32_t(l.size())); flat[w].insert(flat[w].end(), l.begin(), l.end()); }
+    flat[w].reserve(1);
+  }
+  return make_plan_set_n(int32_t(mirror.size()), count[0].data(), flat[0].data(), count[1].data(), flat[1].data(), names);
+}
 // variants of a round over lists of these totals (include/eirgrid_hip.h: none, deletes, replaces, appends)
 int64_t n_variants(int64_t len0, int64_t len1, const eg_refine_opts& o) {
   return 1 + len0 + len1 + int64_t(o.n_replace) * len0 + (len0 < int64_t(snap::kBestCap) ? int64_t(EG_YEARS) * o.n_append : 0);
@@ -59,16 +82,7 @@ int32_t validate_opts(const char* fn, bool name_plan, const eg_plan_set* bases, 
   if (!o) return fail("NULL options");
   if (o->mode != 1 && o->mode != 2) return fail("mode " + std::to_string(o->mode) + " (1: optimization_mode None, 2: cost_only)");
   if (o->max_rounds < 1) return fail("max_rounds = " + std::to_string(o->max_rounds) + " (at least 1)");
-  const char* name[2] = {"replace_with", "append_with"};
-  const int32_t count[2] = {o->n_replace, o->n_append};
-  const uint8_t* list[2] = {o->replace_with, o->append_with};
-  for (int k = 0; k < 2; ++k) {
-    const std::string n_name = k == 0 ? "n_replace" : "n_append";
-    if (count[k] < 0) return fail(n_name + " = " + std::to_string(count[k]));
-    if (count[k] > 0 && !list[k]) return fail(std::string("NULL ") + name[k] + " with " + n_name + " = " + std::to_string(count[k]));
-    for (int32_t i = 0; i < count[k]; ++i)
-      if (list[k][i] >= EG_N_ACTIONS) return fail(std::string(name[k]) + "[" + std::to_string(i) + "]: action " + std::to_string(int(list[k][i])) + " >= " + std::to_string(EG_N_ACTIONS));
-  }
+  EG_TRY(validate_action_lists(fail, o->n_replace, o->replace_with, o->n_append, o->append_with));
   for (int32_t p = 0; p < bases->n_plans; ++p) {
     int64_t len[2] = {0, 0};
     for (int y = 0; y < EG_YEARS; ++y) { len[0] += bases->best_count[size_t(p) * EG_YEARS + y]; len[1] += bases->best_deficit_count[size_t(p) * EG_YEARS + y]; }
@@ -76,6 +90,13 @@ int32_t validate_opts(const char* fn, bool name_plan, const eg_plan_set* bases, 
     if (n > EG_REFINE_MAX_VARIANTS) { set_error(who(fn, name_plan, p) + too_many(0, n)); return EG_ERR_BAD_ARG; }
   }
   return EG_OK;
+}
+// what the two many-plan validators ask of the set
+int32_t validate_set(const char* fn, const eg_plan_set* bases) {
+  EG_TRY(eg_plans_validate(bases));
+  if (bases->n_plans <= EG_REFINE_MAX_PLANS) return EG_OK;
+  set_error(std::string(fn) + ": the set holds " + std::to_string(bases->n_plans) + " plans (at most " + std::to_string(EG_REFINE_MAX_PLANS) + ")");
+  return EG_ERR_BAD_ARG;
 }
 // EIRGRID_REFINE_LAUNCH_VARIANTS: the variants a launch may hold (a plan with more gets a launch to itself), read at every call
 uint32_t launch_variants() {
@@ -92,23 +113,9 @@ struct Seg { int32_t plan; uint32_t first, n; std::vector<eg_plan_edit> edits; s
 int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro,
                uint64_t seed, uint64_t episode_index, eg_plan_set** refined, eg_refine_step* steps, int32_t* n_steps, int32_t* stop_reason, double* start_score,
                eg_episode_out* out, const eg_refine_move_opts* mo = nullptr, eg_refine_move_step* msteps = nullptr) {
-  EG_TRY(check_policy(s, o, fn));
-  EG_HIP(hipSetDevice(c->device));
   *refined = nullptr;
   const int32_t P = bases->n_plans;
-  std::vector<Mirror> mirror((size_t(P)));
-  {
-    const int32_t* count[2] = {bases->best_count, bases->best_deficit_count};
-    const uint8_t* flat[2] = {bases->best_actions, bases->best_deficit_actions};
-    for (int w = 0; w < 2; ++w) {
-      int64_t at = 0;
-      for (int32_t p = 0; p < P; ++p)
-        for (int y = 0; y < EG_YEARS; ++y) {
-          const int32_t k = count[w][size_t(p) * EG_YEARS + y];
-          mirror[size_t(p)].l[w][y].assign(flat[w] + at, flat[w] + at + k); at += k;
-        }
-    }
-  }
+  std::vector<Mirror> mirror = mirrors_of(bases);
   // every buffer once, for the largest launch max_rounds steps can lead to: a plan's best_actions grows by an entry a step at most, and
   // only by an append (a round beyond EG_REFINE_MAX_VARIANTS is refused when it is reached); a launch holds a plan larger than the
   // launch size alone, else no more variants than the launch size
@@ -137,13 +144,7 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
   EG_HIP(c->d_refine_bases.reserve(size_t(P) * snap::kPlanStride));
   {      // the base blocks go up once; from then on k_refine_pick_many keeps them current
     std::vector<uint8_t> blocks(size_t(P) * snap::kPlanStride, 0);
-    int64_t pos = 0, dpos = 0;
-    for (int32_t p = 0; p < P; ++p) {
-      const int32_t* cnt = bases->best_count + size_t(p) * EG_YEARS;
-      const int32_t* dcnt = bases->best_deficit_count + size_t(p) * EG_YEARS;
-      write_lists(blocks.data() + size_t(p) * snap::kPlanStride, cnt, bases->best_actions + pos, dcnt, bases->best_deficit_actions + dpos);
-      pos += mirror[size_t(p)].total(0); dpos += mirror[size_t(p)].total(1);
-    }
+    write_plan_blocks(bases, blocks.data());
     EG_HIP(hipMemcpy(c->d_refine_bases, blocks.data(), blocks.size(), hipMemcpyHostToDevice));
   }
   DevSnapshot S{};
@@ -151,9 +152,8 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
   std::vector<char> active(size_t(P), 1);
   for (int32_t p = 0; p < P; ++p) { n_steps[p] = 0; stop_reason[p] = EG_REFINE_MAX_ROUNDS; if (start_score) start_score[p] = std::nan(""); }
   std::vector<Seg> segs;
-  std::vector<uint8_t> in;
-  std::vector<uint32_t> local_idx, idx, longs;
-  std::vector<uint8_t> entries;
+  std::vector<uint8_t> in, entries;
+  Routing R;
   for (int round = 0;; ++round) {
     // the round's variant counts, plan by plan
     std::vector<std::pair<int32_t, uint32_t>> todo;      // (plan, variants), ascending
@@ -180,7 +180,7 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
       uint32_t* packed = reinterpret_cast<uint32_t*>(in.data());
       uint32_t* slot = reinterpret_cast<uint32_t*>(in.data() + at_slot);
       uint32_t* table = reinterpret_cast<uint32_t*>(in.data() + at_segs);
-      segs.resize(n_segs); idx.clear(); longs.clear();
+      segs.resize(n_segs); R.clear();
       uint32_t first = 0;
       bool any_moves = false;
       for (uint32_t k = 0; k < n_segs; ++k) {
@@ -192,32 +192,14 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
         enumerate_edits(count[0], count[1], ro->replace_with, ro->n_replace, ro->append_with, ro->n_append, m.total(0) < int64_t(snap::kBestCap), sg.edits);
         sg.moves.clear();
         if (mo) enumerate_moves(count[0], mo->max_shift, sg.moves);
-        any_moves = any_moves || !sg.moves.empty();
-        const uint32_t n_edits = uint32_t(sg.edits.size());
         if (sg.edits.size() + sg.moves.size() != size_t(sg.n)) { set_error(who(fn, name_plan, sg.plan) + "round " + std::to_string(round) + ": the enumeration and its count disagree"); return EG_ERR_INTERNAL; }
-        local_idx.resize(n_edits);
-        uint32_t n_short = 0;
-        pack_plan_edits(sg.edits.data(), n_edits, m.total(0), packed + 2 * size_t(first), local_idx.data(), &n_short);
-        for (uint32_t j = 0; j < n_edits; ++j) (j < n_short ? idx : longs).push_back(first + local_idx[j]);
-        for (uint32_t j = n_edits; j < sg.n; ++j) {      // a move keeps the lengths: the base's route
-          pack_plan_move(sg.moves[j - n_edits], packed + 2 * (size_t(first) + j));
-          (m.total(0) > kShortReplayMax ? longs : idx).push_back(first + j);
-        }
-        std::fill(slot + first, slot + first + sg.n, uint32_t(sg.plan));
+        if (pack_neighbourhood(uint32_t(sg.plan), m.total(0), sg.edits.data(), uint32_t(sg.edits.size()), sg.moves.data(), uint32_t(sg.moves.size()), first, packed, slot, R))
+          any_moves = true;
         table[4 * k] = first; table[4 * k + 1] = sg.n; table[4 * k + 2] = uint32_t(sg.plan);
         first += sg.n;
       }
-      const uint32_t n_short = uint32_t(idx.size());
-      idx.insert(idx.end(), longs.begin(), longs.end());
-      EG_HIP(hipMemcpy(c->d_refine_in, in.data(), in.size(), hipMemcpyHostToDevice));
-      EG_HIP(hipMemcpy(c->d_plan_index, idx.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice));
-      const uint8_t* d_edits = c->d_refine_in;
-      EG_LAUNCH("k_plan_edits_many", launch_plan_edits_many(c->d_refine_bases, uint32_t(P), reinterpret_cast<const uint32_t*>(c->d_refine_in + at_slot), d_edits, n, c->d_plans, nullptr));
-      // (the move variants' blocks: over the base copies k_plan_edits_many has just written for them, on the same stream)
-      if (any_moves) EG_LAUNCH("k_plan_moves", launch_plan_moves(c->d_refine_bases, uint32_t(P), reinterpret_cast<const uint32_t*>(c->d_refine_in + at_slot), d_edits, n, c->d_plans, nullptr));
-      c->n_plan_blocks = n;
-      EG_TRY(launch_plans(c, S, seed, episode_index, n, n_short, true));
-      EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + at_segs, n_segs, n, ro->mode, d_edits, c->d_plans, c->d_refine_bases, uint32_t(P),
+      EG_TRY(launch_variants(c, S, c->d_refine_bases, uint32_t(P), in, at_slot, n, R, any_moves, seed, episode_index));
+      EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + at_segs, n_segs, n, ro->mode, c->d_refine_in, c->d_plans, c->d_refine_bases, uint32_t(P),
                                                               c->d_refine_log, nullptr));
       entries.resize(size_t(n_segs) * kRefineEntryStride);
       EG_HIP(hipMemcpy(entries.data(), c->d_refine_log, entries.size(), hipMemcpyDeviceToHost));      // (waits for the launch)
@@ -271,18 +253,7 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
       t0 = t1;
     }
   }
-  {
-    std::vector<int32_t> count[2];
-    std::vector<uint8_t> flat[2];
-    for (int w = 0; w < 2; ++w)
-      for (int32_t p = 0; p < P; ++p)
-        for (int y = 0; y < EG_YEARS; ++y) {
-          const std::vector<uint8_t>& l = mirror[size_t(p)].l[w][y];
-          count[w].push_back(int32_t(l.size())); flat[w].insert(flat[w].end(), l.begin(), l.end());
-        }
-    flat[0].reserve(1); flat[1].reserve(1);
-    *refined = make_plan_set_n(P, count[0].data(), flat[0].data(), count[1].data(), flat[1].data(), bases->names);
-  }
+  *refined = set_of(mirror, bases->names);
   return EG_OK;
 }
 }  // namespace
@@ -294,11 +265,7 @@ extern "C" int32_t eg_refine_validate(const eg_plan_set* base, const eg_refine_o
 }
 
 extern "C" int32_t eg_refine_plans_validate(const eg_plan_set* bases, const eg_refine_opts* o) {
-  EG_TRY(eg_plans_validate(bases));
-  if (bases->n_plans > EG_REFINE_MAX_PLANS) {
-    set_error("eg_refine_plans_validate: the set holds " + std::to_string(bases->n_plans) + " plans (at most " + std::to_string(EG_REFINE_MAX_PLANS) + ")");
-    return EG_ERR_BAD_ARG;
-  }
+  EG_TRY(validate_set("eg_refine_plans_validate", bases));
   return validate_opts("eg_refine_plans_validate", true, bases, o);
 }
 
@@ -306,8 +273,7 @@ extern "C" int32_t eg_refine_plan(eg_ctx* c, const eg_policy_snapshot* s, const 
                                   uint64_t episode_index, eg_plan_set** refined, eg_refine_step* steps, int32_t* n_steps, int32_t* stop_reason,
                                   double* start_score, eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plan: bad argument"); return EG_ERR_BAD_ARG; }
-  if (c->group_member) { set_error("eg_refine_plan: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
-  EG_TRY(eg_refine_validate(base, ro));
+  EG_TRY(plan_entry(c, s, o, "eg_refine_plan", [&] { return eg_refine_validate(base, ro); }));
   return refine("eg_refine_plan", false, c, s, o, base, ro, seed, episode_index, refined, steps, n_steps, stop_reason, start_score, out);
 }
 
@@ -315,18 +281,13 @@ extern "C" int32_t eg_refine_plans(eg_ctx* c, const eg_policy_snapshot* s, const
                                    uint64_t episode_index, eg_plan_set** refined, eg_refine_step* steps, int32_t* n_steps, int32_t* stop_reason,
                                    double* start_score, eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plans: bad argument"); return EG_ERR_BAD_ARG; }
-  if (c->group_member) { set_error("eg_refine_plans: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
-  EG_TRY(eg_refine_plans_validate(bases, ro));
+  EG_TRY(plan_entry(c, s, o, "eg_refine_plans", [&] { return eg_refine_plans_validate(bases, ro); }));
   return refine("eg_refine_plans", true, c, s, o, bases, ro, seed, episode_index, refined, steps, n_steps, stop_reason, start_score, out);
 }
 
 extern "C" int32_t eg_refine_plans_moves_validate(const eg_plan_set* bases, const eg_refine_opts* o, const eg_refine_move_opts* mo) {
   const char* fn = "eg_refine_plans_moves_validate";
-  EG_TRY(eg_plans_validate(bases));
-  if (bases->n_plans > EG_REFINE_MAX_PLANS) {
-    set_error(std::string(fn) + ": the set holds " + std::to_string(bases->n_plans) + " plans (at most " + std::to_string(EG_REFINE_MAX_PLANS) + ")");
-    return EG_ERR_BAD_ARG;
-  }
+  EG_TRY(validate_set(fn, bases));
   if (!mo) { set_error(std::string(fn) + ": NULL move options"); return EG_ERR_BAD_ARG; }
   if (mo->max_shift < 0 || mo->max_shift > EG_YEARS - 1) {
     set_error(std::string(fn) + ": max_shift = " + std::to_string(mo->max_shift) + " (0.." + std::to_string(EG_YEARS - 1) + " years; 0: no moves)");
@@ -339,7 +300,6 @@ extern "C" int32_t eg_refine_plans_moves(eg_ctx* c, const eg_policy_snapshot* s,
                                          const eg_refine_move_opts* mo, uint64_t seed, uint64_t episode_index, eg_plan_set** refined, eg_refine_move_step* steps,
                                          int32_t* n_steps, int32_t* stop_reason, double* start_score, eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plans_moves: bad argument"); return EG_ERR_BAD_ARG; }
-  if (c->group_member) { set_error("eg_refine_plans_moves: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
-  EG_TRY(eg_refine_plans_moves_validate(bases, ro, mo));
+  EG_TRY(plan_entry(c, s, o, "eg_refine_plans_moves", [&] { return eg_refine_plans_moves_validate(bases, ro, mo); }));
   return refine("eg_refine_plans_moves", true, c, s, o, bases, ro, seed, episode_index, refined, nullptr, n_steps, stop_reason, start_score, out, mo, steps);
 }
