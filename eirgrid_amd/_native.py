@@ -13,6 +13,7 @@ GRID, CELLS, YEARLY_FIELDS = 51, 2601, 21
 MAX_GENS, MAX_OFFSETS, RUN_CAP, DEF_CAP, ACT_CAP, ONCHIP_GENS = 4096, 4096, 4096, 4096, 4096, 512
 TOPK_MAX = 64      # EG_TOPK_MAX: entries a top-K archive holds at most
 PARETO_MAX = 256   # EG_PARETO_MAX: entries a Pareto archive holds at most
+PARETO_KEEP_SPREAD = 0x100   # EG_PARETO_KEEP_SPREAD: OR-ed into an archive's mode, the capacity rule "keep spread"
 STATS_LEN = 8 + 2 * YEARS * N_ACTIONS + YEARS * N_DEFICIT
 CANDIDATE_BYTES = 8 + 8 + 32 + 4 * YEARS + 4 * YEARS + RUN_CAP + DEF_CAP
 PACKET_BYTES = 8 * STATS_LEN + CANDIDATE_BYTES

@@ -40,7 +40,7 @@ int eg::pareto_fold(eg_ctx* c, uint32_t n, uint64_t first_index) {
     EG_HIP(c->d_pareto_work.reserve(pareto_work_bytes(n)));
     c->pareto_work_n = n;
   }
-  EG_LAUNCH("k_pareto_filter .. k_pareto_finalize", launch_pareto_fold(c->d_pareto, pareto_work(c->d_pareto_work, c->pareto_work_n), c->out, n, first_index, nullptr));
+  EG_LAUNCH("k_pareto_filter .. k_pareto_finalize", launch_pareto_fold(c->d_pareto, pareto_work(c->d_pareto_work, c->pareto_work_n), c->out, n, first_index, c->pareto_spread, nullptr));
   return EG_OK;
 }
 
@@ -238,8 +238,9 @@ int32_t eg_pareto_track(eg_ctx* c, int32_t cap, int32_t objectives, int32_t mode
   c->pareto_cap = 0;      // (until the new archive stands)
   EG_HIP(c->d_pareto.reserve(kParetoRecords + size_t(cap) * rec::stride));
   ParetoState st{};
-  st.cap = cap; st.objectives = objectives; st.mode = mode;
+  st.cap = cap; st.objectives = objectives; st.mode = pareto_rank_mode(mode); st.pad = pareto_keep_spread(mode) ? kParetoKeepSpread : 0;
   EG_HIP(hipMemcpy(c->d_pareto, &st, sizeof(st), hipMemcpyHostToDevice));
+  c->pareto_spread = pareto_keep_spread(mode);
   c->pareto_cap = cap;
   return EG_OK;
 }

@@ -76,7 +76,8 @@ struct eg_ctx {
   eg::DevBuf<double> d_tk_score; eg::DevBuf<unsigned long long> d_tk_key; eg::DevBuf<eg::TopKBlock> d_tk_blocks;
   // the Pareto archive of outcomes (eg_pareto_track; eg_pareto.h): pareto_cap 0 = not tracked; d_pareto: ParetoState and the cap record
   // slots, allocated by eg_pareto_track; d_pareto_work: what the kernels of a fold hand each other, sized for pareto_work_n episodes
-  int pareto_cap = 0; eg::DevBuf<uint8_t> d_pareto, d_pareto_work; uint32_t pareto_work_n = 0;
+  // pareto_spread: the archive's capacity rule is "keep spread" (EG_PARETO_KEEP_SPREAD): a fold launches k_pareto_spread, not k_pareto_rank
+  int pareto_cap = 0; eg::DevBuf<uint8_t> d_pareto, d_pareto_work; uint32_t pareto_work_n = 0; bool pareto_spread = false;
   // Is the best list long (the replay episodes run the heavy-capable variant and are the batch's long pole)?  `list_exact`: the host
   // KNOWS the list the next launch will find on the device (it uploaded, rewound or pulled it and no on-device update has been
   // enqueued since): the replay variant that has nothing to do is then not launched at all.  Otherwise the device may have replaced
@@ -150,7 +151,8 @@ struct eg_ctx {
   // allocated at the first call, and Pareto work of its own sized for a launch of EG_CROSS_MAX_VARIANTS.  eg_explore_plans uses both the
   // same way (the parent arrays as its frontier arrays); either call starts the archive empty
   eg::DevBuf<uint8_t> d_breed, d_breed_work;
-  bool debug_breed = false;      // eg_debug_breed_begin has started the private archive (the crafted-generation test hooks)
+  bool breed_spread = false;     // the private archive's capacity rule, as pareto_spread (archive_begin sets it from the call's mode)
+  bool debug_breed = false;     // eg_debug_breed_begin has started the private archive (the crafted-generation test hooks)
 };
 
 namespace eg {

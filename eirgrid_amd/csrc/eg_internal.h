@@ -438,7 +438,13 @@ constexpr uint32_t kTopKChunk = 1024;      // episodes per workgroup of k_topk_s
 // never moves while its entry is held; a new entry's record goes to the lowest free one.
 struct ParetoEntry { double metrics[4]; double score; long long index; int32_t slot, pad; };
 static_assert(sizeof(ParetoEntry) == 56, "pareto entry");
+// `pad` of the state: the capacity rule, 0 = keep score (k_pareto_rank), 1 = keep spread (k_pareto_spread; EG_PARETO_KEEP_SPREAD in the
+// mode the caller gave — `mode` itself stays 1 | 2, the rank score).  The host chooses the kernel; the word is the record of it.
 struct ParetoState { int32_t cap, n_held, objectives, mode; long long n_dropped, pad; ParetoEntry e[EG_PARETO_MAX]; };
+// a caller's mode (1 | 2, EG_PARETO_KEEP_SPREAD OR-ed in or not) in its two parts
+constexpr long long kParetoKeepSpread = 1;
+inline int32_t pareto_rank_mode(int32_t mode) { return mode & ~EG_PARETO_KEEP_SPREAD; }
+inline bool pareto_keep_spread(int32_t mode) { return (mode & EG_PARETO_KEEP_SPREAD) != 0; }
 constexpr size_t kParetoRecords = (sizeof(ParetoState) + 255) & ~size_t(255);
 constexpr uint32_t kParetoChunk = 256;      // episodes per workgroup of k_pareto_filter / k_pareto_compact
 // What the kernels of one fold hand each other, sized for a batch of cap_n episodes — the LIST of cap_n + EG_PARETO_MAX entries (the
@@ -454,10 +460,15 @@ struct ParetoWork {
   uint32_t* blk;         // [ceil(cap_n / kParetoChunk)] survivors per chunk
   uint8_t* flag;         // [cap_n] the episode survived k_pareto_filter
   uint8_t* alive;        // [L] not beaten by any entry of the list
+  // k_pareto_spread's (the capacity rule "keep spread"), indexed by an alive entry's number c among the alive ones
+  double* u;             // [L][4] normalised oriented coordinates
+  double* mind;          // [L] smallest squared distance to a picked entry (< 0: picked)
+  uint32_t* pos;         // [L] the entry's place in the list
 };
 inline size_t pareto_work_bytes(uint32_t cap_n) {
   const size_t L = size_t(cap_n) + EG_PARETO_MAX, chunks = (size_t(cap_n) + kParetoChunk - 1) / kParetoChunk;
-  return 64 + L * (32 + 8 + 8 + 4 + 4) + ((chunks * 4 + 7) & ~size_t(7)) + ((size_t(cap_n) + 7) & ~size_t(7)) + L;
+  return 64 + L * (32 + 8 + 8 + 4 + 4) + ((chunks * 4 + 7) & ~size_t(7)) + ((size_t(cap_n) + 7) & ~size_t(7)) + ((L + 7) & ~size_t(7)) +
+         L * (32 + 8 + 4);
 }
 inline ParetoWork pareto_work(uint8_t* base, uint32_t cap_n) {
   const size_t L = size_t(cap_n) + EG_PARETO_MAX, chunks = (size_t(cap_n) + kParetoChunk - 1) / kParetoChunk;
@@ -472,12 +483,16 @@ inline ParetoWork pareto_work(uint8_t* base, uint32_t cap_n) {
   w.rank = reinterpret_cast<uint32_t*>(p); p += L * 4;
   w.blk = reinterpret_cast<uint32_t*>(p); p += (chunks * 4 + 7) & ~size_t(7);
   w.flag = p; p += (size_t(cap_n) + 7) & ~size_t(7);
-  w.alive = p;
+  w.alive = p; p += (L + 7) & ~size_t(7);
+  w.u = reinterpret_cast<double*>(p); p += L * 32;
+  w.mind = reinterpret_cast<double*>(p); p += L * 8;
+  w.pos = reinterpret_cast<uint32_t*>(p);
   return w;
 }
 // One fold of the n results in `o` (global indices first_index..) into the archive at d_state: k_pareto_filter, k_pareto_compact,
-// k_pareto_dominate, k_pareto_rank, k_pareto_finalize, in that order on `stream`.  n <= w.cap_n.
-int launch_pareto_fold(uint8_t* d_state, const ParetoWork& w, const DevOut& o, uint32_t n, uint64_t first_index, void* stream);
+// k_pareto_dominate, k_pareto_rank — `keep_spread` (what the state's `pad` says): k_pareto_spread in its place —, k_pareto_finalize,
+// in that order on `stream`.  n <= w.cap_n.
+int launch_pareto_fold(uint8_t* d_state, const ParetoWork& w, const DevOut& o, uint32_t n, uint64_t first_index, bool keep_spread, void* stream);
 // k_plan_edits (eg_plan_edits.h): the n plan blocks of a plan-edit batch into d_pool (snap::kPlanStride bytes each) from the base
 // plan's block d_base and n packed edits (8 bytes each: kind | list << 8 | year << 16 | action << 24, then pos)
 int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream);

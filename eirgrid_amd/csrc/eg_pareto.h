@@ -12,7 +12,10 @@
 //                         beaten entries are marked dead.  What stays alive is front(held u batch): beats is transitive, so it does not
 //                         matter that a dead j still kills.
 //   4. k_pareto_rank      only when more than cap entries are alive: every alive entry's place by rank score (descending, ties to the lower
-//                         index), counted the same way.
+//                         index), counted the same way.  The capacity rule "keep score" (ParetoState::pad == 0).
+//   4'. k_pareto_spread   in k_pareto_rank's place under the capacity rule "keep spread" (ParetoState::pad == kParetoKeepSpread), again only
+//                         when more than cap entries are alive: greedy farthest-point selection on the normalised front, one workgroup,
+//                         cap rounds of "update a minimum, take an arg-max".  The rank it leaves is the round an entry was picked in.
 //   5. k_pareto_finalize  the alive entries of rank < cap (at most cap) gathered, sorted by global index, given slots — held entries keep
 //                         theirs, new ones take the lowest free — and written to the state; the records of new entries copied, a
 //                         block per record.  Every block derives the same entries and slots; block 0 alone writes the state.
@@ -181,6 +184,219 @@ __global__ void __launch_bounds__(pareto::kBlock) k_pareto_rank(const ParetoStat
     __syncthreads();
   }
   if (mine && ahead) atomicAdd(&W.rank[i], ahead);
+}
+
+// ---- the capacity rule "keep spread" (include/eirgrid_hip.h EG_PARETO_KEEP_SPREAD) ---------------------------------------------------
+// Farthest-point selection among the alive entries A of the list.  u_i: entry i's oriented coordinates, each normalised to [0, 1] over
+// A ((v - lo) / (hi - lo); 0.0 where hi - lo is not a finite number > 0).  d2(i, j) = ((e0*e0 + e1*e1) + e2*e2) + e3*e3, e = u_i - u_j,
+// every operation rounded on its own (the file is built with -ffp-contract=off).  s_0 is the first entry in the order of preference of
+// k_pareto_rank; then cap - 1 times: the entry not yet picked whose smallest d2 to a picked one (`mind`) is largest, ties by the order
+// of preference.  W.rank[s_r] = r, every other alive entry's rank is ~0u.
+// One workgroup.  The c-th alive entry (its place in the list: W.pos[c]) belongs to thread c % kSpreadBlock, which keeps its first
+// entry in registers and the others' u and mind in W.u / W.mind; a round is every thread's pass over its entries (min with the distance
+// to the last pick, the best of them), a wave-level arg-max, a Pick per wave in LDS, ONE barrier (the Picks alternate between two
+// rows), and the same arg-max over the waves' Picks in every wave: the pick's coordinates come out of LDS with it.  The arg-max
+// reduces one key at a time over the lanes still tied (wave_first) on the DPP path; the picks' places are kept in LDS and their ranks
+// written behind the last round.
+namespace pareto {
+
+constexpr int kSpreadBlock = 1024;
+constexpr int kSpreadWaves = kSpreadBlock / kWave;
+static_assert(kSpreadWaves <= kWave && (kSpreadBlock & (kSpreadBlock - 1)) == 0, "the waves' picks are reduced by one wave, a lane each; an entry's owner is c & (kSpreadBlock - 1)");
+
+struct Cand { double d, key; long long idx; uint32_t pos, c; };      // d: mind (< 0: no candidate); c: the entry is the c-th alive one
+struct Pick { Cand b; double u[4]; };
+__device__ __forceinline__ bool before(const Cand& a, const Cand& b) {
+  return a.d > b.d || (a.d == b.d && (a.key > b.key || (a.key == b.key && (a.idx < b.idx || (a.idx == b.idx && a.pos < b.pos)))));
+}
+__device__ __forceinline__ double dist2(const double* a, const double* b) {
+  const double e0 = a[0] - b[0], e1 = a[1] - b[1], e2 = a[2] - b[2], e3 = a[3] - b[3];
+  return ((e0 * e0 + e1 * e1) + e2 * e2) + e3 * e3;
+}
+// Wave-level reductions of a 64-bit value on the DPP path (no LDS, a few cycles a step where a ds_bpermute shuffle costs its LDS round
+// trip; a round of k_pareto_spread is a chain of them).  dpp64<ctrl, rows>(x): lane l's copy of x from the lane the control names,
+// in the rows of the mask; a lane without a source, or outside the mask, keeps its own x — so op(x, dpp64(x)) leaves it unchanged.
+// The steps: row_shr 1, 2, 4, 8 make lane 15 of every row of 16 the row's result; row_bcast:15 carries it into the next row (rows 1, 3),
+// row_bcast:31 lane 31's into rows 2 and 3: lane 63 holds the wave's result, read back as a scalar.
+template <int kCtrl, int kRows> __device__ __forceinline__ long long dpp64(long long x) {
+  const int lo = __builtin_amdgcn_update_dpp((int)x, (int)x, kCtrl, kRows, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp((int)(x >> 32), (int)(x >> 32), kCtrl, kRows, 0xf, false);
+  return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+template <int kCtrl, int kRows> __device__ __forceinline__ double dpp64(double x) { return __longlong_as_double(dpp64<kCtrl, kRows>(__double_as_longlong(x))); }
+__device__ __forceinline__ long long last_lane(long long x) {
+  const int lo = __builtin_amdgcn_readlane((int)x, kWave - 1), hi = __builtin_amdgcn_readlane((int)(x >> 32), kWave - 1);
+  return (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+__device__ __forceinline__ double last_lane(double x) { return __longlong_as_double(last_lane(__double_as_longlong(x))); }
+template <typename T, typename Op> __device__ __forceinline__ T wave_reduce(T x, Op op) {
+  x = op(x, dpp64<0x111, 0xf>(x));      // row_shr:1
+  x = op(x, dpp64<0x112, 0xf>(x));      // row_shr:2
+  x = op(x, dpp64<0x114, 0xf>(x));      // row_shr:4
+  x = op(x, dpp64<0x118, 0xf>(x));      // row_shr:8
+  x = op(x, dpp64<0x142, 0xa>(x));      // row_bcast:15
+  x = op(x, dpp64<0x143, 0xc>(x));      // row_bcast:31
+  return last_lane(x);
+}
+__device__ __forceinline__ double wave_max(double x) { return wave_reduce(x, [](double a, double b) { return b > a ? b : a; }); }
+__device__ __forceinline__ double wave_min(double x) { return wave_reduce(x, [](double a, double b) { return b < a ? b : a; }); }
+__device__ __forceinline__ long long wave_min(long long x) { return wave_reduce(x, [](long long a, long long b) { return b < a ? b : a; }); }
+// The lane whose candidate stands before every other lane's (-1: no lane has one), the same value in every lane.  The lanes still in
+// the running are narrowed a key at a time; a key is only reduced while more than one lane is left.
+__device__ __forceinline__ int wave_first(const Cand& b) {
+  const double d = wave_max(b.d);
+  if (d < 0.0) return -1;
+  bool in = b.d == d;
+  unsigned long long m = __ballot(in);
+  if (__popcll(m) > 1) {
+    const double key = wave_max(in ? b.key : -__builtin_huge_val());
+    in = in && b.key == key;
+    m = __ballot(in);
+    if (__popcll(m) > 1) {
+      const long long idx = wave_min(in ? b.idx : 0x7fffffffffffffffll);
+      in = in && b.idx == idx;
+      m = __ballot(in);
+      if (__popcll(m) > 1) {
+        const long long pos = wave_min(in ? (long long)b.pos : 0x7fffffffffffffffll);
+        m = __ballot(in && (long long)b.pos == pos);
+      }
+    }
+  }
+  return __ffsll((long long)m) - 1;
+}
+
+}  // namespace pareto
+
+__global__ void __launch_bounds__(pareto::kSpreadBlock) k_pareto_spread(const ParetoState* st, ParetoWork W) {
+  using pareto::Cand; using pareto::Pick; using pareto::kSpreadBlock; using pareto::kSpreadWaves;
+  __shared__ Pick s_pick[2][kSpreadWaves];
+  __shared__ double s_lo[kSpreadWaves][4], s_hi[kSpreadWaves][4];
+  __shared__ unsigned s_cnt[kSpreadWaves];
+  __shared__ uint32_t s_sel[EG_PARETO_MAX];      // s_sel[r]: the place in the list of round r's pick
+  const uint32_t tid = threadIdx.x;
+  const int lane = (int)(tid & (kWave - 1)), wave = (int)(tid >> 6);
+  const uint32_t M = pareto::list_len(W);
+  const uint32_t cap = (uint32_t)pareto::clampi(st->cap, 1, EG_PARETO_MAX);
+  const int mask = st->objectives;
+  const double inf = __builtin_huge_val();
+
+  // the alive entries' places, in the order of the list
+  uint32_t A = 0;
+  for (uint32_t j0 = 0; j0 < M; j0 += (uint32_t)kSpreadBlock) {
+    const uint32_t j = j0 + tid;
+    const bool live = j < M && W.alive[j] != 0;
+    const unsigned long long b = __ballot(live);
+    __syncthreads();      // (s_cnt may still be read for the tile before)
+    if (lane == 0) s_cnt[wave] = (unsigned)__popcll(b);
+    __syncthreads();
+    unsigned off = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < kSpreadWaves; ++w) { const unsigned c = s_cnt[w]; off += w < wave ? c : 0u; total += c; }
+    if (live) W.pos[A + off + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = j;      // (< A + total <= M: inside the list)
+    A += total;
+  }
+  if (A <= cap) return;
+  __syncthreads();      // (W.pos: written by other threads of the workgroup)
+
+  // the range of every coordinate over A
+  double lo[4] = {inf, inf, inf, inf}, hi[4] = {-inf, -inf, -inf, -inf};
+#pragma unroll 1
+  for (uint32_t c = tid; c < A; c += (uint32_t)kSpreadBlock) {
+    double v[4];
+    pareto::oriented(W.m + 4 * (size_t)W.pos[c], mask, v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { lo[k] = v[k] < lo[k] ? v[k] : lo[k]; hi[k] = v[k] > hi[k] ? v[k] : hi[k]; }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { lo[k] = pareto::wave_min(lo[k]); hi[k] = pareto::wave_max(hi[k]); }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { s_lo[wave][k] = lo[k]; s_hi[wave][k] = hi[k]; }
+  }
+  __syncthreads();
+  double range[4];
+  bool on[4];
+#pragma unroll 1
+  for (int w = 0; w < kSpreadWaves; ++w) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const double a = s_lo[w][k], b = s_hi[w][k]; lo[k] = a < lo[k] ? a : lo[k]; hi[k] = b > hi[k] ? b : hi[k]; }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    range[k] = hi[k] - lo[k];
+    on[k] = range[k] > 0.0 && range[k] < inf;
+  }
+
+  // normalised coordinates; mind = +inf, so that round 0 is decided by the order of preference alone and the first min is d2 itself
+  Cand mine; mine.d = -1.0; mine.key = 0.0; mine.idx = 0; mine.pos = 0u; mine.c = tid;
+  double mu[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+  for (uint32_t c = tid; c < A; c += (uint32_t)kSpreadBlock) {
+    const uint32_t pos = W.pos[c];
+    double v[4], u[4];
+    pareto::oriented(W.m + 4 * (size_t)pos, mask, v);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = on[k] ? (v[k] - lo[k]) / range[k] : 0.0;
+    W.rank[pos] = ~0u;
+    if (c == tid) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) mu[k] = u[k];
+      mine.d = inf; mine.key = pareto::rank_key(W.score[pos]); mine.idx = W.index[pos]; mine.pos = pos;
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) W.u[4 * (size_t)c + k] = u[k];
+      W.mind[c] = inf;
+    }
+  }
+
+  double pu[4] = {0.0, 0.0, 0.0, 0.0};      // the last pick's coordinates
+  uint32_t done = 0;                        // rounds completed = picks in s_sel
+#pragma unroll 1
+  for (uint32_t r = 0; r < cap; ++r) {
+    if (r > 0 && mine.d >= 0.0) { const double d2 = pareto::dist2(mu, pu); mine.d = d2 < mine.d ? d2 : mine.d; }
+    Cand b = mine;
+    // (its other entries one at a time; loading four ahead of their stores was measured and is slower: 5.0 against 4.4 ms for 16 384 alive)
+#pragma unroll 1
+    for (uint32_t c = tid + (uint32_t)kSpreadBlock; c < A; c += (uint32_t)kSpreadBlock) {
+      double d = W.mind[c];
+      if (d < 0.0) continue;      // picked
+      if (r > 0) {
+        const double u[4] = {W.u[4 * (size_t)c], W.u[4 * (size_t)c + 1], W.u[4 * (size_t)c + 2], W.u[4 * (size_t)c + 3]};
+        const double d2 = pareto::dist2(u, pu);
+        if (d2 < d) { d = d2; W.mind[c] = d; }
+      }
+      if (d >= b.d) {      // (the keys are read only for an entry that may stand first)
+        Cand x; x.d = d; x.pos = W.pos[c]; x.c = c; x.key = pareto::rank_key(W.score[x.pos]); x.idx = W.index[x.pos];
+        if (pareto::before(x, b)) b = x;
+      }
+    }
+    Pick* row = s_pick[r & 1u];
+    const int win = pareto::wave_first(b);
+    if (win < 0) { if (lane == 0) row[wave].b.d = -1.0; }
+    else if (lane == win) {
+      Pick& p = row[wave];
+      p.b = b;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) p.u[k] = b.c == tid ? mu[k] : W.u[4 * (size_t)b.c + k];
+    }
+    __syncthreads();      // (the only barrier of a round: the next round writes the other row, and nobody passes its barrier before all have read this one)
+    Cand x; x.d = -1.0; x.key = 0.0; x.idx = 0; x.pos = 0u; x.c = 0u;
+    if (lane < kSpreadWaves) { x.d = row[lane].b.d; if (x.d >= 0.0) x = row[lane].b; }
+    const int w = pareto::wave_first(x);      // (the same in every wave: the order is total)
+    if (w < 0) break;                         // (never: more than cap entries are alive, so every round has a candidate)
+    const Pick& p = row[w];
+    const uint32_t pc = p.b.c, ppos = p.b.pos;
+    if (pc >= A || ppos >= M) break;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pu[k] = p.u[k];
+    if (pc == tid) mine.d = -1.0;      // its owner marks the pick
+    else if ((pc & (uint32_t)(kSpreadBlock - 1)) == tid) W.mind[pc] = -1.0;
+    if (tid == 0) s_sel[r] = ppos;
+    done = r + 1u;
+  }
+  // (the ranks last and in one go: a store to global memory inside a round would be waited for at the round's barrier)
+  __syncthreads();
+  if (tid < done) W.rank[s_sel[tid]] = tid;
 }
 
 namespace pareto {

@@ -62,8 +62,9 @@ int eg::archive_begin(eg_ctx* c, int32_t cap, int32_t objectives, int32_t mode, 
   EG_HIP(c->d_breed.reserve(breed_at::total));
   EG_HIP(c->d_breed_work.reserve(pareto_work_bytes(EG_CROSS_MAX_VARIANTS)));
   ParetoState st{};
-  st.cap = cap; st.objectives = objectives; st.mode = mode;
+  st.cap = cap; st.objectives = objectives; st.mode = pareto_rank_mode(mode); st.pad = pareto_keep_spread(mode) ? kParetoKeepSpread : 0;
   EG_HIP(hipMemcpy(c->d_breed, &st, sizeof(st), hipMemcpyHostToDevice));
+  c->breed_spread = pareto_keep_spread(mode);
   if (between) EG_TRY(between());
   const BreedCounters zero{};
   EG_HIP(hipMemcpy(c->d_breed + breed_at::counters, &zero, sizeof(zero), hipMemcpyHostToDevice));
@@ -77,7 +78,7 @@ int eg::archive_upload(eg_ctx* c, const eg_plan_set* set, int array) {
 }
 int eg::archive_fold(eg_ctx* c, uint32_t n, uint64_t first_index) {
   const ParetoWork work = pareto_work(c->d_breed_work, EG_CROSS_MAX_VARIANTS);
-  EG_LAUNCH("k_pareto_filter .. k_pareto_finalize", launch_pareto_fold(c->d_breed, work, c->out, n, first_index, nullptr));
+  EG_LAUNCH("k_pareto_filter .. k_pareto_finalize", launch_pareto_fold(c->d_breed, work, c->out, n, first_index, c->breed_spread, nullptr));
   EG_LAUNCH("k_breed_gather", launch_breed_gather(c->d_breed, c->out, n, first_index, c->d_plans, nullptr));
   return EG_OK;
 }
@@ -114,7 +115,8 @@ int eg::decode_device_blocks(const uint8_t* d_blocks, int32_t n, const int32_t* 
 
 // ---------------------------------------------------------------- option checks
 int32_t eg::check_mode(const Fail& fail, int32_t mode) {
-  return mode != 1 && mode != 2 ? fail("mode " + std::to_string(mode) + " is neither 1 (optimization_mode None) nor 2 (cost_only)") : EG_OK;
+  const int32_t rank = pareto_rank_mode(mode);      // (EG_PARETO_KEEP_SPREAD may be OR-ed into either; the message is the one the tests pin)
+  return rank != 1 && rank != 2 ? fail("mode " + std::to_string(mode) + " is neither 1 (optimization_mode None) nor 2 (cost_only)") : EG_OK;
 }
 int32_t eg::check_objectives(const Fail& fail, int32_t objectives) {
   return objectives < 1 || objectives > 15 ? fail("objectives " + std::to_string(objectives) + " is outside 1..15 (bit i = metric i)") : EG_OK;

@@ -3459,7 +3459,7 @@ int launch_topk_merge(uint8_t* d_state, const uint8_t* d_blocks, int n_blocks, s
                      (unsigned long long)block_stride, d_pack, k, o, (unsigned long long)own_first, own_n, step);
   return (int)hipGetLastError();
 }
-int launch_pareto_fold(uint8_t* d_state, const ParetoWork& w, const DevOut& o, uint32_t n, uint64_t first_index, void* stream) {
+int launch_pareto_fold(uint8_t* d_state, const ParetoWork& w, const DevOut& o, uint32_t n, uint64_t first_index, bool keep_spread, void* stream) {
   if (n == 0 || n > w.cap_n) return n == 0 ? 0 : (int)hipErrorInvalidValue;
   ParetoState* st = reinterpret_cast<ParetoState*>(d_state);
   const dim3 chunks((n + kParetoChunk - 1u) / kParetoChunk), block(pareto::kBlock);
@@ -3468,7 +3468,8 @@ int launch_pareto_fold(uint8_t* d_state, const ParetoWork& w, const DevOut& o, u
   hipLaunchKernelGGL(k_pareto_filter, chunks, block, 0, (hipStream_t)stream, o, n, (unsigned long long)first_index, st, w);
   hipLaunchKernelGGL(k_pareto_compact, chunks, block, 0, (hipStream_t)stream, o, n, (unsigned long long)first_index, st, w);
   hipLaunchKernelGGL(k_pareto_dominate, pairs, block, 0, (hipStream_t)stream, st, w);
-  hipLaunchKernelGGL(k_pareto_rank, pairs, block, 0, (hipStream_t)stream, st, w);
+  if (keep_spread) hipLaunchKernelGGL(k_pareto_spread, dim3(1), dim3(pareto::kSpreadBlock), 0, (hipStream_t)stream, st, w);
+  else hipLaunchKernelGGL(k_pareto_rank, pairs, block, 0, (hipStream_t)stream, st, w);
   hipLaunchKernelGGL(k_pareto_finalize, dim3(pareto::kCopyBlocks), block, 0, (hipStream_t)stream, st, w, o, n);
   return (int)hipGetLastError();
 }

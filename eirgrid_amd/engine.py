@@ -379,6 +379,13 @@ def _objective_mask(objectives, who: str) -> int:
     return mask
 
 
+def _archive_mode(cost_only: bool, keep: str, who: str) -> int:
+    """The `mode` of an archive: the rank score (1 | 2) and the capacity rule, "score" or "spread" (EG_PARETO_KEEP_SPREAD)."""
+    if keep not in ("score", "spread"):
+        raise ValueError(f"{who}: keep = {keep!r} (\"score\" or \"spread\")")
+    return (2 if cost_only else 1) | (N.PARETO_KEEP_SPREAD if keep == "spread" else 0)
+
+
 def pareto_filter(front_index, front_metrics, index, metrics, status, mask: int):
     """One step of a streaming non-dominated filter on the host, with eg_pareto_track's definitions over the objectives of `mask` (bit
     i = metric i): an entry is valid with status EG_EP_OK and none of its four metrics NaN; a dominates b when it is at least as good
@@ -899,14 +906,16 @@ class Engine:
         return CrossFront(fi, [crosses[i] for i in fi], fm, score, fi < len(parents), len(crosses), n_valid)
 
     def breed_front(self, weights: ActionWeights, parents, seed: int, index: int = 0, objectives=PARETO_OBJECTIVES, cost_only: bool = False,
-                    cuts=range(1, 26), generations: int = 8, cap: int = N.PARETO_MAX, max_variants: int = N.CROSS_MAX_VARIANTS) -> BreedFront:
+                    cuts=range(1, 26), generations: int = 8, cap: int = N.PARETO_MAX, max_variants: int = N.CROSS_MAX_VARIANTS,
+                    keep: str = "score") -> BreedFront:
         """Generations of cross_front on the device (eg_breed_plans): from the population `parents`, every generation evaluates the
         variants of cross_pairs(len(population), cuts) — less the crosses whose child would outgrow a list — in chunks of at most
         max_variants, every one at global index `index` of `seed`, folds each chunk into a private Pareto archive of `cap` entries
-        over `objectives` (eg_pareto_track's rules; cost_only picks the rank score the capacity rule and the rows use), and makes the
+        over `objectives` (eg_pareto_track's rules; cost_only picks the rank score the capacity rule and the rows use, `keep` the
+        capacity rule: "score" keeps the best-scoring points of a front larger than cap, "spread" a spread-out subset), and makes the
         survivors' plan blocks the next population without leaving the device.  Stops when a generation keeps exactly its parents, after
         `generations` generations, or when nothing was valid.  The context's own Pareto archive is not touched."""
-        mask = _objective_mask(objectives, "breed_front")
+        mask, mode = _objective_mask(objectives, "breed_front"), _archive_mode(cost_only, keep, "breed_front")
         if mask == 0:
             raise ValueError("breed_front: no objectives")
         parents = list(parents)
@@ -916,7 +925,7 @@ class Engine:
             raise ValueError(f"breed_front: cuts = {cut.tolist()} (year indices 1..{N.YEARS - 1}, at least one)")
         cut = cut.astype(np.uint8)
         gens, cap = int(generations), int(cap)
-        bo = N.EgBreedOpts(2 if cost_only else 1, mask, cap, gens, len(cut), _p(cut, C.c_uint8), int(max_variants))
+        bo = N.EgBreedOpts(mode, mask, cap, gens, len(cut), _p(cut, C.c_uint8), int(max_variants))
         L = N.lib()
         N.check(L.eg_breed_validate(C.byref(ps.s), C.byref(bo)), "eg_breed_validate")
         rows = (N.EgBreedGeneration * gens)()
@@ -950,15 +959,15 @@ class Engine:
 
     def explore_front(self, weights: ActionWeights, starts, seed: int, index: int = 0, objectives=PARETO_OBJECTIVES, cost_only: bool = False,
                       generations: int = 8, cap: int = N.PARETO_MAX, replace_with=None, append_with=None, max_shift: int = 0,
-                      max_variants: int = 0, launch: int = 0) -> ExploreFront:
+                      max_variants: int = 0, launch: int = 0, keep: str = "score") -> ExploreFront:
         """A Pareto local search over one-entry edits and moves on the device (eg_explore_plans): generation 0 evaluates the plans of
         `starts` and their neighbourhoods — refine_edits(plan, replace_with, append_with)[1:] + refine_moves(plan, max_shift) —, every
         later generation the neighbourhoods of the members that entered the archive in the one before, every variant at global index
         `index` of `seed` in chunks of `launch` (0: 16 384), each chunk folded into ONE private Pareto archive of `cap` entries over
         `objectives` that lives through the call (eg_pareto_track's rules; cost_only picks the rank score the capacity rule and the
-        rows use).  Stops when no member is left unexplored, when nothing was valid, when the next generation would take the call
+        rows use, `keep` the capacity rule: "score" or "spread", as for breed_front).  Stops when no member is left unexplored, when nothing was valid, when the next generation would take the call
         beyond max_variants (0: no budget) or after `generations` generations.  The context's own Pareto archive is not touched."""
-        mask = _objective_mask(objectives, "explore_front")
+        mask, mode = _objective_mask(objectives, "explore_front"), _archive_mode(cost_only, keep, "explore_front")
         if mask == 0:
             raise ValueError("explore_front: no objectives")
         starts = list(starts)
@@ -969,7 +978,7 @@ class Engine:
                 raise ValueError(f"explore_front: {name} = {l.tolist()} (actions 0..{N.N_ACTIONS - 1})")
         rep, app = rep.astype(np.uint8), app.astype(np.uint8)
         gens, cap = int(generations), int(cap)
-        xo = N.EgExploreOpts(2 if cost_only else 1, mask, cap, gens, len(rep), _p(rep, C.c_uint8) if len(rep) else None, len(app),
+        xo = N.EgExploreOpts(mode, mask, cap, gens, len(rep), _p(rep, C.c_uint8) if len(rep) else None, len(app),
                              _p(app, C.c_uint8) if len(app) else None, int(max_shift), int(launch), int(max_variants))
         L = N.lib()
         N.check(L.eg_explore_validate(C.byref(ps.s), C.byref(xo)), "eg_explore_validate")
@@ -1266,12 +1275,13 @@ class Engine:
         """(BatchResult of the n_held entries in rank order, their rank scores, their global indices)."""
         return _fetch_top_k(N.lib().eg_fetch_top_k, self.h, "eg_fetch_top_k")
 
-    def track_pareto(self, cap: int, objectives=PARETO_OBJECTIVES, cost_only: bool = False) -> None:
+    def track_pareto(self, cap: int, objectives=PARETO_OBJECTIVES, cost_only: bool = False, keep: str = "score") -> None:
         """Start an empty Pareto archive of at most `cap` non-dominated outcomes over the named objectives (eg_pareto_track); every
         training batch launched from now on is folded into it on the device.  cap = 0 stops tracking (the archive stays fetchable).
-        cost_only picks the rank score that decides what stays when the front outgrows cap."""
+        When the front outgrows cap, `keep` decides what stays: "score" the points of the largest rank score (cost_only picks the score),
+        "spread" a farthest-point selection on the normalised front, which starts from the best-scoring point."""
         mask = _objective_mask(objectives, "track_pareto")
-        N.check(N.lib().eg_pareto_track(self.h, int(cap), mask, 2 if cost_only else 1), "eg_pareto_track")
+        N.check(N.lib().eg_pareto_track(self.h, int(cap), mask, _archive_mode(cost_only, keep, "track_pareto")), "eg_pareto_track")
 
     def fetch_pareto(self):
         """(BatchResult of the n_held entries in ascending global index, their global indices, their rank scores, n_dropped)."""

@@ -289,22 +289,41 @@ double eg_rank_score(const double metrics[4], int32_t mode);   /* mode 2: cost_o
  *   front        F(S) = the points of S that no point of S dominates.  While nothing has been dropped (n_dropped == 0) the archive is
  *                exactly F(all episodes folded): it depends only on that set — not on how it was split into batches, on their order, or
  *                on the replay hoist;
- *   capacity     after a batch the archive becomes F(held u valid(batch)).  If that has more than cap points, the cap points with the
- *                largest eg_rank_score(metrics, mode) stay (mode 1: optimization_mode None, 2: cost_only, as for top-K; a NaN score
- *                ranks last), ties to the lower global index, and the sticky counter n_dropped grows by the number removed (points
- *                removed by dominance are not counted).  ONCE n_dropped > 0 THE ARCHIVE IS THE RESULT OF THIS STREAMING RULE AND DEPENDS
- *                ON THE BATCH BOUNDARIES: a dropped point no longer dominates anything;
+ *   capacity     after a batch the archive becomes F(held u valid(batch)).  If that has more than cap points, cap of them stay and the
+ *                sticky counter n_dropped grows by the number removed (points removed by dominance are not counted).  ONCE n_dropped > 0
+ *                THE ARCHIVE IS THE RESULT OF THIS STREAMING RULE AND DEPENDS ON THE BATCH BOUNDARIES: a dropped point no longer
+ *                dominates anything.  Which cap points stay is the CAPACITY RULE, chosen with `mode`: the low part of mode picks the
+ *                rank score (1: optimization_mode None, 2: cost_only, as for top-K), EG_PARETO_KEEP_SPREAD OR-ed into it picks the
+ *                rule — accepted values are 1, 2, 0x101 and 0x102.  Both rules use one ORDER OF PREFERENCE between two entries:
+ *                the larger eg_rank_score(metrics, low part of mode) first (a NaN score last), then the lower global index, then the
+ *                earlier place in the list (held entries in their order, then the batch's in index order);
+ *   keep score   (mode 1 | 2) the first cap points in the order of preference stay: the corner of the front nearest the scalar optimum;
+ *   keep spread  (mode 0x101 | 0x102) farthest-point selection on the normalised front.  Let A be the front F(held u valid(batch)) of
+ *                more than cap points, and v_i[k] entry i's ORIENTED coordinates: metric k where lower is better, its negation where
+ *                higher is better, 0.0 for an inactive metric.
+ *                  Normalise.  For each k, lo_k = min_A v[k], hi_k = max_A v[k], r_k = hi_k - lo_k.  If r_k is a finite number > 0,
+ *                    u_i[k] = (v_i[k] - lo_k) / r_k: one subtraction and one division, each rounded once.  Otherwise u_i[k] = 0.0 for
+ *                    every i: an inactive metric, a metric constant over the front, an infinite metric in the front.
+ *                  Distance.  d2(i,j) = ((e0*e0 + e1*e1) + e2*e2) + e3*e3 with e_k = u_i[k] - u_j[k]; every product and every sum is
+ *                    rounded on its own (no fused multiply-add).  Squared distances are compared; no square root is taken.
+ *                  Selection.  s_0 is the first entry of A in the order of preference: the best-scoring point of the front is never
+ *                    dropped, and cap = 1 gives what keep score gives.  Set mind_i = d2(i, s_0).  For r = 1 .. cap-1: s_r is the
+ *                    not-yet-selected entry of A with the largest mind, ties by the order of preference; then
+ *                    mind_i = min(mind_i, d2(i, s_r)) for all i.
+ *                  Result.  s_0 .. s_{cap-1} stay; held entries among them keep their record slots, new ones take the lowest free.
+ *                This is greedy k-centre selection: every dropped point lies within max_i mind_i of a kept one;
  *   order        eg_fetch_pareto returns the entries in ascending global index.
  * Plan batches (eg_evaluate_plans, eg_evaluate_plan_edits, the rounds of eg_refine_plan) are not training and are not folded
  * automatically: eg_pareto_fold_last_batch(ctx) folds the last batch, whatever kind it was, on request — episode j of it as global index
  * first_episode_index + j, also in a same_index batch ("which of these 16 384 variants are non-dominated").  EG_ERR_BAD_ARG without
  * tracking or without a batch.  eg_pareto_track refuses, naming the field: a cap outside 0..EG_PARETO_MAX, objectives outside 1..15, a
- * mode other than 1 or 2, a rank of a group — a shard's local front has no bounded message size, so there is no group form.  The
+ * mode other than 1, 2, 0x101 or 0x102 (0, 3, EG_PARETO_KEEP_SPREAD alone, any other bit), a rank of a group — a shard's local front has no bounded message size, so there is no group form.  The
  * archive state and cap record slots (10.6 MB at cap 256) are allocated by eg_pareto_track; like best_result the archive lives as long
  * as the context and is not part of any checkpoint.
  * eg_fetch_pareto copies the *n_held <= cap entries: `out` rows (sized for cap episodes; may be NULL), global_index[cap], scores[cap]
  * (eg_rank_score of each entry), *n_dropped (each may be NULL). */
 #define EG_PARETO_MAX 256
+#define EG_PARETO_KEEP_SPREAD 0x100     /* OR-ed into the mode of eg_pareto_track, eg_breed_opts, eg_explore_opts, eg_debug_breed_begin: the capacity rule "keep spread" */
 int32_t eg_pareto_track(eg_ctx *, int32_t cap, int32_t objectives, int32_t mode);
 int32_t eg_pareto_fold_last_batch(eg_ctx *);
 int32_t eg_fetch_pareto(eg_ctx *, eg_episode_out *out /* cap rows, may be NULL */, int32_t *n_held, int64_t *global_index /* [cap] or NULL */,
@@ -570,13 +589,13 @@ int32_t eg_evaluate_plan_crosses(eg_ctx *, const eg_policy_snapshot *policy, con
  * Everything else is the contract of eg_evaluate_plan_crosses: no statistics, update or training folds, the resident policy untouched,
  * a rank of a group refused, the policy checked and staged once per call, the last launch's variants left behind as the last batch.
  * eg_breed_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the field for a parent set that is not a valid set of
- * 1..EG_CROSS_MAX_PARENTS plans, NULL options, a mode other than 1 or 2, objectives outside 1..15, cap outside 1..EG_PARETO_MAX,
+ * 1..EG_CROSS_MAX_PARENTS plans, NULL options, a mode other than 1 or 2 (either with EG_PARETO_KEEP_SPREAD OR-ed in or not), objectives outside 1..15, cap outside 1..EG_PARETO_MAX,
  * max_generations < 1, launch_variants outside 0..EG_CROSS_MAX_VARIANTS, n_cuts outside 0..25, NULL cuts with n_cuts > 0, a cut outside
  * 1..25.  Nothing is launched after a refusal. */
 #define EG_BREED_CONVERGED 0
 #define EG_BREED_MAX_GENERATIONS 1
 #define EG_BREED_EMPTY 2
-typedef struct { int32_t mode /* 1 | 2 */, objectives /* 1..15 */, cap /* 1..EG_PARETO_MAX */, max_generations /* >= 1 */;
+typedef struct { int32_t mode /* 1 | 2, | EG_PARETO_KEEP_SPREAD */, objectives /* 1..15 */, cap /* 1..EG_PARETO_MAX */, max_generations /* >= 1 */;
                  int32_t n_cuts; const uint8_t *cuts /* year indices 1..25; NULL with n_cuts 0: all 25 */;
                  int32_t launch_variants; } eg_breed_opts;
 typedef struct { int32_t n_parents, n_skipped, n_kept, n_children_kept; int64_t n_variants, n_valid, n_dropped; } eg_breed_generation;   /* 40 bytes */
@@ -640,7 +659,7 @@ int32_t eg_breed_plans(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts
  * archives untouched, a rank of a group refused, the policy checked and staged once per call, the last launch's variants left behind
  * as the last batch.
  * eg_explore_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the field for a start set that is not a valid set of
- * 1..EG_CROSS_MAX_PARENTS plans, NULL options, a mode other than 1 or 2, objectives outside 1..15, cap outside 1..EG_PARETO_MAX,
+ * 1..EG_CROSS_MAX_PARENTS plans, NULL options, a mode other than 1 or 2 (either with EG_PARETO_KEEP_SPREAD OR-ed in or not), objectives outside 1..15, cap outside 1..EG_PARETO_MAX,
  * max_generations < 1, n_replace or n_append < 0, a NULL list with a count, an action above 60, max_shift outside 0..25,
  * launch_variants outside 0..EG_CROSS_MAX_VARIANTS, max_variants < 0.  Nothing is launched after a refusal.
  * eg_explore_neighbourhood (host only, the same checks first): sizes[p] = the neighbourhood size of start plan p. */
@@ -648,7 +667,7 @@ int32_t eg_breed_plans(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts
 #define EG_EXPLORE_MAX_GENERATIONS 1
 #define EG_EXPLORE_EMPTY 2
 #define EG_EXPLORE_BUDGET 3
-typedef struct { int32_t mode /* 1 | 2 */, objectives /* 1..15 */, cap /* 1..EG_PARETO_MAX */, max_generations /* >= 1 */;
+typedef struct { int32_t mode /* 1 | 2, | EG_PARETO_KEEP_SPREAD */, objectives /* 1..15 */, cap /* 1..EG_PARETO_MAX */, max_generations /* >= 1 */;
                  int32_t n_replace; const uint8_t *replace_with; int32_t n_append; const uint8_t *append_with;
                  int32_t max_shift /* 0..25; 0: no moves */, launch_variants;
                  int64_t max_variants /* 0: no budget */; } eg_explore_opts;   /* 64 bytes */
@@ -752,7 +771,7 @@ int32_t eg_debug_refine_pick_many(eg_ctx *, int32_t mode, const uint32_t *seg_fi
  * context's own archive (eg_pareto_track, eg_fetch_pareto) is not touched.  All of them refuse a rank of a group; chunk, turnover and
  * fetch refuse a context on which eg_debug_breed_begin has not succeeded; a refusal launches nothing.
  *   eg_debug_breed_begin     reserves the private archive as eg_breed_plans does and starts it: an empty state with cap (1..EG_PARETO_MAX),
- *                            objectives (1..15) and mode (1 | 2), zero counters, and every byte of the record slots, the block slots, the
+ *                            objectives (1..15) and mode (1 | 2, EG_PARETO_KEEP_SPREAD OR-ed in or not), zero counters, and every byte of the record slots, the block slots, the
  *                            two parent / frontier arrays and the readback buffer EG_DEBUG_BREED_CANARY.
  *   eg_debug_breed_chunk     one chunk of a generation, n variants (1..EG_CROSS_MAX_VARIANTS) numbered first_index ..: eg_debug_load_batch(ctx,
  *                            metrics, status, NULL, NULL, NULL, n, first_index) — the tag n_draws of record j is its number g = first_index

@@ -95,6 +95,8 @@ def main():
     ap.add_argument("--cap", type=count(1, 256, "a population size"), default=256, help="plans a generation keeps at most, 1..256 (default 256)")
     ap.add_argument("--cuts", type=years, default=list(range(2026, 2051)), help="years a child may switch parents at, e.g. 2030,2035 (default: 2026..2050)")
     ap.add_argument("--cost-only", action="store_true", help="score by the cost-only score")
+    ap.add_argument("--keep", choices=("score", "spread"), default="score",
+                    help="what stays when the front outgrows --cap: the best-scoring points, or a spread-out subset (default score)")
     ap.add_argument("--out", required=True, help="output directory")
     a = ap.parse_args()
     from eirgrid_amd import synthetic_world
@@ -107,7 +109,7 @@ def main():
     policy = ActionWeights.load_from_file(a.policy) if a.policy else ActionWeights()
     eng = Engine(world, device=0)
     try:
-        front = eng.breed_front(policy, parents, a.seed, 0, cost_only=a.cost_only, cuts=[y - 2025 for y in a.cuts], generations=a.generations, cap=a.cap)
+        front = eng.breed_front(policy, parents, a.seed, 0, cost_only=a.cost_only, cuts=[y - 2025 for y in a.cuts], generations=a.generations, cap=a.cap, keep=a.keep)
     finally:
         eng.close()
     d = write(a.out, front)

@@ -99,6 +99,8 @@ def main():
     ap.add_argument("--shift", type=count(0, 25, "a number of years"), default=0, help="years an entry may be moved by, 0..25 (default 0: no moves)")
     ap.add_argument("--budget", type=count(0, 2**62, "a number of variants"), default=0, help="variants the run may evaluate at most (default 0: no budget)")
     ap.add_argument("--cost-only", action="store_true", help="score by the cost-only score")
+    ap.add_argument("--keep", choices=("score", "spread"), default="score",
+                    help="what stays when the front outgrows --cap: the best-scoring points, or a spread-out subset (default score)")
     ap.add_argument("--out", required=True, help="output directory")
     a = ap.parse_args()
     from eirgrid_amd import synthetic_world
@@ -112,7 +114,7 @@ def main():
     eng = Engine(world, device=0)
     try:
         front = eng.explore_front(policy, starts, a.seed, 0, cost_only=a.cost_only, generations=a.generations, cap=a.cap, replace_with=a.replace,
-                                  append_with=a.append, max_shift=a.shift, max_variants=a.budget)
+                                  append_with=a.append, max_shift=a.shift, max_variants=a.budget, keep=a.keep)
     finally:
         eng.close()
     d = write(a.out, front)

@@ -33,11 +33,11 @@ def objectives(text):
     return tuple(names)
 
 
-def run(eng, n, batch, seed, cap, names, cost_only):
+def run(eng, n, batch, seed, cap, names, cost_only, keep="score"):
     """The loop: batches of `batch` episodes (the last one shorter) at global indices 0 .. n - 1; returns Engine.fetch_pareto()."""
     from eirgrid_amd.engine import ActionWeights
     eng.push(ActionWeights())
-    eng.track_pareto(cap, names, cost_only=cost_only)
+    eng.track_pareto(cap, names, cost_only=cost_only, keep=keep)
     first = 0
     while first < n:
         k = min(batch, n - first)
@@ -72,6 +72,8 @@ def main():
     ap.add_argument("--objectives", type=objectives, default=tuple(LETTERS.values()),
                     help="comma-separated subset of e,o,c,r: emissions, opinion, cost, reliability (default all four)")
     ap.add_argument("--cost-only", action="store_true", help="rank by the cost-only score when the front outgrows --cap")
+    ap.add_argument("--keep", choices=("score", "spread"), default="score",
+                    help="what stays when the front outgrows --cap: the best-scoring points, or a spread-out subset (default score)")
     ap.add_argument("--out", required=True, help="output directory")
     a = ap.parse_args()
     if a.n < 1 or a.batch < 1 or not 1 <= a.cap <= 256:
@@ -82,7 +84,7 @@ def main():
     world = synthetic_world() if a.world == "synthetic" else World.from_json_dict(json.load(open(a.world)))
     eng = Engine(world, device=0)
     try:
-        rows, index, scores, dropped = run(eng, a.n, a.batch, a.seed, a.cap, a.objectives, a.cost_only)
+        rows, index, scores, dropped = run(eng, a.n, a.batch, a.seed, a.cap, a.objectives, a.cost_only, a.keep)
     finally:
         eng.close()
     d = write(a.out, rows, index, scores)
