@@ -15,8 +15,8 @@
 //                     the OTHER parent array — k_plan_crosses read this generation's parents from the one, so no block is read after it
 //                     has been overwritten, and the population of a generation without a valid variant still stands — and one readback
 //                     row written: the entry (index = variant number, metrics, score, slot) and the block's two prefix-offset tables,
-//                     from which the host enumerates and routes the next generation.  The last workgroup to finish empties the state
-//                     and the counters for the next generation.
+//                     from which the host enumerates and routes the next generation (breed::write_row).  The last workgroup to finish
+//                     (breed::last_to_finish) empties the state and the counters for the next generation.
 // ORDER.  A plan batch runs entirely on the null stream: launch_plans leaves RolloutPlan::stream_heavy null, so both replay variants
 // (and k_replay_solo) are launched there, not on the side stream the training batches fork to.  k_plan_crosses, the replay grids, the
 // five fold kernels, k_breed_gather and the next chunk's k_plan_crosses are therefore one in-order queue: the gather runs after the fold
@@ -28,7 +28,7 @@
 
 namespace breed {
 
-using pedit::kOffOff;
+using pblock::kOffOff;
 constexpr int kVec = (int)(snap::kPlanStride / 16);      // 16-byte words of a plan block
 static_assert(snap::kPlanStride % 16 == 0 && kOffOff % 16 == 0 && kBreedRowBytes == 64 + 2 * 4 * 28 && sizeof(ParetoEntry) == 56, "readback row layout");
 
@@ -36,6 +36,23 @@ __device__ __forceinline__ void copy_block(uint8_t* dst, const uint8_t* src, int
   const uint4* s = reinterpret_cast<const uint4*>(src);
   uint4* d = reinterpret_cast<uint4*>(dst);
   for (int w = lane; w < kVec; w += kWave) d[w] = s[w];
+}
+
+// a readback row: the entry in 8 words of 8 bytes (the last one padding), then the two offset tables of its block, 14 words of 16 bytes
+__device__ __forceinline__ void write_row(uint8_t* row, const ParetoEntry* entry, const uint8_t* src_block, int lane) {
+  if (lane < 8) reinterpret_cast<unsigned long long*>(row)[lane] = lane < 7 ? reinterpret_cast<const unsigned long long*>(entry)[lane] : 0ull;
+  else if (lane < 8 + 14) reinterpret_cast<uint4*>(row + 64)[lane - 8] = reinterpret_cast<const uint4*>(src_block + kOffOff)[lane - 8];
+}
+
+// the tail of a turnover kernel (workgroups of one wave): whether this workgroup is the last to get here.  Then everybody has read the
+// state and the counters (the fence stands between a workgroup's reads and its count), so the caller can empty what the next
+// generation wants empty
+__device__ __forceinline__ bool last_to_finish(BreedCounters* cnt, int lane) {
+  __threadfence();
+  unsigned t = 0u;
+  if (lane == 0) t = atomicAdd(&cnt->done, 1u);
+  t = (unsigned)__shfl((int)t, 0, kWave);
+  return t == gridDim.x - 1u;
 }
 
 }  // namespace breed
@@ -73,23 +90,14 @@ __global__ void __launch_bounds__(kWave) k_breed_turnover(ParetoState* st, const
     const int slot = pareto::clampi(st->e[r].slot, 0, EG_PARETO_MAX - 1);
     const uint8_t* src = blocks + (size_t)slot * snap::kPlanStride;
     breed::copy_block(next_parents + (size_t)r * snap::kPlanStride, src, lane);
-    // the row: the entry in 8 words of 8 bytes (the last one padding), then the two offset tables, 14 words of 16 bytes
-    uint8_t* row = readback + kBreedHeaderBytes + (size_t)r * kBreedRowBytes;
-    if (lane < 8) reinterpret_cast<unsigned long long*>(row)[lane] = lane < 7 ? reinterpret_cast<const unsigned long long*>(&st->e[r])[lane] : 0ull;
-    else if (lane < 8 + 14) reinterpret_cast<uint4*>(row + 64)[lane - 8] = reinterpret_cast<const uint4*>(src + breed::kOffOff)[lane - 8];
+    breed::write_row(readback + kBreedHeaderBytes + (size_t)r * kBreedRowBytes, &st->e[r], src, lane);
   }
   if (r == 0 && lane == 0) {
     BreedHeader h;
     h.n_held = held; h.pad = 0; h.n_dropped = st->n_dropped; h.n_valid = (long long)cnt->n_valid; h.pad2 = 0;
     *reinterpret_cast<BreedHeader*>(readback) = h;
   }
-  // the last workgroup to get here: everybody has read the state and the counters (the fence stands between a workgroup's reads and
-  // its count), so they can be emptied for the next generation
-  __threadfence();
-  unsigned t = 0u;
-  if (lane == 0) t = atomicAdd(&cnt->done, 1u);
-  t = (unsigned)__shfl((int)t, 0, kWave);
-  if (t == gridDim.x - 1u && lane == 0) {
+  if (breed::last_to_finish(cnt, lane) && lane == 0) {      // the state and the counters, for the next generation
     st->n_held = 0; st->n_dropped = 0;
     cnt->n_valid = 0ull; cnt->done = 0u;
   }

@@ -1,7 +1,7 @@
 // eg_explore.h — k_explore_turnover: what turns the members that ENTERED the archive in a generation of a Pareto local search into the
 // next generation's frontier without a trip through the host (include/eirgrid_hip.h eg_explore_plans; the loop is csrc/eg_explore.cpp).
-// Included by eg_rollout.hip (eg_rollout.o only) behind eg_breed.h, whose buffer (eg_internal.h breed_at), k_breed_gather and
-// breed::copy_block it shares.
+// Included by eg_rollout.hip (eg_rollout.o only) behind eg_breed.h, whose buffer (eg_internal.h breed_at), k_breed_gather,
+// breed::copy_block, readback row (breed::write_row) and tail (breed::last_to_finish) it shares.
 //
 // The archive of an exploration lives across generations: a member whose neighbourhood has been evaluated is never enumerated again, so
 // after a generation only the entries that entered in it — index >= m_first, the number of the generation's first neighbour; indices
@@ -42,21 +42,13 @@ __global__ void __launch_bounds__(kWave) k_explore_turnover(const ParetoState* s
     const int slot = pareto::clampi(st->e[r].slot, 0, EG_PARETO_MAX - 1);
     const uint8_t* src = blocks + (size_t)slot * snap::kPlanStride;
     breed::copy_block(next_frontier + (size_t)before * snap::kPlanStride, src, lane);
-    // the row: the entry in 8 words of 8 bytes (the last one padding), then the two offset tables, 14 words of 16 bytes
-    uint8_t* row = readback + kBreedHeaderBytes + (size_t)before * kBreedRowBytes;
-    if (lane < 8) reinterpret_cast<unsigned long long*>(row)[lane] = lane < 7 ? reinterpret_cast<const unsigned long long*>(&st->e[r])[lane] : 0ull;
-    else if (lane < 8 + 14) reinterpret_cast<uint4*>(row + 64)[lane - 8] = reinterpret_cast<const uint4*>(src + breed::kOffOff)[lane - 8];
+    breed::write_row(readback + kBreedHeaderBytes + (size_t)before * kBreedRowBytes, &st->e[r], src, lane);
   }
   if (r == 0 && lane == 0) {
     ExploreHeader h;
     h.n_held = held; h.n_new = n_new; h.n_dropped = st->n_dropped; h.n_valid = (long long)cnt->n_valid; h.pad = 0;
     *reinterpret_cast<ExploreHeader*>(readback) = h;
   }
-  // the last workgroup to get here: everybody has read the counters (the fence stands between a workgroup's reads and its count), so
-  // they can be emptied for the next generation.  The state stays: the archive lives on
-  __threadfence();
-  unsigned t = 0u;
-  if (lane == 0) t = atomicAdd(&cnt->done, 1u);
-  t = (unsigned)__shfl((int)t, 0, kWave);
-  if (t == gridDim.x - 1u && lane == 0) { cnt->n_valid = 0ull; cnt->done = 0u; }
+  // the counters, for the next generation.  The state stays: the archive lives on
+  if (breed::last_to_finish(cnt, lane) && lane == 0) { cnt->n_valid = 0ull; cnt->done = 0u; }
 }

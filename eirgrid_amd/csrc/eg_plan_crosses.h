@@ -1,6 +1,7 @@
 // eg_plan_crosses.h — k_plan_crosses: the plan blocks of a plan-cross batch (include/eirgrid_hip.h eg_evaluate_plan_crosses), written on
 // the device from the parents' blocks and an 8-byte cross per variant, on the stream the plan launches use.  Included by eg_rollout.hip
-// (eg_rollout.o only) behind eg_plan_moves.h.
+// (eg_rollout.o only) behind eg_plan_moves.h; what it shares with the other block writers (layout, the wave's variant, bytes_before, the
+// lane mapping of the offset tables, the mask store) is eg_plan_block.h's.
 //
 // Variant j is parent a with BOTH lists of the years from <= y < to replaced by parent b's lists of those years, and block j must be
 // byte for byte what eg_plans.cpp write_lists builds for that child in a zeroed block.  With oA, oB the parents' prefix offsets of one list:
@@ -19,8 +20,7 @@
 
 namespace pcross {
 
-using namespace pedit;      // the block layout (kOff*, kWords)
-using pmove::bytes_before;
+using namespace pblock;
 
 // what the host packs per variant (eg_plans.cpp pack_plan_cross): a | b << 8 | from_year << 16 | to_year << 24, then zero
 struct Cross { uint32_t a, b; int from, to; };
@@ -61,19 +61,19 @@ __device__ __forceinline__ void write_crossed_list(unsigned long long* dst, cons
 
 }  // namespace pcross
 
-// four variants per workgroup of 256, one wave each
 __global__ void __launch_bounds__(256) k_plan_crosses(const uint8_t* __restrict__ parents, uint32_t n_parents, const uint2* __restrict__ crosses, uint32_t n,
                                                       uint8_t* __restrict__ pool) {
   using namespace pcross;
-  const int lane = threadIdx.x & (kWave - 1);
-  const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (j >= n || n_parents == 0u) return;
-  const Cross x = unpack_cross(crosses[j], n_parents);
+  const Wave w = my_variant();
+  const int lane = w.lane;
+  if (w.j >= n || n_parents == 0u) return;
+  const Cross x = unpack_cross(crosses[w.j], n_parents);
   const uint8_t* pa = parents + (size_t)x.a * snap::kPlanStride;
   const uint8_t* pb = parents + (size_t)x.b * snap::kPlanStride;
-  uint8_t* blk = pool + (size_t)j * snap::kPlanStride;
+  uint8_t* blk = pool + (size_t)w.j * snap::kPlanStride;
   // (a rolled loop, one list's code run twice: with both bodies in one block hipcc 7.2's register allocator crashes under the
-  //  iterative-ilp scheduler this file is built with)
+  //  iterative-ilp scheduler this file is built with.  The parents' parts are addressed by their offsets, not through pblock::view:
+  //  with two views the kernel takes 72 vector registers instead of 65)
 #pragma unroll 1
   for (int which = 0; which < 2; ++which) {
     const int32_t* oA = reinterpret_cast<const int32_t*>(pa + (which ? kOffDOff : kOffOff));
@@ -82,26 +82,18 @@ __global__ void __launch_bounds__(256) k_plan_crosses(const uint8_t* __restrict_
     const int p0 = clamp_len(oA[x.from]), a_to = clamp_len(oA[x.to]), b_from = clamp_len(oB[x.from]);
     const int p1 = clamp_len(p0 + clamp_len(oB[x.to]) - b_from);
     const int end = clamp_len(p1 + clamp_len(oA[EG_YEARS]) - a_to);
-    write_crossed_list(reinterpret_cast<unsigned long long*>(blk + (which ? kOffDAct : kOffAct)),
-                       reinterpret_cast<const unsigned long long*>(pa + (which ? kOffDAct : kOffAct)),
-                       reinterpret_cast<const unsigned long long*>(pb + (which ? kOffDAct : kOffAct)), lane, p0, p1, end, b_from - p0, a_to - p1);
+    write_crossed_list(words(blk + (which ? kOffDAct : kOffAct)), words(pa + (which ? kOffDAct : kOffAct)), words(pb + (which ? kOffDAct : kOffAct)), lane,
+                       p0, p1, end, b_from - p0, a_to - p1);
   }
-  // prefix offsets: lanes 0..27 the first list's, 32..59 the second's (entry 27 is padding: parent a's zero)
-  {
-    const int l = lane & 31, which = lane >> 5;
-    if (l < 28) {
-      const int32_t* oA = reinterpret_cast<const int32_t*>(pa + (which ? kOffDOff : kOffOff));
-      const int32_t* oB = reinterpret_cast<const int32_t*>(pb + (which ? kOffDOff : kOffOff));
-      uint32_t v = (uint32_t)oA[l];      // (unsigned: whatever the blocks hold, the sums wrap)
-      if (l > x.from && l <= x.to) v = (uint32_t)oA[x.from] + (uint32_t)oB[l] - (uint32_t)oB[x.from];
-      else if (l > x.to && l <= EG_YEARS) v += ((uint32_t)oB[x.to] - (uint32_t)oB[x.from]) - ((uint32_t)oA[x.to] - (uint32_t)oA[x.from]);
-      reinterpret_cast<int32_t*>(blk + (which ? kOffDOff : kOffOff))[l] = (int32_t)v;
-    }
-  }
+  // prefix offsets: the formula above over the two parents' tables (entry 27 is padding: parent a's zero)
+  write_offset_entries(blk, lane, [=](int which, int l) {
+    const int32_t* oA = reinterpret_cast<const int32_t*>(pa + (which ? kOffDOff : kOffOff));
+    const int32_t* oB = reinterpret_cast<const int32_t*>(pb + (which ? kOffDOff : kOffOff));
+    uint32_t v = (uint32_t)oA[l];      // (unsigned: whatever the blocks hold, the sums wrap)
+    if (l > x.from && l <= x.to) v = (uint32_t)oA[x.from] + (uint32_t)oB[l] - (uint32_t)oB[x.from];
+    else if (l > x.to && l <= EG_YEARS) v += ((uint32_t)oB[x.to] - (uint32_t)oB[x.from]) - ((uint32_t)oA[x.to] - (uint32_t)oA[x.from]);
+    return (int32_t)v;
+  });
   // masks: year y's two are those of the parent its lists come from
-  if (lane < EG_YEARS) {
-    const uint8_t* p = (lane >= x.from && lane < x.to) ? pb : pa;
-    reinterpret_cast<unsigned long long*>(blk + kOffMask)[lane] = reinterpret_cast<const unsigned long long*>(p + kOffMask)[lane];
-    reinterpret_cast<unsigned long long*>(blk + kOffDMask)[lane] = reinterpret_cast<const unsigned long long*>(p + kOffDMask)[lane];
-  }
+  write_masks(blk, view((lane >= x.from && lane < x.to) ? pb : pa), lane, false, {0ull, 0ull});
 }

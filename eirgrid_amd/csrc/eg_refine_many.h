@@ -6,8 +6,8 @@
 // block is block slot_s of a buffer of base blocks (one per plan of the call, uploaded once).
 //   k_plan_edits_many   variant j's block from base block slot[j] and edit j: byte for byte what write_lists builds for the edited plan
 //                       in a zeroed block; one wave per variant, 8-byte words, every store of a wave 512 consecutive bytes; no LDS, no
-//                       scratch memory; writes inside block j only.  It is eg_plan_edits.h's k_plan_edits with the slot indirection and
-//                       two more clamps, and shares only __forceinline__ helpers with it: that kernel's code is pinned.
+//                       scratch memory; writes inside block j only.  It is eg_plan_edits.h's write_edited_block, the body of k_plan_edits,
+//                       with the slot indirection (eg_plan_block.h base_at) and the two start clamps that body's flag switches on.
 //   k_refine_pick_many  one workgroup per segment, on the null stream behind the launch's rollout grids.  Workgroup s
 //     reads    status and metrics of ITS variants straight from the records (32 + 4 bytes of each 12 KB record), a thread a variant,
 //              striding by the workgroup's width when there are more variants than threads — the trip count is the same for every
@@ -37,60 +37,11 @@ static_assert(sizeof(Segment) == 16, "segment table entry");
 
 namespace many {
 
-// four variants per workgroup of 256, one wave each
 __global__ void __launch_bounds__(256) k_plan_edits_many(const uint8_t* __restrict__ bases, uint32_t n_bases, const uint32_t* __restrict__ slot,
                                                          const uint2* __restrict__ edits, uint32_t n, uint8_t* __restrict__ pool) {
-  using namespace pedit;
-  const int lane = threadIdx.x & (kWave - 1);
-  const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6);
-  if (j >= n || n_bases == 0u) return;
-  const uint32_t sl = slot[j];
-  const uint8_t* base = bases + (size_t)(sl < n_bases ? sl : n_bases - 1u) * snap::kPlanStride;
-  const Edit e = unpack(edits[j]);
-  uint8_t* blk = pool + (size_t)j * snap::kPlanStride;
-  const int32_t* off = reinterpret_cast<const int32_t*>(base + kOffOff);
-  const int32_t* doff = reinterpret_cast<const int32_t*>(base + kOffDOff);
-  const uint8_t* act = base + kOffAct;
-  const uint8_t* dact = base + kOffDAct;
-  // the edit point in the flat list, and what the edit does to the length of the list
-  int P = (e.list ? doff : off)[e.year] + e.pos;
-  P = P < 0 ? 0 : (P > (int)snap::kBestCap - 1 ? (int)snap::kBestCap - 1 : P);
-  const int delta = e.kind == kInsert ? 1 : (e.kind == kDelete ? -1 : 0);
-  const int k0 = e.list == 0 ? e.kind : kNone, k1 = e.list == 1 ? e.kind : kNone;
-  write_list(reinterpret_cast<unsigned long long*>(blk + kOffAct), reinterpret_cast<const unsigned long long*>(act), lane, k0, P, e.action);
-  write_list(reinterpret_cast<unsigned long long*>(blk + kOffDAct), reinterpret_cast<const unsigned long long*>(dact), lane, k1, P, e.action);
-  // prefix offsets: lanes 0..27 the first list's, 32..59 the second's (entry 27 is padding)
-  {
-    const int l = lane & 31, which = lane >> 5;
-    if (l < 28) {
-      int v = (which ? doff : off)[l];
-      if (which == e.list && l > e.year && l <= EG_YEARS) v += delta;
-      reinterpret_cast<int32_t*>(blk + (which ? kOffDOff : kOffOff))[l] = v;
-    }
-  }
-  // masks: the edited year's from its two lists as edited, the others copied
-  unsigned long long m = 0ull, dm = 0ull;
-  if (e.kind != kNone) {
-    int a0 = off[e.year], d0 = doff[e.year];
-    const int a1 = off[e.year + 1] + (e.list == 0 ? delta : 0), d1 = doff[e.year + 1] + (e.list == 1 ? delta : 0);
-    a0 = a0 < 0 ? 0 : a0; d0 = d0 < 0 ? 0 : d0;
-    for (int i = a0 + lane; i < a1 && i < (int)snap::kBestCap; i += kWave) {
-      const int a = edited_entry(act, i, k0, P, e.action);
-      if (a < 64) m |= 1ull << a;
-    }
-    for (int i = d0 + lane; i < d1 && i < (int)snap::kBestCap; i += kWave) {
-      const int a = edited_entry(dact, i, k1, P, e.action);
-      if (a < 64) dm |= 1ull << a;
-    }
-    m = wave_or_u64(m | dm); dm = wave_or_u64(dm);
-  }
-  if (lane < EG_YEARS) {
-    const unsigned long long* bm = reinterpret_cast<const unsigned long long*>(base + kOffMask);
-    const unsigned long long* bdm = reinterpret_cast<const unsigned long long*>(base + kOffDMask);
-    const bool mine = e.kind != kNone && lane == e.year;
-    reinterpret_cast<unsigned long long*>(blk + kOffMask)[lane] = mine ? m : bm[lane];
-    reinterpret_cast<unsigned long long*>(blk + kOffDMask)[lane] = mine ? dm : bdm[lane];
-  }
+  const pblock::Wave w = pblock::my_variant();
+  if (w.j >= n || n_bases == 0u) return;
+  pedit::write_edited_block<true>(pblock::base_at(bases, n_bases, slot[w.j]), pedit::unpack(edits[w.j]), pool + (size_t)w.j * snap::kPlanStride, w.lane);
 }
 
 // workgroup s: segment s of the launch's n_total variants
@@ -156,8 +107,8 @@ __global__ void __launch_bounds__(1024) k_refine_pick_many(DevOut O, const refin
     entry->score = base_ok ? best : 0.0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) entry->metrics[k] = m[k];
-    entry->off26 = reinterpret_cast<const int32_t*>(blk + pedit::kOffOff)[EG_YEARS];
-    entry->offd26 = reinterpret_cast<const int32_t*>(blk + pedit::kOffDOff)[EG_YEARS];
+    entry->off26 = reinterpret_cast<const int32_t*>(blk + pblock::kOffOff)[EG_YEARS];
+    entry->offd26 = reinterpret_cast<const int32_t*>(blk + pblock::kOffDOff)[EG_YEARS];
     entry->n = (int32_t)n;
   }
   if (winner > 0 && tid < (int)(snap::kPlanStride / 16)) reinterpret_cast<uint4*>(base)[tid] = reinterpret_cast<const uint4*>(blk)[tid];

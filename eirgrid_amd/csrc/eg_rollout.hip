@@ -2610,6 +2610,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_replay_coop.h"      // k_replay_coop, k_replay_broadcast: the replay episodes of a batch, computed once
 #include "eg_topk.h"             // k_topk_keys, k_topk_select, k_topk_merge: the top-K archive of distinct scenarios
 #include "eg_pareto.h"           // k_pareto_filter .. k_pareto_finalize: the Pareto archive of a run's outcomes
+#include "eg_plan_block.h"       // pblock: the plan-block layout and what the four kernels that write plan blocks share
 #include "eg_plan_edits.h"       // k_plan_edits: the plan blocks of a plan-edit batch from one base block and an edit per variant
 #include "eg_refine.h"           // refine::before, wave_best: what the pick of a refinement round reduces with
 #include "eg_refine_many.h"      // k_plan_edits_many, k_refine_pick_many: a refinement round, a segment of the launch's variants per plan

@@ -4,9 +4,10 @@ scratch memory or LDS, may not spill, and stay small.  They live in eg_rollout.o
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+from tests.kernel_resources import kernel_resource_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
@@ -14,7 +15,7 @@ pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.ex
 
 @pytest.fixture(scope="module")
 def lines():
-    return subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout.splitlines()
+    return list(kernel_resource_lines())
 
 
 @pytest.mark.parametrize("kernel", ["k_breed_gather", "k_breed_turnover"])

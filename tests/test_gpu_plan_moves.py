@@ -5,6 +5,7 @@ moved plans, the records must be those of the host-built plans, and for the shor
 import numpy as np
 import pytest
 
+from eirgrid_amd import _native as N
 from eirgrid_amd._native import EirgridError
 from eirgrid_amd.engine import ActionWeights, HostTables, Plan, PlanMove, rank_score, refine_moves
 from oracle import api as O
@@ -13,6 +14,7 @@ from tests.test_gpu_plan_edits import _junk_plan, _long_policy
 from tests.test_gpu_plans import _engine, _oracle_plan, _same_records
 from tests.test_gpu_replay_hoist import _seeded
 from tests.test_plan_moves import apply_move, round_moves
+from tests.test_refine import round_edits
 
 pytestmark = pytest.mark.gpu
 
@@ -184,6 +186,34 @@ def test_blocks_of_full_lists_long_years_and_the_masks(world, engine):
     moves = [PlanMove(0, 7, 130, 8, 0), PlanMove(0, 7, 130, 6, 0), PlanMove(0, 8, 1, 7, 199), PlanMove(0, 8, 0, 7, 200), PlanMove(0, 7, 0, 7, 199), PlanMove(0, 7, 130, 7, 0),
              PlanMove(1, 7, 70, 9, 1), PlanMove(1, 7, 70, 25, 0), PlanMove(1, 9, 0, 7, 76), PlanMove(1, 7, 75, 7, 0)]
     _check_blocks(engine, pol, wide, moves, "years longer than a wave")
+
+
+def test_blocks_through_a_slot_table_with_two_bases(world, engine):
+    """k_plan_moves behind a slot table: one refinement round with moves over two plans in ONE launch (eg_refine_plans_moves; the round's
+    variants stay behind as the last batch), a segment of edits then moves per plan.  Every move variant's block must be write_lists'
+    block for the move applied to the base of ITS segment, all 8 832 bytes: a kernel that took base 0 for every variant, or the other
+    segment's, would write the other plan's lists.  The moves land in another year of the moved list, up to two years away, at the two
+    ends of the 26 years; an action leaves a year that holds it once, twice, and in the deficit list as well."""
+    pol = ActionWeights()
+    run = [[] for _ in range(26)]; dfc = [[] for _ in range(26)]
+    run[0] = [0, 13]; run[3] = [36]; run[25] = [21]; dfc[3] = [36, 24]; dfc[12] = [24]
+    a = Plan(run, dfc)
+    run = [[] for _ in range(26)]; dfc = [[] for _ in range(26)]
+    run[1] = [12, 12, 4]; run[24] = [7]; run[25] = [7, 2]; dfc[0] = [21]; dfc[24] = [7]
+    b = Plan(run, dfc)
+    plans = [a, b]
+    engine.refine_plans(pol, plans, 7, 0, 1, 1, max_shift=2)
+    picks, first = [], 0
+    for plan in plans:
+        n_edits, moves = len(round_edits(plan)), round_moves(plan, 2)
+        picks += [(first + n_edits + k, apply_move(plan, m), m) for k, m in enumerate(moves)]
+        first += n_edits + len(moves)
+    assert N.lib().eg_last_batch_size(engine.h) == first == 18 + 25 and len(picks) == 10 + 16
+    dev = [engine.debug_fetch_plan_block(j).copy() for j, _, _ in picks]
+    engine.evaluate_plans(pol, [moved for _, moved, _ in picks], 7, 0)
+    for k, ((j, _, m), d) in enumerate(zip(picks, dev)):
+        host = engine.debug_fetch_plan_block(k)
+        assert d.tobytes() == host.tobytes(), (j, m, np.flatnonzero(d != host)[:8])
 
 
 # ---------------------------------------------------------------- the records

@@ -8,16 +8,17 @@ registers of four waves per SIMD, which rests on the register budget its field c
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+from tests.kernel_resources import kernel_resource_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_throughput_kernels_keep_their_register_and_scratch_budget():
-    out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout
+    out = "\n".join(kernel_resource_lines())
     rows = {}
     for line in out.splitlines():
         m = re.match(r"k_rolloutILi(\d)ELi(\d)E.*?VGPRs: (\d+) ScratchSize \[bytes/lane\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", line)

@@ -6,16 +6,17 @@ holds k_replay_solo to: no scratch memory, at most 128 vector registers, no more
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+from tests.kernel_resources import kernel_resource_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_replay_lazy_keeps_four_waves_per_simd_and_no_scratch():
-    out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout
+    out = "\n".join(kernel_resource_lines())
     lazy = [re.search(r"VGPRs: (\d+) .*?ScratchSize \[bytes/lane\]: (\d+).*?LDS Size \[bytes/block\]: (\d+)", line)
             for line in out.splitlines() if re.search(r"\bk_replay_lazy\b", line)]
     long_replay = [re.search(r"LDS Size \[bytes/block\]: (\d+)", line) for line in out.splitlines() if line.startswith("k_rolloutILi0ELi2E")]

@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+from tests.kernel_resources import kernel_resource_lines
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SCRIPT = os.path.join(ROOT, "scripts", "pareto_front.py")
 KERNELS = ("k_pareto_filter", "k_pareto_compact", "k_pareto_dominate", "k_pareto_rank", "k_pareto_finalize")
@@ -101,7 +103,7 @@ def test_library_exports_the_pareto_symbols(built):
 def test_pareto_kernels_compile_without_scratch():
     """The five kernels exist for gfx950 in exactly one of eg_rollout.hip's two objects, spill nothing, need no scratch and at most
     64 KB of LDS."""
-    out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout
+    out = "\n".join(kernel_resource_lines())
     for name in KERNELS:
         lines = [l for l in out.splitlines() if re.search(rf"remark: {name}(\b|E)", l)]
         assert len(lines) == 1, (name, lines)

@@ -13,6 +13,8 @@ import pytest
 
 from tests.test_pareto import Front, front, oriented, valid
 
+from tests.kernel_resources import kernel_resource_lines
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEEP_SPREAD = 0x100
 
@@ -112,7 +114,7 @@ def test_the_constant(built):
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_spread_kernel_compiles_without_scratch():
-    out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout
+    out = "\n".join(kernel_resource_lines())
     lines = [l for l in out.splitlines() if re.search(r"remark: k_pareto_spread(\b|E)", l)]
     assert len(lines) == 1, lines
     m = re.search(r"ScratchSize \[bytes/lane\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+).*?LDS Size \[bytes/block\]: (\d+)", lines[0])

@@ -5,16 +5,17 @@ written once — it must not touch scratch memory or spill a register on the way
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+from tests.kernel_resources import kernel_resource_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_plan_edits_kernel_uses_no_scratch_and_spills_nothing():
-    out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout
+    out = "\n".join(kernel_resource_lines())
     rows = [line for line in out.splitlines() if re.search(r"\bk_plan_edits", line)]
     assert len(rows) == 1, out      # (eg_rollout.o only: the throughput object does not carry it)
     m = re.search(r"VGPRs: (\d+) .*?ScratchSize \[bytes/lane\]: (\d+).*?SGPRs Spill: (\d+).*?VGPRs Spill: (\d+).*?LDS Size \[bytes/block\]: (\d+)", rows[0])

@@ -5,16 +5,17 @@ test_refine_many_resources.py, test_solo_kernel_resources.py and test_kernel_res
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+from tests.kernel_resources import kernel_resource_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 
 
 def test_the_kernel_uses_no_scratch_no_lds_and_few_registers():
-    out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout
+    out = "\n".join(kernel_resource_lines())
     lines = out.splitlines()
     rows = [line for line in lines if "k_plan_moves" in line]
     assert len(rows) == 1, rows      # (eg_rollout.o only: the throughput object does not carry it)

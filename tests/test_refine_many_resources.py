@@ -5,9 +5,10 @@ tests/test_refine_resources.py, test_plan_edit_resources.py, test_solo_kernel_re
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
+
+from tests.kernel_resources import kernel_resource_lines
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
@@ -20,7 +21,7 @@ def _plain(line):
 
 @pytest.fixture(scope="module")
 def resources():
-    out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout
+    out = "\n".join(kernel_resource_lines())
     return [_plain(line) for line in out.splitlines()]
 
 

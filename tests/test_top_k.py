@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.kernel_resources import kernel_resource_lines
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CLI = os.path.join(ROOT, "eirgrid_amd", "eirgrid-hip")
 WORLD = os.path.join(ROOT, "tests", "golden", "world_v1.json")
@@ -81,7 +83,7 @@ def test_rank_score_cost_only_follows_scoring_rs(built):
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_top_k_kernels_compile_without_scratch():
     """The three kernels exist for gfx950 in exactly one of eg_rollout.hip's two objects, spill nothing and need no scratch."""
-    out = subprocess.run(["bash", os.path.join(ROOT, "scripts", "kernel_resources.sh")], capture_output=True, text=True, timeout=900).stdout
+    out = "\n".join(kernel_resource_lines())
     for name in ("k_topk_keys", "k_topk_select", "k_topk_merge"):
         lines = [l for l in out.splitlines() if re.search(rf"remark: {name}(\b|E)", l)]
         assert len(lines) == 1, (name, lines)
