@@ -105,6 +105,14 @@ class EgBreedGeneration(C.Structure):
                 ("n_variants", C.c_int64), ("n_valid", C.c_int64), ("n_dropped", C.c_int64)]
 
 
+class EgActionMap(C.Structure):
+    _fields_ = [("to", C.c_uint8 * N_ACTIONS)]
+
+
+class EgPlanRewrite(C.Structure):
+    _fields_ = [("plan", C.c_uint16), ("map", C.c_uint16), ("from_year", C.c_uint8), ("to_year", C.c_uint8), ("lists", C.c_uint8), ("pad", C.c_uint8)]
+
+
 class EgBreedMember(C.Structure):
     _fields_ = [("cross", EgPlanCross), ("variant", C.c_int32), ("score", C.c_double), ("metrics", C.c_double * 4)]
 
@@ -126,6 +134,7 @@ class EgExploreMember(C.Structure):
 
 
 assert C.sizeof(EgPlanMove) == 12 and C.sizeof(EgPlanCross) == 6
+assert C.sizeof(EgActionMap) == 61 and C.sizeof(EgPlanRewrite) == 8
 assert C.sizeof(EgExploreOpts) == 64 and C.sizeof(EgExploreGeneration) == 40 and C.sizeof(EgExploreMember) == 88
 assert C.sizeof(EgBreedOpts) == 40 and C.sizeof(EgBreedGeneration) == 40 and C.sizeof(EgBreedMember) == 56
 
@@ -135,6 +144,9 @@ REFINE_MAX_VARIANTS = 16384      # EG_REFINE_MAX_VARIANTS
 REFINE_MAX_PLANS = 256           # EG_REFINE_MAX_PLANS
 CROSS_MAX_PARENTS = 256          # EG_CROSS_MAX_PARENTS
 CROSS_MAX_VARIANTS = 16384       # EG_CROSS_MAX_VARIANTS
+REWRITE_DROP = 0xFF              # EG_REWRITE_DROP
+REWRITE_MAX_MAPS = 256           # EG_REWRITE_MAX_MAPS
+REWRITE_MAX_VARIANTS = 16384     # EG_REWRITE_MAX_VARIANTS
 BREED_CONVERGED, BREED_MAX_GENERATIONS, BREED_EMPTY = 0, 1, 2      # EG_BREED_*
 EXPLORE_EXPLORED, EXPLORE_MAX_GENERATIONS, EXPLORE_EMPTY, EXPLORE_BUDGET = 0, 1, 2, 3      # EG_EXPLORE_*
 PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
@@ -177,7 +189,7 @@ EXPORTS = [
     "eg_refine_plans_validate", "eg_refine_plans", "eg_debug_refine_pick_many",
     "eg_debug_breed_begin", "eg_debug_breed_chunk", "eg_debug_breed_turnover", "eg_debug_breed_fetch",
     "eg_plan_moves_validate", "eg_evaluate_plan_moves", "eg_refine_plans_moves_validate", "eg_refine_plans_moves",
-    "eg_plan_crosses_validate", "eg_evaluate_plan_crosses",
+    "eg_plan_crosses_validate", "eg_evaluate_plan_crosses", "eg_plan_rewrites_validate", "eg_evaluate_plan_rewrites",
     "eg_breed_validate", "eg_breed_plans", "eg_explore_validate", "eg_explore_neighbourhood", "eg_explore_plans",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
@@ -370,6 +382,13 @@ def lib():
         L.eg_evaluate_plan_crosses.restype = C.c_int32
         L.eg_evaluate_plan_crosses.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgPlanCross),
                                                C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(EgEpisodeOut)]
+    # (likewise: scripts/rewrite_probe.py may load a build of the parent commit, which has no plan rewrites)
+    if hasattr(L, "eg_evaluate_plan_rewrites") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_plan_rewrites_validate.restype = C.c_int32
+        L.eg_plan_rewrites_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgActionMap), C.c_int32, C.POINTER(EgPlanRewrite), C.c_int32]
+        L.eg_evaluate_plan_rewrites.restype = C.c_int32
+        L.eg_evaluate_plan_rewrites.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgActionMap), C.c_int32,
+                                                C.POINTER(EgPlanRewrite), C.c_int32, C.c_uint64, C.c_uint64, C.c_int32, C.POINTER(EgEpisodeOut)]
     # (likewise: scripts/breed_probe.py may load a build of the parent commit, which crosses one generation a call)
     if hasattr(L, "eg_breed_plans") or not os.environ.get("EIRGRID_LIB"):
         L.eg_breed_validate.restype = C.c_int32

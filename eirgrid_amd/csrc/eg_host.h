@@ -138,7 +138,8 @@ struct eg_ctx {
   eg::DevBuf<uint8_t> d_eval_snap, d_plans;
   eg::DevBuf<uint32_t> d_plan_index;
   // plan-edit batches (eg_evaluate_plan_edits): the base plan's block followed by the packed edits, 8 bytes each — what k_plan_edits reads
-  // (a plan-cross batch, eg_evaluate_plan_crosses: every parent's block, then the packed crosses — what k_plan_crosses reads)
+  // (a plan-cross batch, eg_evaluate_plan_crosses: every parent's block, then the packed crosses — what k_plan_crosses reads; a plan-rewrite
+  //  batch, eg_evaluate_plan_rewrites: every plan's block, the maps, then the packed rewrites — what k_plan_rewrites reads)
   eg::DevBuf<uint8_t> d_plan_edit_in;
   size_t n_plan_blocks = 0;      // blocks of the last plan or plan-edit batch in d_plans (eg_debug_fetch_plan_block)
   // plan refinement (eg_refine_plan, eg_refine_plans): the step log k_refine_pick_many writes, an entry per plan of a launch from the
@@ -174,9 +175,10 @@ DevSnapshot snapshot_of(uint8_t* d_base, const eg_opts* o);
 void write_lists(uint8_t* dst, const int32_t* count, const uint8_t* act, const int32_t* dcount, const uint8_t* dact);
 int stage_eval_snapshot(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, DevSnapshot* S);
 int launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index);
-// ... a move's 8 bytes (eg_plan_moves.h unpack_move) and a cross's (eg_plan_crosses.h unpack_cross)
+// ... a move's 8 bytes (eg_plan_moves.h unpack_move), a cross's (eg_plan_crosses.h unpack_cross) and a rewrite's (eg_plan_rewrites.h unpack_rewrite)
 void pack_plan_move(const eg_plan_move& m, uint32_t* packed);
 void pack_plan_cross(const eg_plan_cross& x, uint32_t* packed);
+void pack_plan_rewrite(const eg_plan_rewrite& r, uint32_t* packed);
 // ... the prefix offsets of every plan of a set (off[w][p * 27 + y]) and a child's list length from them
 void parent_offsets(const eg_plan_set* p, std::vector<int32_t> off[2]);
 int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x);
@@ -184,7 +186,7 @@ int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x);
 void write_plan_blocks(const eg_plan_set* p, uint8_t* dst);
 int decode_plan_blocks(const uint8_t* blocks, int32_t n, const char* who, eg_plan_set** set);
 
-// eg_plan_host.cpp: the pieces a plan search is written from (DESIGN.md 2.18).  `fn` / `who` name the entry point in the messages.
+// eg_plan_host.cpp: the pieces a plan search is written from (DESIGN.md 2.19).  `fn` / `who` name the entry point in the messages.
 // Behind an entry point's own NULL test: a rank of a group is refused, then `validate` runs, then check_policy, then hipSetDevice
 int plan_entry(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const char* fn, const std::function<int32_t()>& validate);
 // The routing of a launch (launch_plans): the variants whose best_actions list is short (<= kShortReplayMax entries) first, then the long

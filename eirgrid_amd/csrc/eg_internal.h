@@ -527,6 +527,12 @@ int launch_plan_moves(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* 
 // n packed crosses (8 bytes each: a | b << 8 | from_year << 16 | to_year << 24, then zero): parent a with the years [from_year, to_year)
 // of both lists taken from parent b
 int launch_plan_crosses(const uint8_t* d_parents, uint32_t n_parents, const void* d_crosses, uint32_t n, uint8_t* d_pool, void* stream);
+// k_plan_rewrites (eg_plan_rewrites.h): the n plan blocks of a plan-rewrite batch into d_pool from the n_plans plan blocks at d_plans, the
+// n_maps action maps at d_maps (kRewriteMapStride bytes each: to[0..60], then drop bytes) and n packed rewrites (8 bytes each: plan |
+// map << 16, then from_year | to_year << 8 | lists << 16): the plan with the map applied to the years [from_year, to_year) of the lists
+constexpr size_t kRewriteMapStride = 64;
+int launch_plan_rewrites(const uint8_t* d_plans, uint32_t n_plans, const uint8_t* d_maps, uint32_t n_maps, const void* d_rewrites, uint32_t n, uint8_t* d_pool,
+                         void* stream);
 // Generations of crosses (include/eirgrid_hip.h eg_breed_plans; eg_breed.h, eg_breed.cpp).  The private archive of a call, one buffer
 // kept with the context: a ParetoState and EG_PARETO_MAX record slots exactly as eg_pareto_track lays them out (so launch_pareto_fold
 // folds into it), a plan BLOCK slot per record slot, two parent arrays of EG_PARETO_MAX blocks (this generation's, the next one's), the

@@ -1,12 +1,13 @@
 // eg_plan_block.h — what the kernels that write plan blocks share: k_plan_edits (eg_plan_edits.h), k_plan_edits_many (eg_refine_many.h),
-// k_plan_moves (eg_plan_moves.h) and k_plan_crosses (eg_plan_crosses.h).  Included by eg_rollout.hip (eg_rollout.o only) behind
+// k_plan_moves (eg_plan_moves.h), k_plan_crosses (eg_plan_crosses.h) and k_plan_rewrites (eg_plan_rewrites.h).  Included by eg_rollout.hip (eg_rollout.o only) behind
 // eg_pareto.h, ahead of eg_plan_edits.h.
 //
 // A plan block is what eg_plans.cpp write_lists builds in a zeroed block of snap::kPlanStride bytes: the masks of the 26 years (a plan
 // list's and the deficit list's), the prefix offsets of the two lists (28 entries each, entry 27 padding), the two flat lists, zeros
 // behind their ends.  A writer runs one wave per variant, four variants per workgroup of 256, and makes block j of the pool from a base
 // block and 8 bytes that say what changes.  Its own header holds what is different: how the 8 bytes unpack and how a changed flat list
-// is written (write_list, write_moved_list, write_crossed_list).  The rest is here:
+// is written (write_list, write_moved_list, write_crossed_list, write_window).  The rest is here:
+//   shifts    bytes_at, 8 bytes of a flat list from any byte on, funnel-shifted from two aligned words (crosses, rewrites);
 //   indexing  the wave's variant and lane; a variant's base block through a slot table, the slot clamped;
 //   offsets   lanes 0..27 write the first list's table, 32..59 the second's: write_offset_entries, a lane an entry the caller
 //             computes (crosses); write_offsets, a base's entries with the starts of a range of years of one list moved (edits: all
@@ -58,6 +59,17 @@ __device__ __forceinline__ int clamp_flat(int i) { return i < 0 ? 0 : (i > (int)
 __device__ __forceinline__ unsigned long long bytes_before(int k, int w) {
   const int b = k - 8 * w;
   return b >= 8 ? ~0ull : (b <= 0 ? 0ull : (1ull << (8 * b)) - 1ull);
+}
+
+// a list length, into 0..kBestCap
+__device__ __forceinline__ int clamp_len(int v) { return v < 0 ? 0 : (v > (int)snap::kBestCap ? (int)snap::kBestCap : v); }
+
+// the 8 bytes of the flat list `src` from byte q on (q of either sign; bytes outside the list are zero); need == false: not loaded
+__device__ __forceinline__ unsigned long long bytes_at(const unsigned long long* src, int q, bool need) {
+  const int k = q >> 3, r = (q & 7) * 8;      // (an arithmetic shift: the word below a negative q)
+  const unsigned long long lo = (need && k >= 0 && k < kWords) ? src[k] : 0ull;
+  const unsigned long long hi = (need && r != 0 && k + 1 >= 0 && k + 1 < kWords) ? src[k + 1] : 0ull;
+  return r == 0 ? lo : (lo >> r) | (hi << (64 - r));
 }
 
 // prefix offsets: lanes 0..27 the first list's, 32..59 the second's (entry 27 is padding); entry(which, l) is the lane's

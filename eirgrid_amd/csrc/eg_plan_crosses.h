@@ -1,7 +1,7 @@
 // eg_plan_crosses.h — k_plan_crosses: the plan blocks of a plan-cross batch (include/eirgrid_hip.h eg_evaluate_plan_crosses), written on
 // the device from the parents' blocks and an 8-byte cross per variant, on the stream the plan launches use.  Included by eg_rollout.hip
-// (eg_rollout.o only) behind eg_plan_moves.h; what it shares with the other block writers (layout, the wave's variant, bytes_before, the
-// lane mapping of the offset tables, the mask store) is eg_plan_block.h's.
+// (eg_rollout.o only) behind eg_plan_moves.h; what it shares with the other block writers (layout, the wave's variant, bytes_before, bytes_at,
+// clamp_len, the lane mapping of the offset tables, the mask store) is eg_plan_block.h's.
 //
 // Variant j is parent a with BOTH lists of the years from <= y < to replaced by parent b's lists of those years, and block j must be
 // byte for byte what eg_plans.cpp write_lists builds for that child in a zeroed block.  With oA, oB the parents' prefix offsets of one list:
@@ -32,15 +32,6 @@ __device__ __forceinline__ Cross unpack_cross(uint2 w, uint32_t n_parents) {
   if (x.to > EG_YEARS) x.to = EG_YEARS;
   if (x.from > x.to) x.from = x.to;
   return x;
-}
-__device__ __forceinline__ int clamp_len(int v) { return v < 0 ? 0 : (v > (int)snap::kBestCap ? (int)snap::kBestCap : v); }
-
-// the 8 bytes of the flat list `src` from byte q on (q of either sign; bytes outside the list are zero); need == false: not loaded
-__device__ __forceinline__ unsigned long long bytes_at(const unsigned long long* src, int q, bool need) {
-  const int k = q >> 3, r = (q & 7) * 8;      // (an arithmetic shift: the word below a negative q)
-  const unsigned long long lo = (need && k >= 0 && k < kWords) ? src[k] : 0ull;
-  const unsigned long long hi = (need && r != 0 && k + 1 >= 0 && k + 1 < kWords) ? src[k + 1] : 0ull;
-  return r == 0 ? lo : (lo >> r) | (hi << (64 - r));
 }
 
 // one flat list of the child: head [0, p0) of A in place, middle [p0, p1) from B's byte p0 + sB on, tail [p1, end) from A's byte

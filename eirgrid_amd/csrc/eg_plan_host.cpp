@@ -1,4 +1,4 @@
-// eg_plan_host.cpp — the pieces a plan search is written from (eg_host.h lists them; DESIGN.md 2.18): the entry preamble, a launch's
+// eg_plan_host.cpp — the pieces a plan search is written from (eg_host.h lists them; DESIGN.md 2.19): the entry preamble, a launch's
 // packing and routing, the launch of a chunk of variants, the private archive of eg_breed_plans / eg_explore_plans and the option checks
 // the validators share.  Each exists once: eg_plans / eg_refine / eg_breed / eg_explore / eg_debug .cpp call them.
 #include <algorithm>

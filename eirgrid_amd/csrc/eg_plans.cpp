@@ -1,8 +1,9 @@
 // eg_plans.cpp — a policy in snapshot layout (shared with eg_upload_snapshot) and plan batches: eg_evaluate_plans, eg_evaluate_plan_edits,
-// eg_evaluate_plan_moves, eg_evaluate_plan_crosses over one tail (evaluate_batch), launch_plans, and plan sets to blocks and back (the
+// eg_evaluate_plan_moves, eg_evaluate_plan_crosses, eg_evaluate_plan_rewrites over one tail (evaluate_batch), launch_plans, and plan sets to blocks and back (the
 // searches are written from these and eg_plan_host.cpp's pieces).
 #include <algorithm>
 #include <cstring>
+#include <unordered_map>
 
 #include "eg_host.h"
 #define EG_RM static inline
@@ -120,14 +121,15 @@ int eg::stage_eval_snapshot(eg_ctx* c, const eg_policy_snapshot* s, const eg_opt
 }
 namespace {
 // The rest of a plan batch of the n variants `idx` routes, the n_short short ones first.  `in` goes up: the plan blocks themselves into c->d_plans (Blocks::kHost), else into
-// c->d_plan_edit_in the base block (a cross batch: the n_parents parent blocks), then the packed edits, moves or crosses, from which
-// k_plan_edits / k_plan_moves / k_plan_crosses writes the blocks on the launches' stream.  Then the index, the policy into its device
+// c->d_plan_edit_in the base block (a cross batch: the n_parents parent blocks; a rewrite batch: behind them the n_maps maps, kRewriteMapStride
+// bytes each), then the packed edits, moves, crosses or rewrites, from which k_plan_edits / k_plan_moves / k_plan_crosses /
+// k_plan_rewrites writes the blocks on the launches' stream.  Then the index, the policy into its device
 // snapshot, the launches and the fetch.
 // (The snapshot is staged last before the launches: a launch's start event takes the time the stream's previous command ended — with
 //  the snapshot staged first, eg_timing_read counted the host building the plan blocks.)
-enum class Blocks { kHost, kEdits, kMoves, kCrosses };      // who writes the plan blocks: the host has, k_plan_edits, k_plan_moves, k_plan_crosses
+enum class Blocks { kHost, kEdits, kMoves, kCrosses, kRewrites };      // who writes the plan blocks: the host has, k_plan_edits, k_plan_moves, k_plan_crosses, k_plan_rewrites
 int evaluate_batch(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, Blocks blocks, const std::vector<uint8_t>& in, const std::vector<uint32_t>& idx,
-                   uint32_t n_short, uint64_t seed, uint64_t first_index, bool same_index, eg_episode_out* out, uint32_t n_parents = 1u) {
+                   uint32_t n_short, uint64_t seed, uint64_t first_index, bool same_index, eg_episode_out* out, uint32_t n_parents = 1u, uint32_t n_maps = 0u) {
   const uint32_t n = uint32_t(idx.size());
   EG_TRY(ensure_outputs(c, n));
   EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
@@ -141,6 +143,10 @@ int evaluate_batch(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, Blo
   if (blocks == Blocks::kEdits) EG_LAUNCH("k_plan_edits", launch_plan_edits(d_in, d_in + snap::kPlanStride, n, c->d_plans, nullptr));
   if (blocks == Blocks::kMoves) EG_LAUNCH("k_plan_moves", launch_plan_moves(d_in, 1u, nullptr, d_in + snap::kPlanStride, n, c->d_plans, nullptr));
   if (blocks == Blocks::kCrosses) EG_LAUNCH("k_plan_crosses", launch_plan_crosses(d_in, n_parents, d_in + size_t(n_parents) * snap::kPlanStride, n, c->d_plans, nullptr));
+  if (blocks == Blocks::kRewrites) {
+    const uint8_t* d_maps = d_in + size_t(n_parents) * snap::kPlanStride;
+    EG_LAUNCH("k_plan_rewrites", launch_plan_rewrites(d_in, n_parents, d_maps, n_maps, d_maps + size_t(n_maps) * kRewriteMapStride, n, c->d_plans, nullptr));
+  }
   c->n_plan_blocks = n;
   EG_TRY(launch_plans(c, S, seed, first_index, n, n_short, same_index));
   return out ? eg_fetch(c, out) : EG_OK;
@@ -362,6 +368,91 @@ extern "C" int32_t eg_evaluate_plan_crosses(eg_ctx* c, const eg_policy_snapshot*
   for (uint32_t j = 0; j < n; ++j) { pack_plan_cross(crosses[j], packed + 2 * size_t(j)); R.add(j, child_len(off[0], crosses[j])); }
   const uint32_t n_short = R.finish();
   return evaluate_batch(c, s, o, Blocks::kCrosses, in, R.idx, n_short, seed, first_index, same_index != 0, out, P);
+}
+
+// ---------------------------------------------------------------- plan rewrites (include/eirgrid_hip.h eg_evaluate_plan_rewrites)
+static_assert(sizeof(eg_action_map) == 61 && sizeof(eg_plan_rewrite) == 8, "the rewrite structs are part of the C ABI");
+static_assert(sizeof(eg_action_map) <= kRewriteMapStride && EG_REWRITE_MAX_MAPS <= 65536 && EG_CROSS_MAX_PARENTS <= 65536, "a plan and a map index are packed into 16 bits each");
+// what goes up per rewrite, 8 bytes (eg_plan_rewrites.h unpack_rewrite)
+void eg::pack_plan_rewrite(const eg_plan_rewrite& r, uint32_t* packed) {
+  packed[0] = uint32_t(r.plan) | uint32_t(r.map) << 16;
+  packed[1] = uint32_t(r.from_year) | uint32_t(r.to_year) << 8 | uint32_t(r.lists) << 16;
+}
+
+extern "C" int32_t eg_plan_rewrites_validate(const eg_plan_set* plans, const eg_action_map* maps, int32_t n_maps, const eg_plan_rewrite* rewrites, int32_t n_rewrites) {
+  auto fail = [](const std::string& m) { set_error("eg_plan_rewrites_validate: " + m); return EG_ERR_BAD_ARG; };
+  EG_TRY(eg_plans_validate(plans));
+  if (plans->n_plans > EG_CROSS_MAX_PARENTS)
+    return fail("the set holds " + std::to_string(plans->n_plans) + " plans (at most " + std::to_string(EG_CROSS_MAX_PARENTS) + ")");
+  if (n_maps < 1 || n_maps > EG_REWRITE_MAX_MAPS) return fail("n_maps = " + std::to_string(n_maps) + " (1.." + std::to_string(EG_REWRITE_MAX_MAPS) + ")");
+  if (!maps) return fail("NULL maps");
+  for (int32_t m = 0; m < n_maps; ++m)
+    for (int e = 0; e < EG_N_ACTIONS; ++e)
+      if (maps[m].to[e] >= EG_N_ACTIONS && maps[m].to[e] != EG_REWRITE_DROP)
+        return fail("map " + std::to_string(m) + ": to[" + std::to_string(e) + "] = " + std::to_string(int(maps[m].to[e])) + " (0.." + std::to_string(EG_N_ACTIONS - 1) + " or 0xFF drop)");
+  if (n_rewrites < 1 || n_rewrites > EG_REWRITE_MAX_VARIANTS)
+    return fail("n_rewrites = " + std::to_string(n_rewrites) + " (1.." + std::to_string(EG_REWRITE_MAX_VARIANTS) + ")");
+  if (!rewrites) return fail("NULL rewrites");
+  for (int32_t j = 0; j < n_rewrites; ++j) {
+    const eg_plan_rewrite& r = rewrites[j];
+    const std::string who = "rewrite " + std::to_string(j) + ": ";
+    if (int32_t(r.plan) >= plans->n_plans) return fail(who + "plan " + std::to_string(int(r.plan)) + " >= n_plans " + std::to_string(plans->n_plans));
+    if (int32_t(r.map) >= n_maps) return fail(who + "map " + std::to_string(int(r.map)) + " >= n_maps " + std::to_string(n_maps));
+    if (r.to_year > EG_YEARS) return fail(who + "to_year " + std::to_string(int(r.to_year)) + " (at most " + std::to_string(EG_YEARS) + ")");
+    if (r.from_year > r.to_year) return fail(who + "from_year " + std::to_string(int(r.from_year)) + " > to_year " + std::to_string(int(r.to_year)));
+    if (r.lists > 3) return fail(who + "lists " + std::to_string(int(r.lists)) + " (bit 0 best_actions, bit 1 best_deficit_actions)");
+    if (r.pad != 0) return fail(who + "pad " + std::to_string(int(r.pad)) + " (must be 0)");
+  }
+  return EG_OK;
+}
+
+extern "C" int32_t eg_evaluate_plan_rewrites(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* plans, const eg_action_map* maps, int32_t n_maps,
+                                             const eg_plan_rewrite* rewrites, int32_t n_rewrites, uint64_t seed, uint64_t first_index, int32_t same_index,
+                                             eg_episode_out* out) {
+  if (!c || !s || !s->weights || !s->deficit_weights) { set_error("eg_evaluate_plan_rewrites: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(plan_entry(c, s, o, "eg_evaluate_plan_rewrites", [&] { return eg_plan_rewrites_validate(plans, maps, n_maps, rewrites, n_rewrites); }));
+  const uint32_t n = uint32_t(n_rewrites), P = uint32_t(plans->n_plans), M = uint32_t(n_maps);
+  // what goes up: every plan's block, once, the maps padded with drop bytes to kRewriteMapStride, and the packed rewrites
+  const size_t at_maps = size_t(P) * snap::kPlanStride, at_packed = at_maps + size_t(M) * kRewriteMapStride;
+  std::vector<uint8_t> in(at_packed + size_t(n) * 8, 0);
+  write_plan_blocks(plans, in.data());
+  for (uint32_t m = 0; m < M; ++m) {
+    std::memset(in.data() + at_maps + size_t(m) * kRewriteMapStride, EG_REWRITE_DROP, kRewriteMapStride);
+    std::memcpy(in.data() + at_maps + size_t(m) * kRewriteMapStride, maps[m].to, sizeof(maps[m].to));
+  }
+  // the routing, from the child's best_actions length: the plan's, less the entries of the window the map drops.  A histogram of every
+  // plan's best_actions by year and action, built once; per (plan, map) pair the call meets, the dropped entries in front of every year
+  std::vector<int32_t> off[2];
+  parent_offsets(plans, off);
+  std::vector<int32_t> hist(size_t(P) * EG_YEARS * EG_N_ACTIONS, 0);
+  {
+    size_t pos = 0;
+    for (uint32_t p = 0; p < P; ++p)
+      for (int y = 0; y < EG_YEARS; ++y)
+        for (int32_t i = 0; i < plans->best_count[size_t(p) * EG_YEARS + y]; ++i) ++hist[(size_t(p) * EG_YEARS + y) * EG_N_ACTIONS + plans->best_actions[pos++]];
+  }
+  std::unordered_map<uint32_t, std::vector<int32_t>> dropped;      // plan | map << 16 -> [27] prefix sums over the years
+  auto dropped_before = [&](uint32_t p, uint32_t m) -> const std::vector<int32_t>& {
+    auto it = dropped.find(p | m << 16);
+    if (it != dropped.end()) return it->second;
+    std::vector<int32_t> d(EG_YEARS + 1, 0);
+    for (int y = 0; y < EG_YEARS; ++y) {
+      d[y + 1] = d[y];
+      for (int e = 0; e < EG_N_ACTIONS; ++e) if (maps[m].to[e] == EG_REWRITE_DROP) d[y + 1] += hist[(size_t(p) * EG_YEARS + y) * EG_N_ACTIONS + e];
+    }
+    return dropped.emplace(p | m << 16, std::move(d)).first->second;
+  };
+  uint32_t* packed = reinterpret_cast<uint32_t*>(in.data() + at_packed);
+  Routing R;
+  for (uint32_t j = 0; j < n; ++j) {
+    const eg_plan_rewrite& r = rewrites[j];
+    pack_plan_rewrite(r, packed + 2 * size_t(j));
+    int64_t len = off[0][size_t(r.plan) * 27 + EG_YEARS];
+    if ((r.lists & 1) && r.to_year > r.from_year) { const std::vector<int32_t>& d = dropped_before(r.plan, r.map); len -= d[r.to_year] - d[r.from_year]; }
+    R.add(j, len);
+  }
+  const uint32_t n_short = R.finish();
+  return evaluate_batch(c, s, o, Blocks::kRewrites, in, R.idx, n_short, seed, first_index, same_index != 0, out, P, M);
 }
 
 extern "C" int32_t eg_debug_fetch_plan_block(eg_ctx* c, uint32_t plan, uint8_t* out) {

@@ -2616,6 +2616,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_refine_many.h"      // k_plan_edits_many, k_refine_pick_many: a refinement round, a segment of the launch's variants per plan
 #include "eg_plan_moves.h"       // k_plan_moves: the plan blocks of the variants that move an entry to another year
 #include "eg_plan_crosses.h"     // k_plan_crosses: the plan blocks of the variants that splice one parent's years into another
+#include "eg_plan_rewrites.h"    // k_plan_rewrites: the plan blocks of the variants that apply an action map to a window of years
 #include "eg_breed.h"            // k_breed_gather, k_breed_turnover: a generation's survivors become the next one's parents on the device
 #include "eg_explore.h"          // k_explore_turnover: the members that entered an exploration's archive become the next frontier
 
@@ -3493,6 +3494,13 @@ int launch_plan_moves(const uint8_t* d_bases, uint32_t n_bases, const uint32_t* 
 int launch_plan_crosses(const uint8_t* d_parents, uint32_t n_parents, const void* d_crosses, uint32_t n, uint8_t* d_pool, void* stream) {
   if (n == 0 || n_parents == 0) return 0;
   hipLaunchKernelGGL(k_plan_crosses, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_parents, n_parents, reinterpret_cast<const uint2*>(d_crosses), n, d_pool);
+  return (int)hipGetLastError();
+}
+int launch_plan_rewrites(const uint8_t* d_plans, uint32_t n_plans, const uint8_t* d_maps, uint32_t n_maps, const void* d_rewrites, uint32_t n, uint8_t* d_pool,
+                         void* stream) {
+  if (n == 0 || n_plans == 0 || n_maps == 0) return 0;
+  hipLaunchKernelGGL(k_plan_rewrites, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_plans, n_plans, d_maps, n_maps,
+                     reinterpret_cast<const uint2*>(d_rewrites), n, d_pool);
   return (int)hipGetLastError();
 }
 int launch_breed_gather(uint8_t* d_breed, const DevOut& o, uint32_t n, uint64_t first, const uint8_t* d_pool, void* stream) {

@@ -362,6 +362,143 @@ def _cross_array(crosses):
     return arr, len(crosses)
 
 
+@dataclass(frozen=True)
+class ActionMap:
+    """An action map (eg_action_map): `to[e]` is what entry e of a plan list becomes, an action 0..60 or ActionMap.DROP (0xFF): e is taken
+    out.  An action is 3 * type + cost tier for the generator types (0..44, world.GENERATOR_TYPE_NAMES; tier 0 is the 100 % one) and
+    the carbon offsets (45..56); 57..60 have no tiers."""
+    to: tuple
+
+    DROP = N.REWRITE_DROP
+    N_TIERED = 57      # the actions below it come in three cost tiers
+
+    def __post_init__(self):
+        to = tuple(int(t) for t in self.to)
+        if len(to) != N.N_ACTIONS or any(not (0 <= t < N.N_ACTIONS or t == self.DROP) for t in to):
+            raise ValueError(f"ActionMap: {N.N_ACTIONS} entries, each an action 0..{N.N_ACTIONS - 1} or {self.DROP} (drop)")
+        object.__setattr__(self, "to", to)
+
+    def struct(self) -> N.EgActionMap:
+        return N.EgActionMap((C.c_uint8 * N.N_ACTIONS)(*self.to))
+
+    @staticmethod
+    def identity() -> "ActionMap":
+        return ActionMap(tuple(range(N.N_ACTIONS)))
+
+    @staticmethod
+    def substitute(pairs) -> "ActionMap":
+        """a becomes b for every a: b of `pairs`; every other action stays"""
+        to = list(range(N.N_ACTIONS))
+        for a, b in dict(pairs).items():
+            to[int(a)] = int(b)
+        return ActionMap(tuple(to))
+
+    @staticmethod
+    def drop(actions) -> "ActionMap":
+        return ActionMap.substitute({int(a): ActionMap.DROP for a in actions})
+
+    @staticmethod
+    def drop_technology(type_index: int) -> "ActionMap":
+        """the three cost tiers of generator type `type_index` dropped"""
+        return ActionMap.drop(range(3 * int(type_index), 3 * int(type_index) + 3))
+
+    @staticmethod
+    def replace_technology(t: int, u: int) -> "ActionMap":
+        """generator type t built as type u at the same cost tier"""
+        return ActionMap.substitute({3 * int(t) + k: 3 * int(u) + k for k in range(3)})
+
+    @staticmethod
+    def cost_tier(k: int) -> "ActionMap":
+        """every generator and offset action at cost tier k (0, 1 or 2)"""
+        if int(k) not in (0, 1, 2):
+            raise ValueError(f"ActionMap.cost_tier: tier {k} (0, 1 or 2)")
+        return ActionMap(tuple(a - a % 3 + int(k) if a < ActionMap.N_TIERED else a for a in range(N.N_ACTIONS)))
+
+    @staticmethod
+    def drop_all() -> "ActionMap":
+        return ActionMap((ActionMap.DROP,) * N.N_ACTIONS)
+
+
+@dataclass(frozen=True)
+class PlanRewrite:
+    """One rewrite of a plan of a set (eg_plan_rewrite): plan `plan` with map `map` of a list of maps applied to every entry of the years
+    from_year <= y < to_year of the selected lists (`lists`: bit 0 best_actions, bit 1 best_deficit_actions) — an entry e becomes to[e]
+    or is taken out, the order kept.  lists == 0 or from_year == to_year is the plan itself.  A best_deficit_actions list that runs short
+    is refilled by seeded draws from the fallback distribution (gas peakers among them): substitute there, do not drop."""
+    plan: int = 0
+    map: int = 0
+    from_year: int = 0
+    to_year: int = N.YEARS
+    lists: int = 1
+
+    def struct(self) -> N.EgPlanRewrite:
+        return N.EgPlanRewrite(self.plan, self.map, self.from_year, self.to_year, self.lists, 0)
+
+    def apply(self, plans, maps) -> "Plan":
+        """The child (a new plan, named after the plan), as the device builds it."""
+        p, to = plans[self.plan], maps[self.map].to
+        def take(lists, bit):
+            if not self.lists >> bit & 1:
+                return [list(l) for l in lists]
+            return [[to[e] for e in l if to[e] != ActionMap.DROP] if self.from_year <= y < self.to_year else list(l) for y, l in enumerate(lists)]
+        return Plan(take(p.best_actions, 0), take(p.best_deficit_actions, 1), p.name)
+
+
+def _map_array(maps):
+    maps = list(maps)
+    arr = (N.EgActionMap * max(len(maps), 1))()
+    for j, m in enumerate(maps):
+        arr[j] = m.struct() if isinstance(m, ActionMap) else m
+    return arr, len(maps)
+
+
+def _rewrite_array(rewrites):
+    rewrites = list(rewrites)
+    arr = (N.EgPlanRewrite * max(len(rewrites), 1))()
+    for j, r in enumerate(rewrites):
+        arr[j] = r.struct() if isinstance(r, PlanRewrite) else r
+    return arr, len(rewrites)
+
+
+@dataclass(frozen=True)
+class TechnologyRow:
+    """A row of Engine.technology_report: plan `plan` without generator type `type` (-1: the plan itself), the best_actions entries that
+    took out, the variant's status, four metrics and rank score, and the score minus the plan's own."""
+    plan: int
+    type: int
+    removed: int
+    status: int
+    metrics: tuple
+    score: float
+    delta: float
+
+
+def technology_rewrites(plans, deficit: str = "substitute", substitute_with: int = 3 * 12):
+    """The variants of Engine.technology_report: (parents, maps, rewrites, rows), rows[j] = (plan, type, entries removed) of rewrites[j]
+    over `parents` and `maps`.  Per plan the plan itself (type -1), then per generator type t its best_actions uses, ascending, the
+    plan without t: the three tiers of t dropped from best_actions.  With deficit == "substitute" every tier of t in
+    best_deficit_actions becomes `substitute_with` as well; a variant applies ONE map, so where the deficit list does hold t the plan
+    with that list substituted on the host rides in `parents` behind the plans, and the variant drops t from ITS best_actions."""
+    if deficit not in ("substitute", "keep"):
+        raise ValueError(f"technology_report: deficit = {deficit!r} (\"substitute\" or \"keep\")")
+    if not 0 <= int(substitute_with) < N.N_ACTIONS:
+        raise ValueError(f"technology_report: substitute_with = {substitute_with} (an action 0..{N.N_ACTIONS - 1})")
+    parents, maps, slot, rewrites, rows = list(plans), [ActionMap.identity()], {}, [], []
+    for p, plan in enumerate(plans):
+        rewrites.append(PlanRewrite(p, 0, 0, 0, 0)); rows.append((p, -1, 0))
+        used = [a for l in plan.best_actions for a in l]
+        in_deficit = {a // 3 for l in plan.best_deficit_actions for a in l}
+        for t in sorted({a // 3 for a in used if a < 3 * N.N_TYPES}):
+            if t not in slot:
+                slot[t] = len(maps); maps.append(ActionMap.drop_technology(t))
+            src = p
+            if deficit == "substitute" and t in in_deficit:
+                sub = ActionMap.substitute({3 * t + k: int(substitute_with) for k in range(3)})
+                src = len(parents); parents.append(PlanRewrite(0, 0, 0, N.YEARS, 2).apply([plan], [sub]))
+            rewrites.append(PlanRewrite(src, slot[t], 0, N.YEARS, 1)); rows.append((p, t, sum(1 for a in used if a // 3 == t)))
+    return parents, maps, rewrites, rows
+
+
 def cross_pairs(n_plans: int, cuts=range(1, 26)) -> "list[PlanCross]":
     """The variants of Engine.cross_front over n_plans parents: every parent itself, PlanCross(p, p, 0, 0), in order; then for a, b != a
     and c of `cuts`, in lexicographic order, the one-point crossover PlanCross(a, b, c, 26): a's years before c, b's from c on."""
@@ -904,6 +1041,64 @@ class Engine:
             fi, fm = pareto_filter(fi, fm, np.arange(first, first + n), metrics, status, mask)
         score = np.array([rank_score(m, cost_only) for m in fm])
         return CrossFront(fi, [crosses[i] for i in fi], fm, score, fi < len(parents), len(crosses), n_valid)
+
+    def evaluate_plan_rewrites(self, weights: ActionWeights, plans, maps, rewrites, seed: int, first_index: int = 0, same_index: bool = True,
+                               enable_energy_sales=True, write_yearly=True) -> BatchResult:
+        """Score rewrites of a set of plans (eg_evaluate_plan_rewrites): variant j is rewrites[j] (PlanRewrite) applied to `plans` and
+        `maps` (ActionMap), evaluated as evaluate_plans would evaluate it — at global index first_index for every variant (same_index),
+        or at first_index + j.  The variants' plan blocks are built on the device."""
+        ps = plans if isinstance(plans, PlanSet) else PlanSet(plans)
+        marr, n_maps = _map_array(maps)
+        arr, n = _rewrite_array(rewrites)
+        res = BatchResult.alloc(max(n, 1))
+        snap = weights.snapshot()
+        opts = self._opts(enable_energy_sales, False, write_yearly)
+        out = res.struct()
+        N.check(N.lib().eg_evaluate_plan_rewrites(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), marr, n_maps, arr, n, C.c_uint64(seed & (2**64 - 1)),
+                                                  C.c_uint64(first_index), int(bool(same_index)), C.byref(out)), "eg_evaluate_plan_rewrites")
+        return res
+
+    def technology_report(self, weights: ActionWeights, plans, seed: int, index: int = 0, cost_only: bool = False, deficit: str = "substitute",
+                          substitute_with: int = 3 * 12, max_variants: int = N.REWRITE_MAX_VARIANTS) -> "list[TechnologyRow]":
+        """What every generator type is worth to every plan: the variants of technology_rewrites(plans, deficit, substitute_with) — per
+        plan the plan itself, then the plan without each type t its best_actions uses: t dropped there and, with deficit ==
+        "substitute", replaced by `substitute_with` (battery storage at 100 %) in best_deficit_actions, where a dropped entry would be
+        refilled by fallback draws; deficit == "keep" leaves that list alone — evaluated in chunks of at most max_variants (<= 16 384)
+        in order, every one at global index `index` of `seed`.  Per variant only the metrics and the status come back (36 bytes); a
+        plan whose deficit list holds the type taken out goes up once more with that list substituted (technology_rewrites).
+        The context's own Pareto archive is not touched.  Rows in the variants' order; cost_only picks the rank score."""
+        if not 1 <= int(max_variants) <= N.REWRITE_MAX_VARIANTS:
+            raise ValueError(f"technology_report: max_variants = {max_variants} (1..{N.REWRITE_MAX_VARIANTS})")
+        plans = list(plans)
+        parents, maps, rewrites, rows = technology_rewrites(plans, deficit, substitute_with)
+        marr, n_maps = _map_array(maps)
+        snap = weights.snapshot()
+        opts = self._opts(True, False, False)      # (no yearly rows: nothing reads them)
+        L = N.lib()
+        metrics = np.zeros((len(rewrites), 4)); status = np.zeros(len(rewrites), np.int32)
+        first = 0
+        while first < len(rewrites):
+            # a chunk: at most max_variants variants over at most CROSS_MAX_PARENTS of the parents, renumbered for the chunk's set
+            local, chunk = {}, []
+            for r in rewrites[first:first + int(max_variants)]:
+                if r.plan not in local and len(local) == N.CROSS_MAX_PARENTS:
+                    break
+                chunk.append(PlanRewrite(local.setdefault(r.plan, len(local)), r.map, r.from_year, r.to_year, r.lists))
+            ps = PlanSet([parents[p] for p in local])
+            arr, n = _rewrite_array(chunk)
+            N.check(L.eg_evaluate_plan_rewrites(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), marr, n_maps, arr, n, C.c_uint64(seed & (2**64 - 1)),
+                                                C.c_uint64(index), 1, None), "eg_evaluate_plan_rewrites")
+            m, st = metrics[first:first + n], status[first:first + n]
+            out = N.EgEpisodeOut(metrics=_p(m, C.c_double), status=_p(st, C.c_int32))
+            N.check(L.eg_fetch(self.h, C.byref(out)), "eg_fetch")
+            first += n
+        report, own = [], 0.0
+        for j, (p, t, removed) in enumerate(rows):
+            score = rank_score(metrics[j], cost_only)
+            if t < 0:
+                own = score
+            report.append(TechnologyRow(p, t, removed, int(status[j]), tuple(float(v) for v in metrics[j]), score, score - own))
+        return report
 
     def breed_front(self, weights: ActionWeights, parents, seed: int, index: int = 0, objectives=PARETO_OBJECTIVES, cost_only: bool = False,
                     cuts=range(1, 26), generations: int = 8, cap: int = N.PARETO_MAX, max_variants: int = N.CROSS_MAX_VARIANTS,

@@ -557,6 +557,44 @@ int32_t eg_evaluate_plan_crosses(eg_ctx *, const eg_policy_snapshot *policy, con
                                  const eg_plan_cross *crosses, int32_t n_crosses, uint64_t seed, uint64_t first_episode_index,
                                  int32_t same_index, eg_episode_out *out /* may be NULL */);
 
+/* Plan rewrites: what is a technology worth to this plan?  What does it score without nuclear, with offshore wind built as onshore, with
+ * every plant bought at the 100 % cost tier, with nothing built after 2040?  All of these are one operation: an ACTION MAP — 61 entries,
+ * to[e] being the action that entry e becomes, or EG_REWRITE_DROP: e is taken out — applied to every entry of a window of years of a plan.
+ * eg_evaluate_plan_rewrites evaluates n_rewrites VARIANTS over a set of 1..EG_CROSS_MAX_PARENTS plans and n_maps maps, variant j being plan
+ * `plan` of the set changed as follows:
+ *   lists                bit 0: best_actions changes, bit 1: best_deficit_actions changes; a list whose bit is clear is the plan's own
+ *   from_year, to_year   year indices with 0 <= from_year <= to_year <= 26; only the years of the window [from_year, to_year) change
+ *   map                  an index into `maps`; in the years of the window a selected list becomes [m.to[e] for e in list if m.to[e] !=
+ *                        EG_REWRITE_DROP], the order of the kept entries preserved
+ * lists == 0, from_year == to_year, or a map that is the identity on the entries it meets give the plan itself, the "none" of rewrites,
+ * so the plans can ride in the batch.  A rewrite never lengthens a list, so no variant can exceed 4 096 entries.
+ * THE DEFICIT LIST IS NOT THE PLAN LIST.  A dropped best_actions entry is simply not acted on: a year's action count is the length of
+ * its list.  A best_deficit_actions list that has become too short is REFILLED, by seeded draws from the fixed fallback distribution
+ * (sampling.rs:492-528), and that distribution holds gas peakers.  So a technology is taken out of the deficit list by SUBSTITUTING it,
+ * not by dropping it.
+ * Everything else is the contract of eg_evaluate_plan_crosses, word for word: variant j is evaluated exactly as eg_evaluate_plans
+ * evaluates the host-built child as plan j — the same replay semantics, seeded draws when a list runs out, no statistics, update or folds,
+ * the resident policy and the context's archives untouched, the batch left behind for eg_fetch / eg_fetch_record /
+ * eg_debug_fetch_plan_block, ranks of a group refused — at global episode first_episode_index + j (same_index = 0), or with same_index = 1
+ * every variant at first_episode_index.  The host uploads every plan's block once, the maps once (64 bytes each) and 8 bytes per variant;
+ * the variants' plan blocks are written on the device (csrc/eg_plan_rewrites.h k_plan_rewrites).  The short or long replay route is
+ * chosen per variant from the child's best_actions length: a rewrite can make a long plan short.
+ * eg_plan_rewrites_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the rewrite or the map and the field ("map 3:
+ * to[17] = 200 (0..60 or 0xFF drop)", "rewrite 5: plan 4 >= n_plans 4") for a set that is not a valid set of 1..EG_CROSS_MAX_PARENTS
+ * plans, n_maps outside 1..EG_REWRITE_MAX_MAPS, NULL maps, a map entry in 61..254, n_rewrites outside 1..EG_REWRITE_MAX_VARIANTS, NULL
+ * rewrites, plan >= n_plans, map >= n_maps, to_year > 26, from_year > to_year, lists > 3, or pad != 0.  Nothing is launched after a
+ * refusal, and the previous last batch stays fetchable. */
+#define EG_REWRITE_DROP 0xFF
+#define EG_REWRITE_MAX_MAPS 256
+#define EG_REWRITE_MAX_VARIANTS 16384          /* = EG_CROSS_MAX_VARIANTS */
+typedef struct { uint8_t to[EG_N_ACTIONS]; } eg_action_map;                                   /* 61 bytes */
+typedef struct { uint16_t plan, map; uint8_t from_year, to_year, lists, pad; } eg_plan_rewrite; /* 8 bytes */
+int32_t eg_plan_rewrites_validate(const eg_plan_set *plans, const eg_action_map *maps, int32_t n_maps,
+                                  const eg_plan_rewrite *rewrites, int32_t n_rewrites);
+int32_t eg_evaluate_plan_rewrites(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, const eg_plan_set *plans /* 1..EG_CROSS_MAX_PARENTS */,
+                                  const eg_action_map *maps, int32_t n_maps, const eg_plan_rewrite *rewrites, int32_t n_rewrites,
+                                  uint64_t seed, uint64_t first_episode_index, int32_t same_index, eg_episode_out *out /* may be NULL */);
+
 /* Breeding a front: generations of plan crosses with Pareto selection, the survivors' plan blocks becoming the next generation's parents
  * on the device.  eg_breed_plans(ctx, policy, opts, parents, breed_opts, seed, episode_index, ...) starts from the population P_0 = the
  * given 1..EG_CROSS_MAX_PARENTS plans, in order.  Generation g = 0, 1, ... :
