@@ -114,7 +114,7 @@ int build_device_blob(const HostTables& H, std::vector<uint8_t>& blob, BlobInfo&
         }
     }
   }
-  {  // heavy episodes (eg_rollout.hip heavy_add): every (class, di, dj) with a factor below 1, i.e. closer than the class radius
+  {  // heavy episodes (eg_field.h heavy_add): every (class, di, dj) with a factor below 1, i.e. closer than the class radius
     uint32_t* box = reinterpret_cast<uint32_t*>(blob.data() + tab::hv_box);
     int nbox = 0;
     for (int k = 0; k < kRadiusClasses; ++k)

@@ -113,14 +113,14 @@ struct eg_ctx {
   eg::DevBuf<uint8_t> d_packet; eg::PinBuf<uint8_t> h_packet;
   // batches of at most this many episodes run the helper-wave kernel (three waves per episode, all resident at once)
   uint32_t helper_max_episodes = 0;
-  // heavy episodes (eg_rollout.hip place_heavy): pool of penalty fields, one slot per episode that outgrows kHeavyGens (d_heavy, d_heavy_claim: what dev.heavy* point to)
+  // heavy episodes (eg_field.h place_heavy): pool of penalty fields, one slot per episode that outgrows kHeavyGens (d_heavy, d_heavy_claim: what dev.heavy* point to)
   // EIRGRID_HEAVY_POOL_GB (default 64): what the pool may grow to, 126 KB per replay episode of a launch; 131 072 replay episodes
   // (an all-replay batch of configs[3]'s size) want 16 GB.  eg_memory_report tells what is held.
   eg::DevBuf<uint8_t> d_heavy; eg::DevBuf<unsigned> d_heavy_claim;
   uint32_t heavy_slots_max = 0, heavy_slots_wanted = 4096, launch_epoch = 0;
   bool heavy_slots_auto = true;      // (EIRGRID_HEAVY_SLOTS fixes the pool size instead)
   // replay hoist (eg_replay_coop.h; eg_replay_hoist / EIRGRID_REPLAY_HOIST=1): the replay episodes of a batch computed once.
-  // d_hoist: HoistInfo {u64 sequence number of the last batch whose hoist succeeded, i32 lengths[5]}; d_coop: the scratch record.
+  // d_hoist: a HoistInfo (eg_internal.h); d_coop: the scratch record.
   bool hoist_on = false, hoist_supported = false;
   unsigned long long hoist_seq = 0;
   eg::DevBuf<uint8_t> d_hoist, d_coop;

@@ -103,20 +103,20 @@ constexpr size_t offv = a16(t12 + 8 * kYears * kTypes);                     // [
 constexpr size_t offc = a16(offv + 8 * kYears * kOffsetTypes * kYears);     // [26][4][3]
 constexpr size_t cc = a16(offc + 8 * kYears * kOffsetTypes * kMults);       // [26][15][26][3][2]
 constexpr size_t ps = a16(cc + 8 * size_t(kYears) * kTypes * kYears * kMults * 2);   // PsRec [26][kMaxVariants][kPsStride]
-constexpr size_t hv_box = a16(ps + sizeof(PsRec) * size_t(kYears) * kMaxVariants * kPsStride);   // u32 [1024 + 16]: heavy episodes, eg_rollout.hip heavy_add
+constexpr size_t hv_box = a16(ps + sizeof(PsRec) * size_t(kYears) * kMaxVariants * kPsStride);   // u32 [1024 + 16]: heavy episodes, eg_field.h heavy_add
 // the throughput kernels' factor table in LDS holds every radius class only up to its own radius (eg_rollout.hip load_factor_table):
 // int32 {first entry of class k} [8] | {squared distance from which the factor is 1.0, class k} [8]
 constexpr size_t dr_meta = a16(hv_box + 4 * (1024 + 16));
 // ... and that table itself as the kernels keep it in LDS (f64 [kDrCompact]: class k's factors by squared distance at entries
 // dr_meta[k] .. dr_meta[k] + dr_meta[8 + k], 1.0 everywhere else), so that an episode copies it with one load per lane and block
 constexpr size_t dr_compact = a16(dr_meta + 4 * 16);
-// the sorted candidates once more as what the approximate scan of the long-replay variant reads of them (eg_rollout.hip place_heavy):
+// the sorted candidates once more as what the approximate scan of the long-replay variant reads of them (eg_field.h place_heavy):
 // the unpenalised score (te * cf) * size_factor and the cell, three registers per chunk in flight instead of eight.  Last, so that the
 // offsets of the tables the lean kernels read stay small.
 constexpr size_t pbase = a16(dr_compact + 8 * size_t(kDrCompact));                     // f64 [26][kMaxVariants][kPcStride]
 constexpr size_t pcell = a16(pbase + 8 * size_t(kYears) * kMaxVariants * kPcStride);     // u32 [26][kMaxVariants][kPcStride]
 // the field update's entry list (hv_box) packed for every subset of radius classes an episode may keep a field for, as the throughput
-// kernel reads it (eg_rollout.hip heavy_add_body: the entry's place in the compact factor table instead of its squared distance),
+// kernel reads it (eg_field.h heavy_add_body: the entry's place in the compact factor table instead of its squared distance),
 // padded to a multiple of four entries per lane; hv_quads = that multiple.  (The small-batch kernel packs its own list into LDS.)
 constexpr size_t hv_lists = a16(pcell + 4 * size_t(kYears) * kMaxVariants * kPcStride);     // u32 [64][1024]
 constexpr size_t hv_quads = a16(hv_lists + 4 * size_t(64) * 1024);                          // i32 [64]
@@ -127,7 +127,7 @@ constexpr size_t coastf = a16(te_cell + 8 * size_t(kYears) * kRadiusClasses * kC
 // ... and the unpenalised score (te * cf) * size_factor of every (year, variant) per cell — tab::pbase in cell order: what the hoisted
 // replay's searches multiply the penalty field with (te_cell / coastf: the exact evaluation of tied candidates)
 constexpr size_t cbase = a16(coastf + 8 * size_t(kCells));                                  // f64 [26][kMaxVariants][2601]
-// the spatial bound of the per-episode replay kernel's searches (eg_rollout.hip place_tiles), the grid in 8 x 8 tiles: per (year,
+// the spatial bound of the per-episode replay kernel's searches (eg_field.h place_tiles), the grid in 8 x 8 tiles: per (year,
 // variant) every cell's place in the sorted list (tab::pbase's rank); per variant u(c), the largest unpenalised score of the cell over
 // the years, and its largest value per tile; per (year, variant) and tile the largest ratio score / u (rounded up by 2^-40; cells
 // with u below 1e-300 left out), the same for every cell up to rounding — the years differ by population factors only
@@ -149,7 +149,7 @@ struct DevTables {
   uint8_t* heavy;
   unsigned* heavy_claim;
   // ... and behind the pool, per slot and variant, an upper bound of u(c) * field(c) on every 8 x 8 tile of the grid (tab::ucell):
-  // [kMaxVariants][64] f64 (eg_rollout.hip place_tiles; never read by the classic variant)
+  // [kMaxVariants][64] f64 (eg_field.h place_tiles; never read by the classic variant)
   double* heavy_tiles;
   uint32_t solo_tiles;      // 1: k_replay_solo searches by tile bounds (place_tiles), 0: by rank (place_heavy; EIRGRID_SOLO_TILES=0)
   // (with solo_tiles) != 0: k_replay_lazy runs in k_replay_solo's place; the longest script, in generators, whose field it brings up to date
@@ -323,8 +323,8 @@ struct RolloutPlan {
   uint32_t off, period;
   void* ev[4];
   // replay hoist (eg_replay_coop.h): hoist_seq != 0 = the replay episodes of this batch are computed ONCE by k_replay_coop into the
-  // scratch record `coop_out` and copied to every replay slot by k_replay_broadcast; d_hoist = {u64 word: the sequence number of the
-  // last batch whose hoist succeeded, i32 lengths[8]} — the per-episode replay variants are launched in between and return at once
+  // scratch record `coop_out` and copied to every replay slot by k_replay_broadcast; d_hoist = the HoistInfo below, whose first word is the sequence
+  // number of the last batch whose hoist succeeded — the per-episode replay variants are launched in between and return at once
   // when the word says their batch has been served
   unsigned long long hoist_seq;
   HoistInfo* d_hoist;
@@ -400,14 +400,14 @@ struct UpdateCandidate {
 };
 static_assert(sizeof(UpdateCandidate) == EG_CANDIDATE_BYTES, "candidate layout is part of the C ABI");
 int launch_pick_best(const DevOut& o, uint32_t n, uint64_t first_index, UpdateCandidate* d_cand, void* stream);
-// The reference's `best_result` fold (core/multi_simulation.rs:613-620; eg_rollout.hip k_fold_best): the held run's metrics, global
+// The reference's `best_result` fold (core/multi_simulation.rs:613-620; eg_update_kernels.h k_fold_best): the held run's metrics, global
 // index and — kFoldRecord bytes behind the state — its whole record (rec:: layout).
 struct FoldState { double metrics[4]; long long index; int32_t has, pad; };
 constexpr size_t kFoldRecord = 64;
 constexpr size_t kFoldBytes = kFoldRecord + rec::stride;
 static_assert(sizeof(FoldState) <= kFoldRecord, "fold state layout");
 int launch_fold_best(const DevOut& o, uint32_t n, uint64_t first_index, bool cost_only, uint8_t* d_fold, void* stream);
-// The same fold over the ranks of a group (eg_group.cpp; eg_rollout.hip k_fold_pack / k_fold_gathered).  Every rank packs what the
+// The same fold over the ranks of a group (eg_group.cpp; eg_update_kernels.h k_fold_pack / k_fold_gathered).  Every rank packs what the
 // fold reads of its shard into a block of FoldEntry behind its update packet; the blocks travel with the packets, and every rank folds
 // all of them in rank order (= global index order).  The state is replicated: identical on every rank.  The record is copied only by
 // the rank whose shard held the winner, which tags it with the winner's global index and the group step of the take-over.

@@ -14,7 +14,7 @@
 //      k_rollout's replay path statement for statement, minus the placement, the in-episode weight nudges (learning.rs:21-88,
 //      deficit.rs:82-135: they only touch the episode's private copy of the tables, which a replay never samples from and which is
 //      dropped at its end — Q5) and every aggregate but the three output class sums.
-//   2. THE PLACEMENTS (k_replay_coop, all eight waves — two per SIMD of a CU: with four, one per SIMD, a placement took 2 545 cycles; a
+//   2. THE PLACEMENTS (k_replay_coop, all EG_COOP_WAVES = 8 waves — two per SIMD of a CU: with four, one per SIMD, a placement took 2 545 cycles; a
 //      second wave per SIMD issues into the first one's waits; sixteen are slower again, profiles/r04_ab_notes.log r04z).  Serial by nature: a
 //      search sees every generator before it.  A search is an arg-max over all 2 601 candidate cells at once, six cells per lane:
 //      the product of the penalty factors of every generator placed so far is kept per radius class and cell in LDS (field[6][2624]
@@ -31,8 +31,8 @@
 //   3. THE YEARLY ROWS (k_replay_books, a wave a year).  Every aggregate of a year is a sum over the generators / offsets in list
 //      order (map_handler.rs:829-965): started from the existing-plant prefix at the year's start and continued with every addition,
 //      i.e. one sequential sum over the list as it stands at the year's end — and the years do not depend on each other once the
-//      lists are known.  Sixteen waves fold them side by side (fold2_row16: one DPP multiply-accumulate per list element and sum),
-//      one lane then runs the three running totals of metrics_calculation.rs:133-153 through the 26 years.
+//      lists are known.  EG_YEARS one-wave workgroups fold them side by side (fold2_row16: one DPP multiply-accumulate per list element
+//      and sum), one lane then runs the three running totals of metrics_calculation.rs:133-153 through the 26 years.
 // The record goes to a scratch slot; k_replay_broadcast copies it into the record of every replay episode of the batch and runs the
 // statistics epilogue for each of them (episode_update_stats: the same function, so the update packet is the per-episode path's by
 // construction).  If the script cannot be finished without a seeded draw (a fallback), or would end with a status other than
@@ -124,6 +124,7 @@ __device__ __forceinline__ int scan_fast(const double (&b)[kPer], int rc, int ti
   // like their bit patterns) with the cell slot k in its four lowest bits — a key bounds its score within 2^-16, which is all the
   // decision below needs, and a v_max / v_med3 pair per cell keeps value, place and runner-up (l1 >= l2 throughout, so the median of
   // {l1, l2, key} is the new runner-up).
+  static_assert(kWaves <= 16 && kPer <= 16, "a key's four lowest bits hold the cell slot; the exchange below reads a wave's entry per lane");
   uint32_t l1 = 0u, l2 = 0u;
 #pragma unroll
   for (int k = 0; k < kPer; ++k) {
@@ -146,7 +147,7 @@ __device__ __forceinline__ int scan_fast(const double (&b)[kPer], int rc, int ti
   EG_CS(4);      // 4: searches: the wave's two largest
   wg_barrier_lds();
   EG_CS(6);      // 6: searches: the exchange's barrier
-  // (lane w < 4 reads wave w's entry — keys and cell in ONE 16-byte read: every LDS round trip of a search is on the batch's serial path)
+  // (lane w < kWaves reads wave w's entry — keys and cell in ONE 16-byte read: every LDS round trip of a search is on the batch's serial path)
   int4 tv = {0, 0, 0, 0};
   if (lane < kWaves) tv = *reinterpret_cast<const int4*>(&sc.top[lane]);
   const uint32_t r1 = (uint32_t)tv.x, r2 = (uint32_t)tv.y;
@@ -393,8 +394,8 @@ __global__ void __launch_bounds__(coop::kThreads, 1) k_replay_coop(DevTables T, 
 }
 
 // The yearly rows of the scratch record: a one-wave workgroup a year (a workgroup that needs one wave slot starts the moment any lean
-// episode ends — a sixteen-wave workgroup waited half a millisecond for a CU to drain, and held the lean grid's dispatch back while it
-// did: profiles/r04_ab_notes.log).  The workgroup that finishes last runs the three running totals through the 26 years, writes the
+// episode ends — this kernel's first form, ONE workgroup of sixteen waves, waited half a millisecond for a CU to drain, and held the lean
+// grid's dispatch back while it did: profiles/r04_ab_notes.log r04c).  The workgroup that finishes last runs the three running totals through the 26 years, writes the
 // record's header, adds the statistics of ALL the batch's replay episodes (`n_replay` identical episodes: every integer sum of
 // episode_update_stats times that — 1 638 waves adding to the same few hundred addresses one after the other took 0.3 ms) and
 // publishes HoistInfo::served_seq.

@@ -11,7 +11,7 @@
 //      field of the pool, the lists' window in LDS and their tail in the record — the same code, so the same cells and the same
 //      accounting of requested chunks) — except that a search of the field goes by tile bounds (place_tiles: the same cell, the same
 //      chunks, fewer instructions; EIRGRID_SOLO_TILES=0: by rank, as k_rollout searches), and that the field is then kept lazily: a
-//      placement leaves it alone, a search brings the tiles it reads up to date (eg_rollout.hip tiles_refresh: the same values, the
+//      placement leaves it alone, a search brings the tiles it reads up to date (eg_field.h tiles_refresh: the same values, the
 //      accounting of the eager update kept) — by k_replay_lazy, the kernel at the end of this file, which contexts with
 //      DevTables::solo_lazy != 0 launch in k_replay_solo's place (EIRGRID_SOLO_LAZY=0: k_replay_solo, its field updated after every
 //      placement, as k_rollout's is),
@@ -126,7 +126,7 @@ __device__ __forceinline__ void replay_solo_episode(const DevTables& T, const De
   PrefixCache prefix_cache0 = {0.0, -1, 0};
   uint32_t search_seq = 0;
   int tile_variants = 0;      // variants whose tile bounds (place_tiles) this episode has set up
-  // the field current only where a search reads it (eg_rollout.hip tiles_refresh) — for scripts up to DevTables::solo_lazy generators: a
+  // the field current only where a search reads it (eg_field.h tiles_refresh) — for scripts up to DevTables::solo_lazy generators: a
   // tile's catch-up walks the list, so its cost grows with the list, the eager update's does not (profiles/r10_ab_notes.log)
   const bool lazy = kLazy && T.solo_tiles != 0u && (uint32_t)n_gens <= T.solo_lazy;
   int pk_block = 0;

@@ -145,7 +145,7 @@ typedef struct {
   double *bytes_moved;  /* [n] algorithmic bytes of the episode, SURVEY.md §8(d) formula (bills the whole 2601 x 8 B score field per search) */
   uint32_t *n_chunks;   /* [n] what the episode's placement searches requested from memory, in units of 2 KB: chunks of 64 sorted
                            candidate records (32 B each) — what the branch-and-bound search reads instead of the score field —
-                           and, for long (replay) episodes, the entries of their penalty field (eg_rollout.hip place_heavy);
+                           and, for long (replay) episodes, the entries of their penalty field (eg_field.h place_heavy);
                            bytes touched = bytes_moved - n_gens * 2601 * 8 + n_chunks * 2048 */
 } eg_episode_out;
 
@@ -926,7 +926,7 @@ int32_t eg_policy_rewind(eg_ctx *);
  * with replay_best_strategy = true takes every action from the stored lists and reads no seeded draw until a list runs out
  * (ai/learning/weights/sampling.rs:78-101, :242-266; core/simulation.rs:146-162), so all replay episodes of a batch are one and the
  * same computation.  With the hoist on (eg_replay_hoist(ctx, 1), or EIRGRID_REPLAY_HOIST=1 in the environment at eg_create; off by
- * default) a batch computes that script ONCE — a cooperative sixteen-wave workgroup, csrc/eg_replay_coop.h — and hands every replay
+ * default) a batch computes that script ONCE — one cooperative workgroup of EG_COOP_WAVES waves, csrc/eg_replay_coop.h — and hands every replay
  * episode of the batch a copy of the record; records, statistics and update packets are those of the per-episode path, byte for byte
  * (n_chunks excepted: it counts what the search that really ran requested).  A script that needs a fallback draw
  * (sampling.rs:445-528) or would end with a status other than EG_EP_OK is not hoisted: the per-episode kernels run those episodes as

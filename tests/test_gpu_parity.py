@@ -515,7 +515,7 @@ eng.close()
 def test_heavy_episodes_match_the_oracle(world):
     """Replay episodes with hundreds of generators (what the reference's replay phase grows into).  From 64
     generators on a search runs through the approximate penalty field + exact evaluation of the few candidates
-    (eg_rollout.hip place_heavy) instead of the exact branch-and-bound scan.  Every output must stay bit-identical: to the
+    (eg_field.h place_heavy) instead of the exact branch-and-bound scan.  Every output must stay bit-identical: to the
     tabled oracle, between the two kernels, and between a pool of field slots that covers every heavy episode, one that
     runs out after three (the rest fall back to the exact scan) and no pool at all."""
     tb = _tabled(world)

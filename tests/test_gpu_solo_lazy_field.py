@@ -1,4 +1,4 @@
-"""GPU: the lazy penalty field of the per-episode replay kernel (csrc/eg_replay_solo.h k_replay_lazy, csrc/eg_rollout.hip tiles_refresh;
+"""GPU: the lazy penalty field of the per-episode replay kernel (csrc/eg_replay_solo.h k_replay_lazy, csrc/eg_field.h tiles_refresh;
 EIRGRID_SOLO_LAZY=0 switches it off: k_replay_solo).  With it a placement leaves the field alone, and a search by tiles brings the
 64 values of every tile it is about to read up to date first: the generators the tile has not seen yet, in list order — the
 multiplications the eager update performs, later.

@@ -1,4 +1,4 @@
-"""GPU: the tile search of the per-episode replay kernel (csrc/eg_rollout.hip place_tiles: the penalty field bounded per 8 x 8 tile
+"""GPU: the tile search of the per-episode replay kernel (csrc/eg_field.h place_tiles: the penalty field bounded per 8 x 8 tile
 instead of scanned by rank) against the rank scan it stands in for (place_heavy, EIRGRID_SOLO_TILES=0) and against the classic
 long-replay variant (EIRGRID_REPLAY_SOLO=0).
 

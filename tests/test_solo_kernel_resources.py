@@ -1,6 +1,6 @@
 """What the compiler makes of the per-episode replay kernel (no GPU needed: scripts/kernel_resources.sh, device code only).
 
-k_replay_solo runs beside the lean grid at four waves per SIMD; its tile search (csrc/eg_rollout.hip place_tiles) must not cost it
+k_replay_solo runs beside the lean grid at four waves per SIMD; its tile search (csrc/eg_field.h place_tiles) must not cost it
 that: no scratch memory, at most 128 vector registers, and no more LDS than the long-replay variant of k_rollout it stands in for."""
 import os
 import re
