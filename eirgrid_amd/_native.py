@@ -187,7 +187,7 @@ EXPORTS = [
     "eg_group_top_k_track", "eg_group_fetch_top_k", "eg_plans_validate", "eg_evaluate_plans", "eg_plans_load", "eg_plans_free",
     "eg_plan_edits_validate", "eg_evaluate_plan_edits", "eg_debug_fetch_plan_block", "eg_plans_save", "eg_refine_validate", "eg_refine_plan",
     "eg_refine_plans_validate", "eg_refine_plans", "eg_debug_refine_pick_many",
-    "eg_debug_breed_begin", "eg_debug_breed_chunk", "eg_debug_breed_turnover", "eg_debug_breed_fetch",
+    "eg_debug_breed_begin", "eg_debug_breed_chunk", "eg_debug_breed_turnover", "eg_debug_breed_fetch", "eg_debug_tiles_refresh",
     "eg_plan_moves_validate", "eg_evaluate_plan_moves", "eg_refine_plans_moves_validate", "eg_refine_plans_moves",
     "eg_plan_crosses_validate", "eg_evaluate_plan_crosses", "eg_plan_rewrites_validate", "eg_evaluate_plan_rewrites",
     "eg_breed_validate", "eg_breed_plans", "eg_explore_validate", "eg_explore_neighbourhood", "eg_explore_plans",
@@ -434,6 +434,9 @@ def lib():
         L.eg_debug_breed_turnover.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64]
         L.eg_debug_breed_fetch.restype = C.c_int32
         L.eg_debug_breed_fetch.argtypes = [C.c_void_p, C.c_void_p, _u8p, _u8p, _u8p, _u8p, C.c_void_p, _u64p]
+    if hasattr(L, "eg_debug_tiles_refresh") or not os.environ.get("EIRGRID_LIB"):      # (likewise: the lazy field's catch-up on one wave)
+        L.eg_debug_tiles_refresh.restype = C.c_int32
+        L.eg_debug_tiles_refresh.argtypes = [C.c_void_p, _u16p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _i32p]
     L.eg_plans_load.restype = C.POINTER(EgPlanSet)
     L.eg_plans_load.argtypes = [C.c_char_p]
     L.eg_plans_free.argtypes = [C.POINTER(EgPlanSet)]

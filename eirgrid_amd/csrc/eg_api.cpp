@@ -48,7 +48,7 @@ struct Options {
   // EIRGRID_SOLO_LAZY: the longest replay script (generators) that runs with the lazy field (k_replay_lazy in k_replay_solo's place); 0: none
   // (k_replay_solo: the field current after every placement, as the classic variant keeps it), all: every script.  Default: measured on the benchmark's states — 9 % faster at
   // 228 generators, 4 % slower at 468, 16 % slower at 916 (profiles/r10_ab_notes.log): six blocks of 64 generators.
-  uint32_t solo_lazy = 384u;
+  uint32_t solo_lazy = 512u;      // (the lists' on-chip window: measured ahead of the eager field at 228 and 468 generators, behind it at 916 — DESIGN §4, round 14)
 };
 Options read_options() {
   Options o;
@@ -238,11 +238,14 @@ int launch_batch(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, con
   if (split) {
     EG_HIP(hipEventRecord(c->ev_fork[slot], nullptr));
     EG_HIP(hipStreamWaitEvent(c->stream_heavy, c->ev_fork[slot], 0));
-    // Long replays are the batch's long pole and want the chip first (a 256-register wave that arrives behind 16 384 lean
-    // episodes waits for two of them to finish on its SIMD: 5.6 instead of 4.95 ms per batch at 468 generators per replay):
-    // the lean grid then waits for an event recorded behind the short-replay variant — which has nothing to do and is gone
-    // in microseconds — i.e. until the long variant is being dispatched.  With short replays (or when the host's idea of the
-    // list is out of date) nobody waits for anybody.
+    // The lean grid waits for an event recorded behind the short-replay variant — which has nothing to do and is gone in
+    // microseconds — i.e. until the long variant is being dispatched.  The hold dates from when a long replay was a 256-register
+    // wave and the batch's long pole (arriving behind 16 384 lean episodes it waited for two of them to finish on its SIMD: 5.6
+    // instead of 4.95 ms per batch at 468 generators per replay).  Today a long replay is a 123-register wave of k_replay_lazy /
+    // k_replay_solo in one slot, and at 228 generators per replay the lean grid ends the batch, so the hold (a 23 us grid and a
+    // 6 us hop in the trace) sits on the critical path there; at 468 and 916 generators the replays still end it.  Launching the
+    // replay kernel first and letting the lean grid go without the hold has not been measured: the order stands as it was.
+    // With short replays (or when the host's idea of the list is out of date) nobody waits for anybody.
     // (the hoisted replay is one workgroup that needs a whole CU: it is dispatched ahead of the lean grid in any case)
     if (list_long || plan.hoist_seq != 0ull) plan.go_event = c->ev_go[slot];
   }

@@ -2,7 +2,8 @@
 // record buffer, and the reductions that decide what a run keeps run over it — the folds launch_batch runs behind a real batch (through the
 // helpers it calls), k_pick_best, k_refine_pick_many — and a crafted generation of eg_breed_plans / eg_explore_plans: tagged plan blocks
 // folded into the private archive, gathered and turned over — through the archive functions the entry points run (eg_plan_host.cpp).
-// Host code only: no kernel is launched here that a run does not launch.
+// Host code only: no kernel is launched here that a run does not launch — but for eg_debug_tiles_refresh, whose one-wave kernel exists to
+// call a device function of the replay kernels (eg_field.h tiles_refresh) on a crafted list and field.
 #include <cstring>
 
 #include "eg_host.h"
@@ -149,6 +150,33 @@ int32_t eg_debug_refine_pick_many(eg_ctx* c, int32_t mode, const uint32_t* seg_f
     if (at != n) { set_error("eg_debug_refine_pick_many: the segments cover " + std::to_string(at) + " of the last batch's " + std::to_string(n) + " records"); return EG_ERR_BAD_ARG; }
   }
   return refine_pick(c, mode, seg_first, seg_count, n_segs, entries, base_blocks);
+}
+
+// ---- the lazy field's catch-up for one pair of tiles: a crafted list and a crafted class field, one wave (k_debug_tiles_refresh: the hook's own kernel
+//      around the device function the searches call) ------
+int32_t eg_debug_tiles_refresh(eg_ctx* c, const uint16_t* cells, int32_t n_cells, int32_t radius_class, int32_t tile_a, int32_t tile_b, double* field, int32_t* folded) {
+  if (!c || !field || !folded || (n_cells > 0 && !cells)) { set_error("eg_debug_tiles_refresh: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_tiles_refresh"));
+  auto fail = [](const std::string& m) { set_error("eg_debug_tiles_refresh: " + m); return EG_ERR_BAD_ARG; };
+  if (n_cells < 0 || n_cells > EG_MAX_GENS) return fail("n_cells = " + std::to_string(n_cells) + " (0..EG_MAX_GENS)");
+  for (int32_t i = 0; i < n_cells; ++i) if (cells[i] >= kCells) return fail("cells[" + std::to_string(i) + "] = " + std::to_string(cells[i]) + " is not a grid cell");
+  if (tile_a < 0 || tile_a >= kTiles || tile_b < -1 || tile_b >= kTiles || tile_b == tile_a) return fail("tiles " + std::to_string(tile_a) + ", " + std::to_string(tile_b) + " (0..48, distinct; tile_b -1: none)");
+  bool has_class = false;
+  for (int t = 0; t < kTypes; ++t) has_class = has_class || c->tables.H.rclass[t] == radius_class;
+  if (radius_class < 0 || radius_class >= kRadiusClasses || !has_class) return fail("radius_class " + std::to_string(radius_class) + " is no generator type's");
+  EG_HIP(hipSetDevice(c->device));
+  DevBuf<double> d_field; DevBuf<uint16_t> d_cells; DevBuf<int> d_out;
+  EG_HIP(d_field.reserve(EG_DEBUG_FIELD_DOUBLES)); EG_HIP(d_cells.reserve(size_t(EG_MAX_GENS))); EG_HIP(d_out.reserve(1));
+  EG_HIP(hipMemcpy(d_field, field, sizeof(double) * EG_DEBUG_FIELD_DOUBLES, hipMemcpyHostToDevice));
+  if (n_cells > 0) EG_HIP(hipMemcpy(d_cells, cells, sizeof(uint16_t) * size_t(n_cells), hipMemcpyHostToDevice));
+  EG_LAUNCH("k_debug_tiles_refresh", launch_debug_tiles_refresh(c->dev, d_field, d_cells, n_cells, radius_class, tile_a, tile_b, d_out, nullptr));
+  // (synchronous copies on the null stream: they wait for the kernel)
+  int out = 0;
+  EG_HIP(hipMemcpy(&out, d_out, sizeof(int), hipMemcpyDeviceToHost));
+  EG_HIP(hipMemcpy(field, d_field, sizeof(double) * EG_DEBUG_FIELD_DOUBLES, hipMemcpyDeviceToHost));
+  if (out < 0) return fail("the device found no generator type of radius class " + std::to_string(radius_class));
+  *folded = out;
+  return EG_OK;
 }
 
 // ---- a crafted generation of eg_breed_plans / eg_explore_plans: the private archive, k_breed_gather and the two turnover kernels ------

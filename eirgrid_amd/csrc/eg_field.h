@@ -432,39 +432,88 @@ static_assert(kNoTile >= kTiles && (kNoTile / kTileCols) * kTileW >= kGrid, "kNo
 constexpr int kTileCounters = kCells + 1;      // (in doubles, class-relative)
 static_assert((kFieldStride - kTileCounters) * 8 >= kTiles * 2 && EG_MAX_GENS <= 0xFFFF, "a 16-bit counter per tile fits behind a class's cells");
 // `fa`, `fb`: the lane's stored field values of tiles ta, tb (tb may be kNoTile) — on return current, and stored with the tiles'
-// counters; `applied`: the class's counters, a tile per lane.  The generators pass by in blocks of 64, one per lane; a lane-parallel
-// test keeps those within `reach` of either tile's box, and their factors are multiplied in one generator at a time (list order).
-// No control flow per generator and tile: one the tile already holds, or that only reaches the other tile, multiplies by the table's
-// 1.0 (measured: uniform branches around the two halves, an exact distance test and stores only for tiles that changed cost a search
-// 9 % more cycles than they saved).  A lane whose cell is off the grid folds along and stores nothing.
-// returns the generators folded
+// counters; `applied`: the class's counters, a tile per lane.  The generators pass by in blocks of 64, one per lane, and are folded the
+// way the lean kernel folds a chunk (chunk_product), whose loop is bound by its instruction count as this one is:
+//   1. a lane-parallel test finds, per tile, the generators the tile still needs — index at or beyond the tile's counter, inside the
+//      list, within `reach` of the tile's box — and those are compacted, in list order, into a staging row per tile: the lane stores
+//      its generator's (gi, gj), two int16, at the count of needed generators in the lanes below it.  The rows are Smem::gstage's two:
+//      nothing keeps them across a tile round here (place_tiles writes its candidates to row 1 behind its tile loop, heavy_exact's
+//      chunk_product stages row 0 anew for every chunk, and the replay kernels' place_search does not keep row 0).  A row of odd
+//      length is padded with chunk_product's generator far off the grid; the eight entries behind a row stay that padding.
+//   2. a row comes back two generators at a time in one broadcast 64-bit read; per generator factor_at's sequence against the lane's
+//      packed cell — packed subtract, dot product, cap, address, table read — and the multiply, in list order.  The two tiles' chains are
+//      independent: as long as both rows last, a trip takes a pair of each — four table reads in flight, then the two chains' multiplications
+//      interleaved, with the next trip's pairs requested in between.  The longer row's rest follows alone.
+//      Pairs, not chunk_product's groups of four with two register sets taking turns: k_replay_lazy keeps its episode in registers across
+//      the call of place_tiles, which therefore has the 70 registers it had and no more.  Groups of four of both tiles with two sets made
+//      it 120 wide and the kernel spill 36 registers; one set 88 and 8; one set filled in halves 84 and 4; pairs 70 and none (the
+//      compiler's resource report each time).  A pair also wastes half a generator's instructions on padding where a group wastes 1.5.
+// The same bits as folding every generator into both tiles: the factors are the same table entries by the same squared distances
+// (whole cells: the dot product is exact), multiplied in the same order, and every multiplication left out — a generator the tile
+// already holds, one beyond the list, one that does not reach the tile's box — is one by the table's 1.0 at the cap, and
+// x * 1.0 == x.  A row's padding multiplies by that 1.0.  A lane whose cell is off the grid folds along and stores nothing.
+// Per generator and tile that is six vector instructions and half a row read, where the loop it replaces — a readlane and two unpacks
+// per generator, then distance, cap, "already held", address, read and multiply per tile — took about fourteen.
+// returns the generators folded (one that both tiles need counts once)
+static_assert(sizeof(sm.gstage[0]) >= (kWave + 2) * sizeof(int) && sizeof(sm.gstage[0]) % 8 == 0, "a row's padding and read-ahead stay inside the row");
+constexpr int kGenPadFar = (int)0xC000C000;      // (chunk_product's: gi = gj = -16384, beyond every cap)
 __device__ __forceinline__ int tiles_refresh(unsigned long long a_s, int applied, int ta, int tb, int lane, int rc, int tbl, int reach, int ngen_s,
                                              unsigned long long tail_cells, double& fa, double& fb) {
-  const int cap = factor_cap<false>(tbl);
+  (void)rc;
+  const int dr_off = tbl & 0xFFFF, cap = factor_cap<false>(tbl);
   const int ra = (ta / kTileCols) * kTileW, ca = (ta % kTileCols) * kTileW, rb = (tb / kTileCols) * kTileW, cb = (tb % kTileCols) * kTileW;
   const int ia = ra + (lane >> 3), ja = ca + (lane & 7), ib = rb + (lane >> 3), jb = cb + (lane & 7);
+  const short2v cpa = __builtin_bit_cast(short2v, ia | (ja << 16)), cpb = __builtin_bit_cast(short2v, ib | (jb << 16));      // (small, not negative)
   const int aa = __builtin_amdgcn_readlane(applied, ta), ab = tb < kTiles ? __builtin_amdgcn_readlane(applied, tb) : ngen_s;
   fa = aa == 0 ? 1.0 : fa; fb = ab == 0 ? 1.0 : fb;
   int folded = 0;
   const unsigned span = (unsigned)(kTileW - 1 + 2 * reach);
+  const int2* rowa = reinterpret_cast<const int2*>(sm.gstage[0]);
+  const int2* rowb = reinterpret_cast<const int2*>(sm.gstage[1]);
   for (int gb = (aa < ab ? aa : ab) & ~(kWave - 1); gb < ngen_s; gb += kWave) {
     const int gc = list_cell(tail_cells, gb, lane, ngen_s, 0), g = gb + lane;
     const int gi = gc / kGrid, gj = gc - gi * kGrid;
     const bool na = g >= aa && g < ngen_s && (unsigned)(gi - ra + reach) <= span && (unsigned)(gj - ca + reach) <= span;
     const bool nb = g >= ab && g < ngen_s && (unsigned)(gi - rb + reach) <= span && (unsigned)(gj - cb + reach) <= span;
-    const int gij = gi | (gj << 8);
-    unsigned long long near = __ballot(na || nb);
-    while (near != 0ull) {
-      const int j = __ffsll((long long)near) - 1;
-      const int w = __builtin_amdgcn_readlane(gij, j), si = w & 255, sj = w >> 8;
-      int qa = (ia - si) * (ia - si) + (ja - sj) * (ja - sj), qb = (ib - si) * (ib - si) + (jb - sj) * (jb - sj);
-      qa = qa < cap && gb + j >= aa ? qa : cap;      // (a generator the tile already holds: 1.0, like one out of reach)
-      qb = qb < cap && gb + j >= ab ? qb : cap;
-      fa = fa * factor_by_q<false>(rc, tbl, qa);
-      fb = fb * factor_by_q<false>(rc, tbl, qb);
-      near &= near - 1ull;
-      ++folded;
+    const unsigned long long ma = __ballot(na), mb = __ballot(nb);
+    if ((ma | mb) == 0ull) continue;      // (uniform, once a block)
+    // 1. the two rows
+    const int gp = gi | (gj << 16);
+    if (na) sm.gstage[0][__builtin_amdgcn_mbcnt_hi((unsigned)(ma >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ma, 0u))] = gp;
+    if (nb) sm.gstage[1][__builtin_amdgcn_mbcnt_hi((unsigned)(mb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mb, 0u))] = gp;
+    const int cnt_a = __popcll(ma), cnt_b = __popcll(mb);      // (at most 64: the padding then falls on the row's own tail)
+    if (lane == 0) { sm.gstage[0][cnt_a] = kGenPadFar; sm.gstage[1][cnt_b] = kGenPadFar; }
+    asm volatile("" ::: "memory");      // LDS executes a wave's accesses in program order: only the compiler must keep it
+    folded += __popcll(ma | mb);
+    const int pairs_a = (cnt_a + 1) >> 1, pairs_b = (cnt_b + 1) >> 1, both = pairs_a < pairs_b ? pairs_a : pairs_b;
+    // 2. both tiles, pair by pair
+    if (both > 0) {
+      double a0, a1, b0, b1;
+      int2 ga = rowa[0], gq = rowb[0];
+#pragma nounroll
+      for (int k = 0; k < both; ++k) {
+        a0 = factor_at(cpa, ga.x, dr_off, cap); b0 = factor_at(cpb, gq.x, dr_off, cap); a1 = factor_at(cpa, ga.y, dr_off, cap); b1 = factor_at(cpb, gq.y, dr_off, cap);
+        __builtin_amdgcn_sched_barrier(0);
+        ga = rowa[k + 1]; gq = rowb[k + 1];      // (the next trip's, into the registers the addresses have left; behind the last pair: padding, or the row's own tail)
+        fa = fa * a0; fb = fb * b0; fa = fa * a1; fb = fb * b1;
+      }
     }
+    // ... and the rest of the longer row
+#define EG_TR_REST(row2, cpk, s, n_pairs)                                                                                          \
+    {                                                                                                                              \
+      double a0, a1;                                                                                                               \
+      int2 gcur = row2[both];                                                                                                      \
+      _Pragma("nounroll") for (int k = both; k < n_pairs; ++k) {                                                                   \
+        a0 = factor_at(cpk, gcur.x, dr_off, cap); a1 = factor_at(cpk, gcur.y, dr_off, cap);                                        \
+        __builtin_amdgcn_sched_barrier(0);                                                                                         \
+        gcur = row2[k + 1];                                                                                                        \
+        s = s * a0; s = s * a1;                                                                                                    \
+      }                                                                                                                            \
+    }
+    if (pairs_a > both) EG_TR_REST(rowa, cpa, fa, pairs_a)
+    else if (pairs_b > both) EG_TR_REST(rowb, cpb, fb, pairs_b)
+#undef EG_TR_REST
+    asm volatile("" ::: "memory");
   }
   if (ia < kGrid && ja < kGrid) *(GlobalF64)(a_s + (unsigned long long)((unsigned)(ia * kGrid + ja) * 8u)) = fa;
   if (ib < kGrid && jb < kGrid) *(GlobalF64)(a_s + (unsigned long long)((unsigned)(ib * kGrid + jb) * 8u)) = fb;

@@ -365,6 +365,8 @@ int launch_rollout(const DevTables& t, const DevSnapshot& s, const DevOut& o, ui
                    uint32_t n, const uint8_t* d_replay_mask, uint32_t replay_period, long long* d_stats, const RolloutPlan& plan);
 int launch_fill_lds(uint32_t value, uint32_t* d_sink, int n_workgroups, void* stream);      // test hook
 int launch_occupy(int variant, unsigned long long cycles, uint32_t* d_sink, void* stream);      // diagnostic hook (eg_debug_occupy)
+// test hook (eg_debug_tiles_refresh): the lazy field's catch-up of one pair of tiles on one wave (tile_b -1: none); d_out: one int
+int launch_debug_tiles_refresh(const DevTables& t, double* d_field, const uint16_t* d_cells, int n_cells, int radius_class, int tile_a, int tile_b, int* d_out, void* stream);
 int launch_stalled_tables(uint8_t* d_snap, void* stream);
 // d_snap = d_held, except the count of failed episodes, which goes on counting (eg_policy_rewind)
 // (`list_len_out`: pinned host word, may be null — the length of the best list as the device now holds it, for the host's launch planning)

@@ -285,3 +285,24 @@ __global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_replay_lazy(DevTables
                                                                        EpisodeMap emap) {
   replay_solo_episode<true>(T, S_in, O, first_index, n_episodes, replay_mask, replay_period, stats, emap);
 }
+// Test hook (eg_debug_tiles_refresh): ONE wave brings a pair of tiles of a crafted class field up to date against a crafted list — the
+// lazy field's catch-up (eg_field.h tiles_refresh) as a search calls it: the list's window in LDS, its tail at `cells_addr`, the tiles'
+// stored values and the class's counters read from the field.  out[0]: the generators folded, or -1 (no type of that radius class)
+__global__ void __launch_bounds__(kWave, EG_HEAVY_WAVES) k_debug_tiles_refresh(DevTables T, unsigned long long field_addr, unsigned long long cells_addr, int n_cells, int rc,
+                                                                               int ta, int tb, int* out) {
+  const int lane = threadIdx.x;
+  load_static_tables(T, lane, true);
+  for (int i = lane; i < kLdsGens && i < n_cells; i += kWave) sm.gcell[i] = (uint16_t)tail_u16(cells_addr, i);
+  wave_sync();
+  int info = 0, type = -1;      // (the info word's top byte is a table offset: any sign)
+  for (int t = kTypes - 1; t >= 0; --t) { const int w = sm.type_info[t]; if (((w >> 4) & 15) == rc) { info = w; type = t; } }
+  info = __builtin_amdgcn_readfirstlane(info);
+  if (__builtin_amdgcn_readfirstlane(type) < 0) { if (lane == 0) out[0] = -1; return; }
+  const int applied = lane < kTiles ? tail_u16(field_addr + 8ull * kTileCounters, lane) : 0;
+  const int ia = (ta / kTileCols) * kTileW + (lane >> 3), ja = (ta % kTileCols) * kTileW + (lane & 7);
+  const int ib = (tb / kTileCols) * kTileW + (lane >> 3), jb = (tb % kTileCols) * kTileW + (lane & 7);
+  const int ca = ia < kGrid && ja < kGrid ? ia * kGrid + ja : 0, cb = ib < kGrid && jb < kGrid ? ib * kGrid + jb : 0;
+  double fa = field_load((GlobalF64)field_addr + ca), fb = field_load((GlobalF64)field_addr + cb);
+  const int folded = tiles_refresh(field_addr, applied, ta, tb, lane, rc, throughput_table(info), (info >> 8) & 15, __builtin_amdgcn_readfirstlane(n_cells), cells_addr, fa, fb);
+  if (lane == 0) out[0] = folded;
+}

@@ -2023,6 +2023,15 @@ int launch_rollout_throughput(int kind, const DevTables& t, const DevSnapshot& s
 #undef EG_LAUNCH_TP
   return (int)hipGetLastError();
 }
+// test hook (eg_debug_tiles_refresh): one wave; `tile_b` -1: the lone last tile of a round.  The caller has checked the tiles, the class
+// and the cells; the field is a class's kFieldStride doubles.
+int launch_debug_tiles_refresh(const DevTables& t, double* d_field, const uint16_t* d_cells, int n_cells, int radius_class, int tile_a, int tile_b, int* d_out, void* stream) {
+  static_assert(kFieldStride == EG_DEBUG_FIELD_DOUBLES && kTileCounters == EG_DEBUG_TILE_COUNTERS && kTiles == EG_DEBUG_TILES && kTileW == EG_DEBUG_TILE_WIDTH,
+                "the class field is what the hook documents");
+  hipLaunchKernelGGL(k_debug_tiles_refresh, dim3(1), dim3(kWave), 0, (hipStream_t)stream, t, (unsigned long long)d_field, (unsigned long long)d_cells, n_cells, radius_class,
+                     tile_a, tile_b < 0 ? kNoTile : tile_b, d_out);
+  return (int)hipGetLastError();
+}
 #else
 namespace {
 template <int kKind>

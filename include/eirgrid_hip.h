@@ -842,6 +842,21 @@ int32_t eg_debug_breed_turnover(eg_ctx *, int32_t kind, int32_t next, int64_t m_
 int32_t eg_debug_breed_fetch(eg_ctx *, void *state /* EG_DEBUG_PARETO_STATE_BYTES */, uint8_t *blocks /* EG_PARETO_MAX * EG_PLAN_BLOCK_BYTES */,
                              uint8_t *array0 /* EG_PARETO_MAX * EG_PLAN_BLOCK_BYTES */, uint8_t *array1 /* likewise */,
                              uint8_t *readback /* EG_DEBUG_BREED_READBACK_BYTES */, void *counters /* 16 bytes */, uint64_t *tags /* [EG_PARETO_MAX] */);
+/* Test hook: the lazy penalty field's catch-up (csrc/eg_field.h tiles_refresh) for ONE pair of tiles on one wave, as a search of
+ * k_replay_lazy calls it, against a crafted generator list.  `cells`: the list, n_cells (0..EG_MAX_GENS) grid cells i * EG_GRID + j in
+ * list order (the first EG_ONCHIP_GENS go to LDS, the rest are read where a record keeps them); radius_class 0..5 (one a generator
+ * type has); tile_a 0..EG_DEBUG_TILES - 1, tile_b likewise and not tile_a, or -1: none (tile t covers the rows (t / 7) * 8 .. + 7 and
+ * the columns (t % 7) * 8 .. + 7 of the grid, edge tiles 3 wide).  `field`, in and out, is the class's field as a slot of the pool holds
+ * it: EG_DEBUG_FIELD_DOUBLES doubles — the value of cell c at [c], and from double EG_DEBUG_TILE_COUNTERS on, as 16-bit words, how many
+ * generators of the list each tile's stored values hold (0: none, the values count as 1.0 whatever is stored).  On return the two
+ * tiles' values are current, their counters n_cells, and nothing else has changed.  `folded`: the generators the call folded (one
+ * that both tiles need counts once).  Refuses a rank of a group. */
+#define EG_DEBUG_FIELD_DOUBLES 2624
+#define EG_DEBUG_TILE_COUNTERS 2602
+#define EG_DEBUG_TILES 49
+#define EG_DEBUG_TILE_WIDTH 8
+int32_t eg_debug_tiles_refresh(eg_ctx *, const uint16_t *cells /* [n_cells] */, int32_t n_cells, int32_t radius_class, int32_t tile_a, int32_t tile_b,
+                               double *field /* EG_DEBUG_FIELD_DOUBLES */, int32_t *folded);
 /* Diagnostic hook: ONE idle workgroup of 256 threads on the library's side stream that stays resident for `cycles` shader cycles;
  * variant 0: 1 KB of LDS, few registers; 1: 150 KB of LDS; 2: 200+ registers a lane; 3: both (the hoisted replay's footprint).  What a
  * resident workgroup costs the grid beside it: scripts/side_kernel_probe.py, profiles/r04_ab_notes.log. */
