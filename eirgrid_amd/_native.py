@@ -19,7 +19,7 @@ CANDIDATE_BYTES = 8 + 8 + 32 + 4 * YEARS + 4 * YEARS + RUN_CAP + DEF_CAP
 PACKET_BYTES = 8 * STATS_LEN + CANDIDATE_BYTES
 
 EG_OK, EG_ERR_NO_DEVICE, EG_ERR_BAD_ARG, EG_ERR_HIP, EG_ERR_UNSUPPORTED, EG_ERR_NOMEM, EG_ERR_INTERNAL = 0, -1, -2, -3, -4, -5, -6
-EG_EP_OK, EG_EP_OVERFLOW, EG_EP_NO_LOCATION, EG_EP_INTERNAL = 0, -1, -2, -3
+EG_EP_OK, EG_EP_OVERFLOW, EG_EP_NO_LOCATION, EG_EP_INTERNAL, EG_EP_INFEASIBLE = 0, -1, -2, -3, -4
 
 # EIRGRID_LIB selects another build of the same library (only used for the -DEG_STAMPS diagnostic build)
 LIB_PATH = os.environ.get("EIRGRID_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "libeirgrid_hip.so")
@@ -133,6 +133,12 @@ class EgExploreMember(C.Structure):
                 ("score", C.c_double), ("metrics", C.c_double * 4)]
 
 
+class EgPlanConstraint(C.Structure):
+    _fields_ = [("column", C.c_uint8), ("aggregate", C.c_uint8), ("op", C.c_uint8), ("from_year", C.c_uint8), ("to_year", C.c_uint8), ("pad", C.c_uint8 * 3),
+                ("bound", C.c_double)]
+
+
+assert C.sizeof(EgPlanConstraint) == 16
 assert C.sizeof(EgPlanMove) == 12 and C.sizeof(EgPlanCross) == 6
 assert C.sizeof(EgActionMap) == 61 and C.sizeof(EgPlanRewrite) == 8
 assert C.sizeof(EgExploreOpts) == 64 and C.sizeof(EgExploreGeneration) == 40 and C.sizeof(EgExploreMember) == 88
@@ -147,6 +153,12 @@ CROSS_MAX_VARIANTS = 16384       # EG_CROSS_MAX_VARIANTS
 REWRITE_DROP = 0xFF              # EG_REWRITE_DROP
 REWRITE_MAX_MAPS = 256           # EG_REWRITE_MAX_MAPS
 REWRITE_MAX_VARIANTS = 16384     # EG_REWRITE_MAX_VARIANTS
+CONSTRAINTS_MAX, CONSTRAINT_SPEC_MAX = 32, 96      # EG_CONSTRAINTS_MAX, EG_CONSTRAINT_SPEC_MAX
+AGG_EVERY, AGG_SUM, OP_LE, OP_GE = 0, 1, 0, 1      # EG_AGG_*, EG_OP_*
+# the lower-case EG_Y_* names, in column order: what eg_plan_constraint_parse reads as COLUMN
+YEARLY_COLUMNS = ("year", "pop", "usage", "gen", "balance", "opinion", "yearly_capital", "total_capital", "inflation", "co2", "offset", "net_co2",
+                  "yearly_credit", "total_credit", "yearly_sales", "total_sales", "active_gens", "upgrade_costs", "closure_costs", "yearly_total_cost",
+                  "total_cost")
 BREED_CONVERGED, BREED_MAX_GENERATIONS, BREED_EMPTY = 0, 1, 2      # EG_BREED_*
 EXPLORE_EXPLORED, EXPLORE_MAX_GENERATIONS, EXPLORE_EMPTY, EXPLORE_BUDGET = 0, 1, 2, 3      # EG_EXPLORE_*
 PLAN_BLOCK_BYTES = 8832      # EG_PLAN_BLOCK_BYTES
@@ -191,6 +203,8 @@ EXPORTS = [
     "eg_plan_moves_validate", "eg_evaluate_plan_moves", "eg_refine_plans_moves_validate", "eg_refine_plans_moves",
     "eg_plan_crosses_validate", "eg_evaluate_plan_crosses", "eg_plan_rewrites_validate", "eg_evaluate_plan_rewrites",
     "eg_breed_validate", "eg_breed_plans", "eg_explore_validate", "eg_explore_neighbourhood", "eg_explore_plans",
+    "eg_plan_constraints_validate", "eg_plan_constraints_set", "eg_fetch_plan_feasibility", "eg_last_batch_constraints", "eg_plan_constraint_parse", "eg_plan_constraint_format",
+    "eg_debug_load_yearly", "eg_debug_constrain_last_batch",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -407,6 +421,24 @@ def lib():
         L.eg_explore_plans.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgExploreOpts),
                                        C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgExploreGeneration),
                                        C.POINTER(EgExploreMember), C.POINTER(C.c_int64), _i32p, _i32p, C.POINTER(EgEpisodeOut)]
+    # (likewise: an A/B build named by EIRGRID_LIB may predate plan constraints)
+    if hasattr(L, "eg_plan_constraints_set") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_plan_constraints_validate.restype = C.c_int32
+        L.eg_plan_constraints_validate.argtypes = [C.POINTER(EgPlanConstraint), C.c_int32]
+        L.eg_plan_constraints_set.restype = C.c_int32
+        L.eg_plan_constraints_set.argtypes = [C.c_void_p, C.POINTER(EgPlanConstraint), C.c_int32]
+        L.eg_fetch_plan_feasibility.restype = C.c_int32
+        L.eg_fetch_plan_feasibility.argtypes = [C.c_void_p, _u32p, _dp]
+        L.eg_last_batch_constraints.restype = C.c_int32
+        L.eg_last_batch_constraints.argtypes = [C.c_void_p, C.POINTER(EgPlanConstraint)]
+        L.eg_plan_constraint_parse.restype = C.c_int32
+        L.eg_plan_constraint_parse.argtypes = [C.c_char_p, C.POINTER(EgPlanConstraint)]
+        L.eg_plan_constraint_format.restype = C.c_int32
+        L.eg_plan_constraint_format.argtypes = [C.POINTER(EgPlanConstraint), C.c_char_p, C.c_int32]
+        L.eg_debug_load_yearly.restype = C.c_int32
+        L.eg_debug_load_yearly.argtypes = [C.c_void_p, _dp, C.c_uint32]
+        L.eg_debug_constrain_last_batch.restype = C.c_int32
+        L.eg_debug_constrain_last_batch.argtypes = [C.c_void_p]
     if hasattr(L, "eg_pareto_track") or not os.environ.get("EIRGRID_LIB"):
         L.eg_pareto_track.restype = C.c_int32
         L.eg_pareto_track.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]

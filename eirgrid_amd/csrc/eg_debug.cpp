@@ -1,6 +1,6 @@
 // eg_debug.cpp — the crafted-batch test hooks (include/eirgrid_hip.h, debug section): a batch of synthetic records in the context's
 // record buffer, and the reductions that decide what a run keeps run over it — the folds launch_batch runs behind a real batch (through the
-// helpers it calls), k_pick_best, k_refine_pick_many — and a crafted generation of eg_breed_plans / eg_explore_plans: tagged plan blocks
+// helpers it calls), k_pick_best, k_refine_pick_many, k_plan_constraints over crafted yearly rows — and a crafted generation of eg_breed_plans / eg_explore_plans: tagged plan blocks
 // folded into the private archive, gathered and turned over — through the archive functions the entry points run (eg_plan_host.cpp).
 // Host code only: no kernel is launched here that a run does not launch — but for eg_debug_tiles_refresh, whose one-wave kernel exists to
 // call a device function of the replay kernels (eg_field.h tiles_refresh) on a crafted list and field.
@@ -88,8 +88,26 @@ int32_t eg_debug_load_batch(eg_ctx* c, const double* metrics, const int32_t* sta
   if (n_act) EG_TRY(put_field(c, rec::n_act, n_act, EG_YEARS * sizeof(int32_t), n));
   if (act_log) EG_TRY(put_field(c, rec::act_log, act_log, EG_ACT_CAP, n));      // the whole row: also what lies behind the log
   if (score_list) EG_HIP(hipMemcpy(c->out.score_list, score_list, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
-  c->last_n = n; c->last_first = first_index;
+  c->last_n = n; c->last_first = first_index; c->feas_k = 0;
   return EG_OK;
+}
+
+// ---- plan constraints over a crafted batch: the rows, then the launch a plan batch ends with (eg_plan_constraints.cpp constrain_batch) ------
+int32_t eg_debug_load_yearly(eg_ctx* c, const double* yearly, uint32_t n) {
+  if (!c || !yearly) { set_error("eg_debug_load_yearly: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_load_yearly"));
+  if (n == 0 || n != c->last_n) { set_error("eg_debug_load_yearly: n = " + std::to_string(n) + ", the last batch holds " + std::to_string(c->last_n) + " records"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  return put_field(c, rec::yearly, yearly, sizeof(double) * EG_YEARS * EG_YEARLY_FIELDS, n);
+}
+
+int32_t eg_debug_constrain_last_batch(eg_ctx* c) {
+  if (!c) { set_error("eg_debug_constrain_last_batch: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_constrain_last_batch"));
+  if (c->last_n == 0) { set_error("eg_debug_constrain_last_batch: there is no last batch"); return EG_ERR_BAD_ARG; }
+  if (c->n_constraints == 0) { set_error("eg_debug_constrain_last_batch: eg_plan_constraints_set first (no constraints are set)"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  return constrain_batch(c, c->last_n);
 }
 
 int32_t eg_debug_fold_last_batch(eg_ctx* c, int32_t what, int32_t use_score_list) {

@@ -1,4 +1,4 @@
-// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_debug / eg_plans / eg_plan_host / eg_refine / eg_breed / eg_explore /
+// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_debug / eg_plans / eg_plan_host / eg_plan_constraints / eg_refine / eg_breed / eg_explore /
 // eg_place / eg_group .cpp): owned buffers, the error macros, the context and the helpers that cross units, listed by the unit that holds them.  Host only: the kernels include eg_internal.h, never this.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -142,6 +142,13 @@ struct eg_ctx {
   //  batch, eg_evaluate_plan_rewrites: every plan's block, the maps, then the packed rewrites — what k_plan_rewrites reads)
   eg::DevBuf<uint8_t> d_plan_edit_in;
   size_t n_plan_blocks = 0;      // blocks of the last plan or plan-edit batch in d_plans (eg_debug_fetch_plan_block)
+  // plan constraints (eg_plan_constraints_set; eg_plan_constraints.cpp): the n_constraints constraints on the device, 16 bytes each, and
+  // the two side buffers k_plan_constraints fills behind a plan batch — a mask per record, an excess row of feas_k doubles per record.
+  // feas_k: the constraints the last batch was judged under, 0 when it was not (every batch that sets last_n sets it)
+  // constraints / judged: host copies of what is set and of what the last judged batch ran under (eg_last_batch_constraints)
+  eg::DevBuf<uint8_t> d_constraints; int n_constraints = 0;
+  eg::DevBuf<uint32_t> d_violated; eg::DevBuf<double> d_excess; int feas_k = 0;
+  eg_plan_constraint constraints[EG_CONSTRAINTS_MAX] = {}, judged[EG_CONSTRAINTS_MAX] = {};
   // plan refinement (eg_refine_plan, eg_refine_plans): the step log k_refine_pick_many writes, an entry per plan of a launch from the
   // start (kRefineLog entries of kRefineEntryStride bytes); the base blocks of the call's plans (uploaded once, kept current by
   // k_refine_pick_many) and what a launch uploads in one copy: the packed edits, the base slot of every variant, the segment table
@@ -185,6 +192,10 @@ int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x);
 // ... a set's plan blocks, and the reverse: n plan blocks read back from the device (host memory) decoded into a plan set (names "")
 void write_plan_blocks(const eg_plan_set* p, uint8_t* dst);
 int decode_plan_blocks(const uint8_t* blocks, int32_t n, const char* who, eg_plan_set** set);
+
+// eg_plan_constraints.cpp: k_plan_constraints over the n records of c->out under the context's constraints (at least one is set), on the
+// null stream; the side buffers reserved, c->feas_k set
+int constrain_batch(eg_ctx* c, uint32_t n);
 
 // eg_plan_host.cpp: the pieces a plan search is written from.  `fn` / `who` name the entry point in the messages.
 // Behind an entry point's own NULL test: a rank of a group is refused, then `validate` runs, then check_policy, then hipSetDevice

@@ -535,6 +535,10 @@ int launch_plan_crosses(const uint8_t* d_parents, uint32_t n_parents, const void
 constexpr size_t kRewriteMapStride = 64;
 int launch_plan_rewrites(const uint8_t* d_plans, uint32_t n_plans, const uint8_t* d_maps, uint32_t n_maps, const void* d_rewrites, uint32_t n, uint8_t* d_pool,
                          void* stream);
+// k_plan_constraints (eg_plan_constraints.h): the k constraints at d_constraints (eg_plan_constraint, 16 bytes each, 1..EG_CONSTRAINTS_MAX)
+// judged over the n records of o: d_violated[j] the mask of the constraints record j violates, d_excess[j * k + i] its excess of
+// constraint i; a record that ended EG_EP_OK with a mask that is not zero becomes EG_EP_INFEASIBLE, nothing else of a record is written
+int launch_plan_constraints(const DevOut& o, uint32_t n, const void* d_constraints, uint32_t k, uint32_t* d_violated, double* d_excess, void* stream);
 // Generations of crosses (include/eirgrid_hip.h eg_breed_plans; eg_breed.h, eg_breed.cpp).  The private archive of a call, one buffer
 // kept with the context: a ParetoState and EG_PARETO_MAX record slots exactly as eg_pareto_track lays them out (so launch_pareto_fold
 // folds into it), a plan BLOCK slot per record slot, two parent arrays of EG_PARETO_MAX blocks (this generation's, the next one's), the

@@ -79,7 +79,8 @@ DevSnapshot eg::snapshot_of(uint8_t* d_base, const eg_opts* o) {
 // A plan batch (eg_evaluate_plans) over the n episodes of c->out: c->d_plan_index lists the n_short short plans (<= kShortReplayMax
 // actions), then the long ones.  The short-replay variant runs over exactly the short ones; the long ones go to k_replay_solo and the
 // long-replay variant, in launches of at most as many episodes as the penalty-field pool has slots (a long replay claims one per
-// launch epoch).  The hoist, the statistics epilogue and the best_result / top-K folds do not run.
+// launch epoch).  The hoist, the statistics epilogue and the best_result / top-K folds do not run.  With plan constraints set
+// (eg_plan_constraints_set) k_plan_constraints runs behind the last grid, once, over the n records.
 int eg::launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index) {
   const uint32_t n_long = n - n_short;
   const bool helper = n <= c->helper_max_episodes;
@@ -100,8 +101,9 @@ int eg::launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t fi
     ring_commit(c, slot, 1);
     done += chunk;
   }
-  c->last_n = n; c->last_first = first_index;
-  return EG_OK;
+  c->last_n = n; c->last_first = first_index; c->feas_k = 0;
+  // the context's constraints over all n records, behind the grids on their stream: what the caller enqueues next reads the demoted statuses
+  return c->n_constraints > 0 ? constrain_batch(c, n) : EG_OK;
 }
 // The policy a plan batch is evaluated under into a device snapshot of its own (c->d_eval_snap) — has_best = 1 and lists present
 // (empty: every episode reads its plan block instead) — with its stalled-sampler tables; *S: what the launches get, the plan pool set.

@@ -26,6 +26,7 @@
 //   eg_plan_moves.h       k_plan_moves                                                                                      eg_rollout.o
 //   eg_plan_crosses.h     k_plan_crosses                                                                                    eg_rollout.o
 //   eg_plan_rewrites.h    k_plan_rewrites                                                                                   eg_rollout.o
+//   eg_plan_constraints.h k_plan_constraints                                                                                eg_rollout.o
 //   eg_breed.h            k_breed_gather, k_breed_turnover                                                                  eg_rollout.o
 //   eg_explore.h          k_explore_turnover                                                                                eg_rollout.o
 //   eg_update_kernels.h   k_place .. k_apply_update: the kernels that are not rollouts                                      eg_rollout.o
@@ -1984,6 +1985,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_plan_moves.h"       // k_plan_moves: the plan blocks of the variants that move an entry to another year
 #include "eg_plan_crosses.h"     // k_plan_crosses: the plan blocks of the variants that splice one parent's years into another
 #include "eg_plan_rewrites.h"    // k_plan_rewrites: the plan blocks of the variants that apply an action map to a window of years
+#include "eg_plan_constraints.h" // k_plan_constraints: the context's plan constraints judged over a plan batch's records
 #include "eg_breed.h"            // k_breed_gather, k_breed_turnover: a generation's survivors become the next one's parents on the device
 #include "eg_explore.h"          // k_explore_turnover: the members that entered an exploration's archive become the next frontier
 
@@ -2306,6 +2308,12 @@ int launch_plan_rewrites(const uint8_t* d_plans, uint32_t n_plans, const uint8_t
   if (n == 0 || n_plans == 0 || n_maps == 0) return 0;
   hipLaunchKernelGGL(k_plan_rewrites, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, d_plans, n_plans, d_maps, n_maps,
                      reinterpret_cast<const uint2*>(d_rewrites), n, d_pool);
+  return (int)hipGetLastError();
+}
+int launch_plan_constraints(const DevOut& o, uint32_t n, const void* d_constraints, uint32_t k, uint32_t* d_violated, double* d_excess, void* stream) {
+  if (n == 0 || k == 0 || k > (uint32_t)EG_CONSTRAINTS_MAX) return n == 0 || k == 0 ? 0 : (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_plan_constraints, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, o, n, reinterpret_cast<const pcons::Packed*>(d_constraints), k, d_violated,
+                     d_excess);
   return (int)hipGetLastError();
 }
 int launch_breed_gather(uint8_t* d_breed, const DevOut& o, uint32_t n, uint64_t first, const uint8_t* d_pool, void* stream) {

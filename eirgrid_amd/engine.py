@@ -13,6 +13,7 @@ from dataclasses import dataclass, fields
 import numpy as np
 
 from . import _native as N
+from .constraints import Constraint, constraint_array, constraint_list
 from .world import World
 
 BASE_YEAR, END_YEAR = 2025, 2050
@@ -965,6 +966,61 @@ class Engine:
                                           C.c_uint64(first_episode_index), C.byref(out)), "eg_evaluate_plans")
         return res
 
+    def set_constraints(self, constraints) -> None:
+        """Plan constraints (eg_plan_constraints_set): a list of Constraint (or specs for Constraint.parse), at most 32; an empty list
+        clears them.  They hold for every later plan batch of this engine — evaluate_plans / _plan_edits / _plan_moves / _plan_crosses /
+        _plan_rewrites, refine_plan(s), breed_front, explore_front, cross_front, technology_report, plan_timing, plan_sensitivity: a variant
+        that ended EG_EP_OK and violates one comes back with status EG_EP_INFEASIBLE (metrics and rows untouched), and every search skips
+        it as it skips a failed variant.  So: refining an infeasible base stops with "base_failed"; a step's n_failed counts the
+        infeasible variants; explore_front from infeasible starts admits their feasible neighbours — the way to repair a plan.  Training
+        batches (rollout_batch, device_step, ...) are never judged.  While constraints are set the plan calls refuse write_yearly=False."""
+        cs = constraint_list(constraints)      # (walked and parsed once: a generator is fine)
+        arr, n = constraint_array(cs)
+        N.check(N.lib().eg_plan_constraints_set(self.h, arr, n), "eg_plan_constraints_set")
+        self._constraints = cs
+
+    def clear_constraints(self) -> None:
+        self.set_constraints([])
+
+    def last_batch_constraints(self) -> "list[Constraint]":
+        """The constraints the LAST batch was judged under (eg_last_batch_constraints) — not those set now; [] when it was not judged."""
+        arr = (N.EgPlanConstraint * N.CONSTRAINTS_MAX)()
+        k = N.lib().eg_last_batch_constraints(self.h, arr)
+        N.check(min(k, 0), "eg_last_batch_constraints")
+        return [Constraint._from_struct(arr[i]) for i in range(k)]
+
+    def fetch_feasibility(self):
+        """(violated [n] uint32, excess [n, k] float64) of the last plan batch (eg_fetch_plan_feasibility): bit i of violated[j] is set iff
+        variant j violates constraint i of last_batch_constraints() — the k constraints that were set when the batch ran, whatever has
+        been set or cleared since; excess[j, i] <= 0 means satisfied, its negative is the slack, NaN violates.  A variant that failed on
+        its own has mask 0 and a row of NaN.  Refused when the last batch ran without constraints."""
+        L = N.lib()
+        n, k = int(L.eg_last_batch_size(self.h)), int(L.eg_last_batch_constraints(self.h, None))
+        if k <= 0 or n == 0:      # the library's own refusal, nothing written
+            N.check(L.eg_fetch_plan_feasibility(self.h, None, None), "eg_fetch_plan_feasibility")
+            raise N.EirgridError("eg_fetch_plan_feasibility: the last batch ran without plan constraints")
+        violated, excess = np.zeros(n, np.uint32), np.zeros((n, k), np.float64)
+        N.check(L.eg_fetch_plan_feasibility(self.h, _p(violated, C.c_uint32), _p(excess, C.c_double)), "eg_fetch_plan_feasibility")
+        return violated, excess
+
+    def plan_feasibility(self, weights: ActionWeights, plans, seed: int, index: int = 0, constraints=None):
+        """Which of `plans` satisfy which constraints: evaluates them as evaluate_plans does (plan j at global index index + j) under
+        `constraints` (None: the ones that are set) and returns (status [n], violated: per plan the list of the violated Constraints,
+        excess [n, k]; a negative excess is the slack).  The engine's own constraints are as before afterwards."""
+        before = list(getattr(self, "_constraints", ()))
+        if constraints is not None:
+            self.set_constraints(constraints)
+        try:
+            if not getattr(self, "_constraints", ()):
+                raise ValueError("plan_feasibility: no constraints given and none set")
+            res = self.evaluate_plans(weights, plans, seed, index)
+            cs = self.last_batch_constraints()
+            mask, excess = self.fetch_feasibility()
+        finally:
+            if constraints is not None:
+                self.set_constraints(before)
+        return res.status.copy(), [[c for i, c in enumerate(cs) if (int(m) >> i) & 1] for m in mask], excess
+
     def evaluate_plan_edits(self, weights: ActionWeights, base: "Plan", edits, seed: int, first_index: int = 0, same_index: bool = True,
                             enable_energy_sales=True, write_yearly=True) -> BatchResult:
         """Score edits of one plan (eg_evaluate_plan_edits): variant j is `base` with edits[j] (PlanEdit) applied, evaluated as
@@ -1520,6 +1576,15 @@ class Engine:
         N.check(N.lib().eg_debug_load_batch(self.h, _p(m, C.c_double), _p(st, C.c_int32), None if na is None else _p(na, C.c_int32),
                                             None if al is None else _p(al, C.c_uint8), None if sl is None else _p(sl, C.c_double), n,
                                             C.c_uint64(int(first_index))), "eg_debug_load_batch")
+
+    def _debug_load_yearly(self, yearly) -> None:
+        """Test hook (eg_debug_load_yearly): the yearly rows [n,26,21] of the crafted batch _debug_load_batch made."""
+        y = np.ascontiguousarray(yearly, dtype=np.float64).reshape(-1, N.YEARS, N.YEARLY_FIELDS)
+        N.check(N.lib().eg_debug_load_yearly(self.h, _p(y, C.c_double), len(y)), "eg_debug_load_yearly")
+
+    def _debug_constrain_last_batch(self) -> None:
+        """Test hook (eg_debug_constrain_last_batch): k_plan_constraints over the last batch, as a plan batch ends."""
+        N.check(N.lib().eg_debug_constrain_last_batch(self.h), "eg_debug_constrain_last_batch")
 
     def _debug_fold_last_batch(self, best_result: bool = False, top_k: bool = False, use_score_list: bool = False) -> None:
         """Test hook (eg_debug_fold_last_batch): what a training batch runs behind its rollout for the chosen folds, on the last batch."""

@@ -76,6 +76,7 @@ extern "C" {
 #define EG_EP_OVERFLOW (-1)
 #define EG_EP_NO_LOCATION (-2)
 #define EG_EP_INTERNAL (-3)      /* the kernel's helper-wave protocol timed out (a defect, never an input property): eg_fetch* report EG_ERR_INTERNAL */
+#define EG_EP_INFEASIBLE (-4)    /* a variant of a plan batch that ended EG_EP_OK and violates a plan constraint (eg_plan_constraints_set) */
 
 /* yearly row columns: the scalar fields of YearlyMetrics, analysis/metrics.rs:7-31 */
 enum {
@@ -594,6 +595,69 @@ int32_t eg_plan_rewrites_validate(const eg_plan_set *plans, const eg_action_map 
 int32_t eg_evaluate_plan_rewrites(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, const eg_plan_set *plans /* 1..EG_CROSS_MAX_PARENTS */,
                                   const eg_action_map *maps, int32_t n_maps, const eg_plan_rewrite *rewrites, int32_t n_rewrites,
                                   uint64_t seed, uint64_t first_episode_index, int32_t same_index, eg_episode_out *out /* may be NULL */);
+
+/* Plan constraints: bounds on the yearly rows of a plan batch's records, enforced on the device.  The plan searches judge a variant by its
+ * four end-of-run metrics; "net zero from 2040 on", "no year's total cost above a budget", "the balance never below a reserve",
+ * "cumulative emissions under a carbon budget" are statements about the 26 x 21 yearly rows every record carries (EG_Y_*).  A context
+ * holds up to EG_CONSTRAINTS_MAX constraints; behind the rollout grids of every plan batch one kernel (csrc/eg_plan_constraints.h
+ * k_plan_constraints) judges them over the batch's records and DEMOTES the status of a variant that violates one to EG_EP_INFEASIBLE.
+ * Every search already skips a variant whose status is not EG_EP_OK, so every search becomes a constrained search.
+ * THE DEFINITION.  For one record with rows v[y][col] (y = 0..25) the EXCESS of a constraint {column, aggregate, op, from_year, to_year,
+ * bound} — the window is the years from_year <= y < to_year — is
+ *   EG_AGG_EVERY   x_y = v[y][column] - bound for EG_OP_LE, bound - v[y][column] for EG_OP_GE (one rounding).  e = x_from; then for
+ *                  y = from_year + 1 .. to_year - 1 in order: if e is NaN it stays, else if x_y is NaN or x_y > e then e = x_y.  The
+ *                  excess is e: the largest x_y, the first of equal ones (-0.0 and +0.0 are equal), and NaN once any x_y is NaN.
+ *   EG_AGG_SUM     s = v[from_year][column], then s = s + v[y][column] for y = from_year + 1 .. to_year - 1 in order (one rounding each,
+ *                  no fused multiply-add).  The excess is s - bound for EG_OP_LE and bound - s for EG_OP_GE.
+ * A NaN excess is reported as the canonical quiet NaN (bits 0x7FF8000000000000), whatever payload or sign the arithmetic gave it.  The
+ * constraint is SATISFIED iff excess <= 0; NaN violates.  A negative excess is the slack.  This literal order is the definition.
+ * AFTER A PLAN BATCH with k > 0 constraints set, for variant j of the batch:
+ *   status EG_EP_OK on entry     excess[j][0..k) as above; violated[j] has bit i set iff constraint i is violated; the status becomes
+ *                                EG_EP_INFEASIBLE iff violated[j] != 0.  The metrics and every other byte of the record are untouched.
+ *   any other status on entry    the status is untouched, violated[j] = 0 and the excess row is all (canonical) NaN.
+ * eg_plan_constraints_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the constraint's index and the field
+ * ("constraint 3: column 21 (an EG_Y_* column 0..20)") for n outside 0..EG_CONSTRAINTS_MAX, NULL constraints with n > 0, column > 20, an
+ * unknown aggregate or op, from_year >= to_year, to_year > 26 or a bound that is not finite.  eg_plan_constraints_set validates, then
+ * uploads the constraints (16 bytes each) to a device buffer of the context; n = 0 clears them.  A rank of a group is refused.  They hold
+ * for every later plan batch of the context — eg_evaluate_plans, _plan_edits, _plan_moves, _plan_crosses, _plan_rewrites,
+ * eg_refine_plan, eg_refine_plans, eg_refine_plans_moves, eg_breed_plans, eg_explore_plans: one launch at the end of every batch of
+ * variants these launch, on the stream the batch ran on, so the picks and folds enqueued behind it read the demoted statuses.  While
+ * constraints are set these calls refuse eg_opts.write_yearly = 0: the rows are what is judged.  Training batches (eg_rollout_batch,
+ * eg_rollout_launch, eg_train_step, eg_device_rollout, eg_device_step, groups) are never judged, and neither are their best_result,
+ * top-K and Pareto folds.  What follows for the searches: a refinement whose base is infeasible stops with EG_REFINE_BASE_FAILED; a
+ * step's n_failed counts the infeasible variants with the failed ones; eg_explore_plans from infeasible starts admits their feasible
+ * neighbours (the way to repair a plan), eg_breed_plans from infeasible parents keeps their feasible children only.
+ * eg_fetch_plan_feasibility serves the LAST batch (for a search: the last launch of the call): violated[n] and excess[n][k], n =
+ * eg_last_batch_size(), k the constraints that were set WHEN IT RAN — not those set now: setting or clearing constraints afterwards
+ * changes neither k nor what is served; either pointer may be NULL.  EG_ERR_BAD_ARG when the last batch ran without constraints (a
+ * training batch, a plan batch with none set, no batch at all).  eg_last_batch_constraints returns that k (0 when the last batch was
+ * not judged; EG_ERR_BAD_ARG for a NULL context) and copies the k constraints the batch was judged under into `out` unless it is NULL: a
+ * caller sizes the excess buffer from it.
+ * One parser for every front end: eg_plan_constraint_parse reads "[sum(]COLUMN[)] (<=|>=) BOUND [@FROM[:TO]]" — COLUMN a lower-case EG_Y_*
+ * name (year, pop, usage, gen, balance, opinion, yearly_capital, total_capital, inflation, co2, offset, net_co2, yearly_credit,
+ * total_credit, yearly_sales, total_sales, active_gens, upgrade_costs, closure_costs, yearly_total_cost, total_cost), BOUND a finite
+ * number, FROM and TO calendar years 2025..2050, both inclusive; no @ means all 26 years, @FROM alone means FROM..2050 ("net_co2 <= 0
+ * @2040", "sum(net_co2) <= 4e8", "balance >= 500 @2030:2039").  EG_ERR_BAD_ARG with a message that quotes the offending token.
+ * eg_plan_constraint_format writes the same form (the bound with 17 significant digits, so parse(format(c)) == c) into buf; EG_ERR_BAD_ARG
+ * for a constraint eg_plan_constraints_validate refuses or a buffer that is too small (EG_CONSTRAINT_SPEC_MAX bytes always suffice).
+ * Test hooks (they refuse a rank of a group): eg_debug_load_yearly overwrites the yearly rows of the n records eg_debug_load_batch made
+ * (n = eg_last_batch_size()); eg_debug_constrain_last_batch launches k_plan_constraints over the last batch through the launcher a plan
+ * batch uses (EG_ERR_BAD_ARG with no constraints set or no last batch). */
+#define EG_CONSTRAINTS_MAX 32
+#define EG_AGG_EVERY 0   /* each year of the window */
+#define EG_AGG_SUM 1     /* the window's sum */
+#define EG_OP_LE 0
+#define EG_OP_GE 1
+#define EG_CONSTRAINT_SPEC_MAX 96
+typedef struct { uint8_t column /* EG_Y_*, 0..20 */, aggregate, op, from_year, to_year /* 0 <= from < to <= 26 */, pad[3]; double bound /* finite */; } eg_plan_constraint; /* 16 bytes */
+int32_t eg_plan_constraints_validate(const eg_plan_constraint *constraints, int32_t n);
+int32_t eg_plan_constraints_set(eg_ctx *, const eg_plan_constraint *constraints, int32_t n /* 0: clear */);
+int32_t eg_fetch_plan_feasibility(eg_ctx *, uint32_t *violated /* [n] or NULL */, double *excess /* [n][k] or NULL */);
+int32_t eg_last_batch_constraints(const eg_ctx *, eg_plan_constraint *out /* [EG_CONSTRAINTS_MAX] or NULL */);
+int32_t eg_plan_constraint_parse(const char *spec, eg_plan_constraint *out);
+int32_t eg_plan_constraint_format(const eg_plan_constraint *c, char *buf, int32_t len);
+int32_t eg_debug_load_yearly(eg_ctx *, const double *yearly /* [n][26][21] */, uint32_t n);
+int32_t eg_debug_constrain_last_batch(eg_ctx *);
 
 /* Breeding a front: generations of plan crosses with Pareto selection, the survivors' plan blocks becoming the next generation's parents
  * on the device.  eg_breed_plans(ctx, policy, opts, parents, breed_opts, seed, episode_index, ...) starts from the population P_0 = the

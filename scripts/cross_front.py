@@ -78,6 +78,8 @@ def main():
     ap.add_argument("--cuts", type=years, default=list(range(2026, 2051)), help="years a child may switch parents at, e.g. 2030,2035 (default: 2026..2050)")
     ap.add_argument("--cost-only", action="store_true", help="score by the cost-only score")
     ap.add_argument("--out", required=True, help="output directory")
+    from eirgrid_amd.constraints import add_constraint_arguments, apply_constraints
+    add_constraint_arguments(ap)
     a = ap.parse_args()
     from eirgrid_amd import synthetic_world
     from eirgrid_amd.engine import ActionWeights, Engine, Plan
@@ -89,6 +91,7 @@ def main():
     policy = ActionWeights.load_from_file(a.policy) if a.policy else ActionWeights()
     eng = Engine(world, device=0)
     try:
+        apply_constraints(eng, a)      # --constraint: every plan batch below is judged under them
         front = eng.cross_front(policy, parents, a.seed, 0, cost_only=a.cost_only, cuts=[y - 2025 for y in a.cuts])
     finally:
         eng.close()

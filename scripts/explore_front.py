@@ -102,6 +102,8 @@ def main():
     ap.add_argument("--keep", choices=("score", "spread"), default="score",
                     help="what stays when the front outgrows --cap: the best-scoring points, or a spread-out subset (default score)")
     ap.add_argument("--out", required=True, help="output directory")
+    from eirgrid_amd.constraints import add_constraint_arguments, apply_constraints
+    add_constraint_arguments(ap)
     a = ap.parse_args()
     from eirgrid_amd import synthetic_world
     from eirgrid_amd.engine import ActionWeights, Engine, Plan
@@ -113,6 +115,7 @@ def main():
     policy = ActionWeights.load_from_file(a.policy) if a.policy else ActionWeights()
     eng = Engine(world, device=0)
     try:
+        apply_constraints(eng, a)      # --constraint: every plan batch below is judged under them
         front = eng.explore_front(policy, starts, a.seed, 0, cost_only=a.cost_only, generations=a.generations, cap=a.cap, replace_with=a.replace,
                                   append_with=a.append, max_shift=a.shift, max_variants=a.budget, keep=a.keep)
     finally:

@@ -84,6 +84,8 @@ def main():
     ap.add_argument("--deficit", choices=("substitute", "keep"), default="substitute", help="the type in best_deficit_actions: battery storage in its place, or left alone")
     ap.add_argument("--replace", type=replacements, default=[], help="pairs t:u, e.g. 1:0,Nuclear:GasCombinedCycle: type t built as type u")
     ap.add_argument("--out", required=True, help="output directory")
+    from eirgrid_amd.constraints import add_constraint_arguments, apply_constraints
+    add_constraint_arguments(ap)
     a = ap.parse_args()
     from eirgrid_amd import synthetic_world
     from eirgrid_amd.engine import ActionMap, ActionWeights, Engine, Plan, PlanRewrite, TechnologyRow, rank_score
@@ -93,6 +95,7 @@ def main():
     policy = ActionWeights.load_from_file(a.policy) if a.policy else ActionWeights()
     eng = Engine(world, device=0)
     try:
+        apply_constraints(eng, a)      # --constraint: every plan batch below is judged under them
         report = eng.technology_report(policy, plans, a.seed, 0, cost_only=a.cost_only, deficit=a.deficit)
         own = {r.plan: r.score for r in report if r.type < 0}
         replaced = []

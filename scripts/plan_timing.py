@@ -51,6 +51,8 @@ def main():
     ap.add_argument("--shift", type=int, default=1, help="years an entry is moved earlier and later at most (default 1)")
     ap.add_argument("--cost-only", action="store_true", help="score by the cost-only score")
     ap.add_argument("--out", required=True, help="output directory")
+    from eirgrid_amd.constraints import add_constraint_arguments, apply_constraints
+    add_constraint_arguments(ap)
     a = ap.parse_args()
     if not 1 <= a.shift <= 25:
         ap.error("--shift takes 1..25 years")
@@ -62,6 +64,7 @@ def main():
     policy = ActionWeights.load_from_file(a.policy) if a.policy else ActionWeights()
     eng = Engine(world, device=0)
     try:
+        apply_constraints(eng, a)      # --constraint: every plan batch below is judged under them
         timings = [eng.plan_timing(policy, base, a.seed, 2 if a.cost_only else 1, a.shift) for base in bases]
     finally:
         eng.close()

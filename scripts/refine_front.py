@@ -88,6 +88,8 @@ def main():
     ap.add_argument("--cost-only", action="store_true", help="rank by the cost-only score")
     ap.add_argument("--shift", type=int, default=0, help="also try every best_actions entry up to N years earlier and later (default 0: no moves)")
     ap.add_argument("--out", required=True, help="output directory")
+    from eirgrid_amd.constraints import add_constraint_arguments, apply_constraints
+    add_constraint_arguments(ap)
     a = ap.parse_args()
     if a.rounds < 1:
         ap.error("--rounds must be at least 1")
@@ -101,6 +103,7 @@ def main():
     policy = ActionWeights.load_from_file(a.policy) if a.policy else ActionWeights()
     eng = Engine(world, device=0)
     try:
+        apply_constraints(eng, a)      # --constraint: every plan batch below is judged under them
         results = eng.refine_plans(policy, bases, a.seed, 0, 2 if a.cost_only else 1, a.rounds, replace_with=a.replace, append_with=a.append, max_shift=a.shift)
     finally:
         eng.close()
