@@ -91,6 +91,12 @@ class EgRefineMoveStep(C.Structure):
                 ("n_failed", C.c_int32), ("score", C.c_double), ("metrics", C.c_double * 4)]
 
 
+class EgRepairStep(C.Structure):
+    _fields_ = [("is_move", C.c_int32), ("edit", EgPlanEdit), ("move", EgPlanMove), ("variant", C.c_int32), ("n_variants", C.c_int32),
+                ("n_failed", C.c_int32), ("n_feasible", C.c_int32), ("violated", C.c_uint32), ("violation", C.c_double), ("score", C.c_double),
+                ("metrics", C.c_double * 4)]
+
+
 class EgPlanCross(C.Structure):
     _fields_ = [("a", C.c_uint16), ("b", C.c_uint16), ("from_year", C.c_uint8), ("to_year", C.c_uint8)]
 
@@ -146,6 +152,7 @@ assert C.sizeof(EgBreedOpts) == 40 and C.sizeof(EgBreedGeneration) == 40 and C.s
 
 EDIT_NONE, EDIT_DELETE, EDIT_REPLACE, EDIT_INSERT = 0, 1, 2, 3
 REFINE_LOCAL_OPTIMUM, REFINE_MAX_ROUNDS, REFINE_BASE_FAILED = 0, 1, 2
+REPAIR_FEASIBLE, REPAIR_MAX_ROUNDS, REPAIR_BASE_FAILED, REPAIR_STUCK = 0, 1, 2, 3      # EG_REPAIR_*
 REFINE_MAX_VARIANTS = 16384      # EG_REFINE_MAX_VARIANTS
 REFINE_MAX_PLANS = 256           # EG_REFINE_MAX_PLANS
 CROSS_MAX_PARENTS = 256          # EG_CROSS_MAX_PARENTS
@@ -184,7 +191,15 @@ class EgDebugRefineEntry(C.Structure):      # eg_debug_refine_pick's step entry 
                 ("base_metrics", C.c_double * 4)]
 
 
+class EgDebugRepairEntry(C.Structure):      # eg_debug_repair_pick_many's entry (EG_DEBUG_REPAIR_ENTRY_BYTES)
+    _fields_ = [("winner", C.c_int32), ("n_failed", C.c_int32), ("edit", C.c_uint32 * 2), ("violation", C.c_double), ("score", C.c_double),
+                ("metrics", C.c_double * 4), ("violated", C.c_uint32), ("n_feasible", C.c_int32), ("off26", C.c_int32), ("offd26", C.c_int32),
+                ("base_ok", C.c_int32), ("n", C.c_int32), ("base_violation", C.c_double), ("base_score", C.c_double), ("base_violated", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
 assert C.sizeof(EgUpdateCandidate) == CANDIDATE_BYTES and C.sizeof(EgDebugRefineEntry) == 112
+assert C.sizeof(EgRepairStep) == 96 and C.sizeof(EgDebugRepairEntry) == 112
 
 # every symbol include/eirgrid_hip.h declares
 EXPORTS = [
@@ -205,6 +220,7 @@ EXPORTS = [
     "eg_breed_validate", "eg_breed_plans", "eg_explore_validate", "eg_explore_neighbourhood", "eg_explore_plans",
     "eg_plan_constraints_validate", "eg_plan_constraints_set", "eg_fetch_plan_feasibility", "eg_last_batch_constraints", "eg_plan_constraint_parse", "eg_plan_constraint_format",
     "eg_debug_load_yearly", "eg_debug_constrain_last_batch",
+    "eg_repair_plans_validate", "eg_repair_plans", "eg_debug_repair_pick_many",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -439,6 +455,16 @@ def lib():
         L.eg_debug_load_yearly.argtypes = [C.c_void_p, _dp, C.c_uint32]
         L.eg_debug_constrain_last_batch.restype = C.c_int32
         L.eg_debug_constrain_last_batch.argtypes = [C.c_void_p]
+    # (likewise: scripts/repair_probe.py may load a build of the parent commit, which has no repair)
+    if hasattr(L, "eg_repair_plans") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_repair_plans_validate.restype = C.c_int32
+        L.eg_repair_plans_validate.argtypes = [C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts), C.POINTER(EgRefineMoveOpts), _dp, C.c_int32]
+        L.eg_repair_plans.restype = C.c_int32
+        L.eg_repair_plans.argtypes = [C.c_void_p, C.POINTER(EgPolicySnapshot), C.POINTER(EgOpts), C.POINTER(EgPlanSet), C.POINTER(EgRefineOpts),
+                                      C.POINTER(EgRefineMoveOpts), _dp, C.c_uint64, C.c_uint64, C.POINTER(C.POINTER(EgPlanSet)), C.POINTER(EgRepairStep),
+                                      _i32p, _i32p, _dp, _dp, C.POINTER(EgEpisodeOut)]
+        L.eg_debug_repair_pick_many.restype = C.c_int32
+        L.eg_debug_repair_pick_many.argtypes = [C.c_void_p, C.c_int32, _dp, _u32p, _u32p, C.c_int32, C.c_void_p, _u8p]
     if hasattr(L, "eg_pareto_track") or not os.environ.get("EIRGRID_LIB"):
         L.eg_pareto_track.restype = C.c_int32
         L.eg_pareto_track.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]

@@ -83,6 +83,34 @@ class Constraint:
     def violated(self, rows) -> bool:
         return not self.excess(rows) <= 0.0
 
+    @staticmethod
+    def violation(excess_row, weights=None) -> float:
+        """The violation measure V of one variant's row of the excess matrix under `weights` (None: 1.0 each): `violation` below."""
+        return violation(excess_row, weights)
+
+
+def violation(excess_row, weights=None) -> float:
+    """The violation measure V of one variant (include/eirgrid_hip.h eg_repair_plans), the header's definition restated literally: over
+    the variant's row of the excess matrix, in constraint order from +0.0, +inf for a NaN excess, weight * excess for an excess > 0 (one
+    rounding), +0.0 otherwise, one rounding per addition.  weights: one per constraint, each finite and > 0; None: 1.0 each."""
+    row = [float(e) for e in np.asarray(excess_row, dtype=np.float64).reshape(-1)]
+    w = [1.0] * len(row) if weights is None else [float(x) for x in weights]
+    if len(w) != len(row):
+        raise ValueError(f"{len(w)} weights for {len(row)} constraints")
+    for i, x in enumerate(w):
+        if not (math.isfinite(x) and x > 0.0):
+            raise ValueError(f"weights[{i}] = {x} (finite and > 0)")
+    v = 0.0
+    for e, x in zip(row, w):
+        if e != e:
+            t = math.inf
+        elif e > 0.0:
+            t = x * e
+        else:
+            t = 0.0
+        v = v + t
+    return v
+
 
 def constraint_list(constraints) -> "list[Constraint]":
     """Constraints and specs (any iterable, walked once; None: none) as a list of Constraint"""

@@ -1,6 +1,6 @@
 // eg_debug.cpp — the crafted-batch test hooks (include/eirgrid_hip.h, debug section): a batch of synthetic records in the context's
 // record buffer, and the reductions that decide what a run keeps run over it — the folds launch_batch runs behind a real batch (through the
-// helpers it calls), k_pick_best, k_refine_pick_many, k_plan_constraints over crafted yearly rows — and a crafted generation of eg_breed_plans / eg_explore_plans: tagged plan blocks
+// helpers it calls), k_pick_best, k_refine_pick_many, k_plan_constraints over crafted yearly rows, k_repair_pick_many behind it — and a crafted generation of eg_breed_plans / eg_explore_plans: tagged plan blocks
 // folded into the private archive, gathered and turned over — through the archive functions the entry points run (eg_plan_host.cpp).
 // Host code only: no kernel is launched here that a run does not launch — but for eg_debug_tiles_refresh, whose one-wave kernel exists to
 // call a device function of the replay kernels (eg_field.h tiles_refresh) on a crafted list and field.
@@ -22,16 +22,20 @@ int put_field(eg_ctx* c, size_t field, const void* src, size_t width, uint32_t n
   return EG_OK;
 }
 // k_refine_pick_many over the last batch, cut into n_segs segments that tile it (checked by the callers): tagged plan blocks, edits and
-// base blocks as include/eirgrid_hip.h documents them, segment s on base slot s; the entries and the base blocks as the kernel left them
-int refine_pick(eg_ctx* c, int32_t mode, const uint32_t* seg_first, const uint32_t* seg_count, int32_t n_segs, void* entries, uint8_t* base_blocks) {
+// base blocks as include/eirgrid_hip.h documents them, segment s on base slot s; the entries and the base blocks as the kernel left them.
+// repair_weights: k_repair_pick_many in its place, over what k_plan_constraints left for the batch (c->feas_k constraints), with these
+// c->feas_k weights, which go up behind the segment table
+int refine_pick(eg_ctx* c, int32_t mode, const uint32_t* seg_first, const uint32_t* seg_count, int32_t n_segs, void* entries, uint8_t* base_blocks,
+                const double* repair_weights = nullptr) {
   static_assert(sizeof(RefineEntry) == EG_DEBUG_REFINE_ENTRY_BYTES, "the step entry's layout is what the hooks document");
+  static_assert(sizeof(RepairEntry) == EG_DEBUG_REPAIR_ENTRY_BYTES, "the repair entry's layout is what the hooks document");
   static_assert(EG_PLAN_BLOCK_BYTES == snap::kPlanStride, "plan block");
   const uint32_t n = c->last_n;
   EG_HIP(hipSetDevice(c->device));
   constexpr size_t kWords = snap::kPlanStride / 4, kOff26 = (snap::best_off - snap::best_mask) / 4 + EG_YEARS, kOffD26 = (snap::bestd_off - snap::best_mask) / 4 + EG_YEARS;
   static_assert(kOff26 == 130 && kOffD26 == 158, "the words of the list totals as the hooks document them");
   const size_t S = size_t(n_segs);
-  std::vector<uint32_t> blocks(size_t(n) * kWords), base(S * kWords), in(size_t(n) * 2 + S * 4);      // in: the packed edits, then the segment table
+  std::vector<uint32_t> blocks(size_t(n) * kWords), base(S * kWords), in(size_t(n) * 2 + S * 4 + (repair_weights ? 2 * size_t(c->feas_k) : 0));      // in: the packed edits, the segment table, the weights
   for (uint32_t j = 0; j < n; ++j) {
     uint32_t* b = blocks.data() + size_t(j) * kWords;
     for (size_t w = 0; w < kWords; ++w) b[w] = j * 0x9E3779B1u + uint32_t(w);
@@ -46,6 +50,8 @@ int refine_pick(eg_ctx* c, int32_t mode, const uint32_t* seg_first, const uint32
     t[0] = seg_first[s]; t[1] = seg_count[s]; t[2] = uint32_t(s); t[3] = 0u;
   }
   static_assert(kRefineSegmentBytes == 16, "segment table entry");
+  const size_t at_weights = (size_t(n) * 2 + S * 4) * 4;      // (a multiple of 8)
+  if (repair_weights) std::memcpy(in.data() + size_t(n) * 2 + S * 4, repair_weights, sizeof(double) * size_t(c->feas_k));
   EG_HIP(c->d_plans.reserve(size_t(n) * snap::kPlanStride));
   EG_HIP(c->d_refine_bases.reserve(S * snap::kPlanStride));
   EG_HIP(c->d_refine_in.reserve(in.size() * 4));
@@ -55,8 +61,14 @@ int refine_pick(eg_ctx* c, int32_t mode, const uint32_t* seg_first, const uint32
   EG_HIP(hipMemcpy(c->d_refine_in, in.data(), in.size() * 4, hipMemcpyHostToDevice));
   EG_HIP(hipMemsetAsync(c->d_refine_log, 0, S * kRefineEntryStride, nullptr));
   c->n_plan_blocks = n;
-  EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + size_t(n) * 8, uint32_t(n_segs), n, mode, c->d_refine_in, c->d_plans, c->d_refine_bases,
-                                                          uint32_t(n_segs), c->d_refine_log, nullptr));
+  if (repair_weights)
+    EG_LAUNCH("k_repair_pick_many", launch_repair_pick_many(c->out, c->d_refine_in + size_t(n) * 8, uint32_t(n_segs), n, mode, c->d_refine_in, c->d_plans, c->d_refine_bases,
+                                                            uint32_t(n_segs), c->d_violated, c->d_excess, uint32_t(c->feas_k),
+                                                            reinterpret_cast<const double*>(c->d_refine_in + at_weights), c->d_refine_log, nullptr));
+  else
+    EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + size_t(n) * 8, uint32_t(n_segs), n, mode, c->d_refine_in, c->d_plans, c->d_refine_bases,
+                                                            uint32_t(n_segs), c->d_refine_log, nullptr));
+  static_assert(sizeof(RefineEntry) == sizeof(RepairEntry), "either entry is read back at the same width");
   EG_HIP(hipMemcpy2D(entries, sizeof(RefineEntry), c->d_refine_log, kRefineEntryStride, sizeof(RefineEntry), S, hipMemcpyDeviceToHost));
   EG_HIP(hipMemcpy(base_blocks, c->d_refine_bases, S * snap::kPlanStride, hipMemcpyDeviceToHost));
   return EG_OK;
@@ -168,6 +180,27 @@ int32_t eg_debug_refine_pick_many(eg_ctx* c, int32_t mode, const uint32_t* seg_f
     if (at != n) { set_error("eg_debug_refine_pick_many: the segments cover " + std::to_string(at) + " of the last batch's " + std::to_string(n) + " records"); return EG_ERR_BAD_ARG; }
   }
   return refine_pick(c, mode, seg_first, seg_count, n_segs, entries, base_blocks);
+}
+
+int32_t eg_debug_repair_pick_many(eg_ctx* c, int32_t mode, const double* weights, const uint32_t* seg_first, const uint32_t* seg_count, int32_t n_segs, void* entries,
+                                  uint8_t* base_blocks) {
+  const char* fn = "eg_debug_repair_pick_many";
+  auto fail = [fn](const std::string& m) { set_error(std::string(fn) + ": " + m); return EG_ERR_BAD_ARG; };
+  if (!c || !seg_first || !seg_count || !entries || !base_blocks || (mode != 1 && mode != 2)) return fail("bad argument");
+  EG_TRY(refuse_rank(c, fn));
+  const uint32_t n = c->last_n;
+  if (n == 0 || n > EG_REFINE_MAX_VARIANTS) return fail("the last batch holds " + std::to_string(n) + " records (1..EG_REFINE_MAX_VARIANTS)");
+  if (c->feas_k == 0) return fail("the last batch was not judged (eg_debug_constrain_last_batch first: the pick reads its masks and excess rows)");
+  if (n_segs < 1 || n_segs > EG_REFINE_MAX_PLANS) return fail("n_segs = " + std::to_string(n_segs) + " (1..EG_REFINE_MAX_PLANS)");
+  EG_TRY(check_repair_weights(fail, weights, c->feas_k));
+  uint64_t at = 0;
+  for (int32_t s = 0; s < n_segs; ++s) {
+    if (seg_first[s] != at || seg_count[s] == 0) return fail("segment " + std::to_string(s) + " does not continue the tiling of the last batch");
+    at += seg_count[s];
+  }
+  if (at != n) return fail("the segments cover " + std::to_string(at) + " of the last batch's " + std::to_string(n) + " records");
+  const std::vector<double> w = weights ? std::vector<double>(weights, weights + c->feas_k) : std::vector<double>(size_t(c->feas_k), 1.0);
+  return refine_pick(c, mode, seg_first, seg_count, n_segs, entries, base_blocks, w.data());
 }
 
 // ---- the lazy field's catch-up for one pair of tiles: a crafted list and a crafted class field, one wave (k_debug_tiles_refresh: the hook's own kernel

@@ -152,6 +152,7 @@ struct eg_ctx {
   // plan refinement (eg_refine_plan, eg_refine_plans): the step log k_refine_pick_many writes, an entry per plan of a launch from the
   // start (kRefineLog entries of kRefineEntryStride bytes); the base blocks of the call's plans (uploaded once, kept current by
   // k_refine_pick_many) and what a launch uploads in one copy: the packed edits, the base slot of every variant, the segment table
+  // (eg_repair_plans, the same loop under its other rule: k_repair_pick_many writes the log and the bases, its weights ride behind the table)
   // EIRGRID_REFINE_LAUNCH_VARIANTS (default and at most 16 384, at least 1; read at every call): the variants a launch may hold — a plan
   // with more gets a launch to itself (so eg_refine_plan's one plan always does); for tests that want many launches per round at small sizes
   eg::DevBuf<uint8_t> d_refine_log, d_refine_bases, d_refine_in;
@@ -238,6 +239,8 @@ int32_t check_objectives(const Fail& fail, int32_t objectives);
 int32_t check_cap(const Fail& fail, int32_t cap);
 int32_t check_launch_variants(const Fail& fail, int32_t launch_variants);
 int32_t validate_action_lists(const Fail& fail, int32_t n_replace, const uint8_t* replace_with, int32_t n_append, const uint8_t* append_with);
+// the weights of a repair (eg_repair_plans, eg_debug_repair_pick_many) for k constraints: k 1..EG_CONSTRAINTS_MAX, each weight finite and > 0 (NULL: 1.0 each)
+int32_t check_repair_weights(const Fail& fail, const double* weights, int32_t k);
 // what eg_breed_validate and eg_explore_validate open with (their options begin alike): the set's size, the options, mode .. max_generations
 template <typename Opts> int32_t validate_front_opts(const Fail& fail, const eg_plan_set* set, const Opts* o) {
   if (set->n_plans > EG_CROSS_MAX_PARENTS) return fail("the set holds " + std::to_string(set->n_plans) + " plans (at most " + std::to_string(EG_CROSS_MAX_PARENTS) + ")");

@@ -539,6 +539,25 @@ int launch_plan_rewrites(const uint8_t* d_plans, uint32_t n_plans, const uint8_t
 // judged over the n records of o: d_violated[j] the mask of the constraints record j violates, d_excess[j * k + i] its excess of
 // constraint i; a record that ended EG_EP_OK with a mask that is not zero becomes EG_EP_INFEASIBLE, nothing else of a record is written
 int launch_plan_constraints(const DevOut& o, uint32_t n, const void* d_constraints, uint32_t k, uint32_t* d_violated, double* d_excess, void* stream);
+// What k_repair_pick_many (eg_repair.h) leaves per plan of a repair round (include/eirgrid_hip.h eg_repair_plans): the candidate — status
+// EG_EP_OK or EG_EP_INFEASIBLE and a rank score that is not NaN — with the smallest violation measure V below the base's, ties to the
+// largest score, then to the lowest variant.  An entry takes a slot of the step log, kRefineEntryStride bytes, as a RefineEntry does.
+struct RepairEntry {
+  int32_t winner, n_failed;        // -1: variant 0 is no candidate; 0: V_0 == 0, or no candidate below V_0 (nothing copied either way); variants that are no candidates
+  uint32_t edit[2];                // the winner's packed edit (winner <= 0: variant 0's)
+  double violation, score, metrics[4];      // the winner's V, score and metrics (winner 0: the base's; winner -1: zeros and variant 0's metrics)
+  uint32_t violated; int32_t n_feasible;    // the winner's mask; candidates with V == 0
+  int32_t off26, offd26;           // the two list totals of the winner's block
+  int32_t base_ok, n;              // variant 0 is a candidate; variants looked at
+  double base_violation, base_score;        // V_0 and s_0 (zeros when the base is no candidate)
+  uint32_t base_violated, pad;
+};
+static_assert(sizeof(RepairEntry) == 112 && sizeof(RepairEntry) <= kRefineEntryStride, "repair entry");
+// k_repair_pick_many: launch_refine_pick_many's arguments, and what k_plan_constraints left for the launch's n_total records — d_violated
+// [n_total], d_excess [n_total][k] — with the k weights at d_weights
+int launch_repair_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs, uint32_t n_total, int mode, const void* d_edits, const uint8_t* d_pool,
+                            uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_violated, const double* d_excess, uint32_t k, const double* d_weights,
+                            uint8_t* d_entries, void* stream);
 // Generations of crosses (include/eirgrid_hip.h eg_breed_plans; eg_breed.h, eg_breed.cpp).  The private archive of a call, one buffer
 // kept with the context: a ParetoState and EG_PARETO_MAX record slots exactly as eg_pareto_track lays them out (so launch_pareto_fold
 // folds into it), a plan BLOCK slot per record slot, two parent arrays of EG_PARETO_MAX blocks (this generation's, the next one's), the

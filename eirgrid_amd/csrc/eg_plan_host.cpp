@@ -2,6 +2,7 @@
 // packing and routing, the launch of a chunk of variants, the private archive of eg_breed_plans / eg_explore_plans and the option checks
 // the validators share.  Each exists once: eg_plans / eg_refine / eg_breed / eg_explore / eg_debug .cpp call them.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "eg_host.h"
@@ -131,6 +132,13 @@ int32_t eg::check_cap(const Fail& fail, int32_t cap) {
 int32_t eg::check_launch_variants(const Fail& fail, int32_t launch_variants) {
   if (launch_variants >= 0 && launch_variants <= EG_CROSS_MAX_VARIANTS) return EG_OK;
   return fail("launch_variants = " + std::to_string(launch_variants) + " (1.." + std::to_string(EG_CROSS_MAX_VARIANTS) + "; 0: " + std::to_string(EG_CROSS_MAX_VARIANTS) + ")");
+}
+int32_t eg::check_repair_weights(const Fail& fail, const double* weights, int32_t k) {
+  if (k < 1) return fail("no plan constraints are set (eg_plan_constraints_set first: a repair descends on their violation)");
+  if (k > EG_CONSTRAINTS_MAX) return fail("k = " + std::to_string(k) + " constraints (at most " + std::to_string(EG_CONSTRAINTS_MAX) + ")");
+  for (int32_t i = 0; weights && i < k; ++i)
+    if (!std::isfinite(weights[i]) || !(weights[i] > 0.0)) return fail("weights[" + std::to_string(i) + "] = " + std::to_string(weights[i]) + " (finite and > 0)");
+  return EG_OK;
 }
 int32_t eg::validate_action_lists(const Fail& fail, int32_t n_replace, const uint8_t* replace_with, int32_t n_append, const uint8_t* append_with) {
   const char* name[2] = {"replace_with", "append_with"};

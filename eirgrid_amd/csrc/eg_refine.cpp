@@ -8,6 +8,9 @@
 // A plan never straddles two launches, so a single plan always gets a launch of exactly its own variants, whatever the launch size.
 // eg_refine_plans_moves runs the same loop with move variants behind every plan's edits: k_plan_moves (eg_plan_moves.h) overwrites their
 // blocks behind k_plan_edits_many, which has written a copy of the base for them.
+// eg_repair_plans runs the same loop with another RULE: which kernel picks a segment's winner, what its entry says of the base, and what a
+// winner means — a step, a stop, both.  RefineRule is the largest score (k_refine_pick_many); RepairRule the smallest violation of the
+// context's plan constraints below the base's (eg_repair.h k_repair_pick_many), its weights uploaded behind the launch's segment table.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -108,11 +111,91 @@ uint32_t launch_variants() {
 // (with moves: its edits, then its moves)
 struct Seg { int32_t plan; uint32_t first, n; std::vector<eg_plan_edit> edits; std::vector<eg_plan_move> moves; };
 
-// the loop, for the validated plans of `bases`: steps [P][max_rounds], n_steps / stop_reason / start_score / out's rows [P].
-// mo: the move variants behind every plan's edits (eg_refine_plans_moves), whose steps go to msteps instead of steps; NULL: none
-int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro,
-               uint64_t seed, uint64_t episode_index, eg_plan_set** refined, eg_refine_step* steps, int32_t* n_steps, int32_t* stop_reason, double* start_score,
-               eg_episode_out* out, const eg_refine_move_opts* mo = nullptr, eg_refine_move_step* msteps = nullptr) {
+// What a rule is given of a winner: where its step goes, and the edit or move it is (against the plan of its round)
+struct Won { size_t at; bool is_move; const eg_plan_edit* edit; const eg_plan_move* move; int32_t n_variants; };
+constexpr int kGoOn = -1;      // (a rule's verdict: the plan stays in the search)
+
+// eg_refine_plan, eg_refine_plans, eg_refine_plans_moves: the largest score; a winner that is the base is a local optimum
+struct RefineRule {
+  using Entry = RefineEntry;
+  static_assert(EG_REFINE_BASE_FAILED == 2 && EG_REFINE_MAX_ROUNDS == 1, "the loop's two own stop reasons");
+  eg_refine_step* steps; eg_refine_move_step* msteps;      // (with moves the steps go to msteps)
+  double* start_score;
+  size_t extra_bytes() const { return 0; }
+  void extra(uint8_t*) const {}
+  void begin(int32_t p) const { if (start_score) start_score[p] = std::nan(""); }
+  void base(int32_t p, const Entry& e) const { if (start_score && e.base_ok) start_score[p] = e.base_score; }
+  int launch(eg_ctx* c, size_t at_segs, size_t, uint32_t n_segs, uint32_t n, int mode, uint32_t P) const {
+    EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + at_segs, n_segs, n, mode, c->d_refine_in, c->d_plans, c->d_refine_bases, P,
+                                                            c->d_refine_log, nullptr));
+    return EG_OK;
+  }
+  // the stop reason when the winner is the base; otherwise the step is recorded and the loop counts it
+  int stays(int32_t, const Entry&) const { return EG_REFINE_LOCAL_OPTIMUM; }
+  int step(int32_t, const Entry& e, const Won& w) const {
+    if (msteps) {
+      eg_refine_move_step& st = msteps[w.at];
+      std::memset(&st, 0, sizeof(st));
+      st.is_move = w.is_move ? 1 : 0;
+      if (w.is_move) st.move = *w.move; else st.edit = *w.edit;
+      st.variant = e.winner; st.n_variants = w.n_variants; st.n_failed = e.n_failed; st.score = e.score;
+      std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
+    } else {
+      eg_refine_step& st = steps[w.at];
+      st.edit = *w.edit; st.variant = e.winner; st.n_variants = w.n_variants; st.n_failed = e.n_failed; st.score = e.score;
+      std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
+    }
+    return kGoOn;
+  }
+};
+
+// eg_repair_plans: the smallest violation below the base's; a base that stays is feasible or stuck, a winner at V == 0 ends the descent
+struct RepairRule {
+  using Entry = RepairEntry;
+  static_assert(EG_REPAIR_BASE_FAILED == EG_REFINE_BASE_FAILED && EG_REPAIR_MAX_ROUNDS == EG_REFINE_MAX_ROUNDS, "the loop's two own stop reasons");
+  eg_repair_step* steps;
+  double* start_violation; double* final_violation;
+  std::vector<double> weights;      // k of them: the context's constraints at the call
+  size_t extra_bytes() const { return sizeof(double) * weights.size(); }
+  void extra(uint8_t* at) const { std::memcpy(at, weights.data(), extra_bytes()); }
+  void begin(int32_t p) const {
+    if (start_violation) start_violation[p] = std::nan("");
+    if (final_violation) final_violation[p] = std::nan("");
+  }
+  void base(int32_t p, const Entry& e) const {
+    if (!e.base_ok) return;
+    if (start_violation) start_violation[p] = e.base_violation;
+    if (final_violation) final_violation[p] = e.base_violation;
+  }
+  int launch(eg_ctx* c, size_t at_segs, size_t at_extra, uint32_t n_segs, uint32_t n, int mode, uint32_t P) const {
+    if (c->feas_k != int(weights.size())) { set_error("eg_repair_plans: the launch was judged under " + std::to_string(c->feas_k) + " constraints, the call began under " + std::to_string(weights.size())); return EG_ERR_INTERNAL; }
+    EG_LAUNCH("k_repair_pick_many", launch_repair_pick_many(c->out, c->d_refine_in + at_segs, n_segs, n, mode, c->d_refine_in, c->d_plans, c->d_refine_bases, P,
+                                                            c->d_violated, c->d_excess, uint32_t(c->feas_k), reinterpret_cast<const double*>(c->d_refine_in + at_extra),
+                                                            c->d_refine_log, nullptr));
+    return EG_OK;
+  }
+  int stays(int32_t, const Entry& e) const { return e.base_violation == 0.0 ? EG_REPAIR_FEASIBLE : EG_REPAIR_STUCK; }
+  int step(int32_t p, const Entry& e, const Won& w) const {
+    eg_repair_step& st = steps[w.at];
+    std::memset(&st, 0, sizeof(st));
+    st.is_move = w.is_move ? 1 : 0;
+    if (w.is_move) st.move = *w.move; else st.edit = *w.edit;
+    st.variant = e.winner; st.n_variants = w.n_variants; st.n_failed = e.n_failed; st.n_feasible = e.n_feasible;
+    st.violated = e.violated; st.violation = e.violation; st.score = e.score;
+    std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
+    if (final_violation) final_violation[p] = e.violation;
+    return e.violation == 0.0 ? EG_REPAIR_FEASIBLE : kGoOn;      // (checked ahead of max_rounds)
+  }
+};
+
+// the loop, for the validated plans of `bases` under `rule`: the rule's steps [P][max_rounds], n_steps / stop_reason / out's rows [P].
+// mo: the move variants behind every plan's edits (eg_refine_plans_moves, eg_repair_plans); NULL: none
+template <typename Rule>
+int32_t search(const Rule& rule, const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases,
+               const eg_refine_opts* ro, uint64_t seed, uint64_t episode_index, eg_plan_set** refined, int32_t* n_steps, int32_t* stop_reason, eg_episode_out* out,
+               const eg_refine_move_opts* mo = nullptr) {
+  using Entry = typename Rule::Entry;
+  static_assert(sizeof(Entry) <= kRefineEntryStride, "an entry takes a slot of the step log");
   *refined = nullptr;
   const int32_t P = bases->n_plans;
   std::vector<Mirror> mirror = mirrors_of(bases);
@@ -138,7 +221,7 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
   EG_TRY(ensure_outputs(c, n_cap));
   EG_HIP(c->d_plans.reserve(size_t(n_cap) * snap::kPlanStride));
   EG_HIP(c->d_plan_index.reserve(n_cap));
-  EG_HIP(c->d_refine_in.reserve(size_t(n_cap) * 12 + 16 + segs_cap * kRefineSegmentBytes));
+  EG_HIP(c->d_refine_in.reserve(size_t(n_cap) * 12 + 16 + segs_cap * kRefineSegmentBytes + rule.extra_bytes()));
   EG_HIP(c->d_refine_log.reserve(size_t(kRefineLog) * kRefineEntryStride));
   static_assert(EG_REFINE_MAX_PLANS <= kRefineLog, "a launch's entries fit the step log");
   EG_HIP(c->d_refine_bases.reserve(size_t(P) * snap::kPlanStride));
@@ -150,7 +233,7 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
   DevSnapshot S{};
   EG_TRY(stage_eval_snapshot(c, s, o, &S));
   std::vector<char> active(size_t(P), 1);
-  for (int32_t p = 0; p < P; ++p) { n_steps[p] = 0; stop_reason[p] = EG_REFINE_MAX_ROUNDS; if (start_score) start_score[p] = std::nan(""); }
+  for (int32_t p = 0; p < P; ++p) { n_steps[p] = 0; stop_reason[p] = EG_REFINE_MAX_ROUNDS; rule.begin(p); }
   std::vector<Seg> segs;
   std::vector<uint8_t> in, entries;
   Routing R;
@@ -173,10 +256,11 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
       while (t1 < todo.size() && n + todo[t1].second <= launch_max) n += todo[t1++].second;
       const uint32_t n_segs = uint32_t(t1 - t0);
       if (n > n_cap || n_segs > segs_cap) { set_error(std::string(fn) + ": round " + std::to_string(round) + ": a launch of " + std::to_string(n) + " variants outgrew its buffers"); return EG_ERR_INTERNAL; }
-      // what goes up in one copy: the packed edits (8 bytes a variant), every variant's base slot, the segment table; and the routing —
-      // the short variants of the whole launch first, then the long ones (launch_plans)
-      const size_t at_slot = size_t(n) * 8, at_segs = (size_t(n) * 12 + 15) / 16 * 16;
-      in.assign(at_segs + size_t(n_segs) * kRefineSegmentBytes, 0);
+      // what goes up in one copy: the packed edits (8 bytes a variant), every variant's base slot, the segment table, what the rule adds;
+      // and the routing — the short variants of the whole launch first, then the long ones (launch_plans)
+      const size_t at_slot = size_t(n) * 8, at_segs = (size_t(n) * 12 + 15) / 16 * 16, at_extra = at_segs + size_t(n_segs) * kRefineSegmentBytes;
+      in.assign(at_extra + rule.extra_bytes(), 0);
+      rule.extra(in.data() + at_extra);
       uint32_t* packed = reinterpret_cast<uint32_t*>(in.data());
       uint32_t* slot = reinterpret_cast<uint32_t*>(in.data() + at_slot);
       uint32_t* table = reinterpret_cast<uint32_t*>(in.data() + at_segs);
@@ -199,8 +283,7 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
         first += sg.n;
       }
       EG_TRY(launch_variants(c, S, c->d_refine_bases, uint32_t(P), in, at_slot, n, R, any_moves, seed, episode_index));
-      EG_LAUNCH("k_refine_pick_many", launch_refine_pick_many(c->out, c->d_refine_in + at_segs, n_segs, n, ro->mode, c->d_refine_in, c->d_plans, c->d_refine_bases, uint32_t(P),
-                                                              c->d_refine_log, nullptr));
+      EG_TRY(rule.launch(c, at_segs, at_extra, n_segs, n, ro->mode, uint32_t(P)));
       entries.resize(size_t(n_segs) * kRefineEntryStride);
       EG_HIP(hipMemcpy(entries.data(), c->d_refine_log, entries.size(), hipMemcpyDeviceToHost));      // (waits for the launch)
       for (uint32_t k = 0; k < n_segs; ++k) {
@@ -208,9 +291,9 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
         const int32_t p = sg.plan;
         const std::string at = who(fn, name_plan, p) + "round " + std::to_string(round) + ": ";
         Mirror& m = mirror[size_t(p)];
-        RefineEntry e{};
+        Entry e{};
         std::memcpy(&e, entries.data() + size_t(k) * kRefineEntryStride, sizeof(e));
-        if (round == 0 && start_score && e.base_ok) start_score[p] = e.base_score;
+        if (round == 0) rule.base(p, e);
         if (!e.base_ok) { stop_reason[p] = EG_REFINE_BASE_FAILED; active[size_t(p)] = 0; continue; }
         const uint32_t* mine = packed + 2 * size_t(sg.first);
         if (e.n != int32_t(sg.n) || e.winner < 0 || e.winner >= int32_t(sg.n) || e.edit[0] != mine[2 * size_t(e.winner)] || e.edit[1] != mine[2 * size_t(e.winner) + 1]) {
@@ -226,21 +309,15 @@ int32_t refine(const char* fn, bool name_plan, eg_ctx* c, const eg_policy_snapsh
                     std::to_string(m.total(0)) + " + " + std::to_string(m.total(1)));
           return EG_ERR_INTERNAL;
         }
-        if (e.winner == 0) { stop_reason[p] = EG_REFINE_LOCAL_OPTIMUM; active[size_t(p)] = 0; }
-        else if (msteps) {
-          eg_refine_move_step& st = msteps[size_t(p) * size_t(ro->max_rounds) + size_t(n_steps[p])];
-          std::memset(&st, 0, sizeof(st));
-          st.is_move = is_move ? 1 : 0;
-          if (is_move) st.move = sg.moves[size_t(e.winner) - sg.edits.size()]; else st.edit = sg.edits[size_t(e.winner)];
-          st.variant = e.winner; st.n_variants = int32_t(sg.n); st.n_failed = e.n_failed; st.score = e.score;
-          std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
-          if (++n_steps[p] == ro->max_rounds) { stop_reason[p] = EG_REFINE_MAX_ROUNDS; active[size_t(p)] = 0; }
-        } else {
-          eg_refine_step& st = steps[size_t(p) * size_t(ro->max_rounds) + size_t(n_steps[p])];
-          st.edit = sg.edits[size_t(e.winner)]; st.variant = e.winner; st.n_variants = int32_t(sg.n); st.n_failed = e.n_failed; st.score = e.score;
-          std::memcpy(st.metrics, e.metrics, sizeof(st.metrics));
-          if (++n_steps[p] == ro->max_rounds) { stop_reason[p] = EG_REFINE_MAX_ROUNDS; active[size_t(p)] = 0; }
+        int stop = kGoOn;
+        if (e.winner == 0) stop = rule.stays(p, e);
+        else {
+          const Won won{size_t(p) * size_t(ro->max_rounds) + size_t(n_steps[p]), is_move, is_move ? nullptr : &sg.edits[size_t(e.winner)],
+                        is_move ? &sg.moves[size_t(e.winner) - sg.edits.size()] : nullptr, int32_t(sg.n)};
+          stop = rule.step(p, e, won);
+          if (++n_steps[p] == ro->max_rounds && stop == kGoOn) stop = EG_REFINE_MAX_ROUNDS;
         }
+        if (stop != kGoOn) { stop_reason[p] = stop; active[size_t(p)] = 0; }
         if (!active[size_t(p)] && out) {      // the refined plan's record, before the next launch overwrites the records
           eg_episode_out row = out_row(out, size_t(p));
           EG_TRY(fetch_records(c->out.base + (size_t(sg.first) + size_t(e.winner)) * rec::stride, 1, &row));
@@ -274,7 +351,7 @@ extern "C" int32_t eg_refine_plan(eg_ctx* c, const eg_policy_snapshot* s, const 
                                   double* start_score, eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plan: bad argument"); return EG_ERR_BAD_ARG; }
   EG_TRY(plan_entry(c, s, o, "eg_refine_plan", [&] { return eg_refine_validate(base, ro); }));
-  return refine("eg_refine_plan", false, c, s, o, base, ro, seed, episode_index, refined, steps, n_steps, stop_reason, start_score, out);
+  return search(RefineRule{steps, nullptr, start_score}, "eg_refine_plan", false, c, s, o, base, ro, seed, episode_index, refined, n_steps, stop_reason, out);
 }
 
 extern "C" int32_t eg_refine_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro, uint64_t seed,
@@ -282,18 +359,24 @@ extern "C" int32_t eg_refine_plans(eg_ctx* c, const eg_policy_snapshot* s, const
                                    double* start_score, eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plans: bad argument"); return EG_ERR_BAD_ARG; }
   EG_TRY(plan_entry(c, s, o, "eg_refine_plans", [&] { return eg_refine_plans_validate(bases, ro); }));
-  return refine("eg_refine_plans", true, c, s, o, bases, ro, seed, episode_index, refined, steps, n_steps, stop_reason, start_score, out);
+  return search(RefineRule{steps, nullptr, start_score}, "eg_refine_plans", true, c, s, o, bases, ro, seed, episode_index, refined, n_steps, stop_reason, out);
 }
 
-extern "C" int32_t eg_refine_plans_moves_validate(const eg_plan_set* bases, const eg_refine_opts* o, const eg_refine_move_opts* mo) {
-  const char* fn = "eg_refine_plans_moves_validate";
+namespace {
+// what eg_refine_plans_moves_validate asks, in `fn`'s name; null_moves: NULL move options mean "no moves" (eg_repair_plans) and are not refused
+int32_t validate_moves(const char* fn, const eg_plan_set* bases, const eg_refine_opts* o, const eg_refine_move_opts* mo, bool null_moves) {
   EG_TRY(validate_set(fn, bases));
-  if (!mo) { set_error(std::string(fn) + ": NULL move options"); return EG_ERR_BAD_ARG; }
-  if (mo->max_shift < 0 || mo->max_shift > EG_YEARS - 1) {
+  if (!mo && !null_moves) { set_error(std::string(fn) + ": NULL move options"); return EG_ERR_BAD_ARG; }
+  if (mo && (mo->max_shift < 0 || mo->max_shift > EG_YEARS - 1)) {
     set_error(std::string(fn) + ": max_shift = " + std::to_string(mo->max_shift) + " (0.." + std::to_string(EG_YEARS - 1) + " years; 0: no moves)");
     return EG_ERR_BAD_ARG;
   }
   return validate_opts(fn, true, bases, o, mo);
+}
+}  // namespace
+
+extern "C" int32_t eg_refine_plans_moves_validate(const eg_plan_set* bases, const eg_refine_opts* o, const eg_refine_move_opts* mo) {
+  return validate_moves("eg_refine_plans_moves_validate", bases, o, mo, false);
 }
 
 extern "C" int32_t eg_refine_plans_moves(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro,
@@ -301,5 +384,25 @@ extern "C" int32_t eg_refine_plans_moves(eg_ctx* c, const eg_policy_snapshot* s,
                                          int32_t* n_steps, int32_t* stop_reason, double* start_score, eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights || !refined || !steps || !n_steps || !stop_reason) { set_error("eg_refine_plans_moves: bad argument"); return EG_ERR_BAD_ARG; }
   EG_TRY(plan_entry(c, s, o, "eg_refine_plans_moves", [&] { return eg_refine_plans_moves_validate(bases, ro, mo); }));
-  return refine("eg_refine_plans_moves", true, c, s, o, bases, ro, seed, episode_index, refined, nullptr, n_steps, stop_reason, start_score, out, mo, steps);
+  return search(RefineRule{nullptr, steps, start_score}, "eg_refine_plans_moves", true, c, s, o, bases, ro, seed, episode_index, refined, n_steps, stop_reason, out, mo);
+}
+
+extern "C" int32_t eg_repair_plans_validate(const eg_plan_set* bases, const eg_refine_opts* o, const eg_refine_move_opts* mo, const double* weights, int32_t k) {
+  const char* fn = "eg_repair_plans_validate";
+  EG_TRY(check_repair_weights([fn](const std::string& m) { set_error(std::string(fn) + ": " + m); return EG_ERR_BAD_ARG; }, weights, k));
+  return validate_moves(fn, bases, o, mo, true);
+}
+
+extern "C" int32_t eg_repair_plans(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, const eg_plan_set* bases, const eg_refine_opts* ro,
+                                   const eg_refine_move_opts* mo, const double* weights, uint64_t seed, uint64_t episode_index, eg_plan_set** repaired,
+                                   eg_repair_step* steps, int32_t* n_steps, int32_t* stop_reason, double* start_violation, double* final_violation,
+                                   eg_episode_out* out) {
+  if (!c || !s || !s->weights || !s->deficit_weights || !repaired || !steps || !n_steps || !stop_reason) { set_error("eg_repair_plans: bad argument"); return EG_ERR_BAD_ARG; }
+  const int32_t k = c->n_constraints;
+  EG_TRY(plan_entry(c, s, o, "eg_repair_plans", [&] {
+    EG_TRY(check_repair_weights([](const std::string& m) { set_error("eg_repair_plans: " + m); return EG_ERR_BAD_ARG; }, weights, k));
+    return validate_moves("eg_repair_plans", bases, ro, mo, true);
+  }));
+  RepairRule rule{steps, start_violation, final_violation, weights ? std::vector<double>(weights, weights + k) : std::vector<double>(size_t(k), 1.0)};
+  return search(rule, "eg_repair_plans", true, c, s, o, bases, ro, seed, episode_index, repaired, n_steps, stop_reason, out, mo);
 }

@@ -27,6 +27,7 @@
 //   eg_plan_crosses.h     k_plan_crosses                                                                                    eg_rollout.o
 //   eg_plan_rewrites.h    k_plan_rewrites                                                                                   eg_rollout.o
 //   eg_plan_constraints.h k_plan_constraints                                                                                eg_rollout.o
+//   eg_repair.h           k_repair_pick_many                                                                                eg_rollout.o
 //   eg_breed.h            k_breed_gather, k_breed_turnover                                                                  eg_rollout.o
 //   eg_explore.h          k_explore_turnover                                                                                eg_rollout.o
 //   eg_update_kernels.h   k_place .. k_apply_update: the kernels that are not rollouts                                      eg_rollout.o
@@ -1986,6 +1987,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_plan_crosses.h"     // k_plan_crosses: the plan blocks of the variants that splice one parent's years into another
 #include "eg_plan_rewrites.h"    // k_plan_rewrites: the plan blocks of the variants that apply an action map to a window of years
 #include "eg_plan_constraints.h" // k_plan_constraints: the context's plan constraints judged over a plan batch's records
+#include "eg_repair.h"           // k_repair_pick_many: the pick of a repair round, by the violation k_plan_constraints measured
 #include "eg_breed.h"            // k_breed_gather, k_breed_turnover: a generation's survivors become the next one's parents on the device
 #include "eg_explore.h"          // k_explore_turnover: the members that entered an exploration's archive become the next frontier
 
@@ -2340,6 +2342,15 @@ int launch_refine_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs
   if (n_segs == 0 || n_total == 0) return 0;
   hipLaunchKernelGGL(many::k_refine_pick_many, dim3(n_segs), dim3(refine::kThreads), 0, (hipStream_t)stream, o, reinterpret_cast<const refine::Segment*>(d_segs), n_total, mode,
                      reinterpret_cast<const uint2*>(d_edits), d_pool, d_bases, n_bases, d_entries);
+  return (int)hipGetLastError();
+}
+int launch_repair_pick_many(const DevOut& o, const void* d_segs, uint32_t n_segs, uint32_t n_total, int mode, const void* d_edits, const uint8_t* d_pool,
+                            uint8_t* d_bases, uint32_t n_bases, const uint32_t* d_violated, const double* d_excess, uint32_t k, const double* d_weights,
+                            uint8_t* d_entries, void* stream) {
+  if (n_segs == 0 || n_total == 0) return 0;
+  if (k == 0 || k > (uint32_t)EG_CONSTRAINTS_MAX) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(repair::k_repair_pick_many, dim3(n_segs), dim3(refine::kThreads), 0, (hipStream_t)stream, o, reinterpret_cast<const refine::Segment*>(d_segs), n_total, mode,
+                     reinterpret_cast<const uint2*>(d_edits), d_pool, d_bases, n_bases, d_violated, d_excess, k, d_weights, d_entries);
   return (int)hipGetLastError();
 }
 int launch_pick_best(const DevOut& o, uint32_t n, uint64_t first_index, UpdateCandidate* d_cand, void* stream) {

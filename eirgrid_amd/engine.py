@@ -789,6 +789,32 @@ def _refine_move_steps(steps) -> "list[RefineStep]":
                        s.score, np.array(s.metrics[:])) for s in steps]
 
 
+@dataclass
+class RepairStep:
+    """One applied edit or move of Engine.repair_plans (eg_repair_step): the edit (a PlanMove where the step is a move) against the plan of
+    its round, its place among the round's n_variants variants, how many of them were no candidates and how many candidates were feasible,
+    and the mask of violated constraints, the violation measure V, the score and the metrics it reached."""
+    edit: "PlanEdit"
+    variant: int
+    n_variants: int
+    n_failed: int
+    n_feasible: int
+    violated: int
+    violation: float
+    score: float
+    metrics: np.ndarray
+
+
+REPAIR_STOP = ("feasible", "max_rounds", "base_failed", "stuck")
+
+
+def _repair_steps(steps) -> "list[RepairStep]":
+    """eg_repair_step structs as RepairSteps, the move where the step is one"""
+    return [RepairStep(PlanMove(s.move.list, s.move.year, s.move.pos, s.move.to_year, s.move.to_pos) if s.is_move else
+                       PlanEdit(PlanEdit.KINDS[s.edit.kind], s.edit.list, s.edit.year, s.edit.pos, s.edit.action), s.variant, s.n_variants, s.n_failed,
+                       s.n_feasible, int(s.violated), s.violation, s.score, np.array(s.metrics[:])) for s in steps]
+
+
 def _refine_opts(mode, max_rounds, replace_with, append_with):
     """(eg_refine_opts, the arrays it points into)"""
     rep = np.array(list(replace_with or []), np.uint8); app = np.array(list(append_with or []), np.uint8)
@@ -972,7 +998,8 @@ class Engine:
         _plan_rewrites, refine_plan(s), breed_front, explore_front, cross_front, technology_report, plan_timing, plan_sensitivity: a variant
         that ended EG_EP_OK and violates one comes back with status EG_EP_INFEASIBLE (metrics and rows untouched), and every search skips
         it as it skips a failed variant.  So: refining an infeasible base stops with "base_failed"; a step's n_failed counts the
-        infeasible variants; explore_front from infeasible starts admits their feasible neighbours — the way to repair a plan.  Training
+        infeasible variants; explore_front from infeasible starts admits their feasible neighbours; repair_plans descends on the violation
+        itself, the directed way to repair a plan.  Training
         batches (rollout_batch, device_step, ...) are never judged.  While constraints are set the plan calls refuse write_yearly=False."""
         cs = constraint_list(constraints)      # (walked and parsed once: a generator is fine)
         arr, n = constraint_array(cs)
@@ -1375,6 +1402,43 @@ class Engine:
             result.append((plans[p], (_refine_move_steps if moves else _refine_steps)(steps[p * rounds:p * rounds + int(n_steps[p])]), reason, float(start[p]), rec))
         return result
 
+    def repair_plans(self, weights: ActionWeights, bases, seed: int, index: int = 0, mode: int = 1, max_rounds: int = 64, replace_with=None,
+                     append_with=None, max_shift: int = 0, violation_weights=None, enable_energy_sales=True):
+        """Greedy descent on the violation of the engine's constraints (eg_repair_plans; set_constraints first): per round the variants of
+        refine_plans(..., max_shift) for every plan of `bases` (1..REFINE_MAX_PLANS plans), of which the candidate with the smallest
+        violation measure V below the plan's own — constraints.violation of its excess row under `violation_weights`, one per constraint,
+        None: 1.0 each; ties to the largest eg_rank_score in `mode`, then to the lowest variant — becomes the plan, until V is 0.  Returns
+        one tuple per plan: (plan, [RepairStep], stop reason — one of REPAIR_STOP —, the base's V (NaN when it failed), the returned plan's
+        V, its record as a BatchResult of one episode, or None when the base failed)."""
+        ps = bases if isinstance(bases, PlanSet) else PlanSet(bases)
+        n = ps.s.n_plans
+        ro, keep = _refine_opts(mode, max_rounds, replace_with, append_with)
+        rounds = max(int(max_rounds), 1)
+        mo = N.EgRefineMoveOpts(int(max_shift))
+        vw = None if violation_weights is None else np.ascontiguousarray(list(violation_weights), dtype=np.float64)
+        k = len(getattr(self, "_constraints", ()))
+        if vw is not None and k and len(vw) != k:      # (none set: the library's own refusal)
+            raise ValueError(f"{len(vw)} violation weights for {k} constraints")
+        steps = (N.EgRepairStep * (max(n, 1) * rounds))()
+        n_steps = np.zeros(max(n, 1), np.int32); stop = np.zeros(max(n, 1), np.int32)
+        start = np.full(max(n, 1), np.nan); final = np.full(max(n, 1), np.nan)
+        repaired = C.POINTER(N.EgPlanSet)()
+        res = BatchResult.alloc(max(n, 1))
+        snap = weights.snapshot()
+        opts = self._opts(enable_energy_sales, False, True)
+        out = res.struct()
+        N.check(N.lib().eg_repair_plans(self.h, C.byref(snap), C.byref(opts), C.byref(ps.s), C.byref(ro), C.byref(mo) if int(max_shift) != 0 else None,
+                                        None if vw is None else _p(vw, C.c_double), C.c_uint64(seed & (2**64 - 1)), C.c_uint64(index), C.byref(repaired), steps,
+                                        _p(n_steps, C.c_int32), _p(stop, C.c_int32), _p(start, C.c_double), _p(final, C.c_double), C.byref(out)), "eg_repair_plans")
+        plans = Plan._take_set(repaired)
+        names = [f.name for f in fields(BatchResult)]
+        result = []
+        for p in range(n):
+            reason = REPAIR_STOP[int(stop[p])]
+            rec = None if reason == "base_failed" else BatchResult(*[np.ascontiguousarray(getattr(res, f)[p:p + 1]) for f in names])
+            result.append((plans[p], _repair_steps(steps[p * rounds:p * rounds + int(n_steps[p])]), reason, float(start[p]), float(final[p]), rec))
+        return result
+
     # device-resident path used by bench.py
     def upload_snapshot(self, weights: ActionWeights, enable_energy_sales=True, write_yearly=True):
         snap = weights.snapshot()
@@ -1613,6 +1677,18 @@ class Engine:
         base = np.zeros((max(len(first), 1), N.PLAN_BLOCK_BYTES), np.uint8)
         N.check(N.lib().eg_debug_refine_pick_many(self.h, int(mode), _p(first, C.c_uint32), _p(count, C.c_uint32), len(first), entries, _p(base, C.c_uint8)),
                 "eg_debug_refine_pick_many")
+        return list(entries), base
+
+    def _debug_repair_pick_many(self, seg_first, seg_count, mode: int = 1, weights=None):
+        """Test hook (eg_debug_repair_pick_many): (the repair entries, one per segment; the base blocks [n_segs, PLAN_BLOCK_BYTES] as the
+        kernel left them) over the last batch, crafted and judged (_debug_constrain_last_batch), cut into the given segments."""
+        first = np.ascontiguousarray(seg_first, np.uint32); count = np.ascontiguousarray(seg_count, np.uint32)
+        assert first.shape == count.shape and first.ndim == 1
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        entries = (N.EgDebugRepairEntry * max(len(first), 1))()
+        base = np.zeros((max(len(first), 1), N.PLAN_BLOCK_BYTES), np.uint8)
+        N.check(N.lib().eg_debug_repair_pick_many(self.h, int(mode), None if w is None else _p(w, C.c_double), _p(first, C.c_uint32), _p(count, C.c_uint32),
+                                                  len(first), entries, _p(base, C.c_uint8)), "eg_debug_repair_pick_many")
         return list(entries), base
 
     def _debug_breed_begin(self, cap: int, mask: int, mode: int = 1) -> None:

@@ -659,6 +659,61 @@ int32_t eg_plan_constraint_format(const eg_plan_constraint *c, char *buf, int32_
 int32_t eg_debug_load_yearly(eg_ctx *, const double *yearly /* [n][26][21] */, uint32_t n);
 int32_t eg_debug_constrain_last_batch(eg_ctx *);
 
+/* Plan repair: what is the smallest change that makes this plan legal?  eg_repair_plans is a greedy descent on the violation of the
+ * context's plan constraints, for the plans eg_refine_plans stops on with EG_REFINE_BASE_FAILED: per round, of a plan's one-entry
+ * variants, it takes the one that violates least.
+ * THE VIOLATION MEASURE.  A variant j of a batch judged under k constraints, with weights w[0..k) — each finite and > 0; NULL: every
+ * weight 1.0 — has
+ *   V_j = t_0 + t_1 + ... + t_{k-1}, folded from +0.0 in constraint order, one rounding per addition, no fused multiply-add
+ *   t_i = +inf               if excess[j][i] is NaN
+ *         w_i * excess[j][i]  if excess[j][i] > 0 (one rounding)
+ *         +0.0               otherwise
+ * V_j == 0 exactly when violated[j] == 0 (a product that underflows to zero aside: the rounds go by V).  A record whose status is
+ * neither EG_EP_OK nor EG_EP_INFEASIBLE has no V.
+ * A ROUND.  The variants of the plan B_r are those of eg_refine_plans_moves for the same eg_refine_opts / eg_refine_move_opts — the
+ * move options may be NULL: no moves —, in its enumeration and order, evaluated the same way under the context's constraints.  Variant
+ * j is a CANDIDATE when its status is EG_EP_OK or EG_EP_INFEASIBLE and s_j = eg_rank_score(metrics_j, mode) is not NaN.  Variant 0 is
+ * the base.
+ *   variant 0 is no candidate   stop with EG_REPAIR_BASE_FAILED; B_r is returned, no step is recorded for the round
+ *   V_0 == 0                    stop with EG_REPAIR_FEASIBLE (only round 0 can end this way)
+ *   otherwise                   the WINNER is the candidate with V_j < V_0 strictly and the smallest V_j, ties to the largest s_j, then to
+ *                               the lowest j (inf < inf is false: a base at +inf moves only to a finite V)
+ *   there is no such candidate  stop with EG_REPAIR_STUCK
+ *   there is one                B_{r+1} is the winner's plan and a step is recorded: its edit or move (against B_r), its variant index,
+ *                               the round's variant count, how many variants were no candidates and how many candidates had V == 0, its
+ *                               mask, V, score and metrics.  A winner with V == 0 stops with EG_REPAIR_FEASIBLE at once — this is
+ *                               checked first —, otherwise max_rounds steps stop with EG_REPAIR_MAX_ROUNDS
+ * V falls strictly from step to step, so the descent cannot cycle.
+ * The call is eg_refine_plans_moves' loop with another pick: the same packing of plans into launches (EIRGRID_REFINE_LAUNCH_VARIANTS),
+ * the same kernels in front of the rollout grids, k_plan_constraints behind them, then csrc/eg_repair.h k_repair_pick_many, a workgroup
+ * per plan of the launch, which folds V from the excess rows, picks and makes the winner's block the plan's next base.  The weights go
+ * up with the launch's other inputs; one entry of at most 128 bytes per plan comes back, in the launch's one copy.  Per plan the result
+ * equals the call over that plan alone; it does not depend on how plans are packed into launches (a record's n_chunks aside, as for
+ * eg_refine_plans).
+ *   *repaired          the plans as the descent left them, in the bases' order, names kept (free with eg_plans_free)
+ *   steps              [n_plans][max_rounds], row p = plan p, entries 0 .. n_steps[p]
+ *   stop_reason[p], start_violation[p] (V_0 of round 0; NaN when the base failed), final_violation[p] (V of the returned plan; NaN when
+ *                      the base failed in round 0); either violation pointer may be NULL
+ *   out                row p (n_plans episodes, may be NULL): the last winner's record when the plan stops on a step; variant 0's of the
+ *                      last round for a feasible base and on EG_REPAIR_STUCK; not written on EG_REPAIR_BASE_FAILED
+ * k is the number of constraints set on the context.  EG_ERR_BAD_ARG, the message naming the cause: no constraints set, a weight that is
+ * not finite or not > 0, a rank of a group, whatever eg_refine_plans_moves_validate refuses (with NULL move options: what
+ * eg_refine_plans_validate refuses).  Everything else is eg_refine_plans' contract: no statistics, update or folds, the resident policy,
+ * the context's constraints and its Pareto archive untouched; the last launch's variants stay behind as the last batch.
+ * eg_repair_plans_validate runs the checks alone, for k constraints. */
+#define EG_REPAIR_FEASIBLE 0
+#define EG_REPAIR_MAX_ROUNDS 1
+#define EG_REPAIR_BASE_FAILED 2
+#define EG_REPAIR_STUCK 3
+typedef struct { int32_t is_move; eg_plan_edit edit; eg_plan_move move; int32_t variant, n_variants, n_failed, n_feasible;
+                 uint32_t violated; double violation, score, metrics[4]; } eg_repair_step;
+int32_t eg_repair_plans_validate(const eg_plan_set *bases, const eg_refine_opts *, const eg_refine_move_opts * /* or NULL */,
+                                 const double *weights /* [k] or NULL */, int32_t k /* 1..EG_CONSTRAINTS_MAX */);
+int32_t eg_repair_plans(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, const eg_plan_set *bases /* 1..EG_REFINE_MAX_PLANS */,
+                        const eg_refine_opts *, const eg_refine_move_opts * /* or NULL */, const double *weights /* [k] or NULL */,
+                        uint64_t seed, uint64_t episode_index, eg_plan_set **repaired, eg_repair_step *steps /* [n_plans][max_rounds] */,
+                        int32_t *n_steps, int32_t *stop_reason, double *start_violation, double *final_violation, eg_episode_out *out);
+
 /* Breeding a front: generations of plan crosses with Pareto selection, the survivors' plan blocks becoming the next generation's parents
  * on the device.  eg_breed_plans(ctx, policy, opts, parents, breed_opts, seed, episode_index, ...) starts from the population P_0 = the
  * given 1..EG_CROSS_MAX_PARENTS plans, in order.  Generation g = 0, 1, ... :
@@ -854,7 +909,16 @@ int32_t eg_debug_fill_lds(eg_ctx *, uint32_t value);
  *                         records [seg_first[s], + seg_count[s]); the segments must tile [0, n) in order): plan block j, the packed
  *                         edits (j, ~j) and the list totals as for eg_debug_refine_pick; base block s is the words 0xBA5E0000 + (s << 8)
  *                         + w with totals 7 and 5.  `entries` receives n_segs step entries of EG_DEBUG_REFINE_ENTRY_BYTES (`winner`
- *                         relative to the segment), `base_blocks` the n_segs base blocks as the kernel left them. */
+ *                         relative to the segment), `base_blocks` the n_segs base blocks as the kernel left them.
+ *   eg_debug_repair_pick_many  k_repair_pick_many the same way — the segments, the tagged plan blocks, packed edits, list totals and base
+ *                         blocks of eg_debug_refine_pick_many — over the last batch as eg_debug_constrain_last_batch judged it (behind
+ *                         eg_debug_load_batch and eg_debug_load_yearly), under the k constraints it was judged under and `weights`
+ *                         ([k], each finite and > 0; NULL: 1.0 each).  EG_ERR_BAD_ARG when the last batch was not judged.  `entries`
+ *                         receives n_segs entries of EG_DEBUG_REPAIR_ENTRY_BYTES: i32 winner (-1: the base is no candidate; 0: V_0 == 0,
+ *                         or no candidate lies below V_0), n_failed | u32 edit[2] | f64 violation, score, metrics[4] — the winner's;
+ *                         for winner 0 the base's; for winner -1 zeros and variant 0's metrics — | u32 violated | i32 n_feasible, off26,
+ *                         offd26, base_ok, n | f64 base_violation, base_score | u32 base_violated, 0 — the base's three are zeros when
+ *                         it is no candidate. */
 #define EG_DEBUG_LIST_LEN 8
 #define EG_DEBUG_FOLD_BEST_RESULT 1
 #define EG_DEBUG_FOLD_TOP_K 2
@@ -867,6 +931,10 @@ int32_t eg_debug_pick_best(eg_ctx *, void *candidate /* EG_CANDIDATE_BYTES */);
 int32_t eg_debug_refine_pick(eg_ctx *, int32_t mode /* 1 | 2 */, void *entry /* EG_DEBUG_REFINE_ENTRY_BYTES */, uint8_t *base_block /* EG_PLAN_BLOCK_BYTES */);
 int32_t eg_debug_refine_pick_many(eg_ctx *, int32_t mode, const uint32_t *seg_first, const uint32_t *seg_count, int32_t n_segs,
                                   void *entries /* n_segs * EG_DEBUG_REFINE_ENTRY_BYTES */, uint8_t *base_blocks /* n_segs * EG_PLAN_BLOCK_BYTES */);
+#define EG_DEBUG_REPAIR_ENTRY_BYTES 112
+int32_t eg_debug_repair_pick_many(eg_ctx *, int32_t mode, const double *weights /* [k] or NULL */, const uint32_t *seg_first, const uint32_t *seg_count,
+                                  int32_t n_segs, void *entries /* n_segs * EG_DEBUG_REPAIR_ENTRY_BYTES */,
+                                  uint8_t *base_blocks /* n_segs * EG_PLAN_BLOCK_BYTES */);
 /* Test hooks: a crafted generation of eg_breed_plans / eg_explore_plans without a rollout — synthetic records and tagged plan blocks
  * folded into the calls' private archive and turned over by the kernels the two calls launch (k_pareto_filter .. k_pareto_finalize,
  * k_breed_gather, k_breed_turnover, k_explore_turnover), through the launch helpers they use, in their order, on the null stream.  The
