@@ -498,8 +498,9 @@ int launch_pareto_fold(uint8_t* d_state, const ParetoWork& w, const DevOut& o, u
 // k_plan_edits (eg_plan_edits.h): the n plan blocks of a plan-edit batch into d_pool (snap::kPlanStride bytes each) from the base
 // plan's block d_base and n packed edits (8 bytes each: kind | list << 8 | year << 16 | action << 24, then pos)
 int launch_plan_edits(const uint8_t* d_base, const void* d_edits, uint32_t n, uint8_t* d_pool, void* stream);
-// What k_refine_pick_many leaves per plan of a refinement round (eg_refine_plan, eg_refine_plans): the best candidate of the plan's n
-// variants — status EG_EP_OK and a rank score that is not NaN; the largest score, ties to the lowest variant.
+// What k_refine_pick_many (eg_refine_many.h: eg_pick.h's pick under the refine rule) leaves per plan of a refinement round (eg_refine_plan,
+// eg_refine_plans): the best candidate of the plan's n variants — status EG_EP_OK and a rank score that is not NaN; the largest score,
+// ties to the lowest variant.
 struct RefineEntry {
   int32_t winner, n_failed;        // -1: variant 0 is no candidate (nothing copied); variants that are no candidates
   uint32_t edit[2];                // the winner's packed edit
@@ -539,9 +540,10 @@ int launch_plan_rewrites(const uint8_t* d_plans, uint32_t n_plans, const uint8_t
 // judged over the n records of o: d_violated[j] the mask of the constraints record j violates, d_excess[j * k + i] its excess of
 // constraint i; a record that ended EG_EP_OK with a mask that is not zero becomes EG_EP_INFEASIBLE, nothing else of a record is written
 int launch_plan_constraints(const DevOut& o, uint32_t n, const void* d_constraints, uint32_t k, uint32_t* d_violated, double* d_excess, void* stream);
-// What k_repair_pick_many (eg_repair.h) leaves per plan of a repair round (include/eirgrid_hip.h eg_repair_plans): the candidate — status
-// EG_EP_OK or EG_EP_INFEASIBLE and a rank score that is not NaN — with the smallest violation measure V below the base's, ties to the
-// largest score, then to the lowest variant.  An entry takes a slot of the step log, kRefineEntryStride bytes, as a RefineEntry does.
+// What k_repair_pick_many (eg_repair.h: eg_pick.h's pick under the repair rule) leaves per plan of a repair round (include/eirgrid_hip.h
+// eg_repair_plans): the candidate — status EG_EP_OK or EG_EP_INFEASIBLE and a rank score that is not NaN — with the smallest violation
+// measure V below the base's, ties to the largest score, then to the lowest variant.  An entry takes a slot of the step log,
+// kRefineEntryStride bytes, as a RefineEntry does.
 struct RepairEntry {
   int32_t winner, n_failed;        // -1: variant 0 is no candidate; 0: V_0 == 0, or no candidate below V_0 (nothing copied either way); variants that are no candidates
   uint32_t edit[2];                // the winner's packed edit (winner <= 0: variant 0's)

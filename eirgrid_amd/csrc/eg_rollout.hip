@@ -21,7 +21,7 @@
 //   eg_pareto.h           the Pareto archive of a run's outcomes                                                            eg_rollout.o
 //   eg_plan_block.h       what the kernels that write plan blocks share                                                     eg_rollout.o
 //   eg_plan_edits.h       k_plan_edits                                                                                      eg_rollout.o
-//   eg_refine.h           what the pick of a refinement round reduces with                                                  eg_rollout.o
+//   eg_pick.h             the pick that ends a round of a plan search: wave_best, pick_segment                              eg_rollout.o
 //   eg_refine_many.h      k_plan_edits_many, k_refine_pick_many                                                             eg_rollout.o
 //   eg_plan_moves.h       k_plan_moves                                                                                      eg_rollout.o
 //   eg_plan_crosses.h     k_plan_crosses                                                                                    eg_rollout.o
@@ -1981,7 +1981,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_pareto.h"           // k_pareto_filter .. k_pareto_finalize: the Pareto archive of a run's outcomes
 #include "eg_plan_block.h"       // pblock: the plan-block layout and what the four kernels that write plan blocks share
 #include "eg_plan_edits.h"       // k_plan_edits: the plan blocks of a plan-edit batch from one base block and an edit per variant
-#include "eg_refine.h"           // refine::before, wave_best: what the pick of a refinement round reduces with
+#include "eg_pick.h"             // refine::wave_best, pick_segment: the pick that ends a round, whatever the rule
 #include "eg_refine_many.h"      // k_plan_edits_many, k_refine_pick_many: a refinement round, a segment of the launch's variants per plan
 #include "eg_plan_moves.h"       // k_plan_moves: the plan blocks of the variants that move an entry to another year
 #include "eg_plan_crosses.h"     // k_plan_crosses: the plan blocks of the variants that splice one parent's years into another

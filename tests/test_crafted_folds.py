@@ -193,7 +193,7 @@ def pick_best(score_list, first_index):
 
 
 def refine_pick(status, metrics, mode):
-    """The definition at the top of csrc/eg_refine.h: variant j is a candidate when its status is EG_EP_OK and its rank score is not NaN;
+    """The definition at the top of csrc/eg_refine_many.h: variant j is a candidate when its status is EG_EP_OK and its rank score is not NaN;
     the winner is the candidate with the largest score, ties to the lowest j; -1 when variant 0 is no candidate.
     Returns (winner, n_failed, the winner's score, base_ok, the base's score)."""
     from eirgrid_amd.engine import rank_score
