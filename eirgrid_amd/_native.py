@@ -144,7 +144,19 @@ class EgPlanConstraint(C.Structure):
                 ("bound", C.c_double)]
 
 
-assert C.sizeof(EgPlanConstraint) == 16
+BUILD_CLASSES, BUILD_SPEC_MAX = 19, 1024      # EG_BUILD_CLASSES, EG_BUILD_SPEC_MAX
+# the build classes in index order: the generator types (models/generator.rs order), then the four offsets
+BUILD_CLASS_NAMES = ("OnshoreWind", "OffshoreWind", "DomesticSolar", "CommercialSolar", "UtilitySolar", "Nuclear", "CoalPlant", "GasCombinedCycle",
+                     "GasPeaker", "Biomass", "HydroDam", "PumpedStorage", "BatteryStorage", "TidalGenerator", "WaveEnergy",
+                     "Forest", "Wetland", "ActiveCapture", "CarbonCredit")
+
+
+class EgBuildConstraint(C.Structure):
+    _fields_ = [("aggregate", C.c_uint8), ("op", C.c_uint8), ("from_year", C.c_uint8), ("to_year", C.c_uint8), ("pad", C.c_uint8 * 4),
+                ("bound", C.c_double), ("weight", C.c_double * BUILD_CLASSES)]
+
+
+assert C.sizeof(EgPlanConstraint) == 16 and C.sizeof(EgBuildConstraint) == 168
 assert C.sizeof(EgPlanMove) == 12 and C.sizeof(EgPlanCross) == 6
 assert C.sizeof(EgActionMap) == 61 and C.sizeof(EgPlanRewrite) == 8
 assert C.sizeof(EgExploreOpts) == 64 and C.sizeof(EgExploreGeneration) == 40 and C.sizeof(EgExploreMember) == 88
@@ -220,6 +232,8 @@ EXPORTS = [
     "eg_breed_validate", "eg_breed_plans", "eg_explore_validate", "eg_explore_neighbourhood", "eg_explore_plans",
     "eg_plan_constraints_validate", "eg_plan_constraints_set", "eg_fetch_plan_feasibility", "eg_last_batch_constraints", "eg_plan_constraint_parse", "eg_plan_constraint_format",
     "eg_debug_load_yearly", "eg_debug_constrain_last_batch",
+    "eg_build_constraints_validate", "eg_build_constraints_set", "eg_last_batch_build_constraints", "eg_build_constraint_parse", "eg_build_constraint_format",
+    "eg_debug_load_built",
     "eg_repair_plans_validate", "eg_repair_plans", "eg_debug_repair_pick_many",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
@@ -455,6 +469,20 @@ def lib():
         L.eg_debug_load_yearly.argtypes = [C.c_void_p, _dp, C.c_uint32]
         L.eg_debug_constrain_last_batch.restype = C.c_int32
         L.eg_debug_constrain_last_batch.argtypes = [C.c_void_p]
+    # (likewise: scripts/build_constraint_probe.py may load a build of the parent commit, which has no build constraints)
+    if hasattr(L, "eg_build_constraints_set") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_build_constraints_validate.restype = C.c_int32
+        L.eg_build_constraints_validate.argtypes = [C.POINTER(EgBuildConstraint), C.c_int32]
+        L.eg_build_constraints_set.restype = C.c_int32
+        L.eg_build_constraints_set.argtypes = [C.c_void_p, C.POINTER(EgBuildConstraint), C.c_int32]
+        L.eg_last_batch_build_constraints.restype = C.c_int32
+        L.eg_last_batch_build_constraints.argtypes = [C.c_void_p, C.POINTER(EgBuildConstraint)]
+        L.eg_build_constraint_parse.restype = C.c_int32
+        L.eg_build_constraint_parse.argtypes = [C.c_char_p, C.POINTER(EgBuildConstraint)]
+        L.eg_build_constraint_format.restype = C.c_int32
+        L.eg_build_constraint_format.argtypes = [C.POINTER(EgBuildConstraint), C.c_char_p, C.c_int32]
+        L.eg_debug_load_built.restype = C.c_int32
+        L.eg_debug_load_built.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.POINTER(C.c_int32), C.POINTER(C.c_uint16), C.c_uint32]
     # (likewise: scripts/repair_probe.py may load a build of the parent commit, which has no repair)
     if hasattr(L, "eg_repair_plans") or not os.environ.get("EIRGRID_LIB"):
         L.eg_repair_plans_validate.restype = C.c_int32

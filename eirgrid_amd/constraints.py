@@ -1,5 +1,6 @@
 """Plan constraints (include/eirgrid_hip.h eg_plan_constraints_set): a bound on one column of the yearly rows over a window of years, judged
-on the device behind every plan batch of an Engine that has them set.  The text form is the library's (eg_plan_constraint_parse /
+on the device behind every plan batch of an Engine that has them set; and build constraints (eg_build_constraints_set, BuildConstraint): a
+bound on the weighted count of what an episode built, per year or over a window, judged with them.  The text form is the library's (eg_plan_constraint_parse /
 _format); `Constraint.excess` restates the definition for users who filter BatchResult.yearly on the host."""
 from __future__ import annotations
 
@@ -112,9 +113,147 @@ def violation(excess_row, weights=None) -> float:
     return v
 
 
-def constraint_list(constraints) -> "list[Constraint]":
-    """Constraints and specs (any iterable, walked once; None: none) as a list of Constraint"""
-    return [c if isinstance(c, Constraint) else Constraint.parse(c) for c in (constraints if constraints is not None else ())]
+def _class_index(key) -> int:
+    if isinstance(key, str):
+        if key not in N.BUILD_CLASS_NAMES:
+            raise ValueError(f"unknown class {key!r} (one of {', '.join(N.BUILD_CLASS_NAMES)})")
+        return N.BUILD_CLASS_NAMES.index(key)
+    if not 0 <= int(key) < N.BUILD_CLASSES:
+        raise ValueError(f"class {key} (0..{N.BUILD_CLASSES - 1})")
+    return int(key)
+
+
+@dataclass(frozen=True)
+class BuildConstraint:
+    """A bound on what an episode BUILT (include/eirgrid_hip.h eg_build_constraints_set): the weighted count of the entries of its record's
+    gen_pack / off_pack lists per class — `weights`: a dict of class name or index -> weight ("any": the 15 generator types), or 19
+    numbers in N.BUILD_CLASS_NAMES order — `op` ("<=" | ">=") `bound`, for every year of the window from_year <= y < to_year (year
+    INDICES, 0 = 2025; aggregate "every": a build rate) or for the window's total ("sum")."""
+    weights: "dict | tuple"
+    op: str
+    bound: float
+    from_year: int = 0
+    to_year: int = N.YEARS
+    aggregate: str = "every"
+
+    def __post_init__(self):
+        if isinstance(self.weights, dict):
+            w = [0.0] * N.BUILD_CLASSES
+            for key, x in self.weights.items():
+                for q in (range(15) if key == "any" else (_class_index(key),)):
+                    w[q] = float(x)
+        else:
+            w = [float(x) for x in self.weights]
+            if len(w) != N.BUILD_CLASSES:
+                raise ValueError(f"{len(w)} weights ({N.BUILD_CLASSES}: one per class)")
+        object.__setattr__(self, "weights", tuple(w))
+        if self.op not in ("<=", ">="):
+            raise ValueError(f"op {self.op!r} ('<=' | '>=')")
+        if self.aggregate not in ("every", "sum"):
+            raise ValueError(f"aggregate {self.aggregate!r} ('every' | 'sum')")
+        object.__setattr__(self, "bound", float(self.bound))
+
+    def struct(self) -> N.EgBuildConstraint:
+        for name in ("from_year", "to_year"):
+            if not 0 <= int(getattr(self, name)) <= 255:
+                raise ValueError(f"{name} {getattr(self, name)} does not fit a byte")
+        return N.EgBuildConstraint(N.AGG_SUM if self.aggregate == "sum" else N.AGG_EVERY, N.OP_GE if self.op == ">=" else N.OP_LE, int(self.from_year),
+                                   int(self.to_year), (C.c_uint8 * 4)(), self.bound, (C.c_double * N.BUILD_CLASSES)(*self.weights))
+
+    @staticmethod
+    def _from_struct(s: N.EgBuildConstraint) -> "BuildConstraint":
+        return BuildConstraint(tuple(s.weight[:]), ">=" if s.op == N.OP_GE else "<=", float(s.bound), int(s.from_year), int(s.to_year),
+                               "sum" if s.aggregate == N.AGG_SUM else "every")
+
+    @staticmethod
+    def parse(spec: str) -> "BuildConstraint":
+        """"[sum(]built([W*]CLASS {(+|-) [W*]CLASS})[)] (<=|>=) BOUND [@FROM[:TO]]" with calendar years (eg_build_constraint_parse)."""
+        s = N.EgBuildConstraint()
+        N.check(N.lib().eg_build_constraint_parse(str(spec).encode(), C.byref(s)), "eg_build_constraint_parse")
+        return BuildConstraint._from_struct(s)
+
+    def __str__(self) -> str:
+        buf = C.create_string_buffer(N.BUILD_SPEC_MAX)
+        s = self.struct()
+        N.check(N.lib().eg_build_constraint_format(C.byref(s), buf, len(buf)), "eg_build_constraint_format")
+        return buf.value.decode()
+
+    @staticmethod
+    def counts(gen_pack, n_gens, off_pack, n_offsets) -> np.ndarray:
+        """c[26][19] of one record's lists, the header's definition restated: the entries in front of the counts (clamped to the lists), a
+        class or a year out of range counts nowhere."""
+        c = np.zeros((N.YEARS, N.BUILD_CLASSES), np.int64)
+        for pack, count, base, classes in ((gen_pack, n_gens, 0, 15), (off_pack, n_offsets, 15, 4)):
+            pack = np.asarray(pack).reshape(-1)
+            for pk in pack[:min(max(int(count), 0), len(pack))].tolist():
+                q, y = int(pk) & 15, (int(pk) >> 4) & 31
+                if q < classes and y < N.YEARS:
+                    c[y, base + q] += 1
+        return c
+
+    def value(self, m) -> float:
+        """value(m) of a count vector m[19]: from +0.0, s = s + weight[q] * m[q] in class order, each product and each sum rounded once"""
+        s = 0.0
+        for q in range(N.BUILD_CLASSES):
+            s = s + self.weights[q] * float(int(m[q]))
+        return s
+
+    def excess(self, gen_pack, n_gens, off_pack, n_offsets) -> float:
+        """The excess of this constraint over one record's lists, the header's definition restated in plain Python floats: satisfied iff
+        the result is <= 0; a negative excess is the slack."""
+        c = self.counts(gen_pack, n_gens, off_pack, n_offsets)
+        ge = self.op == ">="
+        if self.aggregate == "sum":
+            s = self.value(c[self.from_year:self.to_year].sum(axis=0))
+            e = self.bound - s if ge else s - self.bound
+        else:
+            e = None
+            for y in range(self.from_year, self.to_year):
+                s = self.value(c[y])
+                x = self.bound - s if ge else s - self.bound
+                if e is None or (not math.isnan(e) and (math.isnan(x) or x > e)):
+                    e = x
+        return _NAN if math.isnan(e) else float(e)
+
+    def violated(self, gen_pack, n_gens, off_pack, n_offsets) -> bool:
+        return not self.excess(gen_pack, n_gens, off_pack, n_offsets) <= 0.0
+
+
+def constraint_list(constraints) -> "list[Constraint | BuildConstraint]":
+    """Constraints and specs (any iterable, walked once; None: none) as a list of Constraint and BuildConstraint: a spec that contains
+    "built(" is a build constraint's"""
+    def one(c):
+        if isinstance(c, (Constraint, BuildConstraint)):
+            return c
+        return BuildConstraint.parse(c) if "built(" in str(c) else Constraint.parse(c)
+    return [one(c) for c in (constraints if constraints is not None else ())]
+
+
+def record_violates(c, result, e: int) -> bool:
+    """whether episode e of a BatchResult violates the constraint c of either kind, by the host restatements"""
+    if isinstance(c, BuildConstraint):
+        return c.violated(result.gen_pack[e], result.n_gens[e], result.off_pack[e], result.n_offsets[e])
+    return c.violated(result.yearly[e])
+
+
+def split_constraints(constraints) -> "tuple[list[Constraint], list[BuildConstraint]]":
+    """(row constraints, build constraints) of a mixed list, which holds the row constraints first — mask bits, excess columns and repair
+    weights follow the list's order, so a row constraint behind a build constraint is refused, not moved"""
+    cs = constraint_list(constraints)
+    n_rows = next((i for i, c in enumerate(cs) if isinstance(c, BuildConstraint)), len(cs))
+    for i, c in enumerate(cs[n_rows:], n_rows):
+        if isinstance(c, Constraint):
+            raise ValueError(f"constraint {i} ({c}) is a row constraint behind a build constraint ({cs[n_rows]}): list the row constraints first "
+                             "(mask bits, excess columns and weights follow the list's order)")
+    return cs[:n_rows], cs[n_rows:]
+
+
+def build_constraint_array(constraints):
+    """(ctypes array or None, n) of a list of BuildConstraints"""
+    cs = list(constraints)
+    if not cs:
+        return None, 0
+    return (N.EgBuildConstraint * len(cs))(*[c.struct() for c in cs]), len(cs)
 
 
 def constraint_array(constraints):
@@ -129,12 +268,15 @@ def add_constraint_arguments(parser) -> None:
     """--constraint SPEC (repeatable) for a script's argparse parser; apply_constraints puts them on the engine"""
     parser.add_argument("--constraint", action="append", default=[], metavar="SPEC",
                         help="a bound on the yearly rows every plan must meet, \"[sum(]COLUMN[)] (<=|>=) BOUND [@FROM[:TO]]\" with calendar years, e.g. "
-                             "\"net_co2 <= 0 @2040\", \"sum(net_co2) <= 4e8\", \"balance >= 500 @2030:2039\"; repeatable (at most 32)")
+                             "\"net_co2 <= 0 @2040\", \"sum(net_co2) <= 4e8\", \"balance >= 500 @2030:2039\", or on what it builds, "
+                             "\"[sum(]built([W*]CLASS {(+|-) [W*]CLASS})[)] (<=|>=) BOUND [@FROM[:TO]]\", e.g. \"built(GasPeaker + GasCombinedCycle) <= 0\", "
+                             "\"sum(built(Nuclear)) <= 2\"; repeatable (at most 32, the row constraints first)")
 
 
 def apply_constraints(engine, args) -> "list[Constraint]":
-    """the --constraint specs of `args` parsed (eg_plan_constraint_parse) and set on `engine`; returns them (none given: nothing is set)"""
-    cs = [Constraint.parse(spec) for spec in args.constraint]
+    """the --constraint specs of `args` parsed (constraint_list: eg_plan_constraint_parse, eg_build_constraint_parse) and set on `engine`;
+    returns them (none given: nothing is set)"""
+    cs = constraint_list(args.constraint)
     if cs:
         engine.set_constraints(cs)
     return cs

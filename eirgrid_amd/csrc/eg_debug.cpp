@@ -113,11 +113,22 @@ int32_t eg_debug_load_yearly(eg_ctx* c, const double* yearly, uint32_t n) {
   return put_field(c, rec::yearly, yearly, sizeof(double) * EG_YEARS * EG_YEARLY_FIELDS, n);
 }
 
+int32_t eg_debug_load_built(eg_ctx* c, const int32_t* n_gens, const uint16_t* gen_pack, const int32_t* n_offsets, const uint16_t* off_pack, uint32_t n) {
+  if (!c || !n_gens || !gen_pack || !n_offsets || !off_pack) { set_error("eg_debug_load_built: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_load_built"));
+  if (n == 0 || n != c->last_n) { set_error("eg_debug_load_built: n = " + std::to_string(n) + ", the last batch holds " + std::to_string(c->last_n) + " records"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  EG_TRY(put_field(c, rec::n_gens, n_gens, sizeof(int32_t), n));
+  EG_TRY(put_field(c, rec::n_offsets, n_offsets, sizeof(int32_t), n));
+  EG_TRY(put_field(c, rec::gen_pack, gen_pack, sizeof(uint16_t) * EG_MAX_GENS, n));      // the whole rows: also what lies behind the counts
+  return put_field(c, rec::off_pack, off_pack, sizeof(uint16_t) * EG_MAX_OFFSETS, n);
+}
+
 int32_t eg_debug_constrain_last_batch(eg_ctx* c) {
   if (!c) { set_error("eg_debug_constrain_last_batch: bad argument"); return EG_ERR_BAD_ARG; }
   EG_TRY(refuse_rank(c, "eg_debug_constrain_last_batch"));
   if (c->last_n == 0) { set_error("eg_debug_constrain_last_batch: there is no last batch"); return EG_ERR_BAD_ARG; }
-  if (c->n_constraints == 0) { set_error("eg_debug_constrain_last_batch: eg_plan_constraints_set first (no constraints are set)"); return EG_ERR_BAD_ARG; }
+  if (c->n_constraints + c->n_build_constraints == 0) { set_error("eg_debug_constrain_last_batch: eg_plan_constraints_set first (no constraints are set)"); return EG_ERR_BAD_ARG; }
   EG_HIP(hipSetDevice(c->device));
   return constrain_batch(c, c->last_n);
 }

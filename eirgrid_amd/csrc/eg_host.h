@@ -1,4 +1,4 @@
-// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_debug / eg_plans / eg_plan_host / eg_plan_constraints / eg_refine / eg_breed / eg_explore /
+// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_debug / eg_plans / eg_plan_host / eg_plan_constraints / eg_build_constraints / eg_refine / eg_breed / eg_explore /
 // eg_place / eg_group .cpp): owned buffers, the error macros, the context and the helpers that cross units, listed by the unit that holds them.  Host only: the kernels include eg_internal.h, never this.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -149,6 +149,11 @@ struct eg_ctx {
   eg::DevBuf<uint8_t> d_constraints; int n_constraints = 0;
   eg::DevBuf<uint32_t> d_violated; eg::DevBuf<double> d_excess; int feas_k = 0;
   eg_plan_constraint constraints[EG_CONSTRAINTS_MAX] = {}, judged[EG_CONSTRAINTS_MAX] = {};
+  // build constraints (eg_build_constraints_set; eg_build_constraints.cpp): the n_build_constraints constraints on the device, 168 bytes
+  // each, and the two host copies, set and judged.  With one set k_build_constraints judges both kinds: feas_k is their total, feas_builds
+  // how many of them — the last columns of an excess row — are build constraints (constrain_batch sets both)
+  eg::DevBuf<uint8_t> d_build_constraints; int n_build_constraints = 0, feas_builds = 0;
+  eg_build_constraint build_constraints[EG_CONSTRAINTS_MAX] = {}, build_judged[EG_CONSTRAINTS_MAX] = {};
   // plan refinement (eg_refine_plan, eg_refine_plans): the step log k_refine_pick_many writes, an entry per plan of a launch from the
   // start (kRefineLog entries of kRefineEntryStride bytes); the base blocks of the call's plans (uploaded once, kept current by
   // k_refine_pick_many) and what a launch uploads in one copy: the packed edits, the base slot of every variant, the segment table
@@ -194,8 +199,9 @@ int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x);
 void write_plan_blocks(const eg_plan_set* p, uint8_t* dst);
 int decode_plan_blocks(const uint8_t* blocks, int32_t n, const char* who, eg_plan_set** set);
 
-// eg_plan_constraints.cpp: k_plan_constraints over the n records of c->out under the context's constraints (at least one is set), on the
-// null stream; the side buffers reserved, c->feas_k set
+// eg_plan_constraints.cpp: k_plan_constraints — with a build constraint set, k_build_constraints in its place — over the n records of
+// c->out under the context's constraints (at least one of either kind is set), on the null stream; the side buffers reserved, c->feas_k
+// and c->feas_builds set
 int constrain_batch(eg_ctx* c, uint32_t n);
 
 // eg_plan_host.cpp: the pieces a plan search is written from.  `fn` / `who` name the entry point in the messages.

@@ -540,6 +540,11 @@ int launch_plan_rewrites(const uint8_t* d_plans, uint32_t n_plans, const uint8_t
 // judged over the n records of o: d_violated[j] the mask of the constraints record j violates, d_excess[j * k + i] its excess of
 // constraint i; a record that ended EG_EP_OK with a mask that is not zero becomes EG_EP_INFEASIBLE, nothing else of a record is written
 int launch_plan_constraints(const DevOut& o, uint32_t n, const void* d_constraints, uint32_t k, uint32_t* d_violated, double* d_excess, void* stream);
+// k_build_constraints (eg_build_constraints.h), in place of k_plan_constraints where a build constraint is set: the k_rows row constraints at
+// d_constraints (0..EG_CONSTRAINTS_MAX) and the k_builds build constraints at d_build_constraints (eg_build_constraint, 168 bytes each, 1..
+// EG_CONSTRAINTS_MAX - k_rows) judged in one pass; mask bit i and d_excess[j * (k_rows + k_builds) + i] number the row constraints first
+int launch_build_constraints(const DevOut& o, uint32_t n, const void* d_constraints, uint32_t k_rows, const void* d_build_constraints, uint32_t k_builds,
+                             uint32_t* d_violated, double* d_excess, void* stream);
 // What k_repair_pick_many (eg_repair.h: eg_pick.h's pick under the repair rule) leaves per plan of a repair round (include/eirgrid_hip.h
 // eg_repair_plans): the candidate — status EG_EP_OK or EG_EP_INFEASIBLE and a rank score that is not NaN — with the smallest violation
 // measure V below the base's, ties to the largest score, then to the lowest variant.  An entry takes a slot of the step log,

@@ -44,12 +44,15 @@ int validate(const char* who, const eg_plan_constraint* cs, int32_t n) {
 }  // namespace
 
 int eg::constrain_batch(eg_ctx* c, uint32_t n) {
-  const uint32_t k = uint32_t(c->n_constraints);
+  const uint32_t k_rows = uint32_t(c->n_constraints), k_builds = uint32_t(c->n_build_constraints), k = k_rows + k_builds;
   EG_HIP(c->d_violated.reserve(n));
   EG_HIP(c->d_excess.reserve(size_t(n) * k));
-  EG_LAUNCH("k_plan_constraints", launch_plan_constraints(c->out, n, c->d_constraints, k, c->d_violated, c->d_excess, nullptr));
+  // with no build constraint set: the launch as it always was; with one, the kernel that judges both kinds in one pass
+  if (k_builds == 0) EG_LAUNCH("k_plan_constraints", launch_plan_constraints(c->out, n, c->d_constraints, k, c->d_violated, c->d_excess, nullptr));
+  else EG_LAUNCH("k_build_constraints", launch_build_constraints(c->out, n, c->d_constraints, k_rows, c->d_build_constraints, k_builds, c->d_violated, c->d_excess, nullptr));
   std::memcpy(c->judged, c->constraints, sizeof(c->judged));
-  c->feas_k = int(k);
+  std::memcpy(c->build_judged, c->build_constraints, sizeof(c->build_judged));
+  c->feas_k = int(k); c->feas_builds = int(k_builds);
   return EG_OK;
 }
 
@@ -61,6 +64,10 @@ int32_t eg_plan_constraints_set(eg_ctx* c, const eg_plan_constraint* constraints
   if (!c) { set_error("eg_plan_constraints_set: bad argument"); return EG_ERR_BAD_ARG; }
   if (c->group_member) { set_error("eg_plan_constraints_set: the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
   EG_TRY(validate("eg_plan_constraints_set", constraints, n));
+  if (n + c->n_build_constraints > EG_CONSTRAINTS_MAX) {
+    set_error("eg_plan_constraints_set: n = " + std::to_string(n) + " with " + std::to_string(c->n_build_constraints) + " build constraints set (together at most " + std::to_string(EG_CONSTRAINTS_MAX) + ")");
+    return EG_ERR_BAD_ARG;
+  }
   if (n == 0) { c->n_constraints = 0; return EG_OK; }
   EG_HIP(hipSetDevice(c->device));
   // the pad bytes go up as zeros whatever the caller left in them
@@ -77,7 +84,7 @@ int32_t eg_plan_constraints_set(eg_ctx* c, const eg_plan_constraint* constraints
 
 int32_t eg_last_batch_constraints(const eg_ctx* c, eg_plan_constraint* out) {
   if (!c) { set_error("eg_last_batch_constraints: bad argument"); return EG_ERR_BAD_ARG; }
-  const int32_t k = c->last_n > 0 ? c->feas_k : 0;
+  const int32_t k = c->last_n > 0 && c->feas_k > 0 ? c->feas_k - c->feas_builds : 0;      // (the row constraints: the first columns)
   if (out) std::memcpy(out, c->judged, sizeof(eg_plan_constraint) * size_t(k));
   return k;
 }

@@ -28,6 +28,7 @@
 //   eg_plan_rewrites.h    k_plan_rewrites                                                                                   eg_rollout.o
 //   eg_plan_constraints.h k_plan_constraints                                                                                eg_rollout.o
 //   eg_repair.h           k_repair_pick_many                                                                                eg_rollout.o
+//   eg_build_constraints.h k_build_constraints                                                                              eg_rollout.o
 //   eg_breed.h            k_breed_gather, k_breed_turnover                                                                  eg_rollout.o
 //   eg_explore.h          k_explore_turnover                                                                                eg_rollout.o
 //   eg_update_kernels.h   k_place .. k_apply_update: the kernels that are not rollouts                                      eg_rollout.o
@@ -1988,6 +1989,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_plan_rewrites.h"    // k_plan_rewrites: the plan blocks of the variants that apply an action map to a window of years
 #include "eg_plan_constraints.h" // k_plan_constraints: the context's plan constraints judged over a plan batch's records
 #include "eg_repair.h"           // k_repair_pick_many: the pick of a repair round, by the violation k_plan_constraints measured
+#include "eg_build_constraints.h" // k_build_constraints: row and build constraints judged in one pass, where a build constraint is set
 #include "eg_breed.h"            // k_breed_gather, k_breed_turnover: a generation's survivors become the next one's parents on the device
 #include "eg_explore.h"          // k_explore_turnover: the members that entered an exploration's archive become the next frontier
 
@@ -2316,6 +2318,14 @@ int launch_plan_constraints(const DevOut& o, uint32_t n, const void* d_constrain
   if (n == 0 || k == 0 || k > (uint32_t)EG_CONSTRAINTS_MAX) return n == 0 || k == 0 ? 0 : (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_plan_constraints, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, o, n, reinterpret_cast<const pcons::Packed*>(d_constraints), k, d_violated,
                      d_excess);
+  return (int)hipGetLastError();
+}
+int launch_build_constraints(const DevOut& o, uint32_t n, const void* d_constraints, uint32_t k_rows, const void* d_build_constraints, uint32_t k_builds,
+                             uint32_t* d_violated, double* d_excess, void* stream) {
+  if (n == 0 || k_builds == 0) return 0;
+  if (k_rows + k_builds > (uint32_t)EG_CONSTRAINTS_MAX || k_rows > (uint32_t)EG_CONSTRAINTS_MAX) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_build_constraints, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, o, n, reinterpret_cast<const pcons::Packed*>(d_constraints), k_rows,
+                     reinterpret_cast<const bcons::Packed*>(d_build_constraints), k_builds, d_violated, d_excess);
   return (int)hipGetLastError();
 }
 int launch_breed_gather(uint8_t* d_breed, const DevOut& o, uint32_t n, uint64_t first, const uint8_t* d_pool, void* stream) {

@@ -13,7 +13,7 @@ from dataclasses import dataclass, fields
 import numpy as np
 
 from . import _native as N
-from .constraints import Constraint, constraint_array, constraint_list
+from .constraints import BuildConstraint, Constraint, build_constraint_array, constraint_array, constraint_list, split_constraints
 from .world import World
 
 BASE_YEAR, END_YEAR = 2025, 2050
@@ -1000,21 +1000,42 @@ class Engine:
         it as it skips a failed variant.  So: refining an infeasible base stops with "base_failed"; a step's n_failed counts the
         infeasible variants; explore_front from infeasible starts admits their feasible neighbours; repair_plans descends on the violation
         itself, the directed way to repair a plan.  Training
-        batches (rollout_batch, device_step, ...) are never judged.  While constraints are set the plan calls refuse write_yearly=False."""
-        cs = constraint_list(constraints)      # (walked and parsed once: a generator is fine)
-        arr, n = constraint_array(cs)
-        N.check(N.lib().eg_plan_constraints_set(self.h, arr, n), "eg_plan_constraints_set")
-        self._constraints = cs
+        batches (rollout_batch, device_step, ...) are never judged.  While row constraints are set the plan calls refuse write_yearly=False.
+        The list may hold BuildConstraints (specs with "built(": bounds on what an episode builds, eg_build_constraints_set) BEHIND the row
+        constraints, together at most 32: mask bits, excess columns and repair weights follow the list's order, so a row constraint behind
+        a build constraint raises ValueError."""
+        rows, builds = split_constraints(constraints)      # (walked and parsed once: a generator is fine)
+        L = N.lib()
+        # checked before anything is cleared, so a list that is refused leaves what was set: the row setter's own refusal, as ever
+        arr, n = constraint_array(rows)
+        if L.eg_plan_constraints_validate(arr, n) != N.EG_OK:
+            N.check(L.eg_plan_constraints_set(self.h, arr, n), "eg_plan_constraints_set")
+        arr, n = build_constraint_array(builds)
+        N.check(L.eg_build_constraints_validate(arr, n), "eg_build_constraints_validate")
+        # both kinds cleared first, so neither setter meets the other kind's old count
+        N.check(L.eg_plan_constraints_set(self.h, None, 0), "eg_plan_constraints_set")
+        N.check(L.eg_build_constraints_set(self.h, None, 0), "eg_build_constraints_set")
+        self._constraints = []
+        arr, n = constraint_array(rows)
+        N.check(L.eg_plan_constraints_set(self.h, arr, n), "eg_plan_constraints_set")
+        self._constraints = rows
+        arr, n = build_constraint_array(builds)
+        N.check(L.eg_build_constraints_set(self.h, arr, n), "eg_build_constraints_set")
+        self._constraints = rows + builds
 
     def clear_constraints(self) -> None:
         self.set_constraints([])
 
-    def last_batch_constraints(self) -> "list[Constraint]":
-        """The constraints the LAST batch was judged under (eg_last_batch_constraints) — not those set now; [] when it was not judged."""
+    def last_batch_constraints(self) -> "list[Constraint | BuildConstraint]":
+        """The constraints the LAST batch was judged under (eg_last_batch_constraints, then eg_last_batch_build_constraints: the row
+        constraints, then the build constraints) — not those set now; [] when it was not judged."""
         arr = (N.EgPlanConstraint * N.CONSTRAINTS_MAX)()
         k = N.lib().eg_last_batch_constraints(self.h, arr)
         N.check(min(k, 0), "eg_last_batch_constraints")
-        return [Constraint._from_struct(arr[i]) for i in range(k)]
+        barr = (N.EgBuildConstraint * N.CONSTRAINTS_MAX)()
+        kb = N.lib().eg_last_batch_build_constraints(self.h, barr)
+        N.check(min(kb, 0), "eg_last_batch_build_constraints")
+        return [Constraint._from_struct(arr[i]) for i in range(k)] + [BuildConstraint._from_struct(barr[i]) for i in range(kb)]
 
     def fetch_feasibility(self):
         """(violated [n] uint32, excess [n, k] float64) of the last plan batch (eg_fetch_plan_feasibility): bit i of violated[j] is set iff
@@ -1022,7 +1043,8 @@ class Engine:
         been set or cleared since; excess[j, i] <= 0 means satisfied, its negative is the slack, NaN violates.  A variant that failed on
         its own has mask 0 and a row of NaN.  Refused when the last batch ran without constraints."""
         L = N.lib()
-        n, k = int(L.eg_last_batch_size(self.h)), int(L.eg_last_batch_constraints(self.h, None))
+        n = int(L.eg_last_batch_size(self.h))
+        k = int(L.eg_last_batch_constraints(self.h, None)) + int(L.eg_last_batch_build_constraints(self.h, None))      # rows, then builds
         if k <= 0 or n == 0:      # the library's own refusal, nothing written
             N.check(L.eg_fetch_plan_feasibility(self.h, None, None), "eg_fetch_plan_feasibility")
             raise N.EirgridError("eg_fetch_plan_feasibility: the last batch ran without plan constraints")
@@ -1641,13 +1663,22 @@ class Engine:
                                             None if al is None else _p(al, C.c_uint8), None if sl is None else _p(sl, C.c_double), n,
                                             C.c_uint64(int(first_index))), "eg_debug_load_batch")
 
+    def _debug_load_built(self, n_gens, gen_pack, n_offsets, off_pack) -> None:
+        """Test hook (eg_debug_load_built): the counts [n] and the whole lists [n,4096] (uint16) of what the records of the crafted batch
+        _debug_load_batch made built — what lies behind the counts goes up too."""
+        ng, no = np.ascontiguousarray(n_gens, dtype=np.int32), np.ascontiguousarray(n_offsets, dtype=np.int32)
+        gp, op = np.ascontiguousarray(gen_pack, dtype=np.uint16), np.ascontiguousarray(off_pack, dtype=np.uint16)
+        assert gp.shape == (len(ng), N.MAX_GENS) and op.shape == (len(no), N.MAX_OFFSETS) and len(ng) == len(no)
+        N.check(N.lib().eg_debug_load_built(self.h, _p(ng, C.c_int32), _p(gp, C.c_uint16), _p(no, C.c_int32), _p(op, C.c_uint16), len(ng)), "eg_debug_load_built")
+
     def _debug_load_yearly(self, yearly) -> None:
         """Test hook (eg_debug_load_yearly): the yearly rows [n,26,21] of the crafted batch _debug_load_batch made."""
         y = np.ascontiguousarray(yearly, dtype=np.float64).reshape(-1, N.YEARS, N.YEARLY_FIELDS)
         N.check(N.lib().eg_debug_load_yearly(self.h, _p(y, C.c_double), len(y)), "eg_debug_load_yearly")
 
     def _debug_constrain_last_batch(self) -> None:
-        """Test hook (eg_debug_constrain_last_batch): k_plan_constraints over the last batch, as a plan batch ends."""
+        """Test hook (eg_debug_constrain_last_batch): k_plan_constraints — with a build constraint set, k_build_constraints — over the last
+        batch, as a plan batch ends."""
         N.check(N.lib().eg_debug_constrain_last_batch(self.h), "eg_debug_constrain_last_batch")
 
     def _debug_fold_last_batch(self, best_result: bool = False, top_k: bool = False, use_score_list: bool = False) -> None:

@@ -641,8 +641,8 @@ int32_t eg_evaluate_plan_rewrites(eg_ctx *, const eg_policy_snapshot *, const eg
  * eg_plan_constraint_format writes the same form (the bound with 17 significant digits, so parse(format(c)) == c) into buf; EG_ERR_BAD_ARG
  * for a constraint eg_plan_constraints_validate refuses or a buffer that is too small (EG_CONSTRAINT_SPEC_MAX bytes always suffice).
  * Test hooks (they refuse a rank of a group): eg_debug_load_yearly overwrites the yearly rows of the n records eg_debug_load_batch made
- * (n = eg_last_batch_size()); eg_debug_constrain_last_batch launches k_plan_constraints over the last batch through the launcher a plan
- * batch uses (EG_ERR_BAD_ARG with no constraints set or no last batch). */
+ * (n = eg_last_batch_size()); eg_debug_constrain_last_batch launches k_plan_constraints (with a build constraint set: k_build_constraints,
+ * below) over the last batch through the launcher a plan batch uses (EG_ERR_BAD_ARG with no constraints set or no last batch). */
 #define EG_CONSTRAINTS_MAX 32
 #define EG_AGG_EVERY 0   /* each year of the window */
 #define EG_AGG_SUM 1     /* the window's sum */
@@ -652,12 +652,70 @@ int32_t eg_evaluate_plan_rewrites(eg_ctx *, const eg_policy_snapshot *, const eg
 typedef struct { uint8_t column /* EG_Y_*, 0..20 */, aggregate, op, from_year, to_year /* 0 <= from < to <= 26 */, pad[3]; double bound /* finite */; } eg_plan_constraint; /* 16 bytes */
 int32_t eg_plan_constraints_validate(const eg_plan_constraint *constraints, int32_t n);
 int32_t eg_plan_constraints_set(eg_ctx *, const eg_plan_constraint *constraints, int32_t n /* 0: clear */);
-int32_t eg_fetch_plan_feasibility(eg_ctx *, uint32_t *violated /* [n] or NULL */, double *excess /* [n][k] or NULL */);
+int32_t eg_fetch_plan_feasibility(eg_ctx *, uint32_t *violated /* [n] or NULL */, double *excess /* [n][k_rows + k_builds] or NULL */);
 int32_t eg_last_batch_constraints(const eg_ctx *, eg_plan_constraint *out /* [EG_CONSTRAINTS_MAX] or NULL */);
 int32_t eg_plan_constraint_parse(const char *spec, eg_plan_constraint *out);
 int32_t eg_plan_constraint_format(const eg_plan_constraint *c, char *buf, int32_t len);
 int32_t eg_debug_load_yearly(eg_ctx *, const double *yearly /* [n][26][21] */, uint32_t n);
 int32_t eg_debug_constrain_last_batch(eg_ctx *);
+
+/* Build constraints: bounds on what a plan BUILDS, judged on the device with the plan constraints above.  The yearly rows hold totals
+ * (gen, co2, active_gens), no technology: "no new gas", "at most two nuclear plants", "no more than four onshore wind farms a year", "at
+ * least as many batteries as wind farms by 2035", "at most ten carbon-credit purchases" are statements about the fleet an episode
+ * actually built — gen_pack[n_gens] and off_pack[n_offsets] of its record, which include the repair loop's and the fallback draws' builds
+ * (dropping a technology from a plan's text does not keep a fallback draw from building it) and the entries a replay applies twice.
+ * THE DEFINITION.  There are EG_BUILD_CLASSES classes: 0..14 the generator types in models/generator.rs order, 15..18 Forest, Wetland,
+ * ActiveCapture, CarbonCredit.  For one record, c[y][q] (y = 0..25) counts the list entries that match: of gen_pack, the entries
+ * i < clamp(n_gens, 0, EG_MAX_GENS) with (pk & 15) == q, q < 15, and ((pk >> 4) & 31) == y; of off_pack, the entries
+ * i < clamp(n_offsets, 0, EG_MAX_OFFSETS) with (pk & 15) < 4, q == 15 + (pk & 15), and ((pk >> 4) & 31) == y.  An entry whose class is out
+ * of range (generator type 15, offset type >= 4) or whose year index is >= 26 counts nowhere; what lies at or behind the counts is never
+ * read as data.  The VALUE of a count vector m[0..19) under a constraint's weights is
+ *   s = +0.0; for q = 0..18 in order: s = s + weight[q] * (double)m[q]      (the product rounded once, the sum rounded once, no FMA)
+ * and the EXCESS of a constraint {aggregate, op, from_year, to_year, bound, weight[19]} over the window from_year <= y < to_year is
+ *   EG_AGG_EVERY   x_y = value(c[y]) - bound for EG_OP_LE, bound - value(c[y]) for EG_OP_GE, folded over the window exactly as the row
+ *                  definition folds it: e = x_from, then if e is NaN it stays, else if x_y is NaN or x_y > e then e = x_y (the largest,
+ *                  the first of equal ones).  A build-rate cap per year.
+ *   EG_AGG_SUM     m[q] = the sum of c[y][q] over the window (integer, exact); the excess is value(m) - bound or bound - value(m).  A
+ *                  total over the window.
+ * SATISFIED iff excess <= 0.  The weight cap keeps every value finite, so no NaN arises; a NaN excess would be stored as the canonical
+ * quiet NaN all the same, so the two kinds share one rule.
+ * HOW THE TWO KINDS LIVE TOGETHER.  A context holds row constraints (eg_plan_constraints_set) and build constraints
+ * (eg_build_constraints_set), together at most EG_CONSTRAINTS_MAX: either setter refuses a count that would take the total above it,
+ * naming both counts; n = 0 clears that kind only.  A judged batch has k = k_rows + k_builds constraints; mask bit i and excess column i
+ * number the row constraints first, then the build constraints.  With a build constraint set, csrc/eg_build_constraints.h
+ * k_build_constraints runs in place of k_plan_constraints behind every plan batch and judges both kinds in one pass — one mask, one
+ * excess row, one demotion a record; with none set nothing differs from the section above.  eg_fetch_plan_feasibility then serves
+ * excess[n][k_rows + k_builds]; eg_last_batch_constraints keeps returning the ROW constraints and k_rows, eg_last_batch_build_constraints
+ * returns k_builds (0 when the last batch was not judged) and copies the build constraints it was judged under unless `out` is NULL;
+ * eg_repair_plans and eg_debug_repair_pick_many take k = k_rows + k_builds weights and refuse only when neither kind is set;
+ * eg_debug_constrain_last_batch runs when either kind is set.  The write_yearly = 0 refusal stays tied to row constraints: build
+ * constraints alone do not read the rows.  Groups and training batches are not judged, as above.
+ * eg_build_constraints_validate: EG_ERR_BAD_ARG naming index and field ("constraint 3: weight[7] nan (finite, at most 1e300 in
+ * magnitude)") for n outside 0..EG_CONSTRAINTS_MAX, NULL with n > 0, an unknown aggregate or op, to_year > 26, from_year >= to_year, a
+ * bound that is not finite, a weight that is not finite or above 1e300 in magnitude, weights that are all zero.
+ * TEXT FORM, one parser and one formatter: "[sum(]built(TERMS)[)] (<=|>=) BOUND [@FROM[:TO]]", TERMS = [W*]CLASS {(+|-) [W*]CLASS}, CLASS a
+ * generator type name (OnshoreWind, OffshoreWind, DomesticSolar, CommercialSolar, UtilitySolar, Nuclear, CoalPlant, GasCombinedCycle,
+ * GasPeaker, Biomass, HydroDam, PumpedStorage, BatteryStorage, TidalGenerator, WaveEnergy), an offset name (Forest, Wetland,
+ * ActiveCapture, CarbonCredit) or `any` (all 15 generator types); W a finite number, 1 when absent; a class named twice is refused; the
+ * window as in the row grammar ("built(GasPeaker + GasCombinedCycle) <= 0", "sum(built(Nuclear)) <= 2", "built(OnshoreWind) <= 4
+ * @2025:2034", "sum(built(BatteryStorage - OnshoreWind)) >= 0 @2025:2035", "sum(built(CarbonCredit)) <= 10").  Errors quote the offending
+ * token.  eg_build_constraint_format writes the classes with a weight other than zero in index order, the bound and every weight other
+ * than 1 with 17 significant digits, `any` when weights 0..14 are equal and not zero and 15..18 are zero, so parse(format(c)) == c (a
+ * weight of -0.0 reads back as +0.0); EG_BUILD_SPEC_MAX bytes always suffice.
+ * Test hook (it refuses a rank of a group): eg_debug_load_built overwrites the two counts and the two lists of the n records
+ * eg_debug_load_batch made (n = eg_last_batch_size()); whole rows are copied, what lies behind the counts included. */
+#define EG_BUILD_CLASSES 19   /* 0..14: the generator types in models/generator.rs order (gen_pack & 15);
+                                 15..18: Forest, Wetland, ActiveCapture, CarbonCredit (15 + (off_pack & 15)) */
+#define EG_BUILD_SPEC_MAX 1024
+typedef struct { uint8_t aggregate, op, from_year, to_year /* 0 <= from < to <= 26 */, pad[4]; double bound /* finite */;
+                 double weight[EG_BUILD_CLASSES] /* each finite, |w| <= 1e300, not all zero */; } eg_build_constraint; /* 168 bytes */
+int32_t eg_build_constraints_validate(const eg_build_constraint *constraints, int32_t n);
+int32_t eg_build_constraints_set(eg_ctx *, const eg_build_constraint *constraints, int32_t n /* 0: clear */);
+int32_t eg_last_batch_build_constraints(const eg_ctx *, eg_build_constraint *out /* [EG_CONSTRAINTS_MAX] or NULL */);
+int32_t eg_build_constraint_parse(const char *spec, eg_build_constraint *out);
+int32_t eg_build_constraint_format(const eg_build_constraint *c, char *buf, int32_t len);
+int32_t eg_debug_load_built(eg_ctx *, const int32_t *n_gens /* [n] */, const uint16_t *gen_pack /* [n][EG_MAX_GENS] */,
+                            const int32_t *n_offsets /* [n] */, const uint16_t *off_pack /* [n][EG_MAX_OFFSETS] */, uint32_t n);
 
 /* Plan repair: what is the smallest change that makes this plan legal?  eg_repair_plans is a greedy descent on the violation of the
  * context's plan constraints, for the plans eg_refine_plans stops on with EG_REFINE_BASE_FAILED: per round, of a plan's one-entry

@@ -40,7 +40,7 @@ def main():
     ap.add_argument("--policy", help="a policy checkpoint to evaluate the plans under (default: a fresh policy)")
     ap.add_argument("--seed", type=int, required=True)
     ap.add_argument("--out", required=True, help="output directory")
-    from eirgrid_amd.constraints import Constraint, add_constraint_arguments
+    from eirgrid_amd.constraints import add_constraint_arguments, constraint_list
     add_constraint_arguments(ap)
     a = ap.parse_args()
     if not a.constraint:
@@ -48,7 +48,7 @@ def main():
     from eirgrid_amd import synthetic_world
     from eirgrid_amd.engine import ActionWeights, Engine, Plan
     from eirgrid_amd.world import World
-    constraints = [Constraint.parse(spec) for spec in a.constraint]
+    constraints = constraint_list(a.constraint)
     world = synthetic_world() if a.world == "synthetic" else World.from_json_dict(json.load(open(a.world)))
     plans = Plan.load(a.plans)
     policy = ActionWeights.load_from_file(a.policy) if a.policy else ActionWeights()

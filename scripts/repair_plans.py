@@ -46,6 +46,7 @@ def floats(text):
 
 def write(out_dir, bases, results, constraints, cost_only):
     """The three files from Engine.repair_plans' result; returns the directory."""
+    from eirgrid_amd.constraints import record_violates
     from eirgrid_amd.engine import Plan, PlanMove, rank_score
     from refine_front import g17
     d = os.path.join(out_dir, "repair")
@@ -56,8 +57,7 @@ def write(out_dir, bases, results, constraints, cost_only):
         for p, (plan, steps, stop, start, final, rec) in enumerate(results):
             metrics = [g17(v) for v in rec.metrics[0]] if rec is not None else ["nan"] * 4
             score = g17(rank_score(rec.metrics[0], cost_only)) if rec is not None else "nan"
-            rows = rec.yearly[0] if rec is not None else None
-            still = ";".join(str(c) for c in constraints if rows is not None and c.violated(rows))
+            still = ";".join(str(c) for c in constraints if rec is not None and record_violates(c, rec, 0))
             w.writerow([p, bases[p].name, stop, len(steps), g17(start), g17(final), score] + metrics + [still])
     with open(os.path.join(d, "trajectories.csv"), "w", newline="") as f:
         w = csv.writer(f, lineterminator="\n")
