@@ -15,6 +15,44 @@ from . import _native as N
 _NAN = float("nan")      # the canonical quiet NaN a NaN excess is reported as
 
 
+# ---- what Constraint and BuildConstraint share: the fields behind the head and the fold of an "every" window ---------------------------
+def _check_tail(c) -> None:
+    """op and aggregate of a new constraint of either kind checked, its bound made a float"""
+    if c.op not in ("<=", ">="):
+        raise ValueError(f"op {c.op!r} ('<=' | '>=')")
+    if c.aggregate not in ("every", "sum"):
+        raise ValueError(f"aggregate {c.aggregate!r} ('every' | 'sum')")
+    object.__setattr__(c, "bound", float(c.bound))
+
+
+def _bytes(c, *names) -> "list[int]":
+    """the named fields of c as ints that fit a byte"""
+    for name in names:
+        if not 0 <= int(getattr(c, name)) <= 255:
+            raise ValueError(f"{name} {getattr(c, name)} does not fit a byte")
+    return [int(getattr(c, name)) for name in names]
+
+
+def _codes(c) -> "tuple[int, int]":
+    """(aggregate, op) of c as the struct holds them"""
+    return N.AGG_SUM if c.aggregate == "sum" else N.AGG_EVERY, N.OP_GE if c.op == ">=" else N.OP_LE
+
+
+def _names(s) -> "tuple[str, str]":
+    """(op, aggregate) of a struct of either kind as the classes hold them"""
+    return ">=" if s.op == N.OP_GE else "<=", "sum" if s.aggregate == N.AGG_SUM else "every"
+
+
+def _largest(excesses) -> float:
+    """the largest of a window's yearly excesses, a NaN sticky: the first year's value, then year by year in order"""
+    it = iter(excesses)
+    e = next(it, None)      # (None: no year at all)
+    for x in it:
+        if not math.isnan(e) and (math.isnan(x) or x > e):
+            e = x
+    return e
+
+
 @dataclass(frozen=True)
 class Constraint:
     """`column` (an EG_Y_* index or its lower-case name) `op` ("<=" | ">=") `bound` over the years from_year <= y < to_year (year INDICES,
@@ -31,23 +69,16 @@ class Constraint:
             if self.column not in N.YEARLY_COLUMNS:
                 raise ValueError(f"unknown column {self.column!r} (one of {', '.join(N.YEARLY_COLUMNS)})")
             object.__setattr__(self, "column", N.YEARLY_COLUMNS.index(self.column))
-        if self.op not in ("<=", ">="):
-            raise ValueError(f"op {self.op!r} ('<=' | '>=')")
-        if self.aggregate not in ("every", "sum"):
-            raise ValueError(f"aggregate {self.aggregate!r} ('every' | 'sum')")
-        object.__setattr__(self, "bound", float(self.bound))
+        _check_tail(self)
 
     def struct(self) -> N.EgPlanConstraint:
-        for name in ("column", "from_year", "to_year"):
-            if not 0 <= int(getattr(self, name)) <= 255:
-                raise ValueError(f"{name} {getattr(self, name)} does not fit a byte")
-        return N.EgPlanConstraint(int(self.column), N.AGG_SUM if self.aggregate == "sum" else N.AGG_EVERY, N.OP_GE if self.op == ">=" else N.OP_LE,
-                                  int(self.from_year), int(self.to_year), (C.c_uint8 * 3)(), self.bound)
+        column, from_year, to_year = _bytes(self, "column", "from_year", "to_year")
+        return N.EgPlanConstraint(column, *_codes(self), from_year, to_year, (C.c_uint8 * 3)(), self.bound)
 
     @staticmethod
     def _from_struct(s: N.EgPlanConstraint) -> "Constraint":
-        return Constraint(int(s.column), ">=" if s.op == N.OP_GE else "<=", float(s.bound), int(s.from_year), int(s.to_year),
-                          "sum" if s.aggregate == N.AGG_SUM else "every")
+        op, aggregate = _names(s)
+        return Constraint(int(s.column), op, float(s.bound), int(s.from_year), int(s.to_year), aggregate)
 
     @staticmethod
     def parse(spec: str) -> "Constraint":
@@ -74,11 +105,8 @@ class Constraint:
                     s = s + v[y]
                 e = bound - s if ge else s - bound
             else:
-                e = bound - v[self.from_year] if ge else v[self.from_year] - bound
-                for y in range(self.from_year + 1, self.to_year):
-                    x = bound - v[y] if ge else v[y] - bound
-                    if not math.isnan(e) and (math.isnan(x) or x > e):
-                        e = x
+                years = (self.from_year, *range(self.from_year + 1, self.to_year))      # (from_year itself whatever to_year is, as the sum)
+                e = _largest(bound - v[y] if ge else v[y] - bound for y in years)
         return _NAN if math.isnan(e) else float(e)
 
     def violated(self, rows) -> bool:
@@ -147,23 +175,16 @@ class BuildConstraint:
             if len(w) != N.BUILD_CLASSES:
                 raise ValueError(f"{len(w)} weights ({N.BUILD_CLASSES}: one per class)")
         object.__setattr__(self, "weights", tuple(w))
-        if self.op not in ("<=", ">="):
-            raise ValueError(f"op {self.op!r} ('<=' | '>=')")
-        if self.aggregate not in ("every", "sum"):
-            raise ValueError(f"aggregate {self.aggregate!r} ('every' | 'sum')")
-        object.__setattr__(self, "bound", float(self.bound))
+        _check_tail(self)
 
     def struct(self) -> N.EgBuildConstraint:
-        for name in ("from_year", "to_year"):
-            if not 0 <= int(getattr(self, name)) <= 255:
-                raise ValueError(f"{name} {getattr(self, name)} does not fit a byte")
-        return N.EgBuildConstraint(N.AGG_SUM if self.aggregate == "sum" else N.AGG_EVERY, N.OP_GE if self.op == ">=" else N.OP_LE, int(self.from_year),
-                                   int(self.to_year), (C.c_uint8 * 4)(), self.bound, (C.c_double * N.BUILD_CLASSES)(*self.weights))
+        from_year, to_year = _bytes(self, "from_year", "to_year")
+        return N.EgBuildConstraint(*_codes(self), from_year, to_year, (C.c_uint8 * 4)(), self.bound, (C.c_double * N.BUILD_CLASSES)(*self.weights))
 
     @staticmethod
     def _from_struct(s: N.EgBuildConstraint) -> "BuildConstraint":
-        return BuildConstraint(tuple(s.weight[:]), ">=" if s.op == N.OP_GE else "<=", float(s.bound), int(s.from_year), int(s.to_year),
-                               "sum" if s.aggregate == N.AGG_SUM else "every")
+        op, aggregate = _names(s)
+        return BuildConstraint(tuple(s.weight[:]), op, float(s.bound), int(s.from_year), int(s.to_year), aggregate)
 
     @staticmethod
     def parse(spec: str) -> "BuildConstraint":
@@ -207,12 +228,8 @@ class BuildConstraint:
             s = self.value(c[self.from_year:self.to_year].sum(axis=0))
             e = self.bound - s if ge else s - self.bound
         else:
-            e = None
-            for y in range(self.from_year, self.to_year):
-                s = self.value(c[y])
-                x = self.bound - s if ge else s - self.bound
-                if e is None or (not math.isnan(e) and (math.isnan(x) or x > e)):
-                    e = x
+            values = (self.value(c[y]) for y in range(self.from_year, self.to_year))
+            e = _largest(self.bound - s if ge else s - self.bound for s in values)
         return _NAN if math.isnan(e) else float(e)
 
     def violated(self, gen_pack, n_gens, off_pack, n_offsets) -> bool:
@@ -248,20 +265,22 @@ def split_constraints(constraints) -> "tuple[list[Constraint], list[BuildConstra
     return cs[:n_rows], cs[n_rows:]
 
 
-def build_constraint_array(constraints):
-    """(ctypes array or None, n) of a list of BuildConstraints"""
-    cs = list(constraints)
+def struct_array(cs, ctype):
+    """(ctypes array of `ctype` or None, n) of a list of constraints of one kind"""
+    cs = list(cs)
     if not cs:
         return None, 0
-    return (N.EgBuildConstraint * len(cs))(*[c.struct() for c in cs]), len(cs)
+    return (ctype * len(cs))(*[c.struct() for c in cs]), len(cs)
+
+
+def build_constraint_array(constraints):
+    """(ctypes array or None, n) of a list of BuildConstraints"""
+    return struct_array(constraints, N.EgBuildConstraint)
 
 
 def constraint_array(constraints):
     """(ctypes array or None, n) of a list of Constraints and specs"""
-    cs = constraint_list(constraints)
-    if not cs:
-        return None, 0
-    return (N.EgPlanConstraint * len(cs))(*[c.struct() for c in cs]), len(cs)
+    return struct_array(constraint_list(constraints), N.EgPlanConstraint)
 
 
 def add_constraint_arguments(parser) -> None:

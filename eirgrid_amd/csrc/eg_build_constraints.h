@@ -4,14 +4,15 @@
 // eg_repair.h.
 //
 // A wave per variant, four variants per workgroup of 256 (pblock::my_variant), k_plan_constraints' shape.  Per wave: its 26 x 19 bins of
-// uint32_t (1 976 bytes of LDS) are zeroed; with k_rows > 0 the variant's 546 yearly doubles are staged as k_plan_constraints stages them;
-// the two lists of what the episode built — gen_pack[n_gens], off_pack[n_offsets], the counts clamped to 0..4 096 — are walked with 8-byte
+// uint32_t (1 976 bytes of LDS) are zeroed; with k_rows > 0 the variant's 546 yearly doubles are staged by pcons::stage_rows
+// (eg_plan_constraints.h: k_plan_constraints' staging); the two lists of what the episode built — gen_pack[n_gens], off_pack[n_offsets], the counts clamped to 0..4 096 — are walked with 8-byte
 // loads, four entries a lane, the entries at or behind the count masked by index (a load never leaves the list's 8 192 bytes), and every
 // entry with a class and a year in range adds 1 to bin [year][class] with an LDS integer atomic: integer adds commute, so the bins do not
 // depend on the order.  Behind a workgroup barrier lane i < k_rows folds row constraint i (pcons::excess_of, the one definition), lane
 // k_rows <= i < k folds build constraint i - k_rows out of the bins in the order the header defines: per year (EG_AGG_EVERY) or for the
 // window's integer totals (EG_AGG_SUM) s = +0.0, then s = s + weight[q] * (double)count for q = 0..18, a product and a sum each rounded
-// once (the build forms no FMA).  One ballot makes the mask; the stores are k_plan_constraints'.
+// once (the build forms no FMA).  The canonical NaN, the ballot that makes the mask and the stores are pcons::store_judgment, the one
+// definition behind both kernels.
 // No wave returns ahead of a barrier: a wave without a variant and a record that failed skip loads, atomics and fold, not the barriers.
 // No scratch memory, no global atomic; the kernel writes bytes rec::status .. +4 of record j and rows j of the two side buffers, nothing
 // else.  The host has validated every constraint; the kernel clamps the counts, the windows and k all the same.
@@ -82,7 +83,6 @@ __device__ __forceinline__ double excess_of(const uint32_t* c, const Packed* p) 
 __global__ void __launch_bounds__(256) k_build_constraints(DevOut o, uint32_t n, const pcons::Packed* __restrict__ rows_cons, uint32_t k_rows,
                                                            const bcons::Packed* __restrict__ build_cons, uint32_t k_builds,
                                                            uint32_t* __restrict__ violated, double* __restrict__ excess) {
-  using pcons::kQuietNaN;
   __shared__ double rows[4][pcons::kRows];
   __shared__ uint32_t bins[4][bcons::kBins];
   const pblock::Wave w = pblock::my_variant();
@@ -95,14 +95,7 @@ __global__ void __launch_bounds__(256) k_build_constraints(DevOut o, uint32_t n,
   const bool live = w.j < n;
   const bool ok = live && *o.status(live ? w.j : 0u) == EG_EP_OK;      // (the same word in every lane of the wave)
   for (int i = lane; i < bcons::kBins; i += kWave) c[i] = 0u;
-  if (ok && k_rows > 0u) {
-    const double* src = o.yearly(w.j);
-    double r[pcons::kLoads];
-#pragma unroll
-    for (int i = 0; i < pcons::kLoads; ++i) r[i] = lane + i * kWave < pcons::kRows ? src[lane + i * kWave] : 0.0;
-#pragma unroll
-    for (int i = 0; i < pcons::kLoads; ++i) if (lane + i * kWave < pcons::kRows) v[lane + i * kWave] = r[i];
-  }
+  if (ok && k_rows > 0u) pcons::stage_rows(v, o, w.j, lane);
   __syncthreads();      // (the zeros stand before the first add)
   if (ok) {
     bcons::count_list(c, o.gen_pack(w.j), *o.n_gens(w.j), EG_MAX_GENS, 0, bcons::kGenClasses, lane);
@@ -110,17 +103,7 @@ __global__ void __launch_bounds__(256) k_build_constraints(DevOut o, uint32_t n,
   }
   __syncthreads();
   const bool mine = (uint32_t)lane < k;
-  double e = __longlong_as_double((long long)kQuietNaN);
-  if (ok && mine) {
-    e = (uint32_t)lane < k_rows ? pcons::excess_of(v, rows_cons[lane]) : bcons::excess_of(c, build_cons + ((uint32_t)lane - k_rows));
-    if (e != e) e = __longlong_as_double((long long)kQuietNaN);
-  }
-  const uint32_t mask = (uint32_t)__ballot(ok && mine && !(e <= 0.0));
-  if (live) {
-    if (mine) excess[(size_t)w.j * k + (uint32_t)lane] = e;
-    if (lane == 0) {
-      violated[w.j] = mask;
-      if (mask != 0u) *o.status(w.j) = EG_EP_INFEASIBLE;
-    }
-  }
+  pcons::store_judgment(o, live, ok, mine, [=] {
+    return (uint32_t)lane < k_rows ? pcons::excess_of(v, rows_cons[lane]) : bcons::excess_of(c, build_cons + ((uint32_t)lane - k_rows));
+  }, k, lane, w.j, violated, excess);
 }

@@ -104,7 +104,7 @@ int32_t eg_debug_load_batch(eg_ctx* c, const double* metrics, const int32_t* sta
   return EG_OK;
 }
 
-// ---- plan constraints over a crafted batch: the rows, then the launch a plan batch ends with (eg_plan_constraints.cpp constrain_batch) ------
+// ---- plan constraints over a crafted batch: the rows, then the launch a plan batch ends with (eg_constraints.cpp constrain_batch) ------
 int32_t eg_debug_load_yearly(eg_ctx* c, const double* yearly, uint32_t n) {
   if (!c || !yearly) { set_error("eg_debug_load_yearly: bad argument"); return EG_ERR_BAD_ARG; }
   EG_TRY(refuse_rank(c, "eg_debug_load_yearly"));
@@ -128,7 +128,7 @@ int32_t eg_debug_constrain_last_batch(eg_ctx* c) {
   if (!c) { set_error("eg_debug_constrain_last_batch: bad argument"); return EG_ERR_BAD_ARG; }
   EG_TRY(refuse_rank(c, "eg_debug_constrain_last_batch"));
   if (c->last_n == 0) { set_error("eg_debug_constrain_last_batch: there is no last batch"); return EG_ERR_BAD_ARG; }
-  if (c->n_constraints + c->n_build_constraints == 0) { set_error("eg_debug_constrain_last_batch: eg_plan_constraints_set first (no constraints are set)"); return EG_ERR_BAD_ARG; }
+  if (c->rows.n + c->builds.n == 0) { set_error("eg_debug_constrain_last_batch: eg_plan_constraints_set first (no constraints are set)"); return EG_ERR_BAD_ARG; }
   EG_HIP(hipSetDevice(c->device));
   return constrain_batch(c, c->last_n);
 }

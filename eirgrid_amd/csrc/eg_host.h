@@ -1,4 +1,4 @@
-// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_debug / eg_plans / eg_plan_host / eg_plan_constraints / eg_build_constraints / eg_refine / eg_breed / eg_explore /
+// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_debug / eg_plans / eg_plan_host / eg_constraints / eg_refine / eg_breed / eg_explore /
 // eg_place / eg_group .cpp): owned buffers, the error macros, the context and the helpers that cross units, listed by the unit that holds them.  Host only: the kernels include eg_internal.h, never this.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,6 +50,9 @@ struct DevBuf {
   }
 };
 template <typename T> using PinBuf = DevBuf<T, true>;
+// the constraints of one kind that a context holds: the n set ones on the device (EG_CONSTRAINTS_MAX slots, zeros behind the n), their host
+// copy, and the host copy of what the last judged batch ran under (eg_last_batch_constraints, eg_last_batch_build_constraints)
+template <class T> struct ConstraintSet { DevBuf<uint8_t> dev; int n = 0; T set[EG_CONSTRAINTS_MAX] = {}, judged[EG_CONSTRAINTS_MAX] = {}; };
 }  // namespace eg
 
 struct eg_host_tables {
@@ -142,18 +145,13 @@ struct eg_ctx {
   //  batch, eg_evaluate_plan_rewrites: every plan's block, the maps, then the packed rewrites — what k_plan_rewrites reads)
   eg::DevBuf<uint8_t> d_plan_edit_in;
   size_t n_plan_blocks = 0;      // blocks of the last plan or plan-edit batch in d_plans (eg_debug_fetch_plan_block)
-  // plan constraints (eg_plan_constraints_set; eg_plan_constraints.cpp): the n_constraints constraints on the device, 16 bytes each, and
-  // the two side buffers k_plan_constraints fills behind a plan batch — a mask per record, an excess row of feas_k doubles per record.
-  // feas_k: the constraints the last batch was judged under, 0 when it was not (every batch that sets last_n sets it)
-  // constraints / judged: host copies of what is set and of what the last judged batch ran under (eg_last_batch_constraints)
-  eg::DevBuf<uint8_t> d_constraints; int n_constraints = 0;
-  eg::DevBuf<uint32_t> d_violated; eg::DevBuf<double> d_excess; int feas_k = 0;
-  eg_plan_constraint constraints[EG_CONSTRAINTS_MAX] = {}, judged[EG_CONSTRAINTS_MAX] = {};
-  // build constraints (eg_build_constraints_set; eg_build_constraints.cpp): the n_build_constraints constraints on the device, 168 bytes
-  // each, and the two host copies, set and judged.  With one set k_build_constraints judges both kinds: feas_k is their total, feas_builds
-  // how many of them — the last columns of an excess row — are build constraints (constrain_batch sets both)
-  eg::DevBuf<uint8_t> d_build_constraints; int n_build_constraints = 0, feas_builds = 0;
-  eg_build_constraint build_constraints[EG_CONSTRAINTS_MAX] = {}, build_judged[EG_CONSTRAINTS_MAX] = {};
+  // constraints (eg_plan_constraints_set, eg_build_constraints_set; eg_constraints.cpp), a ConstraintSet per kind: rows, the plan constraints
+  // on the yearly rows, 16 bytes each, and builds, the build constraints, 168 bytes each.  The two side buffers are what k_plan_constraints
+  // — with a build constraint set k_build_constraints, which judges both kinds — fills behind a plan batch: a mask per record, an excess
+  // row of feas_k doubles per record.  feas_k: the constraints the last batch was judged under, 0 when it was not (every batch that sets
+  // last_n sets it); feas_builds: how many of them — the last columns of an excess row — are build constraints (constrain_batch sets both)
+  eg::ConstraintSet<eg_plan_constraint> rows; eg::ConstraintSet<eg_build_constraint> builds;
+  eg::DevBuf<uint32_t> d_violated; eg::DevBuf<double> d_excess; int feas_k = 0, feas_builds = 0;
   // plan refinement (eg_refine_plan, eg_refine_plans): the step log k_refine_pick_many writes, an entry per plan of a launch from the
   // start (kRefineLog entries of kRefineEntryStride bytes); the base blocks of the call's plans (uploaded once, kept current by
   // k_refine_pick_many) and what a launch uploads in one copy: the packed edits, the base slot of every variant, the segment table
@@ -199,7 +197,7 @@ int64_t child_len(const std::vector<int32_t>& off, const eg_plan_cross& x);
 void write_plan_blocks(const eg_plan_set* p, uint8_t* dst);
 int decode_plan_blocks(const uint8_t* blocks, int32_t n, const char* who, eg_plan_set** set);
 
-// eg_plan_constraints.cpp: k_plan_constraints — with a build constraint set, k_build_constraints in its place — over the n records of
+// eg_constraints.cpp: k_plan_constraints — with a build constraint set, k_build_constraints in its place — over the n records of
 // c->out under the context's constraints (at least one of either kind is set), on the null stream; the side buffers reserved, c->feas_k
 // and c->feas_builds set
 int constrain_batch(eg_ctx* c, uint32_t n);

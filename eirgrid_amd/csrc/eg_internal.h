@@ -303,6 +303,9 @@ struct DevOut {
 
 void set_error(const std::string& s);
 double action_cost_estimate(int action, int year_index);      // eg_tables.cpp; simulation_summary.csv "Estimated Cost"
+// eg_constraint_text.cpp (T: eg_plan_constraint | eg_build_constraint): n constraints checked on behalf of the entry point `who`; EG_OK,
+// or EG_ERR_BAD_ARG with "<who>: constraint <i>: <what is wrong with it>" set
+template <class T> int validate_constraints(const char* who, const T* constraints, int32_t n);
 
 // launchers implemented in eg_rollout.hip
 struct StatsParams;

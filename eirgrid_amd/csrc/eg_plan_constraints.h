@@ -1,6 +1,7 @@
 // eg_plan_constraints.h — k_plan_constraints: the plan constraints of a context (include/eirgrid_hip.h eg_plan_constraints_set) judged over the
-// n records of a plan batch, behind the batch's rollout grids on the stream they ran on.  Included by eg_rollout.hip (eg_rollout.o only)
-// behind eg_plan_rewrites.h.
+// n records of a plan batch, behind the batch's rollout grids on the stream they ran on; and the two pieces of a judgment that
+// k_build_constraints (eg_build_constraints.h) shares with it: pcons::stage_rows, the staging of a record's yearly rows, and
+// pcons::store_judgment, everything behind the fold.  Included by eg_rollout.hip (eg_rollout.o only) behind eg_plan_rewrites.h.
 //
 // A wave per variant, four variants per workgroup of 256 (pblock::my_variant).  The variant's 26 x 21 yearly rows — 546 doubles, one
 // contiguous stretch of its record — come in with nine coalesced 8-byte loads a lane and are staged in the wave's own 4 368 bytes of LDS;
@@ -13,6 +14,8 @@
 // .. +4 of record j and rows j of the two side buffers, nothing else.  The host has validated every constraint
 // (eg_plan_constraints_validate); the kernel clamps column and window all the same, so what it indexes LDS with stays inside the
 // wave's rows whatever the buffer holds.
+// The staging is stage_rows, the canonical NaN, the ballot and the three stores are store_judgment: the kernel itself is the status
+// test, the barrier and the fold between them.
 #pragma once
 
 namespace pcons {
@@ -48,6 +51,41 @@ __device__ __forceinline__ double excess_of(const double* v, const Packed& p) {
   return e;
 }
 
+// record j's 546 yearly doubles into the wave's rows v: nine coalesced loads a lane, then nine stores
+// (the lane is masked here, where the bounds are tested: the compiler folds the ninth test as it did when the loops stood in the kernel)
+__device__ __forceinline__ void stage_rows(double* v, const DevOut& o, uint32_t j, int lane) {
+  lane &= kWave - 1;
+  const double* src = o.yearly(j);
+  double r[kLoads];
+#pragma unroll
+  for (int i = 0; i < kLoads; ++i) r[i] = lane + i * kWave < kRows ? src[lane + i * kWave] : 0.0;
+#pragma unroll
+  for (int i = 0; i < kLoads; ++i) if (lane + i * kWave < kRows) v[lane + i * kWave] = r[i];
+}
+
+// the judgment of record j from the fold on: lane `lane` of the wave holds constraint `lane` of k (mine: lane < k), live: j < n, ok: the
+// record ended EG_EP_OK.  Where ok && mine the lane's excess is fold(), a NaN as the canonical quiet NaN; everywhere else that NaN.  One
+// ballot makes the mask, the lanes < k store the excess row, lane 0 the mask and, where it is not zero, the demotion.
+// (fold is a closure that captures by value, and mine comes by reference: with either the other way the same statements compile to
+//  other machine code than they did inside the kernels — profiles/r17_constraints_identity.txt)
+template <class Fold>
+__device__ __forceinline__ void store_judgment(const DevOut& o, bool live, bool ok, const bool& mine, Fold fold, uint32_t k, int lane, uint32_t j,
+                                               uint32_t* __restrict__ violated, double* __restrict__ excess) {
+  double e = __longlong_as_double((long long)kQuietNaN);
+  if (ok && mine) {
+    e = fold();
+    if (e != e) e = __longlong_as_double((long long)kQuietNaN);
+  }
+  const uint32_t mask = (uint32_t)__ballot(ok && mine && !(e <= 0.0));
+  if (live) {
+    if (mine) excess[(size_t)j * k + (uint32_t)lane] = e;
+    if (lane == 0) {
+      violated[j] = mask;
+      if (mask != 0u) *o.status(j) = EG_EP_INFEASIBLE;
+    }
+  }
+}
+
 }  // namespace pcons
 
 __global__ void __launch_bounds__(256) k_plan_constraints(DevOut o, uint32_t n, const pcons::Packed* __restrict__ cons, uint32_t k, uint32_t* __restrict__ violated,
@@ -60,27 +98,8 @@ __global__ void __launch_bounds__(256) k_plan_constraints(DevOut o, uint32_t n, 
   k = k > EG_CONSTRAINTS_MAX ? EG_CONSTRAINTS_MAX : k;
   const bool live = w.j < n;
   const bool ok = live && *o.status(live ? w.j : 0u) == EG_EP_OK;      // (the same word in every lane of the wave)
-  if (ok) {
-    const double* src = o.yearly(w.j);
-    double r[kLoads];
-#pragma unroll
-    for (int i = 0; i < kLoads; ++i) r[i] = lane + i * kWave < kRows ? src[lane + i * kWave] : 0.0;
-#pragma unroll
-    for (int i = 0; i < kLoads; ++i) if (lane + i * kWave < kRows) v[lane + i * kWave] = r[i];
-  }
+  if (ok) stage_rows(v, o, w.j, lane);
   __syncthreads();
   const bool mine = (uint32_t)lane < k;
-  double e = __longlong_as_double((long long)kQuietNaN);
-  if (ok && mine) {
-    e = excess_of(v, cons[lane]);
-    if (e != e) e = __longlong_as_double((long long)kQuietNaN);
-  }
-  const uint32_t mask = (uint32_t)__ballot(ok && mine && !(e <= 0.0));
-  if (live) {
-    if (mine) excess[(size_t)w.j * k + (uint32_t)lane] = e;
-    if (lane == 0) {
-      violated[w.j] = mask;
-      if (mask != 0u) *o.status(w.j) = EG_EP_INFEASIBLE;
-    }
-  }
+  store_judgment(o, live, ok, mine, [=] { return excess_of(v, cons[lane]); }, k, lane, w.j, violated, excess);
 }

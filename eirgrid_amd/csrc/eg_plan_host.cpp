@@ -13,8 +13,8 @@ int eg::plan_entry(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts* o, con
   if (c->group_member) { set_error(std::string(fn) + ": the context is a rank of an eg_group (plan batches on a group are not supported)"); return EG_ERR_BAD_ARG; }
   EG_TRY(validate());
   EG_TRY(check_policy(s, o, fn));
-  if (c->n_constraints > 0 && o && !o->write_yearly) {
-    set_error(std::string(fn) + ": write_yearly = 0 while " + std::to_string(c->n_constraints) + " plan constraints are set (the yearly rows are what they judge)");
+  if (c->rows.n > 0 && o && !o->write_yearly) {
+    set_error(std::string(fn) + ": write_yearly = 0 while " + std::to_string(c->rows.n) + " plan constraints are set (the yearly rows are what they judge)");
     return EG_ERR_BAD_ARG;
   }
   EG_HIP(hipSetDevice(c->device));

@@ -103,7 +103,7 @@ int eg::launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t fi
   }
   c->last_n = n; c->last_first = first_index; c->feas_k = 0;
   // the context's constraints over all n records, behind the grids on their stream: what the caller enqueues next reads the demoted statuses
-  return c->n_constraints + c->n_build_constraints > 0 ? constrain_batch(c, n) : EG_OK;
+  return c->rows.n + c->builds.n > 0 ? constrain_batch(c, n) : EG_OK;
 }
 // The policy a plan batch is evaluated under into a device snapshot of its own (c->d_eval_snap) — has_best = 1 and lists present
 // (empty: every episode reads its plan block instead) — with its stalled-sampler tables; *S: what the launches get, the plan pool set.

@@ -398,7 +398,7 @@ extern "C" int32_t eg_repair_plans(eg_ctx* c, const eg_policy_snapshot* s, const
                                    eg_repair_step* steps, int32_t* n_steps, int32_t* stop_reason, double* start_violation, double* final_violation,
                                    eg_episode_out* out) {
   if (!c || !s || !s->weights || !s->deficit_weights || !repaired || !steps || !n_steps || !stop_reason) { set_error("eg_repair_plans: bad argument"); return EG_ERR_BAD_ARG; }
-  const int32_t k = c->n_constraints + c->n_build_constraints;      // (rows first, then builds: the excess row's columns)
+  const int32_t k = c->rows.n + c->builds.n;      // (rows first, then builds: the excess row's columns)
   EG_TRY(plan_entry(c, s, o, "eg_repair_plans", [&] {
     EG_TRY(check_repair_weights([](const std::string& m) { set_error("eg_repair_plans: " + m); return EG_ERR_BAD_ARG; }, weights, k));
     return validate_moves("eg_repair_plans", bases, ro, mo, true);

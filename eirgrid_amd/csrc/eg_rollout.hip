@@ -26,7 +26,7 @@
 //   eg_plan_moves.h       k_plan_moves                                                                                      eg_rollout.o
 //   eg_plan_crosses.h     k_plan_crosses                                                                                    eg_rollout.o
 //   eg_plan_rewrites.h    k_plan_rewrites                                                                                   eg_rollout.o
-//   eg_plan_constraints.h k_plan_constraints                                                                                eg_rollout.o
+//   eg_plan_constraints.h k_plan_constraints (and pcons::stage_rows, store_judgment: shared with k_build_constraints)       eg_rollout.o
 //   eg_repair.h           k_repair_pick_many                                                                                eg_rollout.o
 //   eg_build_constraints.h k_build_constraints                                                                              eg_rollout.o
 //   eg_breed.h            k_breed_gather, k_breed_turnover                                                                  eg_rollout.o

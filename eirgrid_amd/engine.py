@@ -1010,17 +1010,15 @@ class Engine:
         arr, n = constraint_array(rows)
         if L.eg_plan_constraints_validate(arr, n) != N.EG_OK:
             N.check(L.eg_plan_constraints_set(self.h, arr, n), "eg_plan_constraints_set")
-        arr, n = build_constraint_array(builds)
-        N.check(L.eg_build_constraints_validate(arr, n), "eg_build_constraints_validate")
+        barr, nb = build_constraint_array(builds)
+        N.check(L.eg_build_constraints_validate(barr, nb), "eg_build_constraints_validate")
         # both kinds cleared first, so neither setter meets the other kind's old count
         N.check(L.eg_plan_constraints_set(self.h, None, 0), "eg_plan_constraints_set")
         N.check(L.eg_build_constraints_set(self.h, None, 0), "eg_build_constraints_set")
         self._constraints = []
-        arr, n = constraint_array(rows)
         N.check(L.eg_plan_constraints_set(self.h, arr, n), "eg_plan_constraints_set")
         self._constraints = rows
-        arr, n = build_constraint_array(builds)
-        N.check(L.eg_build_constraints_set(self.h, arr, n), "eg_build_constraints_set")
+        N.check(L.eg_build_constraints_set(self.h, barr, nb), "eg_build_constraints_set")
         self._constraints = rows + builds
 
     def clear_constraints(self) -> None:

@@ -1,5 +1,5 @@
 """GPU: build constraints (include/eirgrid_hip.h eg_build_constraints_set; csrc/eg_build_constraints.h k_build_constraints,
-csrc/eg_build_constraints.cpp).  The fused kernel over crafted rows and crafted lists against the two restatements (tests/test_plan_constraints.py
+csrc/eg_constraints.cpp).  The fused kernel over crafted rows and crafted lists against the two restatements (tests/test_plan_constraints.py
 judge for the row constraints, tests/test_build_constraints.py judge_built for the build constraints), byte for byte; the real 239-variant
 edit batch of tests/test_gpu_plan_constraints.py under a bound chosen from its own lists; refine and repair against their host
 restatements fed the restated judgment; build constraints without the yearly rows; and a plan whose emptied deficit lists draw fallbacks."""
@@ -103,6 +103,34 @@ def test_crafted_lists_and_rows_are_judged_as_the_two_definitions_say(engine, n,
             for i in on_bound:
                 e = struct.unpack("<d", want[2][0][k_rows + i])[0]
                 assert e == 0.0 if build_cs[i].aggregate == "sum" or build_cs[i].to_year == build_cs[i].from_year + 1 else e >= 0.0, i
+
+
+def test_the_two_kernels_agree_on_the_row_constraints(engine):
+    """k_plan_constraints under 31 row constraints, k_build_constraints under the same 31 and one build constraint: the staging and
+    everything behind the fold are one piece of text (csrc/eg_plan_constraints.h pcons::stage_rows, store_judgment), so the 31 excess
+    columns, the 31 mask bits and — where the build constraint holds — the statuses are the same bytes"""
+    n = 5
+    rows, row_cs, status, metrics = _crafted(n, 31, 5031)
+    n_gens, gen_pack, n_offsets, off_pack, build_cs = _crafted_lists(n, 1, np.random.default_rng(5031))
+    assert (status == OK).any() and (status != OK).any()
+
+    def judged(cs):
+        with constrained(engine, cs):
+            engine._debug_load_batch(metrics, status, 40)
+            engine._debug_load_yearly(rows)
+            engine._debug_load_built(n_gens, gen_pack, n_offsets, off_pack)
+            engine._debug_constrain_last_batch()
+            violated, excess = engine.fetch_feasibility()
+            return engine.fetch(n).status, violated, excess
+
+    status_rows, violated_rows, excess_rows = judged(row_cs)
+    status_both, violated_both, excess_both = judged(row_cs + build_cs)
+    assert excess_rows.shape == (n, 31) and excess_both.shape == (n, 32)
+    assert np.ascontiguousarray(excess_both[:, :31]).tobytes() == excess_rows.tobytes()
+    assert (violated_both & np.uint32(2**31 - 1)).tolist() == violated_rows.tolist()
+    built = (violated_both >> np.uint32(31)).astype(bool)
+    assert status_both[~built].tolist() == status_rows[~built].tolist()
+    assert built[status == OK].any() and not built[status == OK].all() and violated_rows.any()      # the crafted data does what it is there for
 
 
 def test_the_hooks_and_the_setters_refuse_what_they_cannot_do(engine):

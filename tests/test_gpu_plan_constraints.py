@@ -1,4 +1,4 @@
-"""GPU: plan constraints (include/eirgrid_hip.h eg_plan_constraints_set; csrc/eg_plan_constraints.h k_plan_constraints, csrc/eg_plan_constraints.cpp).
+"""GPU: plan constraints (include/eirgrid_hip.h eg_plan_constraints_set; csrc/eg_plan_constraints.h k_plan_constraints, csrc/eg_constraints.cpp).
 The kernel over crafted rows against the Python restatement (tests/test_plan_constraints.py excess_bytes / judge), byte for byte; a real
 edit batch with and without constraints; and every search — refine, breed, explore — against the host restatement its own tests use,
 fed the statuses as the restatement demotes them."""
