@@ -64,6 +64,8 @@ namespace {
 
 constexpr int kWave = 64;
 constexpr int kD2Max = 144, kD2Stride = 146;   // factor table by squared cell distance: 0..144 (12 km = the largest radius), padded
+constexpr int kDrHiPlane = 384;         // Smem::dr, kPlanes: words from an entry's low word to its high word (a multiple of 64: ds_read2st64_b32's stride)
+static_assert(kDrHiPlane >= kDrCompact && kDrHiPlane % 64 == 0 && kDrHiPlane / 64 < 256, "the high plane lies behind the low one, a two-address read apart");
 constexpr int kCmdYear = 1 << 30;       // helper command: fold next year's starting sums (else: a placement search)
 constexpr int kHelperWaves = 1;         // small-batch kernel: waves per episode beyond the episode wave (see helper_loop)
 // The episode wave polls an LDS flag for the helper's results (s_sleep 1 = 64 cycles per poll).  The helper's longest job —
@@ -91,10 +93,19 @@ __device__ __forceinline__ int deficit_slot_of(int action) {
 }
 
 struct __align__(16) Smem {
-  double dr[kDrCompact];              // d/R by squared cell distance, class k at entries off_k .. off_k + cap_k (tab::dr_meta): only up to its own
-                                      // radius — 1.0 at cap_k, where every larger distance is capped (2.7 instead of 7 KB: with 128 VGPRs that is
-                                      // what lets a fourth wave share the SIMD)
-  int gstage[2][kWave + 8];           // per wave: (gi, gj) as two int16 of the 64 generators being folded (read back four at a time);
+  uint32_t dr[2 * kDrCompact];            // d/R by squared cell distance, class k at entries off_k .. off_k + cap_k (tab::dr_meta): only up to its own
+                                      // radius — 1.0 at cap_k, where every larger distance is capped (2.9 instead of 7 KB: with 128 VGPRs that is
+                                      // what lets a fourth wave share the SIMD).  In one of two layouts, a kernel's choice (kPlanes):
+                                      //  * two planes of 32-bit words (the lean grid, the short-replay variant, k_place — bound by vector issue):
+                                      //    entry i's low word at word i, its high word at kDrHiPlane + i, so that an entry's byte address is
+                                      //    base + 4 i — what the dot product of a doubled coordinate difference with itself yields (factor_at) —
+                                      //    and one two-address read, the second kDrHiPlane words on, returns the double.  The high plane's last
+                                      //    32 words lie in `park`, which these kernels do not use: the block is the size it was;
+                                      //  * kDrCompact doubles (the long-replay kernels, a lone wave bound by latency: reading a factor as two
+                                      //    words measured slower there than the 64-bit read, profiles/r18_ab_notes.log)
+  double park[18];                    // long-replay variant: the year's aggregates while the field code runs (see k_rollout).  kPlanes (never the long-replay
+                                      // variant): the high plane's last kDrHiPlane - kDrCompact words — it starts kDrHiPlane words into dr and ends in here
+  int gstage[2][kWave + 8];           // per wave: (gi, gj) — kPlanes: doubled — as two int16 of the 64 generators being folded (read back four at a time);
                                       // the tail stays at the off-grid padding value: the pipeline reads up to three groups ahead
   double scaled[64];                  // stalled sampler: weights^p in sorted order
   double type_out[16];                // per generator type: output of an operational new plant
@@ -118,7 +129,6 @@ struct __align__(16) Smem {
   uint32_t yflag; int ysum_opcnt;     // year-start sums folded by the helper wave (sequence number, count)
   double ysum[8];                     //   gcost, optot, offs, ocost, co2, tg, ig, sg
   struct { double score, m03; int cell, pad; } hres[2];
-  double park[18];                    // long-replay variant: the year's aggregates while the field code runs (see k_rollout)
 #ifdef EG_STAMPS
   unsigned long long hdbg[2][4];
 #endif
@@ -126,6 +136,7 @@ struct __align__(16) Smem {
 // gfx950 hands out LDS in granules of 1280 bytes (160 KB / 128): seven granules per episode leave room for the sixteen workgroups per
 // CU that four waves per SIMD (128 VGPRs) allow.  (Ten granules and three waves until the factor table was compacted: 1.305 -> 1.194 ms
 // at 16 384 episodes.)
+static_assert(offsetof(Smem, park) == sizeof(uint32_t) * 2 * kDrCompact && sizeof(double) * 18 >= sizeof(uint32_t) * (kDrHiPlane - kDrCompact), "the high plane's end lies in park");
 #ifndef EG_STAMPS
 static_assert(sizeof(Smem) <= 7 * 1280, "sixteen episodes per CU");
 #endif
@@ -300,21 +311,38 @@ __device__ double evaluate_impact(const State& cur, const State& nxt) {   // sco
 // The host table is indexed by (|di|, |dj|) <= 12; the distance, hence the factor, only depends on di^2 + dj^2 (grid
 // coordinates are whole kilometres, so dx^2 + dy^2 is exact), and the kernels index by that: one dot product instead of
 // two absolute values, two clamps and a linearisation.  Sums that are not a sum of two squares are never read.
+// The two planes of Smem::dr (kPlanes) from the blob, word by word: an even word of tab::dr_compact is an entry's low word, an odd one its high
+// word, and a lane keeps to one plane (the high plane ends in Smem::park).  Not inlined, and the blob by ADDRESS (eg_field.h's rule): inlined, whichever way it was written — doubles
+// split into words, or words — k_rollout<0,0> came out a vector register wider than the 121 it has (profiles/r18_ab_notes.log r18g); once an episode.
+static_assert((2 * kDrCompact) % kWave == 0, "whole blocks of 64 words");
+__device__ __noinline__ void load_factor_planes(unsigned long long src_addr, int lane) {
+  typedef const uint32_t __attribute__((address_space(1)))* G32;
+  const G32 src = (G32)src_addr;
+  uint32_t w[2 * kDrCompact / kWave];
+#pragma unroll
+  for (int k = 0; k < 2 * kDrCompact / kWave; ++k) w[k] = src[lane + k * kWave];
+  uint32_t* dst = reinterpret_cast<uint32_t*>(&sm) + offsetof(Smem, dr) / 4 + (lane & 1) * kDrHiPlane + (lane >> 1);      // (the high plane ends in Smem::park)
+#pragma unroll
+  for (int k = 0; k < 2 * kDrCompact / kWave; ++k) dst[k * (kWave / 2)] = w[k];
+}
+template <bool kPlanes>
 __device__ __forceinline__ void load_factor_table(const DevTables& T, int lane) {
   // tails of the staging rows of chunk_product: generators far off the grid (their factor is 1.0), never overwritten
   if (lane < 8) { sm.gstage[0][kWave + lane] = (int)0xC000C000; sm.gstage[1][kWave + lane] = (int)0xC000C000; }
   // (the host lays the compact table out as LDS holds it — tab::dr_compact: one independent load per lane and block of 64, one
   //  memory round trip at the start of an episode where re-indexing the [6][13][13] table here was sixteen dependent ones)
+  if constexpr (kPlanes) { load_factor_planes((unsigned long long)T.dr_compact(), lane); return; }
   double v[(kDrCompact + kWave - 1) / kWave];
 #pragma unroll
   for (int k = 0; k < (kDrCompact + kWave - 1) / kWave; ++k) v[k] = lane + k * kWave < kDrCompact ? T.dr_compact()[lane + k * kWave] : 1.0;
 #pragma unroll
-  for (int k = 0; k < (kDrCompact + kWave - 1) / kWave; ++k) if (lane + k * kWave < kDrCompact) sm.dr[lane + k * kWave] = v[k];
+  for (int k = 0; k < (kDrCompact + kWave - 1) / kWave; ++k) if (lane + k * kWave < kDrCompact) reinterpret_cast<double*>(sm.dr)[lane + k * kWave] = v[k];
 }
-// byte offset of a radius class's factors inside the LDS block | its cap << 16: what chunk_product / factor_by_q take as `table`
-// in the throughput kernels (from the type's info word: bits 16-23 cap, 24-31 first entry / 2)
+// byte offset of a radius class's factors inside the LDS block — kPlanes: of their low words, 4 bytes an entry — | its cap << 16: what
+// chunk_product / factor_by_q take as `table` in the throughput kernels (from the type's info word: bits 16-23 cap, 24-31 first entry / 2)
+template <bool kPlanes = false>
 __device__ __forceinline__ int throughput_table(int info) {
-  return ((int)offsetof(Smem, dr) + (int)(((unsigned)info >> 24) << 4)) | (((info >> 16) & 255) << 16);
+  return ((int)offsetof(Smem, dr) + (int)(((unsigned)info >> 24) << (kPlanes ? 3 : 4))) | (((info >> 16) & 255) << 16);
 }
 // small-batch kernel: the generator list starts as padding everywhere; the factor table goes in at a stride of 16 bytes
 __device__ __forceinline__ void load_latency_tables(const DevTables& T, int lane) {
@@ -325,8 +353,9 @@ __device__ __forceinline__ void load_latency_tables(const DevTables& T, int lane
     if (q <= kD2Max) sl.dr16[2 * (rc * kD2Stride + q)] = T.dr()[i];
   }
 }
+template <bool kPlanes = false>
 __device__ __forceinline__ void load_static_tables(const DevTables& T, int lane, bool with_factors) {
-  if (with_factors) load_factor_table(T, lane);
+  if (with_factors) load_factor_table<kPlanes>(T, lane);
   if (lane < kTypes) {
     const int rc = T.rclass()[lane];
     sm.type_info[lane] = T.variant()[lane] | (rc << 4) | (T.reach()[rc] << 8) | (T.cls()[lane] << 12) | (T.dr_meta()[8 + rc] << 16) |
@@ -425,17 +454,33 @@ __device__ __noinline__ int weighted_pick(int table_offset, int n, double u, int
 }
 
 typedef short short2v __attribute__((ext_vector_type(2)));
-// factor of one generator for this lane's candidate: (ci - gi, cj - gj) as two int16, their squared length by one dot
-// product, capped at 144 (12 km, the largest radius: the table holds 1.0 there)
-__device__ __forceinline__ double factor_at(short2v cpk, int gen_packed, int table_offset, int cap) {
-  short2v g; __builtin_memcpy(&g, &gen_packed, 4);
-  const short2v d = cpk - g;
-  // (the three-operand form with the constant 0 as its accumulator: from the builtin the compiler makes the two-operand
-  //  accumulating v_dot2c and a v_mov to zero its destination first — one instruction in six of this loop)
-  int q, dbits; __builtin_memcpy(&dbits, &d, 4);
-  asm("v_dot2_i32_i16 %0, %1, %1, 0" : "=v"(q) : "v"(dbits));
-  q = q < cap ? q : cap;      // (the class's own radius squared: the table holds 1.0 there)
-  return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(&sm) + (table_offset + q * 8));
+// the double whose low word is at byte `at` of the LDS block and whose high word is kDrHiPlane words on (Smem::dr).  Two plain loads:
+// the compiler joins them into one two-address read (ds_read2st64_b32) and keeps its own wait counts.  (Planes back to back, 352 words
+// apart, make it two ds_read_b32: measured, the lean grid then gains a third of what it gains with one: profiles/r18_ab_notes.log r18g.)
+__device__ __forceinline__ double factor_word_pair(int at) {
+  const uint32_t* p = reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(&sm) + at);
+  return __hiloint2double((int)p[kDrHiPlane], (int)p[0]);
+}
+// factor of one generator for this lane's candidate: 2 (ci - gi, cj - gj) as two int16 — both sides come with their coordinates
+// doubled —, four times their squared length by one dot product whose accumulator is the byte offset of the class's low words
+// (`table_offset`, uniform): the byte address of the factor, capped at the class's own radius squared (`cap_at` = table_offset +
+// 4 cap: the table holds 1.0 there)
+template <bool kPlanes = false>
+__device__ __forceinline__ double factor_at(short2v cpk2, int gen_packed2, int table_offset, int cap_at) {
+  short2v g; __builtin_memcpy(&g, &gen_packed2, 4);
+  const short2v d = cpk2 - g;
+  if constexpr (!kPlanes) {      // the table of doubles: plain coordinates, `cap_at` the class's radius squared; an instruction more for the address
+    int q, dbits; __builtin_memcpy(&dbits, &d, 4);
+    asm("v_dot2_i32_i16 %0, %1, %1, 0" : "=v"(q) : "v"(dbits));
+    q = q < cap_at ? q : cap_at;
+    return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(&sm) + (table_offset + q * 8));
+  }
+  // (the three-operand form with a scalar accumulator: from the builtin the compiler makes the two-operand accumulating
+  //  v_dot2c and a v_mov to set its destination first — one instruction more per factor)
+  int at, dbits; __builtin_memcpy(&dbits, &d, 4);
+  asm("v_dot2_i32_i16 %0, %1, %1, %2" : "=v"(at) : "v"(dbits), "s"(table_offset));
+  at = at < cap_at ? at : cap_at;
+  return factor_word_pair(at);
 }
 
 // A search multiplies te by the factor of every generator, in list order.  Searches of the same (year, variant) revisit
@@ -453,17 +498,19 @@ struct PrefixCache { double product; int key; int count; };      // key: year <<
 // Throughput kernel (one wave per episode, sixteen episodes per CU).  `stage`: the wave's staging row in LDS.
 // The packed coordinates of 64 generators are staged in LDS once and come back four at a time as ONE broadcast 128-bit
 // read (instead of a readlane and a lane-index add each); per generator that leaves a packed subtract, the dot product,
-// the cap, the address, the table read and the multiply.
+// the cap, the table read and the multiply — the dot product is the factor's address already (factor_at, Smem::dr).
 // `row0_kept` (lean / short-replay kernels): staging row 0 is kept up to date by the episode — a generator's packed coordinates are
 // appended to it when the generator is placed (k_rollout), its other entries stay padding — so the first 64 generators need no
 // staging at all: a chunk re-staged the same list, cell -> (i, j) division included, ~15 vector instructions, 95 times an episode.
 // Blocks beyond the first 64 are staged in row 1 (the helper wave's, unused in those kernels).
-// `xy4`: the candidate's packed coordinates times four (PsRec::pad, as the small-batch kernel uses them): a packed shift gives (ci, cj)
-// where dividing the cell by the grid's width took eight instructions per chunk.
+// `xy4`: the candidate's packed coordinates times four (PsRec::pad, as the small-batch kernel uses them): a packed shift gives
+// (2 ci, 2 cj) where dividing the cell by the grid's width took eight instructions per chunk.  The staging rows hold (2 gi, 2 gj).
+template <bool kPlanes = false>
 __device__ __forceinline__ double chunk_product(int table, int lane, int k0, int ngen_s, double s_init, int xy4, int stage, bool row0_kept = false) {
   double s = s_init;
-  const short2v cpk = __builtin_bit_cast(short2v, xy4) >> (short)2;      // (4 ci, 4 cj) -> (ci, cj): both halves are small and not negative
-  const int dr_off = table & 0xFFFF, cap = table >> 16;   // throughput_table(): the class's factors inside the LDS block, and where they end
+  const short2v cpk = __builtin_bit_cast(short2v, xy4) >> (short)(kPlanes ? 1 : 2);      // (4 ci, 4 cj) -> (2 ci, 2 cj) / (ci, cj): both halves are small and not negative
+  // throughput_table(): the class's factors inside the LDS block, and where they end (uniform; behind a call that is not inlined it arrives in a vector register)
+  const int dr_off = table & 0xFFFF, cap = kPlanes ? dr_off + 4 * (table >> 16) : table >> 16;
   const int k0_s = __builtin_amdgcn_readfirstlane(k0);           // uniform (it comes out of a per-wave cache): scalar loop control
   for (int gb = k0_s; gb < ngen_s; gb += kWave) {                 // generators in list order
     const bool kept = row0_kept && gb == 0;
@@ -473,7 +520,7 @@ __device__ __forceinline__ double chunk_product(int table, int lane, int k0, int
       // Lanes beyond the list hold a generator far off the grid: its squared distance caps at 144, where the table is 1.0.
       const int mine = gb + lane < ngen_s ? (int)(sm.gcell[gb + lane] & 0xFFF) : -1;
       const int mi = mine / kGrid;
-      const int mp = mine < 0 ? (int)0xC000C000 : (mi | ((mine - mi * kGrid) << 16));   // (gi, gj) as two int16
+      const int mp = mine < 0 ? (int)0xC000C000 : ((mi | ((mine - mi * kGrid) << 16)) << (kPlanes ? 1 : 0));   // (gi, gj) as two int16; kPlanes: doubled
       row[lane] = mp;
     }
     asm volatile("" ::: "memory");      // LDS executes a wave's accesses in program order: only the compiler must keep it
@@ -483,8 +530,8 @@ __device__ __forceinline__ double chunk_product(int table, int lane, int k0, int
     // out-of-range generators and the padding up to a multiple of four multiply by 1.0 instead of branching.
     // Software-pipelined: while four factors are multiplied in list order (only the multiplies form a chain) the next
     // four are on their way from the table; two register sets take turns.
-#define EG_FACTORS_LOOSE(g4, f0, f1, f2, f3) { f0 = factor_at(cpk, g4.x, dr_off, cap); f1 = factor_at(cpk, g4.y, dr_off, cap); \
-                                               f2 = factor_at(cpk, g4.z, dr_off, cap); f3 = factor_at(cpk, g4.w, dr_off, cap); }
+#define EG_FACTORS_LOOSE(g4, f0, f1, f2, f3) { f0 = factor_at<kPlanes>(cpk, g4.x, dr_off, cap); f1 = factor_at<kPlanes>(cpk, g4.y, dr_off, cap); \
+                                               f2 = factor_at<kPlanes>(cpk, g4.z, dr_off, cap); f3 = factor_at<kPlanes>(cpk, g4.w, dr_off, cap); }
     double a0, a1, a2, a3, b0, b1, b2, b3;
     int4 gc = row4[0], gn = row4[1];
     EG_FACTORS_LOOSE(gc, a0, a1, a2, a3)
@@ -515,7 +562,7 @@ __device__ __forceinline__ double chunk_product(int table, int lane, int k0, int
 //    waves read it): no staging, no cell -> (i, j) division per search, four generators per broadcast 128-bit read;
 //  * coordinates are kept times four and the factor table has a stride of 16 bytes, so the dot product of the packed
 //    difference with itself, accumulated onto the table's address, IS the address of the factor: per generator a packed
-//    subtract, the accumulator move, the dot product, the cap, the table read and the multiply;
+//    subtract, the dot product, the cap, the table read and the multiply;
 //  * one straight-line loop body of two groups, so the wait counts stay exact; padding multiplies by 1.0.
 // k0: generators [0, k0) are already in s_init (kept product); the first group is masked accordingly.
 // kMaskTail (helper wave): entries behind the list are not trusted to be padding — the episode wave may append the next
@@ -531,13 +578,16 @@ __device__ __forceinline__ double chunk_product_latency(int class_off, int k0, i
   const int4* row4 = reinterpret_cast<const int4*>(sl.gpk) + g0;
   const char* t0 = reinterpret_cast<const char*>(sl.dr16);
   const int cap = class_off + 16 * kD2Max;
+  // (the three-operand form with the class's offset, uniform, as a scalar accumulator: from the accumulating builtin the compiler makes the
+  //  two-operand v_dot2c and a v_mov to set its destination first — config 1: 0.2546 -> 0.2505 ms a batch, profiles/r18_ab_notes.log)
+  const int class_off_s = __builtin_amdgcn_readfirstlane(class_off);
+#define EG_LAT_DOT(q_, e_) { int eb_; __builtin_memcpy(&eb_, &e_, 4); asm("v_dot2_i32_i16 %0, %1, %1, %2" : "=v"(q_) : "v"(eb_), "s"(class_off_s)); }
 #define EG_FACTORS(g4, f0, f1, f2, f3) { \
     short2v e0, e1, e2, e3; int q0, q1, q2, q3; \
     { short2v t; __builtin_memcpy(&t, &g4.x, 4); e0 = cpk - t; __builtin_memcpy(&t, &g4.y, 4); e1 = cpk - t; \
       __builtin_memcpy(&t, &g4.z, 4); e2 = cpk - t; __builtin_memcpy(&t, &g4.w, 4); e3 = cpk - t; } \
     __builtin_amdgcn_sched_barrier(0); \
-    q0 = __builtin_amdgcn_sdot2(e0, e0, class_off, false); q1 = __builtin_amdgcn_sdot2(e1, e1, class_off, false); \
-    q2 = __builtin_amdgcn_sdot2(e2, e2, class_off, false); q3 = __builtin_amdgcn_sdot2(e3, e3, class_off, false); \
+    EG_LAT_DOT(q0, e0) EG_LAT_DOT(q1, e1) EG_LAT_DOT(q2, e2) EG_LAT_DOT(q3, e3) \
     __builtin_amdgcn_sched_barrier(0); \
     q0 = q0 < cap ? q0 : cap; q1 = q1 < cap ? q1 : cap; q2 = q2 < cap ? q2 : cap; q3 = q3 < cap ? q3 : cap; \
     __builtin_amdgcn_sched_barrier(0); \
@@ -590,17 +640,18 @@ __device__ __forceinline__ double chunk_product_latency(int class_off, int k0, i
   }
   if (groups & 1) { s = s * a0; s = s * a1; s = s * a2; s = s * a3; }
 #undef EG_FACTORS
+#undef EG_LAT_DOT
   return s;
 }
 // Final score of this lane's candidate (rank r of the sorted list) against the episode's generator list.
 // kLatency: small-batch kernel (`table` = byte offset of the radius class inside sl.dr16, xy4 = the candidate's packed
 // coordinates); otherwise the throughput kernel (`table` = throughput_table() of the type, `cell`).
-template <bool kLatency>
+template <bool kLatency, bool kPlanes = false>
 __device__ __forceinline__ double chunk_score(int table, double size_factor, int lane, int ngen_s, int r, double te,
                                               double cf, int cell, int xy4, bool row0_kept = false) {
   double p;
   if constexpr (kLatency) p = chunk_product_latency<false>(table, 0, ngen_s, te, xy4);
-  else p = chunk_product(table, lane, 0, ngen_s, te, xy4, 0, row0_kept);
+  else p = chunk_product<kPlanes>(table, lane, 0, ngen_s, te, xy4, 0, row0_kept);
   const double s = (p * cf) * size_factor;
   return r < kCells ? s : 0.0;
 }
@@ -944,7 +995,7 @@ __device__ __forceinline__ void helper_loop(const DevTables& T, int lane, int h)
 
 // `between` is called once the candidate records are requested (and, in the small-batch kernel, the helper has its
 // command): whatever the caller has to do before it needs the result goes there and runs under the records' latency.
-template <int kHelpers, bool kRow0Kept = false, class Between>
+template <int kHelpers, bool kRow0Kept = false, bool kPlanes = false, class Between>
 __device__ __forceinline__ int place_search(const DevTables& T, int lane, int yi, int type, int ngen, double* best_score,
                                             double* best_m03, PrefixCache& cache0, Between&& between, int& nchunks,
                                             uint32_t* seq = nullptr, unsigned long long* stamps = nullptr) {
@@ -952,7 +1003,7 @@ __device__ __forceinline__ int place_search(const DevTables& T, int lane, int yi
   const int v = info & 15, rc = (info >> 4) & 15;
   const PsRec* __restrict__ list = T.ps() + (size_t)(yi * kMaxVariants + v) * kPsStride;
   // factor table of the radius class: byte offset inside sl.dr16 (small-batch kernel) / inside the LDS block (sm.dr)
-  const int table = kHelpers > 0 ? rc * (kD2Stride * 16) : throughput_table(info);
+  const int table = kHelpers > 0 ? rc * (kD2Stride * 16) : throughput_table<kPlanes>(info);
   const double size_factor = T.size_factor;
 #ifdef EG_PROBE_NO_GEN_LOOP      // diagnostic build only (profiles/r04_ab_notes.log r04u): the searches fold no generator — what the generator loops cost
   const int ngen_s = 0;
@@ -1033,7 +1084,7 @@ __device__ __forceinline__ int place_search(const DevTables& T, int lane, int yi
     // the single-wave kernel keeps the products of chunks 0 and 1, the episode wave of the helper kernel that of chunk 0
     // (the kept products are used by the small-batch kernel only: in the throughput kernel the extra live registers cost
     //  more than the shorter loops give back)
-    const double s = chunk_score<(kHelpers > 0)>(table, size_factor, lane, ngen_s, r, te_cur, cf_cur, cell_cur, xy_cur, kRow0Kept);
+    const double s = chunk_score<(kHelpers > 0), kPlanes>(table, size_factor, lane, ngen_s, r, te_cur, cf_cur, cell_cur, xy_cur, kRow0Kept);
 #ifdef EG_STAMPS
     const unsigned long long tg1 = __builtin_readcyclecounter();
     if (stamps) stamps[9] += tg1 - tg0;
@@ -1424,7 +1475,7 @@ __global__ void __launch_bounds__(kWave * (1 + kHelpers), kKind == kReplayLong ?
 #ifdef EG_STAMPS
   if (kHeavy && lane < 8) sm.hdbg[lane >> 2][lane & 3] = 0ull;
 #endif
-  load_static_tables(T, lane, kHelpers == 0 || kHeavy);      // (the heavy variant's field update reads sm.dr / sl.dr16)
+  load_static_tables<(kHelpers == 0 && !kHeavy)>(T, lane, kHelpers == 0 || kHeavy);      // (the heavy variant's field update reads sm.dr / sl.dr16)
   if constexpr (kHelpers == 0 && !kHeavy) sm.gstage[0][lane] = (int)0xC000C000;      // the kept staging row starts as padding (chunk_product)
   // bit y: the existing-plant prefix sums of year y equal those of year y-1, so last year's end-of-year class sums carry over
   const uint32_t carry_mask = (uint32_t)__ballot(lane > 0 && lane < EG_YEARS && T.pre_co2()[lane] == T.pre_co2()[lane - 1] &&
@@ -1727,10 +1778,10 @@ __global__ void __launch_bounds__(kWave * (1 + kHelpers), kKind == kReplayLong ?
         }
         if (!placed) {
 #ifdef EG_STAMPS
-          cell = __builtin_amdgcn_readfirstlane(place_search<kHelpers, (kHelpers == 0 && !kHeavy)>(T, lane, yi, t, ep.ngen, nullptr, &m03v, prefix_cache0, between, ep.chunks, &search_seq, stamps));
+          cell = __builtin_amdgcn_readfirstlane(place_search<kHelpers, (kHelpers == 0 && !kHeavy), (kHelpers == 0 && !kHeavy)>(T, lane, yi, t, ep.ngen, nullptr, &m03v, prefix_cache0, between, ep.chunks, &search_seq, stamps));
           stamps[11] += 1;
 #else
-          cell = __builtin_amdgcn_readfirstlane(place_search<kHelpers, (kHelpers == 0 && !kHeavy)>(T, lane, yi, t, ep.ngen, nullptr, &m03v, prefix_cache0, between, ep.chunks, &search_seq));
+          cell = __builtin_amdgcn_readfirstlane(place_search<kHelpers, (kHelpers == 0 && !kHeavy), (kHelpers == 0 && !kHeavy)>(T, lane, yi, t, ep.ngen, nullptr, &m03v, prefix_cache0, between, ep.chunks, &search_seq));
 #endif
         }
         EG_T1(1);
@@ -1771,7 +1822,7 @@ __global__ void __launch_bounds__(kWave * (1 + kHelpers), kKind == kReplayLong ?
           }
           if constexpr (kHelpers == 0 && !kHeavy) if (ep.ngen < kWave) {      // the searches' staging row, kept (chunk_product)
             const int gi = cell / kGrid;
-            sm.gstage[0][ep.ngen] = gi | ((cell - gi * kGrid) << 16);
+            sm.gstage[0][ep.ngen] = (gi | ((cell - gi * kGrid) << 16)) << 1;      // (2 gi, 2 gj)
           }
           gen_cell[ep.ngen] = (uint16_t)cell;
           gen_pack[ep.ngen] = (uint16_t)(t | (yi << 4) | (m << 9));

@@ -25,12 +25,12 @@ __global__ void __launch_bounds__(kWave) k_place(DevTables T, int type, int yi, 
                                                  int n_extra, int32_t* out_cell, double* out_score) {
   const int lane = threadIdx.x;
   for (int g = lane; g < n_extra; g += kWave) sm.gcell[g] = cells[g];
-  load_static_tables(T, lane, true);
+  load_static_tables<true>(T, lane, true);      // (the factor table as two planes, as the lean grid holds it)
   __syncthreads();
   double score = 0.0;
   PrefixCache pc0 = {0.0, -1, 0};
   int nchunks = 0;
-  const int cell = place_search<0>(T, lane, yi, type, n_extra, &score, nullptr, pc0, []() {}, nchunks);
+  const int cell = place_search<0, false, true>(T, lane, yi, type, n_extra, &score, nullptr, pc0, []() {}, nchunks);
   if (lane == 0) { *out_cell = cell; *out_score = score; }
 }
 
