@@ -48,6 +48,7 @@ struct Options {
   // EIRGRID_SOLO_LAZY: the longest replay script (generators) that runs with the lazy field (k_replay_lazy in k_replay_solo's place); 0: none
   // (k_replay_solo: the field current after every placement, as the classic variant keeps it), all: every script.  Default: measured on the benchmark's states — 9 % faster at
   // 228 generators, 4 % slower at 468, 16 % slower at 916 (profiles/r10_ab_notes.log): six blocks of 64 generators.
+  bool uniform_on = true;              // EIRGRID_UNIFORM=0: the lean and the short-replay kind on k_rollout<0, kind>, not on k_episodes (tests, A/B on one library)
   uint32_t solo_lazy = 512u;      // (the lists' on-chip window: measured ahead of the eager field at 228 and 468 generators, behind it at 916 — DESIGN §4, round 14)
 };
 Options read_options() {
@@ -65,6 +66,7 @@ Options read_options() {
   if (const char* so = std::getenv("EIRGRID_REPLAY_SOLO")) o.solo_on = so[0] != '0';
   if (const char* st = std::getenv("EIRGRID_SOLO_TILES")) o.solo_tiles = st[0] != '0' ? 1u : 0u;
   if (const char* sl = std::getenv("EIRGRID_SOLO_LAZY")) o.solo_lazy = std::string(sl) == "all" ? 0xFFFFFFFFu : (uint32_t)std::strtoul(sl, nullptr, 10);
+  if (const char* un = std::getenv("EIRGRID_UNIFORM")) o.uniform_on = un[0] != '0';
   return o;
 }
 
@@ -112,6 +114,7 @@ int eg::ring_take(eg_ctx* c, RolloutPlan& plan, int& slot) {
   if (c->ring_pending == eg_ctx::kTimingRing) EG_TRY(collect_timing(c, 1));
   slot = c->ring_head;
   for (int k = 0; k < 4; ++k) plan.ev[k] = c->ev[slot][k];
+  plan.classic_kernels = !c->uniform_on;      // (every rollout launch takes its events here)
   return EG_OK;
 }
 // ... and behind the launch: which of its pairs were recorded (bit 0: the heavy grid's, bit 1: the lean grid's)
@@ -373,7 +376,7 @@ eg_ctx* eg_create(int32_t device_ordinal, const eg_world* world) {
     c->dev.solo_tiles = opt.solo_tiles; c->dev.solo_lazy = opt.solo_lazy;
     if (!info.box_list_fits) c->heavy_slots_wanted = 0;
     c->hoist_supported = info.hoist_supported; c->hoist_on = info.hoist_supported && opt.replay_hoist;
-    c->coop_force = opt.coop_force; c->solo_on = opt.solo_on;
+    c->coop_force = opt.coop_force; c->solo_on = opt.solo_on; c->uniform_on = opt.uniform_on;
     rc = create_device_state(c, blob, opt.side_stream_plain);
   }
   if (rc != EG_OK) { eg_destroy(c); return nullptr; }

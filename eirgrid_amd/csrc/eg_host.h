@@ -136,6 +136,7 @@ struct eg_ctx {
   // per-episode replay kernel (eg_replay_solo.h; EIRGRID_REPLAY_SOLO=0: off): a word per replay episode of a launch, the launches' sequence
   eg::DevBuf<unsigned long long> d_solo; unsigned long long solo_seq = 0;
   bool solo_on = true;
+  bool uniform_on = true;      // EIRGRID_UNIFORM=0: throughput batches launch k_rollout<0, kind> for the lean and short-replay kinds, not k_episodes
   // plan batches (eg_evaluate_plans): the evaluated policy's own snapshot (the resident one in d_snap stays untouched), the plan blocks
   // (snap::kPlanStride bytes each) and the index lists of the short and the long plans
   eg::DevBuf<uint8_t> d_eval_snap, d_plans;

@@ -348,6 +348,9 @@ struct RolloutPlan {
   const uint32_t* d_index_long;
   // a plan-edit batch with same_index (eg_evaluate_plan_edits): every episode of the plan batch runs as global episode first_index
   bool same_index;
+  // throughput batches: the lean and the short-replay kind run k_rollout<0, kind> as before the uniform kernels (k_episodes, eg_rollout.hip);
+  // EIRGRID_UNIFORM=0, for tests and A/B runs on one library
+  bool classic_kernels;
 };
 constexpr int kStatsReplicas = 64;
 int launch_fold_stats(long long* d_rep, long long* d_stats, void* stream);

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run on the GPU box: SQ counters of the lean grid alone (scripts/ab_kernel.py: sampled episodes, fresh policy, no statistics epilogue) at
 # 16 384 and 131 072 episodes per launch — how busy the vector ALUs are while every SIMD has its four waves, against the batch size's
-# own ramp and tail.   bash scripts/lean_occupancy.sh <outdir>
+# own ramp and tail.   bash scripts/lean_occupancy.sh <outdir>      (the lean grid is k_episodes<0>; with EIRGRID_UNIFORM=0 in the environment, k_rollout<0, 0>)
 set -eo pipefail
 O=${1:-gpurun_out/lean_occ}
 mkdir -p $O
@@ -16,7 +16,7 @@ for b in (16384, 131072):
     rows = collections.defaultdict(dict)
     for path in glob.glob("$O/sq_%d/**/*counter_collection.csv" % b, recursive=True):
         for r in csv.DictReader(open(path)):
-            if "k_rollout" in r["Kernel_Name"] and int(r["Grid_Size"]) == b * 64:
+            if ("k_episodes" in r["Kernel_Name"] or "k_rollout" in r["Kernel_Name"]) and int(r["Grid_Size"]) == b * 64:
                 d = rows[int(r["Dispatch_Id"])]
                 d[r["Counter_Name"]] = float(r["Counter_Value"]); d["ns"] = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
     ids = sorted(rows)[-8:]

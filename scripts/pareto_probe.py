@@ -26,7 +26,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 KERNELS = ("k_pareto_filter", "k_pareto_compact", "k_pareto_dominate", "k_pareto_rank", "k_pareto_finalize",
-           "k_topk_keys", "k_topk_select", "k_topk_merge", "k_rollout", "k_replay_solo", "k_replay_lazy", "k_apply_update")
+           "k_topk_keys", "k_topk_select", "k_topk_merge", "k_rollout", "k_episodes", "k_replay_solo", "k_replay_lazy", "k_apply_update")
 
 
 def kernel_rows(stats_csv):

@@ -61,7 +61,7 @@ def trace_calls(trace_csv):
         name = r["Kernel_Name"]
         if "k_stalled_tables" in name:
             segs.append({"spans": [], "edit_ms": 0.0})
-        elif segs and any(k in name for k in ("k_rollout", "k_replay_solo", "k_replay_lazy", "k_plan_edits")):
+        elif segs and any(k in name for k in ("k_rollout", "k_episodes", "k_replay_solo", "k_replay_lazy", "k_plan_edits")):
             b, e = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
             segs[-1]["spans"].append((b, e))
             if "k_plan_edits" in name:

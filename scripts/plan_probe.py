@@ -99,7 +99,7 @@ def trace_spans(trace_csv, n_calls):
         name = r["Kernel_Name"]
         if "k_stalled_tables" in name:
             segs.append([])
-        elif segs and ("k_rollout" in name or "k_replay_solo" in name or "k_replay_lazy" in name):
+        elif segs and ("k_rollout" in name or "k_episodes" in name or "k_replay_solo" in name or "k_replay_lazy" in name):
             segs[-1].append((int(r["Start_Timestamp"]), int(r["End_Timestamp"])))
     segs = [s for s in segs if s][-n_calls:]
     return [1e-6 * (max(e for _, e in s) - min(b for b, _ in s)) for s in segs]

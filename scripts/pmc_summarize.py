@@ -26,6 +26,7 @@ def variant_of(name):      # k_rollout<helpers, kind>: kind 2 = long-replay (hea
     for key, v in (("k_replay_coop", "coop"), ("k_replay_books", "books"), ("k_replay_broadcast", "bcast"),      # the replay hoist's kernels
                    ("k_replay_solo", "solo"), ("k_replay_lazy", "solo")):      # the per-episode replay kernel, eager / lazy field (k_rollout<.., 2> behind it then has nothing to do)
         if key in name: return v
+    if "k_episodes" in name: return "short" if "<1>" in name else "lean"      # k_episodes<kind>: the same two kinds with the control state uniform
     if "k_rollout" not in name: return None
     return "heavy" if ", 2>" in name else ("short" if ", 1>" in name else "lean")
 

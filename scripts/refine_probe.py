@@ -78,7 +78,7 @@ def main():
         stats = sorted(glob.glob(os.path.join(a.rocprof, "**", "*kernel_stats.csv"), recursive=True))
         if stats:
             ks = kernel_stats(stats[-1])
-            out["kernels"] = {k: v for k, v in ks.items() if any(s in k for s in ("k_refine_pick", "k_plan_edits", "k_rollout", "k_replay_solo", "k_replay_lazy", "k_stalled_tables"))}
+            out["kernels"] = {k: v for k, v in ks.items() if any(s in k for s in ("k_refine_pick", "k_plan_edits", "k_rollout", "k_episodes", "k_replay_solo", "k_replay_lazy", "k_stalled_tables"))}
         else:
             out["rocprof_tail"] = (p.stdout + p.stderr)[-2000:]
         print(json.dumps(out))

@@ -22,8 +22,8 @@ for spec in specs:
         for r in csv.DictReader(open(path)):
             nm = r["Kernel_Name"]
             hoist = [v for key, v in (("k_replay_coop", "coop"), ("k_replay_books", "books"), ("k_replay_broadcast", "bcast"), ("k_replay_solo", "solo"), ("k_replay_lazy", "solo")) if key in nm]
-            if "k_rollout" not in nm and not hoist: continue
-            v = hoist[0] if hoist else ("heavy" if ", 2>" in nm else ("short" if ", 1>" in nm else "lean"))      # k_rollout<helpers, kind>; the replay hoist's kernels
+            if "k_rollout" not in nm and "k_episodes" not in nm and not hoist: continue
+            v = hoist[0] if hoist else ("short" if "k_episodes<1>" in nm else "lean") if "k_episodes" in nm else ("heavy" if ", 2>" in nm else ("short" if ", 1>" in nm else "lean"))      # k_rollout<helpers, kind>; the replay hoist's kernels
             e = per[v].setdefault(int(r["Dispatch_Id"]), {"grid": int(r["Grid_Size"])})
             e[r["Counter_Name"]] = e.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
             e["duration_ns"] = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])

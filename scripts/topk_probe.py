@@ -56,7 +56,7 @@ def kernel_rows(stats_csv):
     with open(stats_csv) as f:
         for r in csv.DictReader(f):
             name = r.get("Name") or r.get("KernelName") or ""
-            for key in ("k_topk_keys", "k_topk_select", "k_topk_merge", "k_rollout", "k_replay_solo", "k_replay_lazy", "k_apply_update"):
+            for key in ("k_topk_keys", "k_topk_select", "k_topk_merge", "k_rollout", "k_episodes", "k_replay_solo", "k_replay_lazy", "k_apply_update"):
                 if key in name:
                     calls = int(r.get("Calls", 0))
                     total = float(r.get("TotalDurationNs", 0.0))
