@@ -56,7 +56,10 @@ extern "C" {
  * best strategy.  Episodes that replay a long best list (more than 96 actions) run a kernel variant whose lists continue in the
  * episode's own record beyond the on-chip window, up to these capacities — the same 4096 the CPU oracle stops at
  * (oracle/eg_oracle.h OG_LOG_CAP).  Sampled episodes and replays of a short list stay within the on-chip window of
- * EG_ONCHIP_GENS generators / offsets (they place 25-200). */
+ * EG_ONCHIP_GENS generators / offsets.  The default policy places 25-200; a year adds up to 20 actions, so a policy with its weight
+ * on one kind of action places up to 520 generators or 520 offsets: up to and including 512 the oracle's episode bit for bit, beyond
+ * it EG_EP_OVERFLOW.  A year's deficit actions are kept up to 128 (the standard world needs 40 at the most; a world of twelve times
+ * its demand passes 128 in 2025), beyond that EG_EP_OVERFLOW as well.  tests/test_gpu_capacity_edges.py holds both edges. */
 #define EG_MAX_GENS 4096
 #define EG_MAX_OFFSETS 4096
 #define EG_RUN_CAP 4096
