@@ -156,6 +156,16 @@ class EgBuildConstraint(C.Structure):
                 ("bound", C.c_double), ("weight", C.c_double * BUILD_CLASSES)]
 
 
+STREAMS_MAX = 64      # EG_STREAMS_MAX: draw streams a plan batch is judged over at most
+
+
+class EgEnsembleRow(C.Structure):      # eg_ensemble_row: what k_ensemble_commit leaves per variant of a batch under plan streams
+    _fields_ = [("nominal", C.c_double * 4), ("committed", C.c_double * 4), ("score_min", C.c_double), ("score_max", C.c_double),
+                ("score_sum", C.c_double), ("n_ok", C.c_int32), ("n_infeasible", C.c_int32), ("n_failed", C.c_int32), ("worst_stream", C.c_int32),
+                ("status", C.c_int32), ("pad", C.c_int32 * 5)]
+
+
+assert C.sizeof(EgEnsembleRow) == 128
 assert C.sizeof(EgPlanConstraint) == 16 and C.sizeof(EgBuildConstraint) == 168
 assert C.sizeof(EgPlanMove) == 12 and C.sizeof(EgPlanCross) == 6
 assert C.sizeof(EgActionMap) == 61 and C.sizeof(EgPlanRewrite) == 8
@@ -235,6 +245,8 @@ EXPORTS = [
     "eg_build_constraints_validate", "eg_build_constraints_set", "eg_last_batch_build_constraints", "eg_build_constraint_parse", "eg_build_constraint_format",
     "eg_debug_load_built",
     "eg_repair_plans_validate", "eg_repair_plans", "eg_debug_repair_pick_many",
+    "eg_plan_streams_validate", "eg_plan_streams_set", "eg_last_batch_streams", "eg_fetch_plan_ensemble", "eg_fetch_plan_streams",
+    "eg_debug_ensemble_keep", "eg_debug_ensemble_commit",
     "eg_host_tables_create", "eg_host_tables_free", "eg_host_tables_f64", "eg_host_tables_i32",
     "eg_policy_new", "eg_policy_free", "eg_policy_snapshot_view", "eg_policy_get_tables", "eg_policy_set_tables",
     "eg_policy_get_scalar", "eg_policy_set_scalar", "eg_policy_get_list", "eg_policy_apply_episode", "eg_score_metrics",
@@ -493,6 +505,22 @@ def lib():
                                       _i32p, _i32p, _dp, _dp, C.POINTER(EgEpisodeOut)]
         L.eg_debug_repair_pick_many.restype = C.c_int32
         L.eg_debug_repair_pick_many.argtypes = [C.c_void_p, C.c_int32, _dp, _u32p, _u32p, C.c_int32, C.c_void_p, _u8p]
+    # (likewise: scripts/ensemble_probe.py may load a build of the parent commit, which has no plan streams)
+    if hasattr(L, "eg_plan_streams_set") or not os.environ.get("EIRGRID_LIB"):
+        L.eg_plan_streams_validate.restype = C.c_int32
+        L.eg_plan_streams_validate.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+        L.eg_plan_streams_set.restype = C.c_int32
+        L.eg_plan_streams_set.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        L.eg_last_batch_streams.restype = C.c_int32
+        L.eg_last_batch_streams.argtypes = [C.c_void_p, _i32p, _i32p]
+        L.eg_fetch_plan_ensemble.restype = C.c_int32
+        L.eg_fetch_plan_ensemble.argtypes = [C.c_void_p, C.POINTER(EgEnsembleRow)]
+        L.eg_fetch_plan_streams.restype = C.c_int32
+        L.eg_fetch_plan_streams.argtypes = [C.c_void_p, _dp, _i32p]
+        L.eg_debug_ensemble_keep.restype = C.c_int32
+        L.eg_debug_ensemble_keep.argtypes = [C.c_void_p, C.c_int32]
+        L.eg_debug_ensemble_commit.restype = C.c_int32
+        L.eg_debug_ensemble_commit.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     if hasattr(L, "eg_pareto_track") or not os.environ.get("EIRGRID_LIB"):
         L.eg_pareto_track.restype = C.c_int32
         L.eg_pareto_track.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]

@@ -266,7 +266,7 @@ int launch_batch(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, con
   if (c->topk_mode != 0) EG_TRY(topk_fold(c, n, first_index, d_stats != nullptr && c->topk_mode == 1));      // the top-K archive, behind the batch as well (the epilogue's scores are the rank scores in mode 1)
   if (c->pareto_cap != 0) EG_TRY(pareto_fold(c, n, first_index));      // the Pareto archive, behind the top-K fold
   ring_commit(c, slot, (plan.n_heavy > 0 ? 1 : 0) | (plan.n_lean > 0 ? 2 : 0));
-  c->last_n = n; c->last_first = first_index; c->feas_k = 0;
+  c->last_n = n; c->last_first = first_index; c->feas_k = 0; c->ran = {};
   return EG_OK;
 }
 
@@ -314,7 +314,7 @@ int find_table(const char* who, const Map& tables, const char* name, const T** p
 
 int device_rollout(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t replay_period, void* d_packet, bool pick) {
   if (!c || !c->snap_valid || !d_packet) { set_error("eg_device_rollout: push a policy first"); return EG_ERR_BAD_ARG; }
-  if (n == 0) { c->last_n = 0; c->feas_k = 0; return EG_OK; }
+  if (n == 0) { c->last_n = 0; c->feas_k = 0; c->ran = {}; return EG_OK; }
   EG_HIP(hipSetDevice(c->device));
   EG_TRY(ensure_outputs(c, n));
   EG_TRY(launch_batch(c, seed, first_index, n, nullptr, replay_period, (long long*)d_packet));
@@ -432,7 +432,7 @@ int32_t eg_upload_snapshot(eg_ctx* c, const eg_policy_snapshot* s, const eg_opts
 
 int32_t eg_rollout_launch(eg_ctx* c, uint64_t seed, uint64_t first_index, uint32_t n, const uint8_t* replay_mask) {
   if (!c || !c->snap_valid) { set_error("eg_rollout_launch: upload a snapshot first"); return EG_ERR_BAD_ARG; }
-  if (n == 0) { c->last_n = 0; c->feas_k = 0; return EG_OK; }
+  if (n == 0) { c->last_n = 0; c->feas_k = 0; c->ran = {}; return EG_OK; }
   EG_HIP(hipSetDevice(c->device));
   EG_TRY(ensure_outputs(c, n));
   return launch_batch(c, seed, first_index, n, replay_mask, 0u, nullptr);
@@ -443,7 +443,7 @@ int32_t eg_rollout_launch_update(eg_ctx* c, uint64_t seed, uint64_t first_index,
   EG_HIP(hipSetDevice(c->device));
   EG_TRY(ensure_outputs(c, n ? n : 1));
   EG_HIP(hipMemsetAsync(d_packet, 0, EG_PACKET_BYTES, nullptr));
-  c->last_n = n; c->last_first = first_index; c->feas_k = 0;
+  c->last_n = n; c->last_first = first_index; c->feas_k = 0; c->ran = {};
   EG_TRY(launch_batch(c, seed, first_index, n, replay_mask, 0u, (long long*)d_packet));
   EG_LAUNCH("k_pick_best", launch_pick_best(c->out, n, first_index, reinterpret_cast<UpdateCandidate*>(static_cast<uint8_t*>(d_packet) + 8 * EG_STATS_LEN), nullptr));
   return EG_OK;

@@ -100,7 +100,7 @@ int32_t eg_debug_load_batch(eg_ctx* c, const double* metrics, const int32_t* sta
   if (n_act) EG_TRY(put_field(c, rec::n_act, n_act, EG_YEARS * sizeof(int32_t), n));
   if (act_log) EG_TRY(put_field(c, rec::act_log, act_log, EG_ACT_CAP, n));      // the whole row: also what lies behind the log
   if (score_list) EG_HIP(hipMemcpy(c->out.score_list, score_list, size_t(n) * sizeof(double), hipMemcpyHostToDevice));
-  c->last_n = n; c->last_first = first_index; c->feas_k = 0;
+  c->last_n = n; c->last_first = first_index; c->feas_k = 0; c->ran = {};
   return EG_OK;
 }
 
@@ -131,6 +131,31 @@ int32_t eg_debug_constrain_last_batch(eg_ctx* c) {
   if (c->rows.n + c->builds.n == 0) { set_error("eg_debug_constrain_last_batch: eg_plan_constraints_set first (no constraints are set)"); return EG_ERR_BAD_ARG; }
   EG_HIP(hipSetDevice(c->device));
   return constrain_batch(c, c->last_n);
+}
+
+// ---- plan streams over crafted records: the two launches a batch under streams puts behind its passes (eg_streams.cpp) ------
+int32_t eg_debug_ensemble_keep(eg_ctx* c, int32_t r) {
+  if (!c) { set_error("eg_debug_ensemble_keep: bad argument"); return EG_ERR_BAD_ARG; }
+  EG_TRY(refuse_rank(c, "eg_debug_ensemble_keep"));
+  if (c->last_n == 0) { set_error("eg_debug_ensemble_keep: there is no last batch"); return EG_ERR_BAD_ARG; }
+  if (r < 0 || r >= EG_STREAMS_MAX) { set_error("eg_debug_ensemble_keep: r = " + std::to_string(r) + " (a stream 0.." + std::to_string(EG_STREAMS_MAX - 1) + ")"); return EG_ERR_BAD_ARG; }
+  EG_HIP(hipSetDevice(c->device));
+  return ensemble_keep(c, c->last_n, r, EG_STREAMS_MAX);
+}
+
+int32_t eg_debug_ensemble_commit(eg_ctx* c, int32_t n_streams, int32_t tail, int32_t mode) {
+  auto fail = [](const std::string& m) { set_error("eg_debug_ensemble_commit: " + m); return EG_ERR_BAD_ARG; };
+  if (!c) return fail("bad argument");
+  EG_TRY(refuse_rank(c, "eg_debug_ensemble_commit"));
+  if (c->last_n == 0) return fail("there is no last batch");
+  if (n_streams < 1 || n_streams > EG_STREAMS_MAX) return fail("n_streams = " + std::to_string(n_streams) + " (1.." + std::to_string(EG_STREAMS_MAX) + ")");
+  if (tail < 1 || tail > n_streams) return fail("tail = " + std::to_string(tail) + " (1..n_streams = " + std::to_string(n_streams) + ")");
+  if (mode != 1 && mode != 2) return fail("mode " + std::to_string(mode) + " is neither 1 (optimization_mode None) nor 2 (cost_only)");
+  const uint64_t want = n_streams == 64 ? ~0ull : (1ull << n_streams) - 1ull;
+  if (c->ens_kept_n != c->last_n || (c->ens_kept_mask & want) != want)
+    return fail("eg_debug_ensemble_keep first (the store does not hold slabs 0.." + std::to_string(n_streams - 1) + " of a batch of " + std::to_string(c->last_n) + " records)");
+  EG_HIP(hipSetDevice(c->device));
+  return ensemble_commit(c, c->last_n, n_streams, tail, mode);
 }
 
 int32_t eg_debug_fold_last_batch(eg_ctx* c, int32_t what, int32_t use_score_list) {

@@ -1,4 +1,4 @@
-// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_debug / eg_plans / eg_plan_host / eg_constraints / eg_refine / eg_breed / eg_explore /
+// eg_host.h — what the host units of the C ABI share (eg_api / eg_fetch / eg_debug / eg_plans / eg_plan_host / eg_constraints / eg_streams / eg_refine / eg_breed / eg_explore /
 // eg_place / eg_group .cpp): owned buffers, the error macros, the context and the helpers that cross units, listed by the unit that holds them.  Host only: the kernels include eg_internal.h, never this.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -153,6 +153,13 @@ struct eg_ctx {
   // last_n sets it); feas_builds: how many of them — the last columns of an excess row — are build constraints (constrain_batch sets both)
   eg::ConstraintSet<eg_plan_constraint> rows; eg::ConstraintSet<eg_build_constraint> builds;
   eg::DevBuf<uint32_t> d_violated; eg::DevBuf<double> d_excess; int feas_k = 0, feas_builds = 0;
+  // plan streams (eg_plan_streams_set; eg_streams.cpp): what is set (n 0: none), what the last batch ran under (ran.n 0: no streams; every batch
+  // that sets last_n sets it), the store of what every pass left — entry (r, j) at (r * last_n + j) * kEnsembleKeptBytes — and the rows
+  // k_ensemble_commit wrote, both reserved by the first batch that needs them
+  struct Streams { int n = 0, tail = 0, mode = 0; } streams, ran;
+  eg::DevBuf<uint8_t> d_ens_kept; eg::DevBuf<eg_ensemble_row> d_ens_rows;
+  // what the store holds: the n its slabs are laid out for and, bit r, the slabs kept since the store was last laid out (ensemble_keep)
+  uint32_t ens_kept_n = 0; uint64_t ens_kept_mask = 0;
   // plan refinement (eg_refine_plan, eg_refine_plans): the step log k_refine_pick_many writes, an entry per plan of a launch from the
   // start (kRefineLog entries of kRefineEntryStride bytes); the base blocks of the call's plans (uploaded once, kept current by
   // k_refine_pick_many) and what a launch uploads in one copy: the packed edits, the base slot of every variant, the segment table
@@ -202,6 +209,11 @@ int decode_plan_blocks(const uint8_t* blocks, int32_t n, const char* who, eg_pla
 // c->out under the context's constraints (at least one of either kind is set), on the null stream; the side buffers reserved, c->feas_k
 // and c->feas_builds set
 int constrain_batch(eg_ctx* c, uint32_t n);
+// eg_streams.cpp: the two launches of a batch under plan streams, on the null stream behind a pass.  keep: the n records of c->out into slab
+// r of a store reserved for `slabs` slabs of n (a store that has to grow loses what it held: the caller reserves for all its slabs with
+// the first one it keeps); commit: k_ensemble_commit over slabs 0..R-1, the rows reserved, c->ran set
+int ensemble_keep(eg_ctx* c, uint32_t n, int r, int slabs);
+int ensemble_commit(eg_ctx* c, uint32_t n, int R, int tail, int mode);
 
 // eg_plan_host.cpp: the pieces a plan search is written from.  `fn` / `who` name the entry point in the messages.
 // Behind an entry point's own NULL test: a rank of a group is refused, then `validate` runs, then check_policy, then hipSetDevice

@@ -551,6 +551,13 @@ int launch_plan_constraints(const DevOut& o, uint32_t n, const void* d_constrain
 // EG_CONSTRAINTS_MAX - k_rows) judged in one pass; mask bit i and d_excess[j * (k_rows + k_builds) + i] number the row constraints first
 int launch_build_constraints(const DevOut& o, uint32_t n, const void* d_constraints, uint32_t k_rows, const void* d_build_constraints, uint32_t k_builds,
                              uint32_t* d_violated, double* d_excess, void* stream);
+// Plan streams (include/eirgrid_hip.h eg_plan_streams_set; eg_ensemble.h).  The context's store holds what every pass left of every record:
+// entry (r, j) — stream r, variant j of a batch of n — is kEnsembleKeptBytes bytes at (r * n + j) * kEnsembleKeptBytes: metrics[4], status, a
+// zero word.  k_ensemble_keep: the n records of o into the slab at d_slab; k_ensemble_commit: the n_streams (1..EG_STREAMS_MAX) slabs at
+// d_slabs reduced per variant — the committed metrics and status over the record's, an eg_ensemble_row into d_rows[j]
+constexpr size_t kEnsembleKeptBytes = 40;
+int launch_ensemble_keep(const DevOut& o, uint32_t n, void* d_slab, void* stream);
+int launch_ensemble_commit(const DevOut& o, uint32_t n, const void* d_slabs, uint32_t n_streams, uint32_t tail, int mode, void* d_rows, void* stream);
 // What k_repair_pick_many (eg_repair.h: eg_pick.h's pick under the repair rule) leaves per plan of a repair round (include/eirgrid_hip.h
 // eg_repair_plans): the candidate — status EG_EP_OK or EG_EP_INFEASIBLE and a rank score that is not NaN — with the smallest violation
 // measure V below the base's, ties to the largest score, then to the lowest variant.  An entry takes a slot of the step log,

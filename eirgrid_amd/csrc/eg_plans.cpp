@@ -81,7 +81,7 @@ DevSnapshot eg::snapshot_of(uint8_t* d_base, const eg_opts* o) {
 // long-replay variant, in launches of at most as many episodes as the penalty-field pool has slots (a long replay claims one per
 // launch epoch).  The hoist, the statistics epilogue and the best_result / top-K folds do not run.  With plan constraints set
 // (eg_plan_constraints_set) k_plan_constraints runs behind the last grid, once, over the n records.
-int eg::launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index) {
+static int plans_pass(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index) {
   const uint32_t n_long = n - n_short;
   const bool helper = n <= c->helper_max_episodes;
   uint32_t done = 0;
@@ -101,9 +101,23 @@ int eg::launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t fi
     ring_commit(c, slot, 1);
     done += chunk;
   }
-  c->last_n = n; c->last_first = first_index; c->feas_k = 0;
+  c->last_n = n; c->last_first = first_index; c->feas_k = 0; c->ran = {};
   // the context's constraints over all n records, behind the grids on their stream: what the caller enqueues next reads the demoted statuses
   return c->rows.n + c->builds.n > 0 ? constrain_batch(c, n) : EG_OK;
+}
+// Every plan batch goes through here.  Without plan streams (eg_plan_streams_set) it is the one pass above.  With R >= 2 set it is R passes,
+// pass r the batch as it runs without streams at first_index + r, from r = R - 1 down to 0 — so the records, the feasibility side buffers,
+// last_n / last_first / feas_k are stream 0's when it returns — with k_ensemble_keep behind each (slab r of the context's store) and
+// k_ensemble_commit behind the last: the committed metrics and status over the records', an eg_ensemble_row a variant (eg_streams.cpp).
+// All on the null stream, behind the grids as the constraint kernel is: a pass's grids start behind the copy of the pass before.
+int eg::launch_plans(eg_ctx* c, const DevSnapshot& S, uint64_t seed, uint64_t first_index, uint32_t n, uint32_t n_short, bool same_index) {
+  const eg_ctx::Streams st = c->streams;
+  if (st.n < 2) return plans_pass(c, S, seed, first_index, n, n_short, same_index);
+  for (int r = st.n - 1; r >= 0; --r) {
+    EG_TRY(plans_pass(c, S, seed, first_index + uint64_t(r), n, n_short, same_index));
+    EG_TRY(ensemble_keep(c, n, r, st.n));
+  }
+  return ensemble_commit(c, n, st.n, st.tail, st.mode);
 }
 // The policy a plan batch is evaluated under into a device snapshot of its own (c->d_eval_snap) — has_best = 1 and lists present
 // (empty: every episode reads its plan block instead) — with its stalled-sampler tables; *S: what the launches get, the plan pool set.

@@ -400,6 +400,10 @@ extern "C" int32_t eg_repair_plans(eg_ctx* c, const eg_policy_snapshot* s, const
   if (!c || !s || !s->weights || !s->deficit_weights || !repaired || !steps || !n_steps || !stop_reason) { set_error("eg_repair_plans: bad argument"); return EG_ERR_BAD_ARG; }
   const int32_t k = c->rows.n + c->builds.n;      // (rows first, then builds: the excess row's columns)
   EG_TRY(plan_entry(c, s, o, "eg_repair_plans", [&] {
+    if (c->streams.n >= 2) {      // (the pick folds V from the excess rows, and those are the last pass's: stream 0's)
+      set_error("eg_repair_plans: " + std::to_string(c->streams.n) + " plan streams are set (eg_plan_streams_set): a repair reads the excess rows, which are stream 0's (clear the streams first)");
+      return EG_ERR_BAD_ARG;
+    }
     EG_TRY(check_repair_weights([](const std::string& m) { set_error("eg_repair_plans: " + m); return EG_ERR_BAD_ARG; }, weights, k));
     return validate_moves("eg_repair_plans", bases, ro, mo, true);
   }));

@@ -1472,6 +1472,7 @@ __global__ void __launch_bounds__(kWave, 7) k_heavy_register_budget(unsigned lon
 #include "eg_plan_constraints.h" // k_plan_constraints: the context's plan constraints judged over a plan batch's records
 #include "eg_repair.h"           // k_repair_pick_many: the pick of a repair round, by the violation k_plan_constraints measured
 #include "eg_build_constraints.h" // k_build_constraints: row and build constraints judged in one pass, where a build constraint is set
+#include "eg_ensemble.h"          // k_ensemble_keep, k_ensemble_commit: a plan batch judged over R draw streams, a lane a stream
 #include "eg_breed.h"            // k_breed_gather, k_breed_turnover: a generation's survivors become the next one's parents on the device
 #include "eg_explore.h"          // k_explore_turnover: the members that entered an exploration's archive become the next frontier
 
@@ -1812,6 +1813,18 @@ int launch_build_constraints(const DevOut& o, uint32_t n, const void* d_constrai
   if (k_rows + k_builds > (uint32_t)EG_CONSTRAINTS_MAX || k_rows > (uint32_t)EG_CONSTRAINTS_MAX) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_build_constraints, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, o, n, reinterpret_cast<const pcons::Packed*>(d_constraints), k_rows,
                      reinterpret_cast<const bcons::Packed*>(d_build_constraints), k_builds, d_violated, d_excess);
+  return (int)hipGetLastError();
+}
+int launch_ensemble_keep(const DevOut& o, uint32_t n, void* d_slab, void* stream) {
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(k_ensemble_keep, dim3((n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, o, n, reinterpret_cast<ens::Kept*>(d_slab));
+  return (int)hipGetLastError();
+}
+int launch_ensemble_commit(const DevOut& o, uint32_t n, const void* d_slabs, uint32_t n_streams, uint32_t tail, int mode, void* d_rows, void* stream) {
+  if (n == 0) return 0;
+  if (n_streams < 1u || n_streams > (uint32_t)EG_STREAMS_MAX || tail < 1u || tail > n_streams) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_ensemble_commit, dim3((n + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, o, n, reinterpret_cast<const ens::Kept*>(d_slabs), n_streams, tail, mode,
+                     reinterpret_cast<eg_ensemble_row*>(d_rows));
   return (int)hipGetLastError();
 }
 int launch_breed_gather(uint8_t* d_breed, const DevOut& o, uint32_t n, uint64_t first, const uint8_t* d_pool, void* stream) {

@@ -187,6 +187,61 @@ def rank_score(metrics, cost_only: bool = False) -> float:
     return N.lib().eg_rank_score(_p(m, C.c_double), 2 if cost_only else 1)
 
 
+@dataclass
+class Ensemble:
+    """The eg_ensemble_row of every variant of a batch that ran under plan streams (Engine.fetch_ensemble), as arrays over the variants."""
+    nominal: np.ndarray        # [n, 4] stream 0's metrics
+    committed: np.ndarray      # [n, 4] what the records hold
+    score_min: np.ndarray      # [n] the smallest / largest stream score that is not NaN (NaN: every score is)
+    score_max: np.ndarray
+    score_sum: np.ndarray      # [n] the stream scores added in ascending stream order
+    n_ok: np.ndarray           # [n] int32: streams that ended EG_EP_OK / EG_EP_INFEASIBLE / any other way
+    n_infeasible: np.ndarray
+    n_failed: np.ndarray
+    worst_stream: np.ndarray   # [n] int32: the first stream of the order (a NaN score, then the smallest score, then the lowest stream)
+    status: np.ndarray         # [n] int32 the committed status
+
+
+def ensemble_reduce(metrics, status, tail: int, cost_only: bool = False) -> dict:
+    """The reduction of one variant's R streams (include/eirgrid_hip.h, plan streams), restated with sequential Python adds: metrics
+    [R, 4], status [R].  Returns the eg_ensemble_row as a dict — nominal and committed as float64 arrays of 4, the scores, the counters,
+    worst_stream and status — bit for bit what k_ensemble_commit writes."""
+    m = np.ascontiguousarray(metrics, dtype=np.float64)
+    st = [int(t) for t in status]
+    R = len(st)
+    if m.shape != (R, 4) or not 1 <= R <= N.STREAMS_MAX or not 1 <= int(tail) <= R:
+        raise ValueError(f"ensemble_reduce: metrics {m.shape}, {R} statuses, tail {tail}")
+    s = [np.float64(rank_score(m[r], cost_only)) for r in range(R)]
+
+    def before(q, r):      # stream q comes before stream r: a NaN score first, then the smaller score, then the lower stream
+        if s[q] != s[q]:
+            return s[r] == s[r] or q < r
+        return s[r] == s[r] and (s[q] < s[r] or (s[q] == s[r] and q < r))
+
+    rank = [sum(1 for q in range(R) if before(q, r)) for r in range(R)]
+    selected = [r for r in range(R) if rank[r] < int(tail)]
+    committed = np.zeros(4, np.float64)
+    with np.errstate(all="ignore"):
+        for i in range(4):
+            c = m[selected[0], i]
+            for r in selected[1:]:
+                c = c + m[r, i]
+            committed[i] = c / np.float64(tail)
+        score_sum = s[0]
+        for r in range(1, R):
+            score_sum = score_sum + s[r]
+    score_min = score_max = None
+    for r in range(R):
+        if s[r] == s[r]:
+            score_min = s[r] if score_min is None or s[r] < score_min else score_min
+            score_max = s[r] if score_max is None or s[r] > score_max else score_max
+    bad = [r for r in range(R) if st[r] != N.EG_EP_OK]
+    n_ok, n_inf = R - len(bad), sum(1 for t in st if t == N.EG_EP_INFEASIBLE)
+    return {"nominal": m[0].copy(), "committed": committed, "score_min": np.float64(np.nan) if score_min is None else score_min,
+            "score_max": np.float64(np.nan) if score_max is None else score_max, "score_sum": np.float64(score_sum), "n_ok": n_ok, "n_infeasible": n_inf,
+            "n_failed": R - n_ok - n_inf, "worst_stream": rank.index(0), "status": st[bad[0]] if bad else N.EG_EP_OK}
+
+
 class Plan:
     """A strategy to score (eg_evaluate_plans): per year the best_actions list and the best_deficit_actions list, canonical action
     indices 0..60 — what update_best_strategy installs and a replay episode reads."""
@@ -1050,10 +1105,56 @@ class Engine:
         N.check(L.eg_fetch_plan_feasibility(self.h, _p(violated, C.c_uint32), _p(excess, C.c_double)), "eg_fetch_plan_feasibility")
         return violated, excess
 
+    def set_streams(self, n: int, tail=None, cost_only: bool = False) -> None:
+        """Plan streams (eg_plan_streams_set): every later plan batch of this engine runs n passes, pass r the batch as it runs without
+        streams at its first index + r, and comes back with stream 0's episode in the records — rows, lists, the feasibility masks — but
+        COMMITTED metrics and status: the mean of the `tail` worst streams by rank_score(., cost_only) (tail=None: all n, the mean
+        outcome; tail=1: the worst stream's metrics), and the first stream's status that is not EG_EP_OK.  evaluate_plans / _plan_edits /
+        _plan_moves / _plan_crosses / _plan_rewrites, refine_plan(s), cross_front, breed_front, explore_front, technology_report,
+        plan_timing, plan_sensitivity, plan_feasibility and fold_pareto_last_batch then work on committed outcomes; repair_plans is
+        refused while streams are set.  n 0 or 1 clears the setting.  Training batches never see it."""
+        n = int(n)
+        N.check(N.lib().eg_plan_streams_set(self.h, n, n if tail is None else int(tail), 2 if cost_only else 1), "eg_plan_streams_set")
+
+    def clear_streams(self) -> None:
+        N.check(N.lib().eg_plan_streams_set(self.h, 0, 0, 0), "eg_plan_streams_set")
+
+    def last_batch_streams(self):
+        """(n, tail, cost_only) the LAST batch ran under (eg_last_batch_streams) — not what is set now; n is 0 when it ran without streams."""
+        tail, mode = C.c_int32(0), C.c_int32(0)
+        n = N.lib().eg_last_batch_streams(self.h, C.byref(tail), C.byref(mode))
+        N.check(min(n, 0), "eg_last_batch_streams")
+        return n, tail.value, mode.value == 2
+
+    def fetch_ensemble(self) -> Ensemble:
+        """The eg_ensemble_row of every variant of the last batch (eg_fetch_plan_ensemble); refused when it ran without streams."""
+        L = N.lib()
+        n = int(L.eg_last_batch_size(self.h))
+        rows = (N.EgEnsembleRow * max(n, 1))()
+        N.check(L.eg_fetch_plan_ensemble(self.h, rows), "eg_fetch_plan_ensemble")
+        a = np.frombuffer(rows, dtype=np.dtype([("nominal", "<f8", 4), ("committed", "<f8", 4), ("score_min", "<f8"), ("score_max", "<f8"), ("score_sum", "<f8"),
+                                                ("n_ok", "<i4"), ("n_infeasible", "<i4"), ("n_failed", "<i4"), ("worst_stream", "<i4"), ("status", "<i4"),
+                                                ("pad", "<i4", 5)]))[:n]
+        return Ensemble(*[a[f.name].copy() for f in fields(Ensemble)])
+
+    def fetch_streams(self):
+        """(metrics [R, n, 4], status [R, n]) of every stream of the last batch (eg_fetch_plan_streams): what pass r left in the records,
+        stream 0's being what the batch would hold without streams; refused when it ran without streams."""
+        L = N.lib()
+        n, R = int(L.eg_last_batch_size(self.h)), int(L.eg_last_batch_streams(self.h, None, None))
+        if R <= 0 or n == 0:      # the library's own refusal, nothing written
+            N.check(L.eg_fetch_plan_streams(self.h, None, None), "eg_fetch_plan_streams")
+            raise N.EirgridError("eg_fetch_plan_streams: the last batch ran without plan streams")
+        metrics, status = np.zeros((R, n, 4), np.float64), np.zeros((R, n), np.int32)
+        N.check(L.eg_fetch_plan_streams(self.h, _p(metrics, C.c_double), _p(status, C.c_int32)), "eg_fetch_plan_streams")
+        return metrics, status
+
     def plan_feasibility(self, weights: ActionWeights, plans, seed: int, index: int = 0, constraints=None):
         """Which of `plans` satisfy which constraints: evaluates them as evaluate_plans does (plan j at global index index + j) under
         `constraints` (None: the ones that are set) and returns (status [n], violated: per plan the list of the violated Constraints,
-        excess [n, k]; a negative excess is the slack).  The engine's own constraints are as before afterwards."""
+        excess [n, k]; a negative excess is the slack).  The engine's own constraints are as before afterwards.
+        Under set_streams the status is the committed one — infeasible as soon as one stream violates a constraint — while the violated
+        lists and the excess rows are stream 0's: fetch_ensemble().n_infeasible tells in how many streams a plan was infeasible."""
         before = list(getattr(self, "_constraints", ()))
         if constraints is not None:
             self.set_constraints(constraints)
@@ -1119,7 +1220,8 @@ class Engine:
         in chunks of at most max_variants (<= 16 384) in order, every one at global index `index` of `seed` (the same fallback draws),
         and filtered on the host with eg_pareto_track's definitions over `objectives` (pareto_filter), chunk by chunk against the
         front so far; an equal point is held once, at the lowest variant number.  Per variant only the metrics and the status come
-        back (36 bytes).  The context's own Pareto archive is not touched.  cost_only picks the rank score of the rows."""
+        back (36 bytes).  The context's own Pareto archive is not touched.  cost_only picks the rank score of the rows.
+        Under set_streams every variant is judged over the R streams: the metrics, statuses and scores here are the committed ones."""
         mask = _objective_mask(objectives, "cross_front")
         if mask == 0:
             raise ValueError("cross_front: no objectives")
@@ -1169,7 +1271,8 @@ class Engine:
         refilled by fallback draws; deficit == "keep" leaves that list alone — evaluated in chunks of at most max_variants (<= 16 384)
         in order, every one at global index `index` of `seed`.  Per variant only the metrics and the status come back (36 bytes); a
         plan whose deficit list holds the type taken out goes up once more with that list substituted (technology_rewrites).
-        The context's own Pareto archive is not touched.  Rows in the variants' order; cost_only picks the rank score."""
+        The context's own Pareto archive is not touched.  Rows in the variants' order; cost_only picks the rank score.
+        Under set_streams every variant is judged over the R streams: the metrics, statuses and scores here are the committed ones."""
         if not 1 <= int(max_variants) <= N.REWRITE_MAX_VARIANTS:
             raise ValueError(f"technology_report: max_variants = {max_variants} (1..{N.REWRITE_MAX_VARIANTS})")
         plans = list(plans)
@@ -1325,7 +1428,8 @@ class Engine:
     def plan_timing(self, weights: ActionWeights, base: "Plan", seed: int, mode: int = 1, max_shift: int = 1) -> Timing:
         """Which entries of `base` would be better placed in another year: the base (row 0) and the moves of refine_moves(base,
         max_shift) in one batch, all at global index 0 of `seed`; per move the metrics, eg_rank_score in `mode` (1: optimization_mode
-        None, 2: cost_only) and their differences from the base's."""
+        None, 2: cost_only) and their differences from the base's.
+        Under set_streams every variant is judged over the R streams: the metrics, statuses and scores here are the committed ones."""
         moves = refine_moves(base, max_shift)
         first = next(((y, 0) for y, l in enumerate(base.best_actions) if l), None)
         if first is None:      # nothing to move: the base alone, through the plan batch
@@ -1349,7 +1453,8 @@ class Engine:
 
     def plan_sensitivity(self, weights: ActionWeights, base: "Plan", seed: int, mode: int = 1, replace_with=None) -> Sensitivity:
         """Which actions of `base` matter: the edits of sensitivity_edits(base, replace_with), all at global index 0 of `seed`; per edit
-        the metrics, eg_rank_score in `mode` (1: optimization_mode None, 2: cost_only) and their differences from the base's."""
+        the metrics, eg_rank_score in `mode` (1: optimization_mode None, 2: cost_only) and their differences from the base's.
+        Under set_streams every variant is judged over the R streams: the metrics, statuses and scores here are the committed ones."""
         edits = sensitivity_edits(base, replace_with)
         res = self.evaluate_plan_edits(weights, base, edits, seed, 0, True)
         L = N.lib()
@@ -1678,6 +1783,14 @@ class Engine:
         """Test hook (eg_debug_constrain_last_batch): k_plan_constraints — with a build constraint set, k_build_constraints — over the last
         batch, as a plan batch ends."""
         N.check(N.lib().eg_debug_constrain_last_batch(self.h), "eg_debug_constrain_last_batch")
+
+    def _debug_ensemble_keep(self, r: int) -> None:
+        """Test hook (eg_debug_ensemble_keep): k_ensemble_keep over the last batch's records, into slab r of the store."""
+        N.check(N.lib().eg_debug_ensemble_keep(self.h, int(r)), "eg_debug_ensemble_keep")
+
+    def _debug_ensemble_commit(self, n_streams: int, tail: int, cost_only: bool = False) -> None:
+        """Test hook (eg_debug_ensemble_commit): k_ensemble_commit over slabs 0..n_streams-1 and the last batch's records."""
+        N.check(N.lib().eg_debug_ensemble_commit(self.h, int(n_streams), int(tail), 2 if cost_only else 1), "eg_debug_ensemble_commit")
 
     def _debug_fold_last_batch(self, best_result: bool = False, top_k: bool = False, use_score_list: bool = False) -> None:
         """Test hook (eg_debug_fold_last_batch): what a training batch runs behind its rollout for the chosen folds, on the last batch."""

@@ -325,7 +325,8 @@ double eg_rank_score(const double metrics[4], int32_t mode);   /* mode 2: cost_o
  * archive state and cap record slots (10.6 MB at cap 256) are allocated by eg_pareto_track; like best_result the archive lives as long
  * as the context and is not part of any checkpoint.
  * eg_fetch_pareto copies the *n_held <= cap entries: `out` rows (sized for cap episodes; may be NULL), global_index[cap], scores[cap]
- * (eg_rank_score of each entry), *n_dropped (each may be NULL). */
+ * (eg_rank_score of each entry), *n_dropped (each may be NULL).
+ * Under plan streams (eg_plan_streams_set, below) eg_pareto_fold_last_batch folds what a plan batch left in the records, the committed metrics and status: no other change. */
 #define EG_PARETO_MAX 256
 #define EG_PARETO_KEEP_SPREAD 0x100     /* OR-ed into the mode of eg_pareto_track, eg_breed_opts, eg_explore_opts, eg_debug_breed_begin: the capacity rule "keep spread" */
 int32_t eg_pareto_track(eg_ctx *, int32_t cap, int32_t objectives, int32_t mode);
@@ -431,7 +432,8 @@ int32_t eg_debug_fetch_plan_block(eg_ctx *, uint32_t plan, uint8_t *out /* EG_PL
  * winner on MAX_ROUNDS, not written on BASE_FAILED.  A round that would enumerate more than EG_REFINE_MAX_VARIANTS variants is refused
  * (EG_ERR_BAD_ARG naming the round and the count): round 0 by eg_refine_validate, later rounds when they are reached.
  * eg_refine_validate runs the checks alone: mode 1 or 2, max_rounds >= 1, actions 0..60, no NULL list with a count, a base of exactly
- * one valid plan. */
+ * one valid plan.
+ * Under plan streams (eg_plan_streams_set, below) every round's variants run as R passes and the pick reads their committed metrics and status: no other change. */
 #define EG_REFINE_LOCAL_OPTIMUM 0
 #define EG_REFINE_MAX_ROUNDS 1
 #define EG_REFINE_BASE_FAILED 2
@@ -474,7 +476,8 @@ int32_t eg_refine_plan(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, co
  * launch's variants.
  * eg_refine_plans_validate runs the checks alone and names the plan in every message about one ("plan 3: round 0 enumerates ..."): a
  * valid set (eg_plans_validate) of 1..EG_REFINE_MAX_PLANS plans; the option checks of eg_refine_validate; per plan, the variant count of
- * round 0. */
+ * round 0.
+ * Under plan streams (eg_plan_streams_set, below) every launch runs as R passes and every plan's pick reads committed metrics and status (eg_refine_plans_moves alike): no other change. */
 #define EG_REFINE_MAX_PLANS 256          /* = EG_PARETO_MAX: a whole front fits */
 int32_t eg_refine_plans_validate(const eg_plan_set *bases, const eg_refine_opts *);
 int32_t eg_refine_plans(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, const eg_plan_set *bases /* 1..EG_REFINE_MAX_PLANS */,
@@ -552,7 +555,8 @@ int32_t eg_refine_plans_moves(eg_ctx *, const eg_policy_snapshot *, const eg_opt
  * eg_plan_crosses_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the cross and the field ("cross 7: best_actions
  * would hold 4212 entries (at most 4096)") for a parent set that is not a valid set of 1..EG_CROSS_MAX_PARENTS plans, n_crosses outside
  * 1..EG_CROSS_MAX_VARIANTS, NULL crosses, a or b >= n_plans, to_year > 26, from_year > to_year, or a child whose best_actions or
- * best_deficit_actions would exceed 4 096 entries.  Nothing is launched after a refusal. */
+ * best_deficit_actions would exceed 4 096 entries.  Nothing is launched after a refusal.
+ * Under plan streams (eg_plan_streams_set, below) the batch runs as R passes and comes back with committed metrics and status (eg_evaluate_plans, _plan_edits, _plan_moves, _plan_rewrites alike): no other change. */
 #define EG_CROSS_MAX_PARENTS 256      /* = EG_PARETO_MAX */
 #define EG_CROSS_MAX_VARIANTS 16384   /* = EG_REFINE_MAX_VARIANTS */
 typedef struct { uint16_t a, b; uint8_t from_year, to_year; } eg_plan_cross;   /* 6 bytes */
@@ -775,6 +779,56 @@ int32_t eg_repair_plans(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, c
                         uint64_t seed, uint64_t episode_index, eg_plan_set **repaired, eg_repair_step *steps /* [n_plans][max_rounds] */,
                         int32_t *n_steps, int32_t *stop_reason, double *start_violation, double *final_violation, eg_episode_out *out);
 
+/* Plan streams: every plan batch judged over R draw streams, on the device.  A plan batch runs each variant once, at seed + first_index:
+ * a replay reads no seeded draw only while its two lists last, and where best_deficit_actions runs short the repair loop falls back to
+ * sampled draws — so a variant the searches made by deleting, splicing or dropping entries is judged by one stream's luck.  With
+ * R = n_streams >= 2 set on a context, every later plan batch of it (everything that launches a plan batch: eg_evaluate_plans, _plan_edits,
+ * _plan_moves, _plan_crosses, _plan_rewrites, eg_refine_plan, eg_refine_plans, eg_refine_plans_moves, eg_breed_plans, eg_explore_plans)
+ * runs R PASSES.  Pass r is the batch exactly as it runs without streams at first_index + r: the same routing, the same long-plan chunks,
+ * the constraint kernel behind the grids when constraints are set.  The passes run from r = R - 1 down to r = 0, so when the batch
+ * returns the records hold STREAM 0's EPISODE — rows, lists, gen_pack, and the feasibility masks and excess rows
+ * eg_fetch_plan_feasibility serves are what the batch holds without streams — but for metrics[4] and status, which hold the COMMITTED
+ * outcome below (the records are not cleared between passes any more than between batches: what lies behind a list's count is whatever
+ * was written there last).  eg_last_batch_size and the first index of the batch are as after one pass at first_index.  Behind each pass
+ * csrc/eg_ensemble.h k_ensemble_keep copies metrics and status of the n records into slab r of a store of the context (40 bytes a variant
+ * and stream, reserved at the first batch that needs it); behind the last pass k_ensemble_commit runs once, a wave a variant and a lane a
+ * stream, overwrites every record's metrics and status and writes an eg_ensemble_row.  The picks and folds a search enqueues behind a
+ * batch, and eg_pareto_fold_last_batch, read the committed outcome: every search becomes a search on committed outcomes.
+ * THE DEFINITION.  For one variant let m_r be stream r's metrics and t_r its status, r = 0..R-1, and s_r = eg_rank_score(m_r, mode).
+ *   committed status    EG_EP_OK when every t_r is EG_EP_OK, otherwise t_r of the lowest r with t_r != EG_EP_OK: a variant is infeasible as
+ *                       soon as one stream violates a constraint
+ *   order of streams    worst first: a stream whose score is NaN ranks before every stream whose score is a number, then the smaller
+ *                       score (-0.0 and +0.0 are equal), then the lower r.  The order covers all R streams, whatever their status
+ *   committed metrics   for each i: of the `tail` worst streams, in ascending r, c = m_r[i] of the lowest selected r, then c = c + m_r[i]
+ *                       for the others (plain double adds, one rounding each), then c / (double)tail.  tail == R is the mean outcome,
+ *                       tail == 1 the worst stream's metrics bit for bit, anything between the mean of the worst tail (CVaR)
+ *   eg_ensemble_row     nominal = m_0; committed as above; score_sum = s_0, then + s_r in ascending r; score_min / score_max the smallest /
+ *                       largest s_r that is not NaN (the first of equal ones), both the quiet NaN 0x7FF8000000000000 when every s_r is
+ *                       NaN; n_ok, n_infeasible the streams with t_r == EG_EP_OK, == EG_EP_INFEASIBLE, n_failed the others; worst_stream the
+ *                       first stream of the order; status the committed status; pad zero
+ * eg_plan_streams_validate: EG_ERR_BAD_ARG for n_streams outside 0..EG_STREAMS_MAX and, with n_streams >= 2, tail outside 1..n_streams or a
+ * mode other than 1 | 2 (eg_rank_score's).  eg_plan_streams_set validates and stores the setting; n_streams 0 or 1 clears it (tail and mode
+ * are then not read) and nothing runs differently from a context that never had one.  A rank of a group is refused.  Training batches
+ * never see the setting.  eg_last_batch_streams returns the R the LAST batch ran under — 0 when it ran without streams, whatever is set
+ * now; EG_ERR_BAD_ARG for a NULL context — with its tail and mode (either pointer may be NULL).  eg_fetch_plan_ensemble copies the n =
+ * eg_last_batch_size() rows of it, eg_fetch_plan_streams every stream's metrics [R][n][4] and status [R][n] (either may be NULL);
+ * both EG_ERR_BAD_ARG when the last batch ran without streams.
+ * eg_repair_plans is refused while streams are set (EG_ERR_BAD_ARG): its pick reads the excess rows, which are stream 0's.  A chance level
+ * for feasibility ("feasible in q of R") and streams on a group are not implemented.
+ * Test hooks (they refuse a rank of a group): eg_debug_load_batch runs no passes; eg_debug_ensemble_keep copies the last batch's n records
+ * into slab r (0..EG_STREAMS_MAX-1; the store is reserved for EG_STREAMS_MAX slabs of n), eg_debug_ensemble_commit runs k_ensemble_commit
+ * over slabs 0..R-1 (R 1..EG_STREAMS_MAX) and the last batch's records, after which the two fetches serve it. */
+#define EG_STREAMS_MAX 64
+typedef struct { double nominal[4], committed[4]; double score_min, score_max, score_sum; int32_t n_ok, n_infeasible, n_failed, worst_stream;
+                 int32_t status; int32_t pad[5]; } eg_ensemble_row;   /* 128 bytes */
+int32_t eg_plan_streams_validate(int32_t n_streams, int32_t tail, int32_t mode);
+int32_t eg_plan_streams_set(eg_ctx *, int32_t n_streams /* 0 or 1: clear */, int32_t tail /* 1..n_streams */, int32_t mode /* 1 | 2 */);
+int32_t eg_last_batch_streams(const eg_ctx *, int32_t *tail, int32_t *mode);
+int32_t eg_fetch_plan_ensemble(eg_ctx *, eg_ensemble_row *rows /* [n] */);
+int32_t eg_fetch_plan_streams(eg_ctx *, double *metrics /* [R][n][4] or NULL */, int32_t *status /* [R][n] or NULL */);
+int32_t eg_debug_ensemble_keep(eg_ctx *, int32_t r);
+int32_t eg_debug_ensemble_commit(eg_ctx *, int32_t n_streams, int32_t tail, int32_t mode);
+
 /* Breeding a front: generations of plan crosses with Pareto selection, the survivors' plan blocks becoming the next generation's parents
  * on the device.  eg_breed_plans(ctx, policy, opts, parents, breed_opts, seed, episode_index, ...) starts from the population P_0 = the
  * given 1..EG_CROSS_MAX_PARENTS plans, in order.  Generation g = 0, 1, ... :
@@ -809,7 +863,8 @@ int32_t eg_repair_plans(eg_ctx *, const eg_policy_snapshot *, const eg_opts *, c
  * eg_breed_validate runs the checks alone: EG_ERR_BAD_ARG with a message naming the field for a parent set that is not a valid set of
  * 1..EG_CROSS_MAX_PARENTS plans, NULL options, a mode other than 1 or 2 (either with EG_PARETO_KEEP_SPREAD OR-ed in or not), objectives outside 1..15, cap outside 1..EG_PARETO_MAX,
  * max_generations < 1, launch_variants outside 0..EG_CROSS_MAX_VARIANTS, n_cuts outside 0..25, NULL cuts with n_cuts > 0, a cut outside
- * 1..25.  Nothing is launched after a refusal. */
+ * 1..25.  Nothing is launched after a refusal.
+ * Under plan streams (eg_plan_streams_set, below) every chunk runs as R passes and the selection folds committed metrics and status: no other change. */
 #define EG_BREED_CONVERGED 0
 #define EG_BREED_MAX_GENERATIONS 1
 #define EG_BREED_EMPTY 2
@@ -880,7 +935,8 @@ int32_t eg_breed_plans(eg_ctx *, const eg_policy_snapshot *policy, const eg_opts
  * 1..EG_CROSS_MAX_PARENTS plans, NULL options, a mode other than 1 or 2 (either with EG_PARETO_KEEP_SPREAD OR-ed in or not), objectives outside 1..15, cap outside 1..EG_PARETO_MAX,
  * max_generations < 1, n_replace or n_append < 0, a NULL list with a count, an action above 60, max_shift outside 0..25,
  * launch_variants outside 0..EG_CROSS_MAX_VARIANTS, max_variants < 0.  Nothing is launched after a refusal.
- * eg_explore_neighbourhood (host only, the same checks first): sizes[p] = the neighbourhood size of start plan p. */
+ * eg_explore_neighbourhood (host only, the same checks first): sizes[p] = the neighbourhood size of start plan p.
+ * Under plan streams (eg_plan_streams_set, below) every chunk runs as R passes and the archive folds committed metrics and status: no other change. */
 #define EG_EXPLORE_EXPLORED 0
 #define EG_EXPLORE_MAX_GENERATIONS 1
 #define EG_EXPLORE_EMPTY 2

@@ -80,6 +80,8 @@ def main():
     ap.add_argument("--out", required=True, help="output directory")
     from eirgrid_amd.constraints import add_constraint_arguments, apply_constraints
     add_constraint_arguments(ap)
+    from eirgrid_amd.streams import add_stream_arguments, apply_streams
+    add_stream_arguments(ap)
     a = ap.parse_args()
     from eirgrid_amd import synthetic_world
     from eirgrid_amd.engine import ActionWeights, Engine, Plan
@@ -92,6 +94,7 @@ def main():
     eng = Engine(world, device=0)
     try:
         apply_constraints(eng, a)      # --constraint: every plan batch below is judged under them
+        apply_streams(eng, a)          # --streams R [--tail K]: ... over R draw streams, and ranked by committed outcomes
         front = eng.cross_front(policy, parents, a.seed, 0, cost_only=a.cost_only, cuts=[y - 2025 for y in a.cuts])
     finally:
         eng.close()

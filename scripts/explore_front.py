@@ -104,6 +104,8 @@ def main():
     ap.add_argument("--out", required=True, help="output directory")
     from eirgrid_amd.constraints import add_constraint_arguments, apply_constraints
     add_constraint_arguments(ap)
+    from eirgrid_amd.streams import add_stream_arguments, apply_streams
+    add_stream_arguments(ap)
     a = ap.parse_args()
     from eirgrid_amd import synthetic_world
     from eirgrid_amd.engine import ActionWeights, Engine, Plan
@@ -116,6 +118,7 @@ def main():
     eng = Engine(world, device=0)
     try:
         apply_constraints(eng, a)      # --constraint: every plan batch below is judged under them
+        apply_streams(eng, a)          # --streams R [--tail K]: ... over R draw streams, and ranked by committed outcomes
         front = eng.explore_front(policy, starts, a.seed, 0, cost_only=a.cost_only, generations=a.generations, cap=a.cap, replace_with=a.replace,
                                   append_with=a.append, max_shift=a.shift, max_variants=a.budget, keep=a.keep)
     finally:

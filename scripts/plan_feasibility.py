@@ -9,6 +9,8 @@ script writes
     DIR/feasibility/index.csv   a row per plan: its position and name, its status (0 feasible, -4 infeasible, another negative number: the
                                 plan failed on its own and was not judged), the violated constraints (their specs, joined by "; ") and
                                 one `excess` column per constraint, as %.17g: <= 0 is satisfied and its negative is the slack, nan violates
+--streams R [--tail K] judges every plan over R draw streams (Engine.set_streams): the status is then infeasible as soon as one stream
+violates a constraint, the violated constraints and the excess columns are those of the first stream.
 --world takes a world as World.to_json_dict writes it, or the word `synthetic`; without --policy the plans are evaluated under a fresh
 policy."""
 import argparse
@@ -42,6 +44,8 @@ def main():
     ap.add_argument("--out", required=True, help="output directory")
     from eirgrid_amd.constraints import add_constraint_arguments, constraint_list
     add_constraint_arguments(ap)
+    from eirgrid_amd.streams import add_stream_arguments, apply_streams
+    add_stream_arguments(ap)
     a = ap.parse_args()
     if not a.constraint:
         ap.error("at least one --constraint is needed")
@@ -54,6 +58,7 @@ def main():
     policy = ActionWeights.load_from_file(a.policy) if a.policy else ActionWeights()
     eng = Engine(world, device=0)
     try:
+        apply_streams(eng, a)      # --streams R [--tail K]: a plan is infeasible as soon as one stream violates; the excess columns stay stream 0's
         status, violated, excess = eng.plan_feasibility(policy, plans, a.seed, 0, constraints=constraints)
     finally:
         eng.close()

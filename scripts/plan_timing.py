@@ -53,6 +53,8 @@ def main():
     ap.add_argument("--out", required=True, help="output directory")
     from eirgrid_amd.constraints import add_constraint_arguments, apply_constraints
     add_constraint_arguments(ap)
+    from eirgrid_amd.streams import add_stream_arguments, apply_streams
+    add_stream_arguments(ap)
     a = ap.parse_args()
     if not 1 <= a.shift <= 25:
         ap.error("--shift takes 1..25 years")
@@ -65,6 +67,7 @@ def main():
     eng = Engine(world, device=0)
     try:
         apply_constraints(eng, a)      # --constraint: every plan batch below is judged under them
+        apply_streams(eng, a)          # --streams R [--tail K]: ... over R draw streams, and ranked by committed outcomes
         timings = [eng.plan_timing(policy, base, a.seed, 2 if a.cost_only else 1, a.shift) for base in bases]
     finally:
         eng.close()

@@ -90,6 +90,8 @@ def main():
     ap.add_argument("--out", required=True, help="output directory")
     from eirgrid_amd.constraints import add_constraint_arguments, apply_constraints
     add_constraint_arguments(ap)
+    from eirgrid_amd.streams import add_stream_arguments, apply_streams
+    add_stream_arguments(ap)
     a = ap.parse_args()
     if a.rounds < 1:
         ap.error("--rounds must be at least 1")
@@ -104,6 +106,7 @@ def main():
     eng = Engine(world, device=0)
     try:
         apply_constraints(eng, a)      # --constraint: every plan batch below is judged under them
+        apply_streams(eng, a)          # --streams R [--tail K]: ... over R draw streams, and ranked by committed outcomes
         results = eng.refine_plans(policy, bases, a.seed, 0, 2 if a.cost_only else 1, a.rounds, replace_with=a.replace, append_with=a.append, max_shift=a.shift)
     finally:
         eng.close()
